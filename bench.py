@@ -2,6 +2,7 @@
 """Benchmark of the CalliReader image->text hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W           (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR                  (also writes what the last timed step computed, DIR/<name>.npy)
 
 Metric (BASELINE.json): calligraphy pages/sec through ViT + resampler + LLM greedy decode.
 One "step" = one batch of synthetic pages per GPU through the whole path:
@@ -59,6 +60,35 @@ from benchlib import plan  # noqa: E402
 from benchlib.plan import PAGE_TILES, CHAR_TILES, TEXT_TOKENS, build_ids, plan_workload, plan_strong_share  # noqa: E402,F401  (tests import them from here)
 from benchlib.measure import PEAK_BF16_TFLOPS, PEAK_HBM_GBS, cpu_baseline, cpu_baseline_full, measure_traffic  # noqa: E402
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: the files of all ranks together stay within this
+DUMP_SAMPLE = 1 << 21          # elements kept of one larger tensor at most (8 MB of float32: one GPU's dump of the default step is ~16 MB)
+NPY_HEADER = 4096              # bytes reserved per .npy file for its header (numpy writes 128 for these shapes)
+
+
+def dump_outputs(out_dir, page_ids, tensors, suffix='', world=1):
+    """--dump-outputs: `page_ids` (one list of greedy ids per page of the step) as out_dir/token_ids<suffix>.npy, and each tensor of `tensors`
+    (name -> tensor, or None: skipped) as out_dir/<name><suffix>.npy -- whole when it fits, else a sample at sorted positions drawn by a
+    generator of fixed seed (the same positions in every run of the same shape and world size).  All float32 (ids < 2^24 are exact).
+    Each of the `world` ranks writes its own files within DUMP_BYTES / world; the ids are written whole and the tensors share the rest
+    equally, at most DUMP_SAMPLE elements each.  Returns the names written."""
+    import numpy as np
+    arrays = {'token_ids': np.asarray(page_ids, dtype=np.float32)}
+    present = {name: t for name, t in tensors.items() if t is not None}
+    room = DUMP_BYTES // world - (1 + len(present)) * NPY_HEADER - arrays['token_ids'].nbytes
+    if room < 4 * len(present):
+        raise ValueError(f'--dump-outputs: the ids of {len(page_ids)} pages alone exceed this rank\'s {DUMP_BYTES // world} bytes')
+    n = min(DUMP_SAMPLE, room // (4 * max(1, len(present))))
+    for name, t in present.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > n:
+            pos = np.sort(np.random.default_rng(0).integers(0, flat.numel(), n))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        arrays[name] = flat.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + '.npy'), a)
+    return sorted(arrays)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -90,7 +120,12 @@ def main():
     ap.add_argument('--no-api', action='store_true', help='N = 1: skip the api_level block (the same batch from JPEG files through chat_ocr_stream / folder_rec to strings)')
     ap.add_argument('--api-batches', type=int, default=6, help='batches of --pages pages the api_level block streams')
     ap.add_argument('--no-pipeline', action='store_true', help='one batch at a time (the decode of a batch does not run beside the visual stage of the next)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): the greedy ids of its pages and a fixed, '
+                         'seeded sample of its page-tile features and pseudo-token embeddings (the inputs are seeded: two builds compare output for output)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     plan.NEW_TOKENS = NEW_TOKENS = args.new_tokens
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -146,9 +181,10 @@ def main():
     page_px, char_px, ids = make_inputs(wl)
     headline_inputs = (page_px, char_px, ids)
 
-    def step(new_tokens=None, stamps=None, w=None, inputs=None, merged=None):
+    def step(new_tokens=None, stamps=None, w=None, inputs=None, merged=None, keep=None):
         """merged = [inputs, inputs, ...]: the visual stage (with its all-gather) and the splice of SEVERAL consecutive steps of workload `w`, then ONE prefill + decode over all
-        their pages -- the decode batch of a rank fed from several steps (a page's ids do not depend on its batch); returns the pages of all of them, in order."""
+        their pages -- the decode batch of a rank fed from several steps (a page's ids do not depend on its batch); returns the pages of all of them, in order.
+        keep: a dict that receives this step's page-tile features and pseudo-token embeddings (--dump-outputs)."""
         new_tokens = NEW_TOKENS if new_tokens is None else new_tokens
         embeds = []
         for one in (merged if merged is not None else [inputs]):
@@ -167,6 +203,8 @@ def main():
                 gathered = all_gather_rows_async(pseudo_local.reshape(-1, 3, dims.llm_hidden), n_pages * CHAR_TILES,      # 24.5 KB per tile, over xGMI ...
                                                  counts=None if w is None else w.get('ct_counts'))
             vit_mine = model.extract_feature(page_px) if len(mine) else None             # ... underneath the owner's page tiles (my pages * 11, 256, 4096)
+            if keep is not None:
+                keep.update(visual=vit_mine, pseudo=pseudo_local)
             if stamps is not None:
                 torch.cuda.synchronize(); stamps.append(time.perf_counter())
             pseudo_all = gathered()
@@ -197,11 +235,13 @@ def main():
             e.record(torch.cuda.current_stream())
             marks.append((tag, e, time.perf_counter()))
 
-    def step_pipelined():
+    def step_pipelined(keep=None):
         mark('step start')
         pseudo_local, _ = model.align_tiles(char_px)
         gathered = all_gather_rows_async(pseudo_local.reshape(-1, 3, dims.llm_hidden), n_pages * CHAR_TILES)
         vit_mine = model.extract_feature(page_px)
+        if keep is not None:
+            keep.update(visual=vit_mine, pseudo=pseudo_local)
         mark('visual done')
         pseudo_all = gathered()
         embeds = []
@@ -213,10 +253,11 @@ def main():
         mark('prefill issued + previous collected')
         return out
 
-    def run_steps(k):
+    def run_steps(k, keep=None):
+        """k steps; returns the ids of every step's pages.  keep: filled by the LAST step only (the earlier steps' tensors are not held)."""
         if pipe is None:
-            return [step() for _ in range(k)]
-        outs = [step_pipelined() for _ in range(k)]
+            return [step(keep=keep if i == k - 1 else None) for i in range(k)]
+        outs = [step_pipelined(keep=keep if i == k - 1 else None) for i in range(k)]
         outs = outs[1:] + [pipe.finish()]
         assert all(o is not None and all(len(x) == NEW_TOKENS for x in o) for o in outs)
         return outs
@@ -236,8 +277,9 @@ def main():
     prof_ctx = [eng._h] + ([pipe.dec._h] if pipe is not None else [])      # the decode thread launches through its own context
     for h in prof_ctx:
         B.check(B.lib.cr_profile(h, 1))
+    kept = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    timed_outs = run_steps(args.steps, keep=kept)
     sync()
     elapsed = time.perf_counter() - t0
     if marks and rank == 0:
@@ -253,6 +295,10 @@ def main():
         B.check(B.lib.cr_profile_stats(h, ps))
         prof = [a + b for a, b in zip(prof, pr)]
         pstat = [pstat[0] + ps[0], pstat[1] + ps[1], pstat[2] + ps[2], max(pstat[3], ps[3])]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_outs[-1], {'page_features_sample': kept.get('visual'), 'pseudo_tokens_sample': kept.get('pseudo')},
+                     suffix='' if world == 1 else f'_rank{rank}', world=world)
+        kept.clear()
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

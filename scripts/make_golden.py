@@ -69,6 +69,7 @@ def main():
     install_stubs()
     torch.manual_seed(0)
     torch.set_num_threads(os.cpu_count())
+    torch.backends.mkldnn.enabled = False        # PyTorch's own CPU kernels: the same bits on any AVX-512 host and thread count (oneDNN's differ per ISA / threads)
     from callireader_amd.config import ModelDims
     from callireader_amd import synthetic
 

@@ -123,6 +123,7 @@ def synth_page(rng, w, h, n_cols, per_col, seal=False, dup=0):
 
 def main():
     torch.manual_seed(0)
+    torch.backends.mkldnn.enabled = False        # PyTorch's own CPU kernels: the same bits on any AVX-512 host and thread count (oneDNN's differ per ISA / threads)
     torch.set_default_dtype(torch.bfloat16)          # the reference builds the sorter inside a bf16 from_pretrained
     sorter = ref_model.OrderFormer(max_nums=50, input_dim=4, model_dim=256, num_heads=8, num_layers=4, output_dim=1,
                                    device=torch.device('cpu'), label_name='turn', norm=False)

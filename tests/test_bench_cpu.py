@@ -15,7 +15,7 @@ def test_bench_help_lists_every_block_switch_and_benchlib_imports():
     out = r.stdout.decode()
     assert r.returncode == 0, out[-2000:]
     for flag in ('--gpus', '--steps', '--warmup', '--pages', '--no-api', '--api-batches', '--no-ragged', '--two-steps-one-decode', '--no-strong-share', '--no-traffic',
-                 '--no-cpu-baseline', '--no-vit-extra', '--no-pipeline', '--scaling', '--total-pages'):
+                 '--no-cpu-baseline', '--no-vit-extra', '--no-pipeline', '--scaling', '--total-pages', '--dump-outputs'):
         assert flag in out, flag
     sys.path.insert(0, ROOT)
     import bench
@@ -24,6 +24,46 @@ def test_bench_help_lists_every_block_switch_and_benchlib_imports():
     assert measure.PEAK_BF16_TFLOPS == 2500.0 and measure.PEAK_HBM_GBS == 8000.0
     for fn in ('strong_share_block', 'strong_scaling_block', 'single_gpu_extras', 'ragged_balanced', 'measure_balanced'):
         assert callable(getattr(extras, fn))
+
+
+def test_dump_outputs_writes_ids_and_fixed_samples(tmp_path):
+    """bench.dump_outputs (--dump-outputs): the ids whole, a small tensor whole, a large one as the same seeded sample on every call; float32 only."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = [[5, 92542, 7], [1, 2, 3]]
+    small = torch.arange(12, dtype=torch.bfloat16).reshape(3, 4)
+    big = torch.randn(bench.DUMP_SAMPLE + 1000, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    names = bench.dump_outputs(str(tmp_path / 'a'), ids, {'small': small, 'big': big, 'absent': None}, suffix='_rank1')
+    assert names == ['big', 'small', 'token_ids']
+    assert sorted(os.listdir(tmp_path / 'a')) == ['big_rank1.npy', 'small_rank1.npy', 'token_ids_rank1.npy']
+    got = {n: np.load(tmp_path / 'a' / f'{n}_rank1.npy') for n in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got['token_ids'], np.array(ids, dtype=np.float32)) and np.array_equal(got['small'], small.float().numpy().reshape(-1))
+    assert got['big'].shape == (bench.DUMP_SAMPLE,) and np.isin(got['big'], big.float().numpy()).all()
+    bench.dump_outputs(str(tmp_path / 'b'), ids, {'big': big.clone()})
+    assert np.array_equal(np.load(tmp_path / 'b' / 'big.npy'), got['big'])
+
+
+def test_dump_outputs_of_all_ranks_stay_within_the_cap(tmp_path):
+    """Every rank writes its own files: at 8 ranks of the default step's shapes (64 pages x 128 ids, two tensors far larger than a sample)
+    all files together stay within bench.DUMP_BYTES, each rank's samples are as large as its share allows, and the positions are fixed."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = [[p] * 128 for p in range(64)]
+    big = torch.randn(3 * bench.DUMP_SAMPLE, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    world = 8
+    for r in range(world):
+        bench.dump_outputs(str(tmp_path / 'all'), ids, {'a': big, 'b': big[1:]}, suffix=f'_rank{r}', world=world)
+    files = os.listdir(tmp_path / 'all')
+    assert len(files) == 3 * world
+    assert sum(os.path.getsize(tmp_path / 'all' / f) for f in files) <= bench.DUMP_BYTES
+    a0 = np.load(tmp_path / 'all' / 'a_rank0.npy')
+    assert 4 * 2 * a0.size > bench.DUMP_BYTES // world - 4 * bench.NPY_HEADER - 64 * 128 * 4 - 8 and a0.size < bench.DUMP_SAMPLE
+    assert np.array_equal(a0, np.load(tmp_path / 'all' / f'a_rank{world - 1}.npy'))
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'none'), [[0] * (1 << 20)] * 64, {'a': big}, world=world)
 
 
 def test_api_level_tokenizer_dir_has_the_references_structure(tmp_path):

@@ -13,7 +13,8 @@ MaxLengthCriteria:
   B10  the B prompt with repetition_penalty 1.0 and max_new_tokens 40: loops, stops on the length.
 The reference's top-2 margin is >= 1.8 at every step, so there is NO near-tie escape here: the HIP path, through the drop-in
 `InternVLChatModel.generate_ocr`, must return exactly the reference's ids -- same length, same EOS.  The raw logits of every
-step are compared as well (top-16 of the reference).  Results: profiles/round4/peaked_streams.json (round 3's run: profiles/round3/).
+step are compared as well (top-16 of the reference).  Results: test_output/peaked_streams.json (ignored by git: a test run leaves the tree
+as it was); committed records: profiles/round4/peaked_streams.json (round 3's run: profiles/round3/).
 """
 import json
 import os
@@ -33,13 +34,13 @@ RESULTS = {}
 
 
 def _dump():
-    for d in (os.path.join(ROOT, 'profiles', 'round4'), os.path.join(ROOT, 'gpurun_out')):
-        try:
-            os.makedirs(d, exist_ok=True)
-            with open(os.path.join(d, 'peaked_streams.json'), 'w') as f:
-                json.dump(RESULTS, f, indent=1)
-        except OSError:
-            pass
+    d = os.path.join(ROOT, 'test_output')
+    try:
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, 'peaked_streams.json'), 'w') as f:
+            json.dump(RESULTS, f, indent=1)
+    except OSError:
+        pass
 
 
 @pytest.fixture(scope='module')

@@ -19,6 +19,16 @@ from oracle import vision, calli_align, internlm2, generate
 GOLD = os.path.join(os.path.dirname(__file__), 'golden', 'reference_vectors.npz')
 
 
+@pytest.fixture(scope='module', autouse=True)
+def native_cpu_kernels():
+    """The vectors were made with oneDNN off (scripts/make_golden.py): PyTorch's own CPU kernels give the same bits on any AVX-512 host and
+    thread count, oneDNN's differ between ISAs (AMX or not) and thread counts."""
+    before = torch.backends.mkldnn.enabled
+    torch.backends.mkldnn.enabled = False
+    yield
+    torch.backends.mkldnn.enabled = before
+
+
 @pytest.fixture(scope='module')
 def gold():
     return np.load(GOLD)

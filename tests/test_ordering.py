@@ -15,6 +15,16 @@ GOLD = json.load(open(os.path.join(os.path.dirname(__file__), 'golden', 'orderin
 PAGES = [k for k in GOLD if not k.startswith('_')]
 
 
+@pytest.fixture(scope='module', autouse=True)
+def native_cpu_kernels():
+    """The vectors were made with oneDNN off (scripts/make_golden_ordering.py): PyTorch's own CPU kernels give the same bits on any AVX-512
+    host and thread count, oneDNN's differ between ISAs (AMX or not) and thread counts."""
+    before = torch.backends.mkldnn.enabled
+    torch.backends.mkldnn.enabled = False
+    yield
+    torch.backends.mkldnn.enabled = before
+
+
 @pytest.fixture(scope='module')
 def scorer():
     return oracle_of.CpuScorer(synthetic.make_orderformer_state_dict(seed=GOLD['_model']['state_dict_seed']))

@@ -1,12 +1,15 @@
 """Self-contained InternLM2 tokenizer pinned against the sentencepiece library itself:
   * a BPE model trained inside the test with the same spec as the reference's (identity normaliser, no dummy prefix,
     byte fallback, user-defined symbols): pieces, ids and decoded text must equal sentencepiece's on random text;
-  * the reference's own tokenizer.model when it is reachable (env CALLIREADER_TOKENIZER_DIR, or the build container's
-    /root/reference): same comparison after patching the one NUL-containing piece that newer sentencepiece rejects,
-    plus the golden ids in tests/golden/tokenizer_vectors.json (produced with that model)."""
+  * the reference's own tokenizer model, rebuilt from tests/golden/internlm2_tokenizer/ (its 92 544 ids, its specs, and the pieces
+    that can take part in encoding the texts below): same comparison after patching the one NUL-containing piece that newer
+    sentencepiece rejects, plus the golden ids in tests/golden/tokenizer_vectors.json (produced with the whole model)."""
+import base64
+import hashlib
 import json
 import os
 import random
+import shutil
 
 import pytest
 import torch
@@ -15,6 +18,7 @@ from callireader_amd.tokenization_internlm2 import SentencePieceBPE, InternLM2To
 
 spm = pytest.importorskip('sentencepiece')
 GOLD = os.path.join(os.path.dirname(__file__), 'golden', 'tokenizer_vectors.json')
+REAL_DIR = os.path.join(os.path.dirname(__file__), 'golden', 'internlm2_tokenizer')     # pieces.json + the three JSON files of the reference's checkpoint
 ALPHABETS = ['abcdefghijklmnopqrstuvwxyz', 'ABCDEFGH', '0123456789', ' ', ' ', '，。？！：', '书法作品内容是什么君不见黄河之水天上来奔流到海不复回', '\n\t', 'éüñ', '😀']
 
 
@@ -53,21 +57,65 @@ def test_bpe_equals_sentencepiece_on_trained_model(trained):
         assert mine.decode(ids) == sp.decode(ids), t
 
 
-def _reference_dir():
-    for d in (os.environ.get('CALLIREADER_TOKENIZER_DIR'), '/root/reference/InternVL'):
-        if d and os.path.exists(os.path.join(d, 'tokenizer.model')):
-            return d
-    return None
+def real_model_texts():
+    """The texts test_real_model_equals_sentencepiece encodes with the real model."""
+    rng = random.Random(2)
+    texts = ['这幅书法作品内容是什么？', '君不见，黄河之水天上来，奔流到海不复回。', 'Hello world 123', '输出图片中所有文字:', ' x  y ', '\n']
+    return texts + [rand_text(rng, rng.randint(1, 60)) for _ in range(200)]
+
+
+def chat_query():
+    """The chat prompt test_real_model_chat_prompt_and_golden tokenizes, and the template's system message."""
+    from callireader_amd.conversation import get_conv_template
+    t = get_conv_template('internlm2-chat')
+    t.append_message(t.roles[0], '<image>\n这幅书法作品内容是什么？' + '[UNUSED_TOKEN_140]' * 6)
+    t.append_message(t.roles[1], None)
+    return t.get_prompt().replace('<image>', '<img>' + '<IMG_CONTEXT>' * 4 + '</img>', 1), t.system_message
+
+
+def fixture_texts():
+    """Every text the real-model tests encode; tests/golden/internlm2_tokenizer/pieces.json keeps the pieces that can take part in encoding
+    them, and records the sha256 of this list: a text added here needs scripts/make_golden_tokenizer_fixture.py run again."""
+    query, sys_msg = chat_query()
+    gold = json.load(open(GOLD, encoding='utf-8'))
+    return real_model_texts() + [query, 'system\n' + sys_msg, '君不见，黄河之水天上来'] + [c['text'] for c in gold['cases']]
+
+
+def texts_sha256(texts):
+    return hashlib.sha256(json.dumps(texts, ensure_ascii=False).encode('utf-8')).hexdigest()
+
+
+def placeholder_piece(i):
+    """The piece the rebuilt model holds at an id whose real piece is not stored: one private-use character per id, which no text
+    here contains, so it takes part in no encoding."""
+    return chr(0xF0000 + i) if i < 0xFFFE else chr(0x100000 + i - 0xFFFE)
+
+
+def rebuild_real_model(src):
+    """src/pieces.json (scripts/make_golden_tokenizer_fixture.py): the reference's tokenizer.model without its pieces, the number of
+    pieces, and the pieces kept -- every one that is a substring of a text these tests encode (sentencepiece BPE only ever merges into
+    substrings of its input), every special and byte piece, and every id the golden vectors decode.  The other ids get
+    placeholder_piece; the ids, the specs and every encoding and decoding done here are the whole model's."""
+    from sentencepiece import sentencepiece_model_pb2 as pb
+    f = json.load(open(os.path.join(src, 'pieces.json'), encoding='utf-8'))
+    assert f['texts_sha256'] == texts_sha256(fixture_texts()), \
+        'the texts of the real-model tests changed: run scripts/make_golden_tokenizer_fixture.py <reference>/InternVL'
+    m = pb.ModelProto()
+    m.ParseFromString(base64.b64decode(f['model_without_pieces']))
+    kept = {i: (piece, score, typ) for i, piece, score, typ in f['pieces']}
+    for i in range(f['n_pieces']):
+        piece, score, typ = kept.get(i, (placeholder_piece(i), 0.0, pb.ModelProto.SentencePiece.NORMAL))
+        m.pieces.add(piece=piece, score=score, type=typ)
+    return m
 
 
 @pytest.fixture(scope='module')
 def real(tmp_path_factory):
-    d = _reference_dir()
-    if d is None:
-        pytest.skip('reference tokenizer.model not reachable')
-    from sentencepiece import sentencepiece_model_pb2 as pb
-    m = pb.ModelProto()
-    m.ParseFromString(open(os.path.join(d, 'tokenizer.model'), 'rb').read())
+    d = str(tmp_path_factory.mktemp('internlm2'))
+    m = rebuild_real_model(REAL_DIR)
+    open(os.path.join(d, 'tokenizer.model'), 'wb').write(m.SerializeToString())
+    for name in ('tokenizer_config.json', 'added_tokens.json', 'special_tokens_map.json'):
+        shutil.copy(os.path.join(REAL_DIR, name), d)
     for p in m.pieces:
         if '\x00' in p.piece:
             p.piece = '<NUL_PLACEHOLDER_PIECE>'
@@ -81,27 +129,19 @@ def test_real_model_equals_sentencepiece(real):
     d, sp, tok = real
     assert tok.vocab_size == 92544 and tok.convert_tokens_to_ids('[UNUSED_TOKEN_140]') == 92537
     assert tok.convert_tokens_to_ids('<|im_end|>') == 92542 and tok.convert_tokens_to_ids('<IMG_CONTEXT>') == 92546
-    rng = random.Random(2)
-    texts = ['这幅书法作品内容是什么？', '君不见，黄河之水天上来，奔流到海不复回。', 'Hello world 123', '输出图片中所有文字:', ' x  y ', '\n']
-    texts += [rand_text(rng, rng.randint(1, 60)) for _ in range(200)]
-    for t in texts:
+    for t in real_model_texts():
         assert tok.sp_model.encode(t) == sp.encode(t), t
         assert tok.sp_model.decode(sp.encode(t)) == sp.decode(sp.encode(t)), t
 
 
 def test_real_model_chat_prompt_and_golden(real):
     d, sp, tok = real
-    from callireader_amd.conversation import get_conv_template
-    t = get_conv_template('internlm2-chat')
-    t.append_message(t.roles[0], '<image>\n这幅书法作品内容是什么？' + '[UNUSED_TOKEN_140]' * 6)
-    t.append_message(t.roles[1], None)
-    query = t.get_prompt().replace('<image>', '<img>' + '<IMG_CONTEXT>' * 4 + '</img>', 1)
+    query, sys_msg = chat_query()
     enc = tok(query, return_tensors='pt')
     ids = enc['input_ids'][0].tolist()
     assert enc['attention_mask'].shape == enc['input_ids'].shape and ids[0] == 1              # BOS (add_bos_token)
     assert ids.count(92546) == 4 and ids.count(92537) == 6 and ids.count(92543) == 3 and ids.count(92542) == 2
     # every stretch between added tokens is what sentencepiece gives for that stretch
-    sys_msg = t.system_message
     assert ids[1] == 92543 and ids[2:2 + len(sp.encode('system\n' + sys_msg))] == sp.encode('system\n' + sys_msg)
     gold = json.load(open(GOLD, encoding='utf-8'))
     for item in gold['cases']:
