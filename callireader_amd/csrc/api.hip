@@ -162,6 +162,11 @@ int cr_destroy(cr_ctx* c) {
     if (!c->borrowed) for (auto& kv : c->w) if (kv.second.ptr) hipFree(kv.second.ptr);
     if (c->ws) hipFree(c->ws);
     if (c->scratch) hipFree(c->scratch);
+    if (c->d_seqs) hipFree(c->d_seqs);
+    for (auto& h : c->seq_stage) {
+        if (h.host) hipHostFree(h.host);
+        if (h.copied) hipEventDestroy(h.copied);
+    }
     if (c->side) hipStreamDestroy(c->side);
     for (auto& r : c->prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto e : c->prof_pool) hipEventDestroy(e);

@@ -49,6 +49,14 @@ struct cr_ctx {
     std::shared_ptr<std::atomic<uint64_t>> owner_cell;      // borrowed: the owning context's cell, and its value when the map was copied: a reload /
     uint64_t owner_gen = 0;             //     re-finalize / fp8 toggle / destroy of the owner frees or replaces tensors this copy still points at -> the
                                         //     stage entry points refuse to run (ctx_share_ok)
+    // the seqs[] of the last prefill / decode call (llm.hip stage_seqs); per context, so that two contexts sharing weights can work on one KV cache
+    int32_t* d_seqs = nullptr;
+    int d_seqs_cap = 0;
+    std::vector<int32_t> seqs_on_device;   // what d_seqs holds
+    struct SeqStage { int32_t* host = nullptr; int cap = 0; hipEvent_t copied = nullptr; };   // pinned source of one staging copy, and its completion
+    static constexpr int SEQ_STAGES = 8;
+    SeqStage seq_stage[SEQ_STAGES];
+    int seq_stage_next = 0;
     // small persistent device scratch (counters, argmax partials)
     char* scratch = nullptr;
     size_t scratch_bytes = 0;

@@ -28,16 +28,17 @@ struct cr_kv {
     int32_t* d_len;      // [n_seqs] tokens cached
     int32_t* d_ngen;     // [n_seqs] ids generated
     int64_t* d_gen;      // [n_seqs][gen_cap]
-    int32_t* d_seqs;     // [n_seqs] staging for the seqs[] of one decode call
-    std::vector<int32_t> seqs_on_device;   // what d_seqs holds (decode skips the host-to-device copy of an unchanged list: a pageable copy
-                                           // makes the host wait for the stream, which stops it from feeding a second stream)
+    // stop tracking (cr_kv_set_stop / cr_kv_poll_finished), one block of 1 + 4 n_seqs int32:
+    //   [0] finished count (monotonic), [1, 1 + n) ring of finished sequence indices (entry k at 1 + k % n),
+    //   [1 + n, 1 + 2n) stop count per sequence (0 = not stopped), [1 + 2n, 1 + 3n) EOS id (< 0: none), [1 + 3n, 1 + 4n) budget (<= 0: none)
+    int32_t* d_stop;
     std::vector<int> len, ngen;
     // batched decode as a hipGraph (CR_DECODE_GRAPH=1): a step is ~290 short launches whose parameters only change with
     // the row count and the number of attention splits (positions, ids and cache lengths live in device memory), so the
     // launch sequence is captured once per (rows, splits, penalty) and replayed.  OFF by default: on ROCm 7.2 / MI355X the
     // replay measured 0.3 % slower than plain launches at 64 pages per step (6.86 vs 6.88 pages/s) and 5 % slower for a
     // single page (0.711 vs 0.678 s) -- the ~3 us gaps between dependent kernels are not launch overhead the graph removes
-    struct DecodeGraph { int n, nsplit; float penalty; char* ws; uint64_t weight_gen; hipGraphExec_t exec; int warm; };
+    struct DecodeGraph { int n, nsplit; float penalty; char* ws; const int32_t* seqs; uint64_t weight_gen; hipGraphExec_t exec; int warm; };
     std::vector<DecodeGraph> graphs;
 };
 
@@ -174,11 +175,24 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
     *(bf16x8*)(dst + c * 8) = y;
 }
 
-// RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) + argmax (first max wins) + append the id.
+// Stop criteria of cr_kv_set_stop, checked against the id a sequence has just appended (its `count`-th): the first time it is the EOS id or
+// the count reaches the budget, the count is recorded and the sequence index pushed onto the finished ring.  One thread per sequence per launch.
+__device__ inline void stop_check(int32_t* __restrict__ stop, int n_seqs, int seq, int64_t id, int count) {
+    int32_t* at = stop + 1 + n_seqs;
+    const int eos = stop[1 + 2 * n_seqs + seq], budget = stop[1 + 3 * n_seqs + seq];
+    if (at[seq] == 0 && ((eos >= 0 && id == eos) || (budget > 0 && count >= budget))) {
+        at[seq] = count;
+        const int k = atomicAdd(stop, 1);
+        stop[1 + k % n_seqs] = seq;
+    }
+}
+
+// RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) + argmax (first max wins) + append the id (+ its stop check).
 // One workgroup of 1024 per row.
 __global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty,
                                                     int seq0, const int32_t* __restrict__ seqs, int64_t* __restrict__ gen,
-                                                    int32_t* __restrict__ ngen, int32_t* __restrict__ lens, int gen_cap, int len_add) {
+                                                    int32_t* __restrict__ ngen, int32_t* __restrict__ lens, int gen_cap, int len_add,
+                                                    int32_t* __restrict__ stop, int n_seqs) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -216,9 +230,45 @@ __global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, 
         __syncthreads();
     }
     if (tid == 0) {
-        if (ng < gen_cap) { g[ng] = bi[0]; ngen[seq] = ng + 1; }
+        if (ng < gen_cap) {
+            g[ng] = bi[0]; ngen[seq] = ng + 1;
+            stop_check(stop, n_seqs, seq, bi[0], ng + 1);
+        }
         lens[seq] += len_add;
     }
+}
+
+// cr_kv_set_stop: install the criteria of `seq` and apply them to the ids it has generated already (a call after the prefill sees its first id).
+// A sequence that has stopped keeps its first stop (pushed once); only the criteria are replaced.  One workgroup.
+__global__ __launch_bounds__(256) void set_stop_kernel(int32_t* __restrict__ stop, int n_seqs, int seq, int eos, int budget,
+                                                       const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen, int gen_cap) {
+    __shared__ int first;
+    if (threadIdx.x == 0) first = 0x7fffffff;
+    __syncthreads();
+    const int ng = ngen[seq];
+    if (eos >= 0)
+        for (int i = threadIdx.x; i < ng; i += 256)
+            if (gen[(int64_t)seq * gen_cap + i] == eos) atomicMin(&first, i + 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stop[1 + 2 * n_seqs + seq] = eos;
+        stop[1 + 3 * n_seqs + seq] = budget;
+        if (stop[1 + n_seqs + seq] == 0) {
+            int at = first <= ng ? first : 0;
+            if (budget > 0 && ng >= budget && (at == 0 || at > budget)) at = budget;
+            if (at) {
+                stop[1 + n_seqs + seq] = at;
+                const int k = atomicAdd(stop, 1);
+                stop[1 + k % n_seqs] = seq;
+            }
+        }
+    }
+}
+
+// prefill: the cached length of every page's sequence = its first position + its rows (d_seg: 4 per page, see cr_llm_prefill_batch).
+// Only the prefilled sequences are written: another context may be decoding other sequences of the same cache meanwhile.
+__global__ __launch_bounds__(256) void set_len_kernel(const int32_t* __restrict__ seg, int n, int32_t* __restrict__ lens) {
+    for (int i = threadIdx.x; i < n; i += 256) lens[seg[4 * i + 3]] = seg[4 * i + 2] + seg[4 * i + 1];
 }
 
 // w13 rows: [16q + e] = w1[8q + e], [16q + 8 + e] = w3[8q + e]   (pairs gate/up for the SwiGLU epilogue)
@@ -535,6 +585,37 @@ size_t layers_ws(cr_ctx* c, int M, int nsplit = 0, int n_pages = 0) {
 
 }  // namespace
 
+// The seqs[] of a prefill / decode call in the context's device staging (per context, not per cache: two contexts that share weights may work
+// on different sequences of one cache at once).  `always` = false skips the host-to-device copy of an unchanged list.  The copy goes through one of
+// a few pinned host buffers (a pageable copy makes the host wait for the stream, which would stall a decode thread whose rows change every few
+// steps); a buffer is reused once the copy that last read it has run.
+static int stage_seqs(cr_ctx* c, const int32_t* seqs, int n, hipStream_t st, bool always) {
+    if (n > c->d_seqs_cap) {
+        CR_HIP(hipDeviceSynchronize());                 // the old staging may still be read by enqueued work
+        if (c->d_seqs) CR_HIP(hipFree(c->d_seqs));
+        c->d_seqs = nullptr; c->d_seqs_cap = 0; c->seqs_on_device.clear();
+        const int cap = n > 256 ? n : 256;
+        if (hipMalloc((void**)&c->d_seqs, (size_t)cap * 4) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "sequence staging of %d entries", cap);
+        c->d_seqs_cap = cap;
+    }
+    if (always || (int)c->seqs_on_device.size() != n || memcmp(c->seqs_on_device.data(), seqs, (size_t)n * 4) != 0) {
+        cr_ctx::SeqStage& h = c->seq_stage[c->seq_stage_next++ % cr_ctx::SEQ_STAGES];
+        if (h.copied) CR_HIP(hipEventSynchronize(h.copied));
+        else CR_HIP(hipEventCreateWithFlags(&h.copied, hipEventDisableTiming));
+        if (h.cap < n) {
+            if (h.host) CR_HIP(hipHostFree(h.host));
+            h.host = nullptr; h.cap = 0;
+            CR_HIP(hipHostMalloc((void**)&h.host, (size_t)c->d_seqs_cap * 4, hipHostMallocDefault));
+            h.cap = c->d_seqs_cap;
+        }
+        memcpy(h.host, seqs, (size_t)n * 4);
+        CR_HIP(hipMemcpyAsync(c->d_seqs, h.host, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        CR_HIP(hipEventRecord(h.copied, st));
+        c->seqs_on_device.assign(seqs, seqs + n);
+    }
+    return CR_OK;
+}
+
 int build_fp8_copy(cr_ctx* c, const std::string& nm, int k_multiple, hipStream_t st) {
     const DevTensor* src = WT(c, nm);
     if (!src) return CR_ERR_STATE;
@@ -774,13 +855,16 @@ int cr_kv_alloc(cr_ctx* c, int n_seqs, int max_tokens, cr_kv** out) {
     const size_t bytes = (size_t)kv->layers * n_seqs * NKV * max_tokens * HD * 2;
     if (hipMalloc((void**)&kv->k, bytes) != hipSuccess || hipMalloc((void**)&kv->v, bytes) != hipSuccess ||
         hipMalloc((void**)&kv->d_len, n_seqs * 4) != hipSuccess || hipMalloc((void**)&kv->d_ngen, n_seqs * 4) != hipSuccess ||
-        hipMalloc((void**)&kv->d_seqs, n_seqs * 4) != hipSuccess ||
+        hipMalloc((void**)&kv->d_stop, ((size_t)4 * n_seqs + 1) * 4) != hipSuccess ||
         hipMalloc((void**)&kv->d_gen, (size_t)n_seqs * kv->gen_cap * 8) != hipSuccess) {
         cr_kv_free(kv);
         return cr_fail(CR_ERR_NOMEM, "cr_kv_alloc: %zu bytes per K/V", bytes);
     }
     CR_HIP(hipMemset(kv->d_len, 0, n_seqs * 4));
     CR_HIP(hipMemset(kv->d_ngen, 0, n_seqs * 4));
+    CR_HIP(hipMemset(kv->d_stop, 0, ((size_t)2 * n_seqs + 1) * 4));
+    CR_HIP(hipMemset(kv->d_stop + 1 + 2 * n_seqs, 0xff, (size_t)n_seqs * 4));       // no EOS id
+    CR_HIP(hipMemset(kv->d_stop + 1 + 3 * n_seqs, 0, (size_t)n_seqs * 4));          // no budget
     kv->len.assign(n_seqs, 0); kv->ngen.assign(n_seqs, 0);
     *out = kv;
     return CR_OK;
@@ -793,7 +877,7 @@ int cr_kv_free(cr_kv* kv) {
     if (kv->v) hipFree(kv->v);
     if (kv->d_len) hipFree(kv->d_len);
     if (kv->d_ngen) hipFree(kv->d_ngen);
-    if (kv->d_seqs) hipFree(kv->d_seqs);
+    if (kv->d_stop) hipFree(kv->d_stop);
     if (kv->d_gen) hipFree(kv->d_gen);
     for (auto& e : kv->graphs) if (e.exec) hipGraphExecDestroy(e.exec);
     delete kv;
@@ -809,7 +893,34 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
     const int s0 = seq < 0 ? 0 : seq, n = seq < 0 ? kv->n_seqs : 1;
     CR_HIP(hipMemsetAsync(kv->d_len + s0, 0, (size_t)n * 4, st));
     CR_HIP(hipMemsetAsync(kv->d_ngen + s0, 0, (size_t)n * 4, st));
+    const int N = kv->n_seqs;
+    CR_HIP(hipMemsetAsync(kv->d_stop + 1 + N + s0, 0, (size_t)n * 4, st));              // not stopped
+    CR_HIP(hipMemsetAsync(kv->d_stop + 1 + 2 * N + s0, 0xff, (size_t)n * 4, st));       // no EOS id
+    CR_HIP(hipMemsetAsync(kv->d_stop + 1 + 3 * N + s0, 0, (size_t)n * 4, st));          // no budget
+    if (seq < 0) CR_HIP(hipMemsetAsync(kv->d_stop, 0, 4, st));                          // every sequence: the finished ring starts over
     for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; }
+    return CR_OK;
+}
+
+int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream) {
+    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: bad sequence");
+    if (max_new > kv->gen_cap) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: budget %d exceeds the generated-id capacity (%d)", max_new, kv->gen_cap);
+    if (max_new > kv->max_tokens - kv->len[seq])
+        return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: budget %d exceeds what the cache leaves after %d tokens (%d)", max_new, kv->len[seq], kv->max_tokens);
+    if (eos_id >= kv->ctx->d.vocab) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: EOS id %d outside the vocabulary", eos_id);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipLaunchKernelGGL(set_stop_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kv->d_stop, kv->n_seqs, seq, eos_id < 0 ? -1 : eos_id,
+                       max_new > 0 ? max_new : 0, kv->d_gen, kv->d_ngen, kv->gen_cap);
+    CR_HIP(hipGetLastError());
+    return CR_OK;
+}
+
+int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream) {
+    if (!kv || !host_out) return cr_fail(CR_ERR_ARG, "cr_kv_poll_finished: bad argument");
+    const int need = 1 + 2 * kv->n_seqs;
+    if (max < need) return cr_fail(CR_ERR_ARG, "cr_kv_poll_finished: %d int32 of room, %d needed", max, need);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    CR_HIP(hipMemcpyAsync(host_out, kv->d_stop, (size_t)need * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     return CR_OK;
 }
 
@@ -874,8 +985,7 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         }
         CR_HIP(hipMemcpyAsync(d_row_seq, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
     }
-    CR_HIP(hipMemcpyAsync(kv->d_seqs, seqs, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    kv->seqs_on_device.assign(seqs, seqs + n);
+    CR_TRY(stage_seqs(c, seqs, n, st, true));
     CR_HIP(hipMemcpyAsync(x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
     CR_TRY(run_layers(c, kv, x, M, false, segs, d_row_seq, d_row_pos, nullptr, 0, st, d_seg, d_last, d_seg_last));
     const bf16 *nw = W(c, "language_model.model.norm.weight"), *ow = W(c, "language_model.output.weight");
@@ -885,14 +995,14 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         CR_TRY(rms(x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, D, hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
     CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st));
     if (last_logits) CR_HIP(hipMemcpyAsync(last_logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, kv->d_seqs, kv->d_gen, kv->d_ngen,
-                       kv->d_len, kv->gen_cap, 0);
+    hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, c->d_seqs, kv->d_gen, kv->d_ngen,
+                       kv->d_len, kv->gen_cap, 0, kv->d_stop, kv->n_seqs);
+    hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, d_seg, n, kv->d_len);
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
         kv->len[sg.seq] += sg.S;
         if (kv->ngen[sg.seq] < kv->gen_cap) kv->ngen[sg.seq] += 1;
     }
-    CR_HIP(hipMemcpyAsync(kv->d_len, kv->len.data(), (size_t)kv->n_seqs * 4, hipMemcpyHostToDevice, st));
     return CR_OK;
 }
 
@@ -931,16 +1041,14 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
     bf16* hl = x + (size_t)n * D;
     float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
-    if ((int)kv->seqs_on_device.size() != n || memcmp(kv->seqs_on_device.data(), seqs, (size_t)n * 4) != 0) {      // prefill uses d_seqs too
-        CR_HIP(hipMemcpyAsync(kv->d_seqs, seqs, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        kv->seqs_on_device.assign(seqs, seqs + n);
-    }
+    CR_TRY(stage_seqs(c, seqs, n, st, false));
+    const int32_t* d_seqs = c->d_seqs;
     const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
     const bf16 *nw = W(c, "language_model.model.norm.weight"), *ow = W(c, "language_model.output.weight");
     if (!table || !nw || !ow) return CR_ERR_STATE;
     auto enqueue_step = [&](hipStream_t st) -> int {
-        hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(256), 0, st, table, force_tokens, kv->d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, x);
-        CR_TRY(run_layers(c, kv, x, n, true, {}, nullptr, nullptr, kv->d_seqs, nsplit, st));
+        hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(256), 0, st, table, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, x);
+        CR_TRY(run_layers(c, kv, x, n, true, {}, nullptr, nullptr, d_seqs, nsplit, st));
         const DevTensor *q_out = opt(c, "fp8.language_model.output.weight"), *s_out = opt(c, "fp8s.language_model.output.weight");
         const int ff_ = (int)WT(c, "derived.w13.0")->shape[0] / 2;
         if (c->fused_decode && !c->fp8_decode && !c->no_sliced_decode && decode_fused_supported(n, ff_)) {
@@ -954,8 +1062,8 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         else CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st, false, opt(c, "declayout.language_model.output.weight")));
         }
         if (logits) CR_HIP(hipMemcpyAsync(logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, kv->d_seqs, kv->d_gen, kv->d_ngen,
-                           kv->d_len, kv->gen_cap, 1);
+        hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
+                           kv->d_len, kv->gen_cap, 1, kv->d_stop, kv->n_seqs);
         return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
     };
     // graph path: the plain generation loop (no forced ids, no logits copy), nothing recording events on these launches
@@ -970,13 +1078,13 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     if (graphable && c->decode_graph && gs) {
         cr_kv::DecodeGraph* g = nullptr;
         for (auto& e : kv->graphs)
-            if (e.n == n && e.nsplit == nsplit && e.penalty == penalty && e.ws == c->ws && e.weight_gen == c->weight_gen) { g = &e; break; }
+            if (e.n == n && e.nsplit == nsplit && e.penalty == penalty && e.ws == c->ws && e.seqs == d_seqs && e.weight_gen == c->weight_gen) { g = &e; break; }
         if (!g) {
             if (kv->graphs.size() >= 24) {                       // stale keys (grown workspace, reloaded weights, old split counts)
                 for (auto& e : kv->graphs) if (e.exec) hipGraphExecDestroy(e.exec);
                 kv->graphs.clear();
             }
-            kv->graphs.push_back({n, nsplit, penalty, c->ws, c->weight_gen, nullptr, 0});
+            kv->graphs.push_back({n, nsplit, penalty, c->ws, d_seqs, c->weight_gen, nullptr, 0});
             g = &kv->graphs.back();
         }
         if (g->exec) {

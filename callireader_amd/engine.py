@@ -93,6 +93,13 @@ class Engine:
         B.check(B.lib.cr_share_weights(self._h, other._h), 'cr_share_weights')
         self._shared_from = other
 
+    def shared_context(self):
+        """A fresh Engine on this device that uses this engine's finalized weights (share_weights_from): own workspace, own staging, for a second
+        host thread on its own stream.  This engine must outlive it."""
+        other = Engine(self.dims, device=self.device.index, max_pos=self.max_pos)
+        other.share_weights_from(self)
+        return other
+
     def enable_fp8_decode(self, on=True):
         """Batched decode streams e4m3 copies of the LLM's linear weights (one fp32 scale per output row) instead of the
         bf16 ones: half the HBM bytes per step.  Off by default: the reference computes in bf16 (include/callireader_hip.h)."""
@@ -265,6 +272,18 @@ class KVCache:
         out = torch.empty(8, 128, device=self.eng.device, dtype=torch.bfloat16)
         B.check(B.lib.cr_kv_read(self._h, layer, seq, pos, which, _p(out), _stream()), 'cr_kv_read')
         return out
+
+    def set_stop(self, seq, eos_id=None, max_new=0):
+        """cr_kv_set_stop on the current stream: from now on the greedy pick records the sequence's stop (its first `eos_id`, or its
+        `max_new`-th generated id) and pushes it once onto the finished queue read by poll_finished."""
+        B.check(B.lib.cr_kv_set_stop(self._h, seq, -1 if eos_id is None else int(eos_id), int(max_new), _stream()), 'cr_kv_set_stop')
+
+    def poll_finished(self, out):
+        """cr_kv_poll_finished: enqueue on the current stream an asynchronous copy of the finished queue into `out`, a pinned int32 CPU tensor of
+        at least 1 + 2 n_seqs entries ([0] count pushed, [1 + k % n_seqs] the k-th sequence pushed, [1 + n_seqs + s] stop count of s).  Read it
+        after an event recorded behind this call has completed."""
+        assert out.dtype == torch.int32 and not out.is_cuda and out.is_contiguous()
+        B.check(B.lib.cr_kv_poll_finished(self._h, C.c_void_p(out.data_ptr()), out.numel(), _stream()), 'cr_kv_poll_finished')
 
     def generated(self, seq, max_tokens=4096):
         buf = (C.c_int64 * max_tokens)()

@@ -77,12 +77,14 @@ DEFAULT_BATCH_PAGES = 64       # pages per decode batch in folder mode: the most
 
 
 def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, prompt, save_name, use_p, hard_vq, drop_zero, repetition_penalty,
-               verbose, batch_pages=DEFAULT_BATCH_PAGES):
+               verbose, batch_pages=DEFAULT_BATCH_PAGES, continuous=False):
     """inference.py:47-62: every image of the folder -> results JSON [{imagePath, prompt, response}], an image that fails -> "ERROR!" for that entry only.
     The reference calls chat_ocr image after image; here the images go through `chat_ocr_stream` in batches of `batch_pages` (two batches in flight, files
     decoded ahead on threads): each response is the one the image's own chat_ocr call gives, pages/s is what changes (batch_pages <= 1: the serial loop).
     Failures stay per image: a page that cannot be read, has no boxes JSON / no box, or whose prompt is too long is reported alone; if a batch fails as a whole
-    its pages are run one by one, each in its own try/except, as the reference does."""
+    its pages are run one by one, each in its own try/except, as the reference does.
+    continuous=True: the images go through `chat_ocr_continuous` instead (`batch_pages` decode rows, a row refilled as soon as its page stops);
+    the same responses, JSON and console lines."""
     paths = get_image_paths(folder_path)
     responses = {}
 
@@ -100,7 +102,28 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
         print(f'User: {prompt}\nAssistant: {response}')
         responses[pic_path] = response
 
-    if batch_pages <= 1 or not hasattr(model, 'chat_ocr_stream'):
+    if continuous and batch_pages > 1:
+        boxes, ready = {}, []
+        for pic_path in paths:
+            try:
+                boxes[pic_path] = boxes_for(pic_path) if (use_p and detect_model is None) else None
+                ready.append(pic_path)
+            except Exception as e:
+                responses[pic_path] = e
+        try:
+            for i, r in model.chat_ocr_continuous(tokenizer, detect_model, ready, prompt, generation_config,
+                                                  boxes_list=[boxes[p] for p in ready] if (use_p and detect_model is None) else None, use_p=use_p,
+                                                  drop_zero=drop_zero, hard_vq=hard_vq, repetition_penalty=repetition_penalty, slots=batch_pages,
+                                                  errors='return'):
+                responses[ready[i]] = r
+        except Exception as e:
+            left = [p for p in ready if p not in responses]
+            print(f'[folder_rec] continuous batching failed ({e}); its {len(left)} remaining pages run one by one')
+            for pic_path in left:
+                responses[pic_path] = one(pic_path)
+        for pic_path in paths:
+            record(pic_path, responses[pic_path])
+    elif batch_pages <= 1 or not hasattr(model, 'chat_ocr_stream'):
         for pic_path in paths:
             record(pic_path, one(pic_path))
     else:
@@ -154,6 +177,8 @@ def main(argv=None):
     parser.add_argument('--max_new_tokens', type=int, default=1024, help='generation_config.max_new_tokens (inference.py:92-96: 1024)')
     parser.add_argument('--batch_pages', type=int, default=DEFAULT_BATCH_PAGES,
                         help='folder mode: pages per batch through chat_ocr_stream (two batches in flight; same responses as the serial loop, which 1 selects)')
+    parser.add_argument('--continuous', action='store_true',
+                        help='folder mode: continuous batching (chat_ocr_continuous): --batch_pages decode rows, each refilled as soon as its page stops; same responses')
     parser.add_argument('--fp8_decode', action='store_true', help='e4m3 weights for the decode (cr_enable_fp8_decode; off by default: the reference computes in bf16)')
     parser.add_argument('--fp8_mfma', type=int, nargs='?', const=1, default=0, choices=(0, 1, 2),
                         help='e4m3 x e4m3 matrix-core linears (cr_enable_fp8_mfma; off by default; a throughput option, not parity-preserving): 1 = the norm-fed linears of the ViT / projector / prefill, 2 = also ViT fc2 and the prefill\'s wo / w2')
@@ -186,7 +211,8 @@ def main(argv=None):
         print('Multiple images recognition mode')
         os.makedirs('results', exist_ok=True)
         folder_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, os.path.join('results', args.save_name),
-                   args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose, batch_pages=args.batch_pages)
+                   args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose, batch_pages=args.batch_pages,
+                   continuous=args.continuous)
     else:
         raise ValueError('The target should be either a image path or a folder that contain images!')
 

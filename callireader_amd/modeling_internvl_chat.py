@@ -575,6 +575,72 @@ class InternVLChatModel:
                 stats['compute_stream_idle_ms_between_batches'] = idle
                 stats['host'] = {k: v - host0[k] for k, v in dict(feeder.stats, tokenize_s=self._tok_s).items()}       # this call's share of the feeder's counters
 
+    def chat_ocr_continuous(self, tokenizer, detect_model, images, question, generation_config, boxes_list=None, use_p=True, drop_zero=False,
+                            hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
+                            ALIGNED_TOKEN='[UNUSED_TOKEN_140]', slots=64, admit_group=16, visual_group=16, errors='raise', stats=None):
+        """chat_ocr_pages over any number of pages with continuous batching (continuous.ContinuousPipeline): a generator that yields
+        (index into `images`, response) as pages finish -- a page that stops early frees its decode row for the next page at once, instead of
+        waiting for the longest page of a batch.  The visual stage runs `visual_group` pages at a time ahead of admission (the next group's files
+        are decoded on pageio.PageFeeder's threads meanwhile); prefill admits up to `admit_group` pages at once into `slots` decode rows.  Every
+        response is the one the page's own chat_ocr call gives.  errors='return': a page whose own chat_ocr call would raise before generation
+        yields that exception (chat_ocr_pages' semantics; when a group's visual stage fails as a whole, its pages are retried one by one).
+        stats (a dict) receives the pipeline's counters."""
+        from .continuous import ContinuousPipeline
+        images = list(images)
+        feeder = self._feeder()
+        groups = [list(range(i, min(len(images), i + visual_group))) for i in range(0, len(images), visual_group)]
+
+        def pull(g):
+            return feeder.decode([images[i] for i in g]) if g is not None else None
+
+        def embed(idx, decoded):
+            bx = [boxes_list[i] for i in idx] if boxes_list is not None else None
+            tiles = feeder.tiles(decoded, bx, detect_model, use_p, errors)
+            return self._ocr_embeds(tokenizer, None, [images[i] for i in idx], question, generation_config, None, use_p, drop_zero, hard_vq,
+                                    IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, tiles=tiles, errors=errors)
+        template = get_conv_template(self.template)
+        gc = dict(generation_config, eos_token_id=tokenizer.convert_tokens_to_ids(template.sep))      # what _ocr_embeds gives every page
+        max_new, eos = self._gen_args(gc)
+        failed = []
+
+        def items():
+            nxt = pull(groups[0]) if groups else None
+            for gi, idx in enumerate(groups):
+                cur, nxt = nxt, pull(groups[gi + 1]) if gi + 1 < len(groups) else None
+                try:
+                    parts = [(idx, embed(idx, cur))]
+                except Exception:
+                    if errors != 'return' or len(idx) == 1:
+                        raise
+                    parts = []
+                    for i in idx:                       # the group failed as a whole: each page on its own, with its own exception
+                        try:
+                            parts.append(([i], embed([i], pull([i]))))
+                        except Exception as e:
+                            failed.append((i, e))
+                for sub, (embeds, meta) in parts:
+                    failed.extend((sub[k], e) for k, e in meta['failed'].items())
+                    for k, emb in zip(meta['ok'], embeds):
+                        yield sub[k], emb, None
+
+        def response(ids):
+            return tokenizer.batch_decode(torch.tensor([ids]), skip_special_tokens=True)[0].split(template.sep)[0].strip()
+        if not images:
+            return
+        pipe = ContinuousPipeline(self, slots=slots, max_new_tokens=max_new, eos_token_id=eos, repetition_penalty=repetition_penalty,
+                                  admit_group=admit_group)
+        try:
+            for i, ids in pipe.map(items(), errors=errors):
+                while failed:
+                    yield failed.pop(0)
+                yield i, (ids if isinstance(ids, BaseException) else response(ids))
+            while failed:
+                yield failed.pop(0)
+        finally:
+            if stats is not None:
+                stats.update(pipe.stats)
+            pipe.close()
+
     def _feeder(self):
         if getattr(self, '_pagefeeder', None) is None:
             from .pageio import PageFeeder
@@ -794,6 +860,7 @@ class PagePipeline:
         self.jobs, self.results = queue.Queue(), queue.Queue()
         self.in_flight = 0
         self.host_s, self.host_steps = 0.0, 0         # host time the decode thread spent issuing steps (diagnostic)
+        self.row_steps = 0                            # decode rows summed over those steps (diagnostic)
         self.worker = threading.Thread(target=self._decode_loop, daemon=True)
         self.worker.start()
 
@@ -811,7 +878,7 @@ class PagePipeline:
             job = self.jobs.get()
             if job is None:
                 return
-            kv, P, ready = job
+            kv, P, ready, budgets = job
             try:
                 with torch.cuda.stream(self.side):
                     self.side.wait_event(ready)                        # the prefill that filled this cache, on the caller's stream
@@ -827,7 +894,15 @@ class PagePipeline:
                             self.dec.decode(kv, live, penalty=self.penalty)
                         self.host_s += time.perf_counter() - t0
                         self.host_steps += steps
+                        self.row_steps += steps * len(live)
                         n += steps
+                        if budgets is not None:
+                            for i in list(live):
+                                if n >= budgets[i]:
+                                    done[i] = kv.generated(i)[:budgets[i]]
+                                    if self.eos is not None and self.eos in done[i]:
+                                        done[i] = done[i][:done[i].index(self.eos) + 1]
+                                    live.remove(i)
                         if self.eos is not None:
                             for i in list(live):
                                 ids = kv.generated(i)                  # synchronises the side stream only
@@ -844,7 +919,7 @@ class PagePipeline:
                     for i in range(P):
                         ids = done.get(i)
                         if ids is None:
-                            ids = kv.generated(i)[:self.max_new_tokens]
+                            ids = kv.generated(i)[:self.max_new_tokens if budgets is None else budgets[i]]
                             if self.eos is not None and self.eos in ids:
                                 ids = ids[:ids.index(self.eos) + 1]
                         outs.append(ids)
@@ -861,9 +936,10 @@ class PagePipeline:
             raise out
         return out
 
-    def start(self, embeds_list):
+    def start(self, embeds_list, budgets=None):
         """Prefill a batch on the caller's stream and hand it to the decode thread; returns the previous batch's ids (None if there
-        was none), waiting for them if they are not there yet."""
+        was none), waiting for them if they are not there yet.  budgets: optional per-page max_new_tokens (<= the pipeline's): a page
+        leaves the batch at the first EOS check at or past its budget and its ids are cut there, as its own generate_pages call would."""
         P = len(embeds_list)
         # The OTHER slot may be under the worker's decode right now (the previous batch, not collected yet): it is only ever
         # CREATED here, on the first batch (28 GB at 64 pages: not inside a later step), never regrown -- a batch larger than it
@@ -879,7 +955,7 @@ class PagePipeline:
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream())
         prev = self._collect()
-        self.jobs.put((kv, P, ready))
+        self.jobs.put((kv, P, ready, None if budgets is None else [min(int(b), self.max_new_tokens) for b in budgets]))
         self.in_flight += 1
         return prev
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 10  /* 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 11  /* 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -68,7 +68,13 @@ int cr_destroy(cr_ctx* ctx);
  * copying them: a second host thread can then run stages through `dst` on its own stream (own workspace, own profiler) while
  * the first works through `src`.  KV caches (cr_kv_alloc) are plain device state and may be filled through one context and read
  * through the other; ordering between the two streams is the caller's (events).  `src` must outlive `dst`; call again after
- * reloading weights or toggling the fp8 options on `src`. */
+ * reloading weights or toggling the fp8 options on `src`.
+ * One cache, two contexts at once (continuous batching): a context can prefill some sequences of a cache on its stream while a
+ * context that shares its weights decodes OTHER sequences of the same cache on another stream -- prefill and decode touch only the
+ * device state of the sequences they are given (the seqs[] staging is per context), and cr_kv_reset / cr_kv_set_stop only that
+ * of their sequence.  Each sequence is used by one context at a time, and reusing a sequence (cr_kv_reset, then a prefill through
+ * the other context) must be ordered after the last decode step that included it: record an event on the decoding stream after
+ * that step and make the prefilling stream wait for it.  A decode must likewise wait for the prefill of a sequence it adds. */
 int cr_share_weights(cr_ctx* dst, const cr_ctx* src);
 /* One call per checkpoint tensor; `name` is the safetensors key (InternVL/model.safetensors.index.json), or
  *   "calli.mu" / "calli.sigma"  (vocab,1)  — params/gauss_norm_mu_sigma.pth columns (modeling_internvl_chat.py:153-155)
@@ -136,6 +142,22 @@ int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, voi
 /* Copy the ids generated so far for `seq` into host memory (at most `max`); returns the count, or < 0.
  * Synchronises `stream`. */
 int cr_kv_generated(cr_kv* kv, int seq, int64_t* out_host, int max, void* stream);
+/* Stop criteria of `seq`, checked by the greedy pick of every later prefill / decode of it (and, at this call, against the ids it has
+ * generated already): the first time the sequence appends `eos_id` (< 0: no EOS id) or its generated-id count reaches `max_new`
+ * (<= 0: no budget), the count so far (the stop included) is recorded as its stop count and its index is pushed ONCE onto the cache's
+ * finished queue.  Nothing else changes: ids, lengths and the host-side counts keep advancing with every step that includes the
+ * sequence; ids past the stop are speculative and are the caller's to cut.  Without criteria a step computes exactly what it did
+ * before.  cr_kv_reset clears a sequence's criteria and stop; call this once per sequence after it.  CR_ERR_ARG when max_new exceeds
+ * the generated-id capacity (4096) or what the cache leaves after the tokens cached so far (max_tokens - cr_kv_length(seq)).
+ * Enqueued on `stream`. */
+int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream);
+/* Enqueue on `stream` an asynchronous copy of the finished queue into host_out (caller-owned PINNED memory of max >= 1 + 2 n_seqs
+ * int32): host_out[0] = sequences pushed since the last cr_kv_reset(kv, -1) (a running count c), host_out[1 + k % n_seqs] = the
+ * k-th of them (the ring holds the last n_seqs: a sequence is pushed again only after a reset, so a caller that releases a sequence
+ * only after reading its entry never loses one), host_out[1 + n_seqs + s] = stop count of sequence s (0: not stopped).  The copy
+ * reflects the work enqueued on `stream` before it: record an event after the call and read host_out once it has completed --
+ * nothing synchronises. */
+int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream);
 
 /* InternLM2ForCausalLM.forward(inputs_embeds=…, use_cache=True) — InternVL/modeling_internlm2.py:1022-1110 —
  * for ONE sequence `seq`, appended at its current length; then the first greedy pick of
