@@ -14,7 +14,7 @@ _LIB_PATH = os.environ.get('CR_HIP_LIB') or os.path.join(os.path.dirname(os.path
 
 CR_OK = 0
 CR_BF16, CR_F32, CR_I64, CR_I32 = 0, 1, 2, 3
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class ModelDesc(C.Structure):
@@ -53,6 +53,7 @@ SIGNATURES = {
     'cr_kv_generated': (i32, [vp, i32, C.POINTER(i64), i32, vp]),
     'cr_kv_set_stop': (i32, [vp, i32, i32, i32, vp]),
     'cr_kv_poll_finished': (i32, [vp, vp, i32, vp]),
+    'cr_kv_set_sampling': (i32, [vp, i32, f32, i32, f32, C.c_uint64, vp]),
     'cr_llm_prefill': (i32, [vp, vp, i32, vp, i32, f32, vp, vp]),
     'cr_llm_prefill_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), f32, vp, vp]),
     'cr_llm_hidden_probe': (i32, [vp, vp, i32, i32]),
@@ -73,6 +74,7 @@ SIGNATURES = {
     'cr_op_decode_gemm': (i32, [i32, i32, vp, i64, i32, i32, i32, vp, i64, vp, vp, f32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     'cr_op_attention': (i32, [vp, vp, vp, vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp]),
     'cr_op_decode_attention_scratch_floats': (i64, [i32, i32]),
+    'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'cr_op_decode_attention': (i32, [i32, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
 }
 

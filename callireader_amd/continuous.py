@@ -20,7 +20,7 @@ Per page the ids are those of its own generate_pages([page], max_new_tokens=budg
 depend on the other rows of its steps.
 
     pipe = ContinuousPipeline(model, slots=64, max_new_tokens=1024, eos_token_id=eos, repetition_penalty=1.5)
-    t = pipe.submit(embeds, max_new_tokens=None)       # any number of pages; each gets a ticket
+    t = pipe.submit(embeds, max_new_tokens=None)       # any number of pages; each gets a ticket (sampling=, seed=: a sampled page)
     done = pipe.ready()                                 # [(ticket, ids)] finished so far, without waiting
     for ticket, ids in pipe.results(): ...              # the rest, in the order they finish
     pipe.close()
@@ -115,9 +115,11 @@ class ContinuousPipeline:
         self.worker.start()
 
     # ---- caller side ----------------------------------------------------------------------------
-    def submit(self, embeds, max_new_tokens=None):
+    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None):
         """Queue one page's prompt embeddings ([S, hidden] on the device) with its budget of new ids (default, and at most, the pipeline's);
-        returns its ticket.  Prefills a group when one is complete.  ValueError for a budget the pipeline cannot take."""
+        returns its ticket.  Prefills a group when one is complete.  ValueError for a budget the pipeline cannot take.  sampling (a
+        sampling.SamplingParams) with a 64-bit `seed`: the page samples (its sequence's state is set after its reset, before its prefill);
+        None: greedy."""
         t0 = time.perf_counter()
         self._raise_worker_error()
         budget = self.max_new_tokens if max_new_tokens is None else int(max_new_tokens)
@@ -128,7 +130,9 @@ class ContinuousPipeline:
             raise ValueError(f'prompt of {S} tokens + {budget} new exceeds max_tokens={self.max_tokens}')
         ticket = self.next_ticket
         self.next_ticket += 1
-        self.waiting.append((ticket, embeds, budget))
+        if sampling is not None and seed is None:
+            raise ValueError('a sampled page needs its seed')
+        self.waiting.append((ticket, embeds, budget, sampling, seed))
         self.outstanding += 1
         self._pump(flush=False, block=False)
         self.stats['caller_host_s'] += time.perf_counter() - t0
@@ -156,13 +160,13 @@ class ContinuousPipeline:
                 yield item
 
     def map(self, items, errors='raise'):
-        """items: an iterable of (key, embeds, budget or None), consumed as pages are admitted (a generator can compute the next pages' embeddings
+        """items: an iterable of (key, embeds, budget or None[, sampling, seed]), consumed as pages are admitted (a generator can compute the next pages' embeddings
         meanwhile); yields (key, ids) as pages finish.  errors='return': a page whose budget the pipeline refuses yields (key, that ValueError) and
         the others run; 'raise': the ValueError propagates."""
         keys = {}
-        for key, emb, budget in items:
+        for key, emb, budget, *samp in items:
             try:
-                keys[self.submit(emb, budget)] = key
+                keys[self.submit(emb, budget, *samp)] = key
             except ValueError as e:
                 if errors != 'return':
                     raise
@@ -219,16 +223,18 @@ class ContinuousPipeline:
                 return
             group = [self.waiting.popleft() for _ in range(k)]
             seqs = [self.free.popleft() for _ in range(k)]
-            for s in seqs:
+            for s, (_, _, _, sp, seed) in zip(seqs, group):
                 self.kv.reset(s)
-            self.eng.prefill_batch(self.kv, seqs, [e for _, e, _ in group], penalty=self.penalty)
+                if sp is not None:
+                    self.kv.set_sampling(s, sp.temperature, sp.top_k, sp.top_p, seed)
+            self.eng.prefill_batch(self.kv, seqs, [g[1] for g in group], penalty=self.penalty)
             ready = self.ops.record(self.ops.current())
-            for s, (ticket, _, _) in zip(seqs, group):
+            for s, (ticket, *_) in zip(seqs, group):
                 self.owner[s] = ticket
             self.stats['admissions'] += 1
             self.stats['pages_admitted'] += k
             with self.cv:
-                self.inbox.append((seqs, [b for _, _, b in group], ready))
+                self.inbox.append((seqs, [g[2] for g in group], ready))
                 self.cv.notify_all()
 
     # ---- decode thread --------------------------------------------------------------------------

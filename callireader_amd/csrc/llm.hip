@@ -19,6 +19,7 @@
 #include "decode.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
+#include "pick.hpp"
 
 struct cr_kv {
     cr_ctx* ctx;
@@ -32,6 +33,11 @@ struct cr_kv {
     //   [0] finished count (monotonic), [1, 1 + n) ring of finished sequence indices (entry k at 1 + k % n),
     //   [1 + n, 1 + 2n) stop count per sequence (0 = not stopped), [1 + 2n, 1 + 3n) EOS id (< 0: none), [1 + 3n, 1 + 4n) budget (<= 0: none)
     int32_t* d_stop;
+    // sampling state (cr_kv_set_sampling), one block: temperature float[n] (<= 0: greedy), top_k int32[n], top_p float[n], seed uint64[n];
+    // `sampled` mirrors "temperature > 0" on the host: a launch whose rows are all greedy keeps pick_kernel (and the graph path)
+    char* d_samp;
+    float* d_temp; int32_t* d_topk; float* d_topp; uint64_t* d_seed;
+    std::vector<char> sampled;
     std::vector<int> len, ngen;
     // batched decode as a hipGraph (CR_DECODE_GRAPH=1): a step is ~290 short launches whose parameters only change with
     // the row count and the number of attention splits (positions, ids and cache lengths live in device memory), so the
@@ -175,20 +181,8 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
     *(bf16x8*)(dst + c * 8) = y;
 }
 
-// Stop criteria of cr_kv_set_stop, checked against the id a sequence has just appended (its `count`-th): the first time it is the EOS id or
-// the count reaches the budget, the count is recorded and the sequence index pushed onto the finished ring.  One thread per sequence per launch.
-__device__ inline void stop_check(int32_t* __restrict__ stop, int n_seqs, int seq, int64_t id, int count) {
-    int32_t* at = stop + 1 + n_seqs;
-    const int eos = stop[1 + 2 * n_seqs + seq], budget = stop[1 + 3 * n_seqs + seq];
-    if (at[seq] == 0 && ((eos >= 0 && id == eos) || (budget > 0 && count >= budget))) {
-        at[seq] = count;
-        const int k = atomicAdd(stop, 1);
-        stop[1 + k % n_seqs] = seq;
-    }
-}
-
 // RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) + argmax (first max wins) + append the id (+ its stop check).
-// One workgroup of 1024 per row.
+// One workgroup of 1024 per row.  The three steps are pick.hpp's, shared with the sampling pick (sample.hip).
 __global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty,
                                                     int seq0, const int32_t* __restrict__ seqs, int64_t* __restrict__ gen,
                                                     int32_t* __restrict__ ngen, int32_t* __restrict__ lens, int gen_cap, int len_add,
@@ -200,35 +194,8 @@ __global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, 
     float* lg = logits + (int64_t)row * ld;
     const int ng = ngen[seq];
     int64_t* g = gen + (int64_t)seq * gen_cap;
-    if (penalty != 1.0f && ng > 0) {
-        // gather every score first, then scatter: duplicates of an id all see the ORIGINAL score
-        float sv[4]; int64_t si[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int h = tid + k * 1024;
-            si[k] = h < ng ? g[h] : -1;
-            sv[k] = si[k] >= 0 ? lg[si[k]] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (si[k] >= 0) lg[si[k]] = sv[k] < 0.f ? sv[k] * penalty : sv[k] / penalty;
-        __syncthreads();
-    }
-    float best = -INFINITY; int besti = 0x7fffffff;
-    for (int c = tid; c < vocab; c += 1024) {
-        const float v = lg[c];
-        if (v > best) { best = v; besti = c; }
-    }
-    bv[tid] = best; bi[tid] = besti;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (tid < o) {
-            const float v2 = bv[tid + o]; const int i2 = bi[tid + o];
-            if (v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid])) { bv[tid] = v2; bi[tid] = i2; }
-        }
-        __syncthreads();
-    }
+    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid);
+    argmax_row(lg, vocab, tid, bv, bi);
     if (tid == 0) {
         if (ng < gen_cap) {
             g[ng] = bi[0]; ngen[seq] = ng + 1;
@@ -263,6 +230,12 @@ __global__ __launch_bounds__(256) void set_stop_kernel(int32_t* __restrict__ sto
             }
         }
     }
+}
+
+// cr_kv_set_sampling: one sequence's sampling state
+__global__ __launch_bounds__(64) void set_sampling_kernel(float* __restrict__ temp, int32_t* __restrict__ topk, float* __restrict__ topp,
+                                                          uint64_t* __restrict__ seed, int seq, float t, int k, float p, uint64_t sd) {
+    if (threadIdx.x == 0) { temp[seq] = t; topk[seq] = k; topp[seq] = p; seed[seq] = sd; }
 }
 
 // prefill: the cached length of every page's sequence = its first position + its rows (d_seg: 4 per page, see cr_llm_prefill_batch).
@@ -728,6 +701,11 @@ int llm_finalize(cr_ctx* c, hipStream_t st) {
     return CR_OK;
 }
 
+static bool any_sampled(const cr_kv* kv, const int32_t* seqs, int n) {
+    for (int i = 0; i < n; i++) if (kv->sampled[seqs[i]]) return true;
+    return false;
+}
+
 extern "C" {
 
 int cr_op_quantize_fp8(const void* w, int64_t ldw, int N, int K, void* q, float* scale, void* stream) {
@@ -856,6 +834,7 @@ int cr_kv_alloc(cr_ctx* c, int n_seqs, int max_tokens, cr_kv** out) {
     if (hipMalloc((void**)&kv->k, bytes) != hipSuccess || hipMalloc((void**)&kv->v, bytes) != hipSuccess ||
         hipMalloc((void**)&kv->d_len, n_seqs * 4) != hipSuccess || hipMalloc((void**)&kv->d_ngen, n_seqs * 4) != hipSuccess ||
         hipMalloc((void**)&kv->d_stop, ((size_t)4 * n_seqs + 1) * 4) != hipSuccess ||
+        hipMalloc((void**)&kv->d_samp, (size_t)n_seqs * 24) != hipSuccess ||
         hipMalloc((void**)&kv->d_gen, (size_t)n_seqs * kv->gen_cap * 8) != hipSuccess) {
         cr_kv_free(kv);
         return cr_fail(CR_ERR_NOMEM, "cr_kv_alloc: %zu bytes per K/V", bytes);
@@ -865,6 +844,10 @@ int cr_kv_alloc(cr_ctx* c, int n_seqs, int max_tokens, cr_kv** out) {
     CR_HIP(hipMemset(kv->d_stop, 0, ((size_t)2 * n_seqs + 1) * 4));
     CR_HIP(hipMemset(kv->d_stop + 1 + 2 * n_seqs, 0xff, (size_t)n_seqs * 4));       // no EOS id
     CR_HIP(hipMemset(kv->d_stop + 1 + 3 * n_seqs, 0, (size_t)n_seqs * 4));          // no budget
+    kv->d_seed = (uint64_t*)kv->d_samp; kv->d_temp = (float*)(kv->d_seed + n_seqs); kv->d_topk = (int32_t*)(kv->d_temp + n_seqs);
+    kv->d_topp = (float*)(kv->d_topk + n_seqs);
+    CR_HIP(hipMemset(kv->d_samp, 0, (size_t)n_seqs * 24));                           // greedy
+    kv->sampled.assign(n_seqs, 0);
     kv->len.assign(n_seqs, 0); kv->ngen.assign(n_seqs, 0);
     *out = kv;
     return CR_OK;
@@ -878,6 +861,7 @@ int cr_kv_free(cr_kv* kv) {
     if (kv->d_len) hipFree(kv->d_len);
     if (kv->d_ngen) hipFree(kv->d_ngen);
     if (kv->d_stop) hipFree(kv->d_stop);
+    if (kv->d_samp) hipFree(kv->d_samp);
     if (kv->d_gen) hipFree(kv->d_gen);
     for (auto& e : kv->graphs) if (e.exec) hipGraphExecDestroy(e.exec);
     delete kv;
@@ -898,7 +882,8 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
     CR_HIP(hipMemsetAsync(kv->d_stop + 1 + 2 * N + s0, 0xff, (size_t)n * 4, st));       // no EOS id
     CR_HIP(hipMemsetAsync(kv->d_stop + 1 + 3 * N + s0, 0, (size_t)n * 4, st));          // no budget
     if (seq < 0) CR_HIP(hipMemsetAsync(kv->d_stop, 0, 4, st));                          // every sequence: the finished ring starts over
-    for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; }
+    CR_HIP(hipMemsetAsync(kv->d_temp + s0, 0, (size_t)n * 4, st));                      // greedy
+    for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; kv->sampled[s] = 0; }
     return CR_OK;
 }
 
@@ -912,6 +897,19 @@ int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream) {
     hipLaunchKernelGGL(set_stop_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kv->d_stop, kv->n_seqs, seq, eos_id < 0 ? -1 : eos_id,
                        max_new > 0 ? max_new : 0, kv->d_gen, kv->d_ngen, kv->gen_cap);
     CR_HIP(hipGetLastError());
+    return CR_OK;
+}
+
+int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float top_p, uint64_t seed, void* stream) {
+    if (!(temperature >= 0.f && temperature <= 3.402823466e38f) || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f))
+        return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: temperature %g, top_k %d, top_p %g (want a finite temperature >= 0, top_k >= 0, 0 <= top_p <= 1)",
+                       temperature, top_k, top_p);
+    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: bad sequence");
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed, seq,
+                       temperature, top_k, top_p, seed);
+    CR_HIP(hipGetLastError());
+    kv->sampled[seq] = temperature > 0.f;
     return CR_OK;
 }
 
@@ -995,8 +993,12 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         CR_TRY(rms(x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, D, hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
     CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st));
     if (last_logits) CR_HIP(hipMemcpyAsync(last_logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, c->d_seqs, kv->d_gen, kv->d_ngen,
-                       kv->d_len, kv->gen_cap, 0, kv->d_stop, kv->n_seqs);
+    if (any_sampled(kv, seqs, n))
+        CR_TRY(launch_sample(lg, V, V, penalty, n, c->d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
+                             nullptr, 1, kv->d_len, 0, kv->d_stop, kv->n_seqs, nullptr, nullptr, st));
+    else
+        hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, c->d_seqs, kv->d_gen, kv->d_ngen,
+                           kv->d_len, kv->gen_cap, 0, kv->d_stop, kv->n_seqs);
     hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, d_seg, n, kv->d_len);
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
@@ -1046,6 +1048,7 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
     const bf16 *nw = W(c, "language_model.model.norm.weight"), *ow = W(c, "language_model.output.weight");
     if (!table || !nw || !ow) return CR_ERR_STATE;
+    const bool sampled = any_sampled(kv, seqs, n);
     auto enqueue_step = [&](hipStream_t st) -> int {
         hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(256), 0, st, table, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, x);
         CR_TRY(run_layers(c, kv, x, n, true, {}, nullptr, nullptr, d_seqs, nsplit, st));
@@ -1062,12 +1065,17 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         else CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st, false, opt(c, "declayout.language_model.output.weight")));
         }
         if (logits) CR_HIP(hipMemcpyAsync(logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
-                           kv->d_len, kv->gen_cap, 1, kv->d_stop, kv->n_seqs);
+        if (sampled)
+            CR_TRY(launch_sample(lg, V, V, penalty, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
+                                 nullptr, 1, kv->d_len, 1, kv->d_stop, kv->n_seqs, nullptr, nullptr, st));
+        else
+            hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
+                               kv->d_len, kv->gen_cap, 1, kv->d_stop, kv->n_seqs);
         return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
     };
     // graph path: the plain generation loop (no forced ids, no logits copy), nothing recording events on these launches
-    const bool graphable = c->decode_graph && !force_tokens && !logits && !(c->prof && c->prof_mode != 2);
+    // (a step with a sampled row launches the sampling pick: it is left out of the graph path)
+    const bool graphable = c->decode_graph && !force_tokens && !logits && !sampled && !(c->prof && c->prof_mode != 2);
     bool done = false;
     hipStream_t gs = st;                               // the null stream cannot be captured: use the context's blocking side stream
     if (graphable && !st) {

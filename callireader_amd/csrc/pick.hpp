@@ -1,0 +1,59 @@
+// Token choice shared by the greedy pick (llm.hip pick_kernel) and the sampling pick (sample.hip): the repetition penalty, the
+// first-max-wins argmax and the stop check run the same device code in both kernels, so a greedy row gets the same bits from either.
+#pragma once
+#include "common.hpp"
+
+// Stop criteria of cr_kv_set_stop, checked against the id a sequence has just appended (its `count`-th): the first time it is the EOS id or
+// the count reaches the budget, the count is recorded and the sequence index pushed onto the finished ring.  One thread per sequence per launch.
+__device__ inline void stop_check(int32_t* __restrict__ stop, int n_seqs, int seq, int64_t id, int count) {
+    int32_t* at = stop + 1 + n_seqs;
+    const int eos = stop[1 + 2 * n_seqs + seq], budget = stop[1 + 3 * n_seqs + seq];
+    if (at[seq] == 0 && ((eos >= 0 && id == eos) || (budget > 0 && count >= budget))) {
+        at[seq] = count;
+        const int k = atomicAdd(stop, 1);
+        stop[1 + k % n_seqs] = seq;
+    }
+}
+
+// RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) in place over the `ng` ids of history g (ng <= 4096).  Every thread of a
+// 1024-thread workgroup calls it.  The scores are gathered first, then scattered: duplicates of an id all see the ORIGINAL score.
+__device__ __forceinline__ void apply_penalty(float* __restrict__ lg, const int64_t* __restrict__ g, int ng, float penalty, int tid) {
+    float sv[4]; int64_t si[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int h = tid + k * 1024;
+        si[k] = h < ng ? g[h] : -1;
+        sv[k] = si[k] >= 0 ? lg[si[k]] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (si[k] >= 0) lg[si[k]] = sv[k] < 0.f ? sv[k] * penalty : sv[k] / penalty;
+    __syncthreads();
+}
+
+// Argmax of lg[0, vocab), the first maximum winning; every thread of a 1024-thread workgroup calls it, the result is bi[0] after the call.
+__device__ __forceinline__ void argmax_row(const float* __restrict__ lg, int vocab, int tid, float* bv, int* bi) {
+    float best = -INFINITY; int besti = 0x7fffffff;
+    for (int c = tid; c < vocab; c += 1024) {
+        const float v = lg[c];
+        if (v > best) { best = v; besti = c; }
+    }
+    bv[tid] = best; bi[tid] = besti;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (tid < o) {
+            const float v2 = bv[tid + o]; const int i2 = bi[tid + o];
+            if (v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid])) { bv[tid] = v2; bi[tid] = i2; }
+        }
+        __syncthreads();
+    }
+}
+
+// Sampling pick (sample.hip) over `rows` rows of logits (modified in place: penalty).  Per row, seq = seqs[row] (seqs NULL: seq = row) indexes the
+// history (gen [.][gen_cap], ngen) and the sampling state (temp / topk / topp / seed); a row whose temperature is not > 0 is greedy (pick_kernel's
+// result).  step NULL: step = ngen[seq]; else step[row].  append != 0: the id is appended to the sequence's history with pick_kernel's stop check and
+// lens update (lens[seq] += len_add).  out_ids / out_kept (may be NULL): the id and the size of the kept set of each row (0 for a greedy row).
+int launch_sample(float* logits, int64_t ld, int vocab, float penalty, int rows, const int32_t* seqs, int64_t* gen, int32_t* ngen, int gen_cap,
+                  const float* temp, const int32_t* topk, const float* topp, const uint64_t* seed, const int32_t* step, int append, int32_t* lens,
+                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st);

@@ -278,6 +278,12 @@ class KVCache:
         `max_new`-th generated id) and pushes it once onto the finished queue read by poll_finished."""
         B.check(B.lib.cr_kv_set_stop(self._h, seq, -1 if eos_id is None else int(eos_id), int(max_new), _stream()), 'cr_kv_set_stop')
 
+    def set_sampling(self, seq, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+        """cr_kv_set_sampling on the current stream: the sequence's later picks sample (temperature > 0; 0 = greedy).  Call after reset(seq) and
+        before the sequence's prefill, which makes its first pick."""
+        B.check(B.lib.cr_kv_set_sampling(self._h, seq, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
+                'cr_kv_set_sampling')
+
     def poll_finished(self, out):
         """cr_kv_poll_finished: enqueue on the current stream an asynchronous copy of the finished queue into `out`, a pinned int32 CPU tensor of
         at least 1 + 2 n_seqs entries ([0] count pushed, [1 + k % n_seqs] the k-th sequence pushed, [1 + n_seqs + s] stop count of s).  Read it
@@ -455,3 +461,26 @@ def op_decode_attention(q, kc, vc, seqs, lens, s_div=11.313708498984761, which=0
     B.check(B.lib.cr_op_decode_attention(which, _p(q), _p(kc), _p(vc), max_tokens, _p(seqs), _p(lens), Bn, max_keys, float(s_div), _p(scratch), _p(out), _stream()),
             'cr_op_decode_attention')
     return out
+
+
+def op_sample(eng, logits, temperature, top_k, top_p, seed, step, history=None, hist_len=None, penalty=1.0):
+    """cr_op_sample: the sampling pick on given fp32 logits [n, vocab] (per-row temperature / top_k / top_p / seed / step sequences; history
+    [n, cap] int64 with hist_len ids per row for the repetition penalty).  Returns (ids int64 [n], kept int32 [n]) on the device."""
+    dev = eng.device
+    lg = logits.to(dev, torch.float32).contiguous()
+    n, V = lg.shape
+    col = lambda v, dt: torch.as_tensor(v, dtype=dt).reshape(-1).expand(n).contiguous().to(dev)
+    t, k, p, st = col(temperature, torch.float32), col(top_k, torch.int32), col(top_p, torch.float32), col(step, torch.int32)
+    u64 = [int(x) & 0xFFFFFFFFFFFFFFFF for x in (seed if hasattr(seed, '__len__') else [seed] * n)]
+    sd = torch.tensor([x - (1 << 64) if x >> 63 else x for x in u64], dtype=torch.int64).to(dev)      # the uint64 bits
+    if history is None:
+        hist, cap, hl = None, 0, torch.zeros(n, dtype=torch.int32, device=dev)
+    else:
+        hist = history.to(dev, torch.int64).contiguous()
+        cap = hist.shape[1]
+        hl = (torch.full((n,), cap, dtype=torch.int32) if hist_len is None else col(hist_len, torch.int32)).to(dev)
+    ids = torch.empty(n, dtype=torch.int64, device=dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    B.check(B.lib.cr_op_sample(eng._h, _p(lg), n, V, _p(hist), cap, _p(hl), float(penalty), _p(t), _p(k), _p(p), _p(sd), _p(st), _p(ids), _p(kept),
+                               _stream()), 'cr_op_sample')
+    return ids, kept

@@ -182,6 +182,11 @@ def main(argv=None):
     parser.add_argument('--fp8_decode', action='store_true', help='e4m3 weights for the decode (cr_enable_fp8_decode; off by default: the reference computes in bf16)')
     parser.add_argument('--fp8_mfma', type=int, nargs='?', const=1, default=0, choices=(0, 1, 2),
                         help='e4m3 x e4m3 matrix-core linears (cr_enable_fp8_mfma; off by default; a throughput option, not parity-preserving): 1 = the norm-fed linears of the ViT / projector / prefill, 2 = also ViT fc2 and the prefill\'s wo / w2')
+    parser.add_argument('--do_sample', action='store_true', help='sample instead of the greedy default (transformers semantics: do_sample=True alone is top-50 sampling)')
+    parser.add_argument('--temperature', type=float, default=None, help='with --do_sample (default 1.0)')
+    parser.add_argument('--top_k', type=int, default=None, help='with --do_sample (default 50; 0: off)')
+    parser.add_argument('--top_p', type=float, default=None, help='with --do_sample (default 1.0: off)')
+    parser.add_argument('--seed', type=int, default=None, help='torch.manual_seed before the run: --do_sample output becomes reproducible')
     args = parser.parse_args(argv)
     if not isinstance(args.tgt, str):
         raise ValueError(f'The target should a string, not a instance of {type(args.tgt)}!')
@@ -202,6 +207,11 @@ def main(argv=None):
     if isinstance(tid, int) and 0 < tid < model.dims.vocab and tid != tokenizer.sp_model.unk_id:
         model.aligned_token_id = tid
     generation_config = dict(num_beams=1, max_new_tokens=args.max_new_tokens, do_sample=False)
+    if args.do_sample:
+        generation_config['do_sample'] = True
+        generation_config.update({k: getattr(args, k) for k in ('temperature', 'top_k', 'top_p') if getattr(args, k) is not None})
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
     detect_model = load_detector(args.params)
     if is_image(args.tgt):
         print('Single image recognition mode.')

@@ -25,6 +25,7 @@ from .config import ModelDims, IMG_CONTEXT_TOKEN_ID, ALIGNED_TOKEN_ID, EOS_TOKEN
 from .conversation import get_conv_template
 from .engine import Engine
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
+from .sampling import base_seed, page_seeds, parse as sampling_parse, splitmix64
 
 
 class InternVLChatModel:
@@ -211,13 +212,16 @@ class InternVLChatModel:
         return self.sorter
 
     # ---- generation ----------------------------------------------------------------------------
-    def _greedy(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, check_every=16):
-        """transformers 4.45.2 GenerationMixin._sample with do_sample=False, num_beams=1, for ONE sequence:
-        returns only the new ids, EOS included (oracle/generate.py documents the semantics)."""
+    def _generate(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, sampling=None, check_every=16):
+        """transformers 4.45.2 GenerationMixin._sample with num_beams=1 for ONE sequence: greedy (sampling None), or do_sample=True with
+        `sampling` (a sampling.SamplingParams; the page's seed is page_seeds(1)[0]); returns only the new ids, EOS included (oracle/generate.py
+        documents the semantics)."""
         kv = self.kv(1)
         kv.reset(0)
         if input_embeds.shape[0] + max_new_tokens > self.max_tokens:
             raise ValueError(f'prompt of {input_embeds.shape[0]} tokens + {max_new_tokens} new exceeds max_tokens={self.max_tokens}')
+        if sampling is not None:
+            kv.set_sampling(0, sampling.temperature, sampling.top_k, sampling.top_p, page_seeds(1)[0])
         self.engine.prefill(kv, 0, input_embeds, penalty=repetition_penalty)
         n = 1
         while n < max_new_tokens:
@@ -234,9 +238,8 @@ class InternVLChatModel:
 
     @staticmethod
     def _gen_args(generate_kwargs):
-        if generate_kwargs.get('num_beams', 1) != 1 or generate_kwargs.get('do_sample', False):
-            raise NotImplementedError('the CalliReader path is greedy (inference.py:92-96): num_beams=1, do_sample=False')
-        return generate_kwargs.get('max_new_tokens', 1024), generate_kwargs.get('eos_token_id', EOS_TOKEN_ID)
+        """(max_new_tokens, eos_token_id, SamplingParams or None for greedy): transformers' defaults and validation (sampling.parse)."""
+        return generate_kwargs.get('max_new_tokens', 1024), generate_kwargs.get('eos_token_id', EOS_TOKEN_ID), sampling_parse(generate_kwargs)
 
     @torch.no_grad()
     def generate_ocr(self, pixel_values=None, input_ids=None, attention_mask=None, visual_features=None,
@@ -256,8 +259,8 @@ class InternVLChatModel:
                                                     img_id=self.img_context_token_id, ref_id=self.aligned_token_id)
         else:
             input_embeds = self.engine.embed_splice(input_ids.reshape(-1))  # :1107
-        max_new, eos = self._gen_args(generate_kwargs)
-        return self._greedy(input_embeds, max_new, eos, repetition_penalty)
+        max_new, eos, sp = self._gen_args(generate_kwargs)
+        return self._generate(input_embeds, max_new, eos, repetition_penalty, sp)
 
     @torch.no_grad()
     def generate_origin(self, pixel_values=None, input_ids=None, attention_mask=None, visual_features=None,
@@ -287,8 +290,8 @@ class InternVLChatModel:
             input_embeds = self.engine.embed_splice(ids, vit_embeds, None, img_id=self.img_context_token_id)
         else:
             input_embeds = self.engine.embed_splice(input_ids.reshape(-1))  # :1172
-        max_new, eos = self._gen_args(generate_kwargs)
-        return self._greedy(input_embeds, max_new, eos, penalty)
+        max_new, eos, sp = self._gen_args(generate_kwargs)
+        return self._generate(input_embeds, max_new, eos, penalty, sp)
 
     # ---- chat API ------------------------------------------------------------------------------
     def _build_query(self, question, history, num_patches_list, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN):
@@ -464,8 +467,17 @@ class InternVLChatModel:
         exception object in its slot and the other pages run -- what folder mode's per-image try/except needs (inference.py:55-57)."""
         embeds, meta = self._ocr_embeds(tokenizer, detect_model, images, question, generation_config, boxes_list, use_p, drop_zero,
                                         hard_vq, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, errors=errors)
-        outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty) if embeds else []
+        outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, sampling=meta['sampling'],
+                                   seeds=self._ok_seeds(meta)) if embeds else []
         return self._responses(tokenizer, outs, meta)
+
+    @staticmethod
+    def _ok_seeds(meta):
+        """Seeds of the pages that reach the language model: page j of the call (input order, failed pages included) has page_seeds(n)[j]."""
+        if meta['sampling'] is None:
+            return None
+        seeds = page_seeds(meta['n'])
+        return [seeds[i] for i in meta['ok']]
 
     @staticmethod
     def _responses(tokenizer, outs, meta):
@@ -487,6 +499,8 @@ class InternVLChatModel:
         response of its own chat_ocr call.  stats (a dict) receives the host seconds per stage and, per batch, how long the compute stream
         sat between the previous batch's prefill and this batch's first kernel."""
         pipe, pending = None, None
+        sampled = sampling_parse(generation_config) is not None
+        base, page0, n_prev = (base_seed() if sampled else 0), 0, 0           # page j of the call (over all batches) samples with splitmix64(base + j)
         feeder = self._feeder()
         marks, host0 = [], dict(feeder.stats, tokenize_s=self._tok_s)
         it = iter(image_batches)
@@ -520,6 +534,8 @@ class InternVLChatModel:
             while ahead:
                 cur = ahead.popleft()
                 tile(cur)
+                page0 += n_prev                                 # counted before anything can fail: a failed batch's pages keep their place
+                n_prev = len(cur[0])
                 try:
                     if isinstance(cur[3], Exception):
                         raise cur[3]
@@ -546,7 +562,8 @@ class InternVLChatModel:
                     continue
                 if pipe is None:
                     pipe = self.page_pipeline(max_new_tokens=meta['max_new'], eos_token_id=meta['eos'], repetition_penalty=repetition_penalty)
-                prev = pipe.start(embeds)
+                prev = pipe.start(embeds, sampling=meta['sampling'],
+                                  seeds=[splitmix64(base + page0 + i) for i in meta['ok']] if sampled else None)
                 if stats is not None:
                     e = torch.cuda.Event(enable_timing=True)
                     e.record(torch.cuda.current_stream())
@@ -600,7 +617,8 @@ class InternVLChatModel:
                                     IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, tiles=tiles, errors=errors)
         template = get_conv_template(self.template)
         gc = dict(generation_config, eos_token_id=tokenizer.convert_tokens_to_ids(template.sep))      # what _ocr_embeds gives every page
-        max_new, eos = self._gen_args(gc)
+        max_new, eos, sp = self._gen_args(gc)
+        seeds = page_seeds(len(images)) if sp is not None else None
         failed = []
 
         def items():
@@ -621,7 +639,7 @@ class InternVLChatModel:
                 for sub, (embeds, meta) in parts:
                     failed.extend((sub[k], e) for k, e in meta['failed'].items())
                     for k, emb in zip(meta['ok'], embeds):
-                        yield sub[k], emb, None
+                        yield sub[k], emb, None, sp, (seeds[sub[k]] if sp is not None else None)
 
         def response(ids):
             return tokenizer.batch_decode(torch.tensor([ids]), skip_special_tokens=True)[0].split(template.sep)[0].strip()
@@ -709,8 +727,8 @@ class InternVLChatModel:
         template = get_conv_template(self.template)
         generation_config = dict(generation_config)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
-        max_new, eos = self._gen_args(generation_config)
-        meta = {'n': len(images), 'ok': [], 'failed': dict(batch.failed), 'max_new': max_new, 'eos': eos, 'template': template}
+        max_new, eos, sp = self._gen_args(generation_config)
+        meta = {'n': len(images), 'ok': [], 'failed': dict(batch.failed), 'max_new': max_new, 'eos': eos, 'template': template, 'sampling': sp}
         if not batch.ok:
             return [], meta
         feeder.hand_over(batch)
@@ -740,7 +758,7 @@ class InternVLChatModel:
         for k, i in enumerate(batch.ok):
             S = all_ids[k].numel()
             if S + max_new > self.max_tokens:
-                err = ValueError(f'prompt of {S} tokens + {max_new} new exceeds max_tokens={self.max_tokens}')       # _greedy's check, per page
+                err = ValueError(f'prompt of {S} tokens + {max_new} new exceeds max_tokens={self.max_tokens}')       # _generate's check, per page
                 if errors == 'raise':
                     raise err
                 meta['failed'][i] = err
@@ -776,8 +794,9 @@ class InternVLChatModel:
                                                    img_id=self.img_context_token_id))
             off += num_patches
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
-        max_new, eos = self._gen_args(generation_config)
-        outs = self.generate_pages(embeds, max_new, eos, generation_config.get('repetition_penalty', 1.0))
+        max_new, eos, sp = self._gen_args(generation_config)
+        outs = self.generate_pages(embeds, max_new, eos, generation_config.get('repetition_penalty', 1.0), sampling=sp,
+                                   seeds=page_seeds(len(embeds)) if sp is not None else None)
         responses = [tokenizer.batch_decode(torch.tensor([o]), skip_special_tokens=True)[0] for o in outs]
         return [r.split(template.sep)[0].strip() for r in responses]
 
@@ -787,10 +806,13 @@ class InternVLChatModel:
         return PagePipeline(self, **kw)
 
     def generate_pages(self, embeds_list, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0,
-                       check_every=16, prefill_batch=16):
+                       check_every=16, prefill_batch=16, sampling=None, seeds=None):
         """Prefill every page, then decode all unfinished pages as ONE batch per step: the 14.7 GB of LLM weights are
-        streamed once per step for all pages.  Per page the ids equal the single-page greedy result."""
+        streamed once per step for all pages.  Per page the ids equal the single-page greedy result.
+        sampling: None (every page greedy), one sampling.SamplingParams for every page, or a list with one entry (or None: greedy) per page;
+        seeds: one 64-bit seed per page (default page_seeds(P)).  A sampled page's ids depend only on its prompt, its parameters and its seed."""
         P = len(embeds_list)
+        per_page = _per_page_sampling(sampling, seeds, P)
         if self._kv is None or self._kv.n_seqs < P:
             if self._kv is not None:
                 self._kv.free()
@@ -798,6 +820,7 @@ class InternVLChatModel:
             self._kv = self.engine.kv_alloc(self.max_pages, self.max_tokens)
         kv = self._kv
         kv.reset()
+        _set_sampling(kv, per_page)
         for i0 in range(0, P, prefill_batch):                       # prompts of several pages share the linear layers' GEMMs
             idx = list(range(i0, min(P, i0 + prefill_batch)))
             self.engine.prefill_batch(kv, idx, [embeds_list[i] for i in idx], penalty=repetition_penalty)
@@ -936,11 +959,13 @@ class PagePipeline:
             raise out
         return out
 
-    def start(self, embeds_list, budgets=None):
+    def start(self, embeds_list, budgets=None, sampling=None, seeds=None):
         """Prefill a batch on the caller's stream and hand it to the decode thread; returns the previous batch's ids (None if there
         was none), waiting for them if they are not there yet.  budgets: optional per-page max_new_tokens (<= the pipeline's): a page
-        leaves the batch at the first EOS check at or past its budget and its ids are cut there, as its own generate_pages call would."""
+        leaves the batch at the first EOS check at or past its budget and its ids are cut there, as its own generate_pages call would.
+        sampling / seeds: as generate_pages takes them."""
         P = len(embeds_list)
+        per_page = _per_page_sampling(sampling, seeds, P)
         # The OTHER slot may be under the worker's decode right now (the previous batch, not collected yet): it is only ever
         # CREATED here, on the first batch (28 GB at 64 pages: not inside a later step), never regrown -- a batch larger than it
         # holds regrows it when that slot's turn comes, i.e. after _collect() has returned the batch that last used it.
@@ -949,6 +974,7 @@ class PagePipeline:
         kv = self._kv(self.turn, P)                # last used two batches ago, and that batch has been collected
         self.turn ^= 1
         kv.reset()
+        _set_sampling(kv, per_page)
         for i0 in range(0, P, self.prefill_batch):
             idx = list(range(i0, min(P, i0 + self.prefill_batch)))
             self.eng.prefill_batch(kv, idx, [embeds_list[i] for i in idx], penalty=self.penalty)
@@ -976,6 +1002,27 @@ class PagePipeline:
         if self.dec is not None:
             self.dec.close()
             self.dec = None
+
+
+def _per_page_sampling(sampling, seeds, P):
+    """[(SamplingParams, seed) or None] per page from generate_pages' sampling / seeds arguments."""
+    if sampling is None:
+        return None
+    sps = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * P
+    if len(sps) != P:
+        raise ValueError(f'sampling: {len(sps)} entries for {P} pages')
+    if seeds is None:
+        seeds = page_seeds(P)
+    if len(seeds) != P:
+        raise ValueError(f'seeds: {len(seeds)} entries for {P} pages')
+    return [None if sp is None else (sp, int(sd)) for sp, sd in zip(sps, seeds)]
+
+
+def _set_sampling(kv, per_page):
+    """The sampled pages' state, after the cache's reset and before the prefill (which makes every page's first pick)."""
+    for i, e in enumerate(per_page or ()):
+        if e is not None:
+            kv.set_sampling(i, e[0].temperature, e[0].top_k, e[0].top_p, e[1])
 
 
 def load_boxes_json(path):

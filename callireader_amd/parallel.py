@@ -442,6 +442,9 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     `sharded_generate`: each rank crops and encodes ITS contiguous shard of the flat character-box list (GPU resize / pad / normalise, ViT -> mlp1 -> resampler ->
     VQ -> de-norm), one all-gather of the pseudo-token rows, and the owners of a page (plan_balanced over the pages' real sizes, or `plan`) encode its own
     tiles, splice, prefill and decode.  drop_zero is not offered here: it makes a page's prompt length depend on the VQ result of tiles another rank encodes."""
+    if dict(generation_config).get('do_sample', False):
+        raise NotImplementedError('chat_ocr_pages_sharded: do_sample=True is not implemented across GPUs yet (it needs the per-call seed broadcast '
+                                  'to every rank); use chat_ocr_pages / chat_ocr_continuous on one GPU')
     from PIL import Image
     from . import ordering
     from .conversation import get_conv_template
@@ -505,7 +508,7 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     template = get_conv_template(model.template)
     gen = dict(generation_config)
     gen['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
-    max_new, eos = model._gen_args(gen)
+    max_new, eos, _ = model._gen_args(gen)            # greedy: do_sample=True was refused on entry
     q = question if '<image>' in question else '<image>\n' + question
     ids = [model._prompt_ids(tokenizer, q, page_jobs[p][1], 3 * n_chars[p], IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN) for p in range(n_pages)]
     if plan is None:

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 11  /* 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 12  /* 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -151,6 +151,19 @@ int cr_kv_generated(cr_kv* kv, int seq, int64_t* out_host, int max, void* stream
  * the generated-id capacity (4096) or what the cache leaves after the tokens cached so far (max_tokens - cr_kv_length(seq)).
  * Enqueued on `stream`. */
 int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream);
+/* Sampling state of `seq` (transformers 4.45.2 _sample with do_sample=True): every later pick of the sequence applies the repetition penalty,
+ * then scores / temperature (fp32), top-k (top_k == 0: off; ties at the k-th value kept), top-p (top_p >= 1: off; ascending fp32(1 - top_p)
+ * cut of the softmax cumsum, the maximum always kept, every id tied at the boundary value kept) and draws from the softmax of the kept ids by an
+ * exponential race: argmax over kept i of z_i - log(-log u_i) (double), lowest id on a tie, with
+ *     u_i = ((x >> 8) + 0.5) * 2^-24,   x = word (i % 4) of Philox-4x32-10(counter = {i / 4, step, 0, 0}, key = {seed & 0xffffffff, seed >> 32}),
+ *     step = the sequence's generated-id count before the pick (0 for the prefill's pick),
+ * so a draw depends only on (seed, step, logits, history), not on the batch, the row or the decode kernels.  temperature == 0 means greedy (the
+ * default, what cr_kv_reset restores).  CR_ERR_ARG for a negative, infinite or NaN temperature, top_k < 0, or top_p outside [0, 1] (checked
+ * before the cache and sequence).  A finite temperature small enough for logit / temperature to overflow is accepted: those scores are +-inf, a
+ * +inf score wins the draw (the lowest such id); NaN scores are never kept, and a row with no kept score above -inf gets the greedy pick's id.  The prefill makes the
+ * sequence's first pick: call this after cr_kv_reset and BEFORE the sequence's prefill (cr_kv_set_stop may come after it).  A launch whose rows
+ * are all greedy runs the greedy pick exactly as before.  Enqueued on `stream`. */
+int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
 /* Enqueue on `stream` an asynchronous copy of the finished queue into host_out (caller-owned PINNED memory of max >= 1 + 2 n_seqs
  * int32): host_out[0] = sequences pushed since the last cr_kv_reset(kv, -1) (a running count c), host_out[1 + k % n_seqs] = the
  * k-th of them (the ring holds the last n_seqs: a sequence is pushed again only after a reset, so a caller that releases a sequence
@@ -272,6 +285,13 @@ int cr_op_decode_gemm(int which, int flags, const void* W, int64_t ldw, int M, i
  * bytes, in the kernel's own tile order (which = 0: RoPE tiles of 8 + 8 rows) -- a wave's load is one contiguous KiB instead of 16 rows x 64 bytes.
  * dst: ceil(N / 16) * 16 * K bf16.  cr_finalize keeps such a copy of every LLM linear (+15 GB on InternLM2.5-7B) for decode batches of <= 8 rows. */
 int cr_op_decode_swizzle(int which, const void* W, int64_t ldw, int N, int K, void* dst, void* stream);
+/* The sampling pick of cr_kv_set_sampling alone (test / tuning entry; the prefill and decode launch the same kernel): logits [n][vocab] fp32 (not
+ * modified), history [n][hist_cap] int64 with hist_len[n] ids per row (hist_cap <= 4096; history may be NULL when hist_cap == 0) for the penalty,
+ * per row temperature / top_k / top_p / seed / step as above (temperature <= 0: the greedy pick).  out_ids[n] = the id, out_kept[n] = the size of
+ * the kept set (0 for a greedy row).  All pointers are DEVICE arrays.  ABI v12. */
+int cr_op_sample(cr_ctx* ctx, const float* logits, int n, int vocab, const int64_t* history, int hist_cap, const int32_t* hist_len, float penalty,
+                 const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed, const int32_t* step, int64_t* out_ids,
+                 int32_t* out_kept, void* stream);
 /* q/k/v/o addressed as base + b*bs + row*rs + head*hs (elements) */
 int cr_op_attention(const void* q, const void* k, const void* v, void* o, const int64_t* strides12, int B, int H,
                     int Sq, int Sk, int head_dim, int kv_group, int causal, int q_pos0, float q_prescale, float s_div,
