@@ -3,6 +3,12 @@
 
   python bench.py --gpus N --steps K --warmup W           (N > 1: launched by torch.distributed.run, one rank per GPU)
   python bench.py ... --dump-outputs DIR                  (also writes what the last timed step computed, DIR/<name>.npy)
+  python bench.py ... --full                              (also the untimed blocks after the timed steps; see untimed_blocks)
+
+A plain run (no --full) sets up, warms up, times its steps, writes --dump-outputs and prints the line: the headline and what the
+timed steps measured themselves (roofline / decode_gemm from HIP events around their launches).  Everything that takes runs of its
+own -- the one-batch-at-a-time step, vit_prefill, strong_share / strong_scaling, api_level, configs 2 / 3, fp8, roofline.by_kernel,
+the rocprofv3 traffic passes, the CPU baseline -- runs with --full only, where the --no-* switches leave single blocks out.
 
 Metric (BASELINE.json): calligraphy pages/sec through ViT + resampler + LLM greedy decode.
 One "step" = one batch of synthetic pages per GPU through the whole path:
@@ -90,7 +96,11 @@ def dump_outputs(out_dir, page_ids, tensors, suffix='', world=1):
     return sorted(arrays)
 
 
-def main():
+# options that only shape a block of --full: given without it they would change nothing, so they are refused there
+FULL_ONLY = ('cpu_baseline', 'strong_steps', 'balanced_owners', 'two_steps_one_decode', 'share_world', 'share_steps', 'fp8_extras', 'api_batches')
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=2)
@@ -123,9 +133,46 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): the greedy ids of its pages and a fixed, '
                          'seeded sample of its page-tile features and pseudo-token embeddings (the inputs are seeded: two builds compare output for output)')
-    args = ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every untimed block this world size has (one-batch-at-a-time step, vit_prefill, all-gather alone, strong_share / '
+                         'strong_scaling, api_level, configs 2 / 3, preprocessing, ordering, fp8, roofline.by_kernel, traffic, CPU baseline); the --no-* switches drop single blocks')
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:
+        given = ['--' + d.replace('_', '-') for d in FULL_ONLY if getattr(args, d) != ap.get_default(d)]
+        if given:
+            ap.error(f'{", ".join(given)} only shape(s) a block of --full: add --full')
+    return args
+
+
+def untimed_blocks(args, world, rank):
+    """The names of the untimed blocks this rank runs after the timed steps (the same decision on every rank for those that hold a collective).
+    Empty without --full; with it, every block the world size has, less those its --no-* switches drop."""
+    if not args.full:
+        return set()
+    one = world == 1 and rank == 0
+    weak = args.scaling == 'weak'
+    todo = {'one_batch_at_a_time', 'vit_prefill'}                 # (the first needs the page pipeline, main() checks)
+    if world > 1:
+        todo.add('all_gather')
+        if weak and not args.no_strong_block:
+            todo.add('strong_scaling')
+    if one and weak and not args.no_strong_share and args.pages >= args.share_world and args.pages % args.share_world == 0:
+        todo.add('strong_share')
+    if one and not args.no_api:
+        todo.add('api_level')
+    if one and not args.no_vit_extra:
+        todo.add('single_gpu_extras')                             # configs 2 / 3, preprocessing, ordering, fp8, roofline.by_kernel
+    if one and not args.no_traffic and args.pages >= 16 and weak:
+        todo.add('traffic')
+    if one and not args.no_cpu_baseline:
+        todo.add('cpu_baseline')
+    return todo
+
+
+def main():
+    args = parse_args()
     plan.NEW_TOKENS = NEW_TOKENS = args.new_tokens
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -164,7 +211,8 @@ def main():
     n_pages, mine, ct_lo, ct_hi = wl['n_pages'], wl['mine'], wl['ct_lo'], wl['ct_hi']
     P = wl['pages_per_gpu']                              # pages this rank owns per step (round-robin; = --pages with weak scaling)
     S_page = PAGE_TILES * 256 + CHAR_TILES * 3 + TEXT_TOKENS
-    # (room for the ragged batch of strong_share.balanced_ragged: pages of up to 13 page tiles and 250 character tiles; a longer cache changes no step's work)
+    # (room for the ragged batch of strong_share.balanced_ragged: pages of up to 13 page tiles and 250 character tiles; a longer cache changes no step's work.
+    #  Sized so with or without --full: the timed steps of both kinds of run use the same cache layout)
     longest_prompt = max(S_page, 13 * 256 + 250 * 3 + TEXT_TOKENS) if (world == 1 and not args.no_strong_share and not args.no_ragged) else S_page
     model = InternVLChatModel.from_synthetic(dims, seed=0, device=local_rank, max_tokens=longest_prompt + NEW_TOKENS + 128, max_pages=P)
     model.img_context_token_id = IMG_CONTEXT_TOKEN_ID
@@ -303,6 +351,7 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    todo = untimed_blocks(args, world, rank)
 
     # the path's one collective, alone on the wire (untimed extra): the pseudo-token all-gather of one step
     def gather_standalone(w):
@@ -322,11 +371,11 @@ def main():
                 'bytes_per_rank_sent': (w['ct_hi'] - w['ct_lo']) * 3 * dims.llm_hidden * 2, 'bytes_gathered': total_bytes,
                 'standalone_ms': round(ms, 3), 'gb_per_s_received': round(total_bytes * (world - 1) / world / (ms * 1e-3) / 1e9, 1),
                 'note': 'inside a step the gather runs underneath the page tiles\' ViT (all_gather_rows_async)'}
-    gather = gather_standalone(wl) if world > 1 else None
+    gather = gather_standalone(wl) if 'all_gather' in todo else None
 
     # one un-pipelined step for comparison (untimed extra) and a self-check: the pipelined run's ids are the sequential step's
     seq_ms, same_ids, seq_frac, seq_dec, seq_out = None, None, None, None, None
-    if pipe is not None:
+    if pipe is not None and 'one_batch_at_a_time' in todo:
         last_pipe = run_steps(1)[-1]
         if os.environ.get('CR_PIPE_MARKS') and pipe.host_steps:
             print(f'[marks] decode thread: {1e3 * pipe.host_s / pipe.host_steps:.2f} ms of host time per decode step issued ({pipe.host_steps} steps)', file=sys.stderr)
@@ -344,19 +393,23 @@ def main():
         seq_frac = (pr[2] / (pr[1] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS) if pr[1] > 0 else None      # the same kernels with the chip to themselves
         seq_dec = (pr[7] / (pr[5] * 1e-3) / 1e9, pr[5]) if pr[5] > 0 else None                     # weight-streaming class, GB/s and ms of that un-overlapped step
         same_ids = bool(seq_out == last_pipe)
+    elif pipe is not None:
+        pipe.close()                                # (a plain run: nothing runs after the timed steps)
 
     # north_star's "MFMA utilisation on ViT + LLM prefill": one extra, untimed pass that stops after the first token
     # (visual stage, then splice + prefill + the first LM-head row), algorithmic FLOPs of SURVEY 8(d) over its wall time
-    st = [0.0]
-    torch.cuda.synchronize(); st[0] = time.perf_counter()
-    step(new_tokens=1, stamps=st)
-    my_tiles = len(mine) * PAGE_TILES + (ct_hi - ct_lo)
-    vis_fl = my_tiles * (723.6e9 + 17.18e9) + (ct_hi - ct_lo) * (12.02e9 + 2.27e9)
-    pre_fl = len(mine) * (S_page * 13.96e9 + 0.524e6 * S_page * (S_page + 1) / 2 + 0.758e9)
-    vit_prefill = {'what': 'visual stage (ViT + mlp1 + resampler + VQ) and LLM prefill of one batch, attention and norms included; algorithmic FLOPs of SURVEY 8(d) / wall time of an untimed extra pass on rank 0',
-                   'visual_ms': round((st[1] - st[0]) * 1e3, 1), 'prefill_ms': round((st[2] - st[1]) * 1e3, 1),
-                   'tflops': round((vis_fl + pre_fl) / (st[2] - st[0]) / 1e12, 1),
-                   'mfma_frac': round((vis_fl + pre_fl) / (st[2] - st[0]) / 1e12 / PEAK_BF16_TFLOPS, 4)}
+    vit_prefill = None
+    if 'vit_prefill' in todo:
+        st = [0.0]
+        torch.cuda.synchronize(); st[0] = time.perf_counter()
+        step(new_tokens=1, stamps=st)
+        my_tiles = len(mine) * PAGE_TILES + (ct_hi - ct_lo)
+        vis_fl = my_tiles * (723.6e9 + 17.18e9) + (ct_hi - ct_lo) * (12.02e9 + 2.27e9)
+        pre_fl = len(mine) * (S_page * 13.96e9 + 0.524e6 * S_page * (S_page + 1) / 2 + 0.758e9)
+        vit_prefill = {'what': 'visual stage (ViT + mlp1 + resampler + VQ) and LLM prefill of one batch, attention and norms included; algorithmic FLOPs of SURVEY 8(d) / wall time of an untimed extra pass on rank 0',
+                       'visual_ms': round((st[1] - st[0]) * 1e3, 1), 'prefill_ms': round((st[2] - st[1]) * 1e3, 1),
+                       'tflops': round((vis_fl + pre_fl) / (st[2] - st[0]) / 1e12, 1),
+                       'mfma_frac': round((vis_fl + pre_fl) / (st[2] - st[0]) / 1e12 / PEAK_BF16_TFLOPS, 4)}
 
     # ---- the optional, untimed blocks (benchlib/extras.py) ----
     import types
@@ -364,12 +417,8 @@ def main():
     S = types.SimpleNamespace(args=args, world=world, rank=rank, dev=dev, dims=dims, model=model, eng=eng, wl=wl, P=P, S_page=S_page, n_pages=n_pages, mine=mine,
                               ct_lo=ct_lo, ct_hi=ct_hi, page_px=page_px, char_px=char_px, ids=ids, step=step, sync=sync, make_inputs=make_inputs,
                               elapsed=elapsed, seq_ms=seq_ms, seq_out=seq_out)
-    strong_share = None
-    if world == 1 and rank == 0 and args.scaling == 'weak' and not args.no_strong_share and args.pages >= args.share_world and args.pages % args.share_world == 0:
-        strong_share = extras.strong_share_block(S)
-    strong = None
-    if world > 1 and args.scaling == 'weak' and not args.no_strong_block:
-        strong = extras.strong_scaling_block(S, gather_standalone)
+    strong_share = extras.strong_share_block(S) if 'strong_share' in todo else None
+    strong = extras.strong_scaling_block(S, gather_standalone) if 'strong_scaling' in todo else None
 
     result = None
     if rank == 0:
@@ -388,7 +437,7 @@ def main():
         result = {
             'metric': 'calligraphy pages/sec (ViT+resampler+LLM greedy)', 'value': round(value, 4), 'unit': 'pages/s',
             'n_gpus': dist.get_world_size() if world > 1 else 1, 'backend': dist.get_backend() if world > 1 else None, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 2),
-            'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
+            'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic', 'full': args.full,
             'config': {'workload': (f'{args.scaling} scaling: ' + (f'{n_pages} pages/step over {world} GPU(s) = ' if args.scaling == 'strong' else '')) + f'full page path, {P} pages/GPU/step of the examples/0.jpg shape (11 page + 96 char tiles 448x448, '
                                    f'{S_page}-token prompt, {NEW_TOKENS} greedy tokens, repetition_penalty 1.0); InternVL2-8B shapes '
                                    '(InternViT-300M 24L + mlp1 + PerceiverResampler 4L + 92553-row cosine VQ + InternLM2.5-7B 32L), random-init bf16 weights',
@@ -426,16 +475,16 @@ def main():
                 'what': 'two batches in flight (PagePipeline): a worker thread runs the HBM-bound batched decode of batch i-1 on a second HIP stream '
                         '(second context sharing the weights) beside the matrix-bound visual stage and prefill of batch i; a run of K steps ends '
                         'with the last decode alone, inside the timed region',
-                'one_batch_at_a_time_ms_per_step': round(seq_ms, 1), 'ids_equal_one_batch_at_a_time': same_ids,
+                'one_batch_at_a_time_ms_per_step': round(seq_ms, 1) if seq_ms else None, 'ids_equal_one_batch_at_a_time': same_ids,
                 'roofline_frac_one_batch_at_a_time': round(seq_frac, 4) if seq_frac else None,
                 'note': 'roofline.frac above is measured live in the timed steps, where the tiled GEMMs share the chip with the decode kernels of the '
                         'other batch (each launch takes longer, the step takes less); roofline_frac_one_batch_at_a_time is the same measurement on one '
                         'un-overlapped step'},
         }
 
-    # ---- extras on rank 0 at N == 1: BASELINE config 2 (ViT only, 32 tiles) and the CPU baseline ----
+    # ---- extras on rank 0 at N == 1 (--full): the API path, BASELINE configs 2 / 3 and the other single-GPU blocks, traffic, the CPU baseline ----
     if rank == 0 and world == 1:
-        if not args.no_api:
+        if 'api_level' in todo:
             # the headline's batch through the reference's API, from image files to strings (benchlib/api.py); untimed extra, same model object
             from benchlib.api import api_level
             try:
@@ -451,7 +500,7 @@ def main():
                 import traceback
                 traceback.print_exc()
                 result['api_level'] = {'error': f'{type(e).__name__}: {e}'}
-        if not args.no_vit_extra:
+        if 'single_gpu_extras' in todo:
             extras.single_gpu_extras(S, result, strong_share)
             # the kernels one at a time against their own rooflines (benchlib/kernels.py)
             from benchlib.kernels import by_kernel
@@ -459,7 +508,7 @@ def main():
                 result['roofline']['by_kernel'] = by_kernel(dev)
             except Exception as e:
                 result['roofline']['by_kernel'] = {'error': f'{type(e).__name__}: {e}'}
-        if not args.no_traffic and args.pages >= 16 and args.scaling == 'weak':
+        if 'traffic' in todo:
             # HBM-side bytes per launch of the dominant kernel class, measured on THIS box in THIS run (untimed, after everything else)
             try:
                 pipe = None
@@ -476,7 +525,7 @@ def main():
                 result['roofline']['traffic_note'] = note
             else:
                 result['roofline']['traffic_note'] += f' [live measurement unavailable: {note}]'
-        if not args.no_cpu_baseline:
+        if 'cpu_baseline' in todo:
             try:
                 del model
             except NameError:

@@ -88,7 +88,8 @@ def measure_traffic(pages=16):
     prof = shutil.which('rocprofv3') or '/opt/rocm/bin/rocprofv3'
     if not os.path.exists(prof):
         return None, 'rocprofv3 not found'
-    args = ['--steps', '1', '--warmup', '0', '--pages', str(pages), '--new-tokens', '2', '--no-cpu-baseline', '--no-vit-extra', '--no-pipeline', '--no-traffic', '--no-strong-share', '--no-api']
+    args = ['--steps', '1', '--warmup', '0', '--pages', str(pages), '--new-tokens', '2', '--full', '--no-cpu-baseline', '--no-vit-extra', '--no-pipeline', '--no-traffic',
+            '--no-strong-share', '--no-api']
     work = tempfile.mkdtemp(prefix='cr_pmc_', dir='/tmp')
     env = dict(os.environ, TMPDIR='/tmp')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'LOCAL_WORLD_SIZE', 'GROUP_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'TORCHELASTIC_RUN_ID'):

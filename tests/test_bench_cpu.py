@@ -15,7 +15,7 @@ def test_bench_help_lists_every_block_switch_and_benchlib_imports():
     out = r.stdout.decode()
     assert r.returncode == 0, out[-2000:]
     for flag in ('--gpus', '--steps', '--warmup', '--pages', '--no-api', '--api-batches', '--no-ragged', '--two-steps-one-decode', '--no-strong-share', '--no-traffic',
-                 '--no-cpu-baseline', '--no-vit-extra', '--no-pipeline', '--scaling', '--total-pages', '--dump-outputs'):
+                 '--no-cpu-baseline', '--no-vit-extra', '--no-pipeline', '--scaling', '--total-pages', '--dump-outputs', '--full'):
         assert flag in out, flag
     sys.path.insert(0, ROOT)
     import bench
@@ -24,6 +24,40 @@ def test_bench_help_lists_every_block_switch_and_benchlib_imports():
     assert measure.PEAK_BF16_TFLOPS == 2500.0 and measure.PEAK_HBM_GBS == 8000.0
     for fn in ('strong_share_block', 'strong_scaling_block', 'single_gpu_extras', 'ragged_balanced', 'measure_balanced'):
         assert callable(getattr(extras, fn))
+
+
+def test_a_plain_run_has_no_untimed_block_and_full_has_every_one():
+    """Without --full the run does only what its headline needs; --full runs every untimed block of the world size, less what its --no-* switches drop."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.untimed_blocks(bench.parse_args([]), 1, 0) == set()
+    assert bench.untimed_blocks(bench.parse_args(['--gpus', '2', '--steps', '3', '--warmup', '0', '--no-pipeline']), 2, 1) == set()
+    one = {'one_batch_at_a_time', 'vit_prefill', 'strong_share', 'api_level', 'single_gpu_extras', 'traffic', 'cpu_baseline'}
+    assert bench.untimed_blocks(bench.parse_args(['--full']), 1, 0) == one
+    assert bench.untimed_blocks(bench.parse_args(['--full', '--cpu-baseline', 'full', '--fp8-extras']), 1, 0) == one
+    for rank in (0, 1):
+        assert bench.untimed_blocks(bench.parse_args(['--gpus', '2', '--full']), 2, rank) == {'one_batch_at_a_time', 'vit_prefill', 'all_gather', 'strong_scaling'}
+    assert bench.untimed_blocks(bench.parse_args(['--gpus', '2', '--full', '--no-strong-block']), 2, 0) == {'one_batch_at_a_time', 'vit_prefill', 'all_gather'}
+    drops = {'--no-api': 'api_level', '--no-vit-extra': 'single_gpu_extras', '--no-traffic': 'traffic', '--no-cpu-baseline': 'cpu_baseline', '--no-strong-share': 'strong_share'}
+    for flag, block in drops.items():
+        assert bench.untimed_blocks(bench.parse_args(['--full', flag]), 1, 0) == one - {block}, flag
+    assert 'traffic' not in bench.untimed_blocks(bench.parse_args(['--full', '--pages', '8']), 1, 0)
+    assert 'strong_share' not in bench.untimed_blocks(bench.parse_args(['--full', '--pages', '12']), 1, 0)     # not a multiple of --share-world
+
+
+def test_options_of_full_blocks_are_refused_without_full():
+    """An option that only shapes a block of --full would change nothing in a plain run: the script says so instead of printing a line without it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for argv in (['--cpu-baseline', 'full'], ['--fp8-extras'], ['--two-steps-one-decode'], ['--balanced-owners', '4'], ['--api-batches', '2'],
+                 ['--share-world', '4'], ['--share-steps', '1'], ['--strong-steps', '1']):
+        with pytest.raises(SystemExit) as e:
+            bench.parse_args(argv)
+        assert e.value.code == 2, argv
+        assert bench.parse_args(argv + ['--full']).full
+    assert not bench.parse_args(['--cpu-baseline', 'sample', '--no-api', '--no-traffic']).full      # defaults and --no-* switches are fine either way
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--fp8-extras'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert r.returncode == 2 and b'--full' in r.stdout, r.stdout[-2000:]
 
 
 def test_dump_outputs_writes_ids_and_fixed_samples(tmp_path):
