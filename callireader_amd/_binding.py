@@ -14,7 +14,8 @@ _LIB_PATH = os.environ.get('CR_HIP_LIB') or os.path.join(os.path.dirname(os.path
 
 CR_OK = 0
 CR_BF16, CR_F32, CR_I64, CR_I32 = 0, 1, 2, 3
-ABI_VERSION = 12
+CR_KV_BF16, CR_KV_E4M3 = 0, 1
+ABI_VERSION = 13
 
 
 class ModelDesc(C.Structure):
@@ -46,6 +47,9 @@ SIGNATURES = {
     'cr_denorm': (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     'cr_embed_splice': (i32, [vp, vp, i32, vp, i32, i64, vp, i32, i64, vp, vp]),
     'cr_kv_alloc': (i32, [vp, i32, i32, C.POINTER(vp)]),
+    'cr_kv_alloc_ex': (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
+    'cr_kv_format': (i32, [vp]),
+    'cr_kv_read_e4m3': (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
     'cr_kv_free': (i32, [vp]),
     'cr_kv_length': (i32, [vp, i32]),
     'cr_kv_reset': (i32, [vp, i32, vp]),
@@ -76,6 +80,7 @@ SIGNATURES = {
     'cr_op_decode_attention_scratch_floats': (i64, [i32, i32]),
     'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'cr_op_decode_attention': (i32, [i32, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
+    'cr_op_decode_attention_e4m3': (i32, [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
 }
 
 

@@ -90,7 +90,11 @@ class ContinuousPipeline:
         self.max_new_tokens, self.eos, self.penalty = max_new_tokens, eos_token_id, repetition_penalty
         self.n_seqs = slots + (slots if spare is None else spare)
         self.max_tokens = model.max_tokens
-        self.kv = self.eng.kv_alloc(self.n_seqs, self.max_tokens)
+        kv_dtype = getattr(model, 'kv_cache_dtype', 'bf16')      # the model's cache format (InternVLChatModel.kv_cache_dtype)
+        self.kv = self.eng.kv_alloc(self.n_seqs, self.max_tokens) if kv_dtype == 'bf16' else self.eng.kv_alloc(self.n_seqs, self.max_tokens, dtype=kv_dtype)
+        self.closed = False
+        if getattr(model, '_pipes', None) is not None:
+            model._pipes.add(self)                        # the model refuses a kv_cache_dtype change while this is open
         self.kv.reset()
         self.dec = self.eng.shared_context()
         self.side = self.ops.stream(priority=-1)          # another priority level also lands on another hardware queue than the caller's
@@ -331,6 +335,7 @@ class ContinuousPipeline:
         if self.dec is not None:
             self.dec.close()
             self.dec = None
+        self.closed = True
 
     def __enter__(self):
         return self

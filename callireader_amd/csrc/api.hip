@@ -404,4 +404,26 @@ int cr_op_decode_attention(int which, const void* q, const void* kc, const void*
     return CR_OK;
 }
 
+int cr_op_decode_attention_e4m3(int which, const void* q, const void* kc, const void* vc, const float* ks, const float* vs, int max_tokens, const int32_t* seqs,
+                                const int32_t* lens, int B, int max_keys, float s_div, float* scratch, void* out, void* stream) {
+    if (!q || !kc || !vc || !ks || !vs || !seqs || !lens || !scratch || !out || B <= 0 || max_keys <= 0 || max_tokens < max_keys || (which != 0 && which != 1))
+        return cr_fail(CR_ERR_ARG, "cr_op_decode_attention_e4m3: bad argument");
+    if (which == 1) return cr_fail(CR_ERR_ARG, "cr_op_decode_attention_e4m3: the matrix-core split kernel reads bf16 caches only");
+    if (!decode_attn8_available())
+        return cr_fail(CR_ERR_ARG, "cr_op_decode_attention_e4m3: CR_DECODE_ATTN=0 selects the matrix-core split kernel, which reads bf16 caches only");
+    constexpr int HD = 128, NKV = 8, G = 4, D = NKV * G * HD;
+    AttnParams ap{};
+    ap.K8 = (const unsigned char*)kc; ap.V8 = (const unsigned char*)vc; ap.k_scale = ks; ap.v_scale = vs; ap.Q = (const bf16*)q; ap.O = (bf16*)out;
+    ap.k_bs = ap.v_bs = (int64_t)NKV * max_tokens * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)max_tokens * HD;
+    ap.s_bs = (int64_t)NKV * max_tokens; ap.s_hs = max_tokens;
+    ap.q_prescale = 1.0f; ap.s_div = s_div;
+    ap.q_bs = D; ap.q_rs = HD; ap.q_hs = G * HD; ap.o_bs = D; ap.o_rs = HD; ap.o_hs = G * HD;
+    ap.B = B; ap.H = NKV; ap.Sq = G; ap.Sk = 0; ap.kv_group = 1; ap.q_pos0 = 0;
+    ap.seq_map = seqs; ap.sk_arr = lens; ap.sk_add = 1;
+    ap.nsplit = ((max_keys + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
+    ap.part_ml = scratch; ap.part_o = scratch + (size_t)B * NKV * ap.nsplit * G * 2;
+    if (launch_flash_attn_split(ap, HD, (hipStream_t)stream) != CR_OK) return cr_fail(CR_ERR_HIP, "cr_op_decode_attention_e4m3: launch failed");
+    return CR_OK;
+}
+
 }  // extern "C"

@@ -432,6 +432,12 @@ int launch_flash_attn_split(const AttnParams& p, int head_dim, hipStream_t strea
     if (p.Sq <= 0 || p.Sq > 32 || p.H <= 0 || p.B <= 0 || p.nsplit <= 0 || !p.part_ml || !p.part_o) return CR_ERR_ARG;
     if ((p.q_rs & 7) || (p.k_rs & 7) || (p.v_rs & 7)) return CR_ERR_ARG;
     const bool dv = p.s_div != 1.0f;
+    if (p.K8 || p.V8) {                                       // an e4m3 cache: attention_decode.hip's e4m3 kernel or nothing (never bytes read as bf16)
+        if (!decode_attn8_supported(p, head_dim)) return CR_ERR_ARG;
+        if (launch_decode_attn(p, stream) != CR_OK) return CR_ERR_HIP;
+        hipLaunchKernelGGL((attn_combine_kernel<128>), dim3(p.Sq, p.H, p.B), dim3(128), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
+    }
     if (decode_attn_supported(p, head_dim)) {                 // attention_decode.hip writes the same partials; the combine is this file's
         if (launch_decode_attn(p, stream) != CR_OK) return CR_ERR_HIP;
         hipLaunchKernelGGL((attn_combine_kernel<128>), dim3(p.Sq, p.H, p.B), dim3(128), 0, stream, p);
@@ -443,6 +449,7 @@ int launch_flash_attn_split(const AttnParams& p, int head_dim, hipStream_t strea
 }
 
 int launch_flash_attn(const AttnParams& p, int head_dim, bool causal, hipStream_t stream) {
+    if (p.K8 || p.V8) return CR_ERR_ARG;                      // e4m3 K / V are read by the decode kernel only (prefill attends over bf16)
     if (p.Sq <= 0 || (p.Sk <= 0 && !p.sk_arr && !p.seg) || p.H <= 0 || p.B <= 0 || p.kv_group <= 0 || (p.seg && !causal)) return CR_ERR_ARG;
     if ((p.q_rs & 7) || (p.k_rs & 7) || (p.v_rs & 7) || (p.o_rs & 3)) return CR_ERR_ARG;
     if (vit_attn_supported(p, head_dim, causal)) return launch_vit_attn(p, stream);

@@ -34,9 +34,19 @@ struct AttnParams {
     int64_t qkv_ld;
     const bf16* rope_cos;     // [max_pos][128]
     const bf16* rope_sin;
+    // decode over an e4m3 cache (cr_kv_alloc_ex CR_KV_E4M3; K / V unused): K8 / V8 bytes addressed with the k_* / v_* strides above (one byte per element),
+    // one fp32 scale per cached row at k_scale / v_scale + slot * s_bs + head * s_hs + key.  Only attention_decode.hip's decode_attn8_kernel reads it.
+    const unsigned char* K8;
+    const unsigned char* V8;
+    const float* k_scale;
+    const float* v_scale;
+    int64_t s_bs, s_hs;
 };
 
 bool decode_attn_fold_supported(const AttnParams& p, int head_dim);
+// e4m3 caches: false when the process runs with CR_DECODE_ATTN=0 (the matrix-core split kernel reads bf16 only); launch_flash_attn_split then refuses them
+bool decode_attn8_available();
+bool decode_attn8_supported(const AttnParams& p, int head_dim);
 
 constexpr int ATTN_SPLIT_TILES = 4;      // 256 keys per split: depends only on the row's own key count
 

@@ -229,13 +229,202 @@ __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const AttnParams p)
     }
 }
 
+// ---- e4m3 cache (cr_kv_alloc_ex CR_KV_E4M3): the same streaming structure over 128-byte keys ----
+// A lane owns 16 bytes (16 dimensions) of every eighth key -- lane = (key sub-index 0..7, 16-byte chunk 0..7) -- so one load instruction still reads
+// 8 consecutive keys = ONE contiguous KiB; a wave's 64 keys are 8 K and 8 V loads per lane, all issued up front (256 bytes per lane), plus one fp32 scale
+// of K and of V per lane (key = the wave's first + lane: 256 contiguous bytes each), handed to the key's lanes by ds_bpermute.  Per key: 16 bytes -> 16
+// bf16 (exact: e4m3 is a subset of bf16), q . k by v_dot2c_f32_bf16, summed over the key's 8 lanes (quad_perm xor 1, xor 2, row_half_mirror: every
+// lane ends with the same sum), times the key's scale in fp32, then the bf16 kernel's rounding points (bf16, / sqrt(128), bf16).  P . V: the bf16
+// probability times the key's V scale in fp32, FMAs on the converted bytes, fp32 accumulation.  The two 8-key groups of a DPP row merge their partials
+// in registers (row_ror:8) in a fixed order, so the workgroup leaves 16 partials in LDS as the bf16 kernel does and merges them in index order: a row's
+// result depends on its own key count only.
+constexpr int IT8 = 8;                   // keys per lane group and wave (8 groups x 8 = 64 keys per wave)
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
+
+// sum over the 8 lanes of a half DPP row, left in every lane (the same adds, in the same order, in every lane group)
+__device__ __forceinline__ float half_row_sum8(float v) {
+    v += dpp<0xb1>(v);       // quad_perm [1, 0, 3, 2]
+    v += dpp<0x4e>(v);       // quad_perm [2, 3, 0, 1]
+    v += dpp<0x141>(v);      // row_half_mirror
+    return v;
+}
+__device__ __forceinline__ void e4m3x4_to_bf16(unsigned w, bf16x2_t& lo, bf16x2_t& hi) {
+    lo = __builtin_convertvector(__builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), bf16x2_t);     // exact both ways
+    hi = __builtin_convertvector(__builtin_amdgcn_cvt_pk_f32_fp8((int)w, true), bf16x2_t);
+}
+
+template <bool DIV>
+__global__ __launch_bounds__(256, 2) void decode_attn8_kernel(const AttnParams p) {
+    __shared__ __attribute__((aligned(16))) float s_o[16][NQ][HD];      // the workgroup's 16 partials: un-normalised O ...
+    __shared__ float s_ml[16][NQ][2];                                   // ... maximum and row sum
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int split = blockIdx.x, head = blockIdx.y, batch = blockIdx.z;
+    const int slot = p.seq_map ? p.seq_map[batch] : batch;
+    const int Sk = p.sk_arr ? p.sk_arr[slot] + p.sk_add : p.Sk;
+    const int64_t prow = (((int64_t)batch * p.H + head) * p.nsplit + split) * NQ;
+    if (split * 256 >= Sk) {                                  // a shorter row's empty split: (-inf, 0, 0)
+        for (int idx = tid; idx < NQ * HD; idx += 256) p.part_o[prow * HD + idx] = 0.f;
+        if (tid < NQ) { p.part_ml[(prow + tid) * 2] = -INFINITY; p.part_ml[(prow + tid) * 2 + 1] = 0.f; }
+        return;
+    }
+    const int ksub = lane >> 3, c = lane & 7, own = c & 3;
+    const int kw = split * 256 + wave * 64;                   // the wave's first key
+    const int key0 = kw + ksub;                               // this lane's keys: key0 + 8 i
+    const unsigned char* Kb = p.K8 + (int64_t)slot * p.k_bs + (int64_t)head * p.k_hs;
+    const unsigned char* Vb = p.V8 + (int64_t)slot * p.v_bs + (int64_t)head * p.v_hs;
+    const float* KSb = p.k_scale + (int64_t)slot * p.s_bs + (int64_t)head * p.s_hs;
+    const float* VSb = p.v_scale + (int64_t)slot * p.s_bs + (int64_t)head * p.s_hs;
+    const unsigned k_rs = (unsigned)p.k_rs, v_rs = (unsigned)p.v_rs, lane_off = (unsigned)c * 16u;
+    bf16x8 q[NQ][2];                                          // dimensions 16 c .. 16 c + 15 of the four query heads
+    {
+        const bf16* qp = p.Q + (int64_t)batch * p.q_bs + (int64_t)head * p.q_hs + c * 16;
+#pragma unroll
+        for (int h = 0; h < NQ; h++) { q[h][0] = *(const bf16x8*)(qp + (int64_t)h * p.q_rs); q[h][1] = *(const bf16x8*)(qp + (int64_t)h * p.q_rs + 8); }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    u32x4_t kr[IT8], vr[IT8];
+#pragma unroll
+    for (int i = 0; i < IT8; i++) kr[i] = __builtin_nontemporal_load((const u32x4_t*)(Kb + ((unsigned)min(key0 + 8 * i, Sk - 1) * k_rs + lane_off)));
+#pragma unroll
+    for (int i = 0; i < IT8; i++) vr[i] = __builtin_nontemporal_load((const u32x4_t*)(Vb + ((unsigned)min(key0 + 8 * i, Sk - 1) * v_rs + lane_off)));
+    const float ks_lane = KSb[min(kw + lane, Sk - 1)], vs_lane = VSb[min(kw + lane, Sk - 1)];
+    __builtin_amdgcn_sched_barrier(0);
+    const float inv_div = 1.0f / p.s_div;
+
+    // ---- scores of this lane's own query head for its group's 8 keys: s_k . (q . k^) in fp32, then bf16, / sqrt(128), bf16 ----
+    float sc[IT8];
+#pragma unroll
+    for (int i = 0; i < IT8; i++) {
+        bf16x2_t kk[8];
+#pragma unroll
+        for (int w = 0; w < 4; w++) e4m3x4_to_bf16(kr[i][w], kk[2 * w], kk[2 * w + 1]);
+        float d[NQ];
+#pragma unroll
+        for (int h = 0; h < NQ; h++) {
+            float a = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                const bf16x2_t qq = {q[h][e >> 2][2 * (e & 3)], q[h][e >> 2][2 * (e & 3) + 1]};
+                a = __builtin_amdgcn_fdot2_f32_bf16(qq, kk[e], a, false);
+            }
+            d[h] = half_row_sum8(a);
+        }
+        float s = own == 0 ? d[0] : own == 1 ? d[1] : own == 2 ? d[2] : d[3];
+        s = rbf1(s * __shfl(ks_lane, ksub + 8 * i, 64));
+        if (DIV) s = rbf1(s * inv_div);
+        sc[i] = key0 + 8 * i < Sk ? s : -INFINITY;
+    }
+    float m = sc[0];
+#pragma unroll
+    for (int i = 1; i < IT8; i++) m = fmaxf(m, sc[i]);
+    const float m2 = (m == -INFINITY ? 0.f : m) * LOG2E;      // a group with no key below Sk: every P is exp(-inf) = 0
+    float l = 0.f;
+#pragma unroll
+    for (int i = 0; i < IT8; i++) {
+        const float pe = __builtin_amdgcn_exp2f(fmaf(sc[i], LOG2E, -m2));
+        l += pe;                                              // fp32 softmax: the sum of the un-rounded exponentials
+        sc[i] = rbf1(pe);                                     // probabilities go to bf16 before .V
+    }
+
+    // ---- O[h][16 dims of this lane] += bf16(P[h]) * s_v . V^ ----
+    float o[NQ][16];
+#pragma unroll
+    for (int h = 0; h < NQ; h++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) o[h][e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < IT8; i++) {
+        float v[16];
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)vr[i][w], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)vr[i][w], true);
+            v[4 * w] = lo[0]; v[4 * w + 1] = lo[1]; v[4 * w + 2] = hi[0]; v[4 * w + 3] = hi[1];
+        }
+        const float sv = __shfl(vs_lane, ksub + 8 * i, 64);
+        const float p0 = dpp<0x00>(sc[i]) * sv, p1 = dpp<0x55>(sc[i]) * sv, p2 = dpp<0xaa>(sc[i]) * sv, p3 = dpp<0xff>(sc[i]) * sv;     // quad_perm: lane (quad, h) holds head h's P
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            o[0][e] = fmaf(p0, v[e], o[0][e]);
+            o[1][e] = fmaf(p1, v[e], o[1][e]);
+            o[2][e] = fmaf(p2, v[e], o[2][e]);
+            o[3][e] = fmaf(p3, v[e], o[3][e]);
+        }
+    }
+
+    // ---- groups 2k and 2k + 1 of a wave (one DPP row) merge in registers; the even group's lanes hold the result ----
+    float mh[NQ] = {dpp<0x00>(m), dpp<0x55>(m), dpp<0xaa>(m), dpp<0xff>(m)};
+    float lh[NQ] = {dpp<0x00>(l), dpp<0x55>(l), dpp<0xaa>(l), dpp<0xff>(l)};
+#pragma unroll
+    for (int h = 0; h < NQ; h++) {
+        const float mp = dpp<0x128>(mh[h]), lp = dpp<0x128>(lh[h]);      // row_ror:8: the other group of the row
+        const float mx = fmaxf(mh[h], mp);
+        const float wa = mh[h] == -INFINITY ? 0.f : __expf(mh[h] - mx), wb = mp == -INFINITY ? 0.f : __expf(mp - mx);
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const float op = dpp<0x128>(o[h][e]);
+            o[h][e] = wa * o[h][e] + wb * op;
+        }
+        lh[h] = wa * lh[h] + wb * lp;
+        mh[h] = mx;
+    }
+    const int j = wave * 4 + (ksub >> 1);
+    if (!(ksub & 1)) {
+#pragma unroll
+        for (int h = 0; h < NQ; h++)
+#pragma unroll
+            for (int e = 0; e < 16; e += 4) *(f32x4*)&s_o[j][h][c * 16 + e] = f32x4{o[h][e], o[h][e + 1], o[h][e + 2], o[h][e + 3]};
+        if (c == 0) {
+#pragma unroll
+            for (int h = 0; h < NQ; h++) { s_ml[j][h][0] = mh[h]; s_ml[j][h][1] = lh[h]; }
+        }
+    }
+    __syncthreads();
+    {
+        const int h = tid >> 6, d0 = (tid & 63) * 2;
+        float M = -INFINITY;
+#pragma unroll
+        for (int jj = 0; jj < 16; jj++) M = fmaxf(M, s_ml[jj][h][0]);
+        float L = 0.f, a0 = 0.f, a1 = 0.f;
+        if (M != -INFINITY) {
+#pragma unroll
+            for (int jj = 0; jj < 16; jj++) {
+                const float mj = s_ml[jj][h][0];
+                const float w = mj == -INFINITY ? 0.f : __expf(mj - M);
+                L += w * s_ml[jj][h][1];
+                a0 += w * s_o[jj][h][d0];
+                a1 += w * s_o[jj][h][d0 + 1];
+            }
+        }
+        *(f32x2_t*)(p.part_o + (prow + h) * HD + d0) = f32x2_t{a0, a1};
+        if ((tid & 63) == 0) { p.part_ml[(prow + h) * 2] = M; p.part_ml[(prow + h) * 2 + 1] = L; }
+    }
+}
+
+bool decode_attn_off() {
+    static const bool off = [] { const char* e = getenv("CR_DECODE_ATTN"); return e && e[0] == '0'; }();      // A/B aid: the matrix-core split kernel
+    return off;
+}
+
 }  // namespace
+
+bool decode_attn8_available() { return !decode_attn_off(); }
+
+// the e4m3 kernel's shape: the streaming kernel's, with 128-byte keys (16-byte aligned rows and planes) and fp32 scales
+bool decode_attn8_supported(const AttnParams& p, int head_dim) {
+    return decode_attn8_available() && !p.force_matrix_core && p.K8 && p.V8 && p.k_scale && p.v_scale && !p.qkv_part && p.kv_group == 1 && head_dim == HD &&
+           p.Sq == NQ && ATTN_SPLIT_TILES == 4 && p.q_prescale == 1.0f && p.part_ml && p.part_o && p.nsplit > 0 &&
+           (p.q_rs & 7) == 0 && (p.q_hs & 7) == 0 && (p.q_bs & 7) == 0 && (p.k_rs & 15) == 0 && (p.v_rs & 15) == 0 && (p.k_hs & 15) == 0 && (p.v_hs & 15) == 0 &&
+           (p.k_bs & 15) == 0 && (p.v_bs & 15) == 0 && (p.sk_arr || p.Sk > 0) && p.k_rs > 0 && p.v_rs > 0 && p.k_rs < 65536 && p.v_rs < 65536 &&
+           (int64_t)p.nsplit * 256 * (p.k_rs > p.v_rs ? p.k_rs : p.v_rs) < (1ll << 32) &&
+           (((uintptr_t)p.Q | (uintptr_t)p.K8 | (uintptr_t)p.V8) & 15) == 0 && (((uintptr_t)p.k_scale | (uintptr_t)p.v_scale) & 3) == 0 &&
+           ((uintptr_t)p.part_o & 7) == 0;
+}
 
 // the shape the kernel is written for: d = 128, four query rows per (batch, head) (the GQA group), splits of 256 keys (ATTN_SPLIT_TILES = 4)
 bool decode_attn_supported(const AttnParams& p, int head_dim) {
-    static const bool off = [] { const char* e = getenv("CR_DECODE_ATTN"); return e && e[0] == '0'; }();      // A/B aid: the matrix-core split kernel
     // kv_group == 1: the kernel indexes K / V by blockIdx.y itself, i.e. H counts KV heads and the GQA group is the Sq = 4 query rows
-    return !off && !p.force_matrix_core && p.kv_group == 1 && head_dim == HD && p.Sq == NQ && ATTN_SPLIT_TILES == 4 && p.q_prescale == 1.0f && p.part_ml && p.part_o && p.nsplit > 0 &&
+    return !decode_attn_off() && !p.K8 && !p.force_matrix_core && p.kv_group == 1 && head_dim == HD && p.Sq == NQ && ATTN_SPLIT_TILES == 4 && p.q_prescale == 1.0f && p.part_ml && p.part_o && p.nsplit > 0 &&
            (p.q_rs & 7) == 0 && (p.q_hs & 7) == 0 && (p.q_bs & 7) == 0 && (p.k_rs & 7) == 0 && (p.v_rs & 7) == 0 && (p.k_hs & 7) == 0 && (p.v_hs & 7) == 0 &&
            (p.k_bs & 7) == 0 && (p.v_bs & 7) == 0 && (p.sk_arr || p.Sk > 0) && p.k_rs > 0 && p.v_rs > 0 && p.k_rs < 65536 && p.v_rs < 65536 &&
            (int64_t)p.nsplit * 256 * (p.k_rs > p.v_rs ? p.k_rs : p.v_rs) < (1ll << 32) &&      // key * row stride stays in the 32-bit per-lane offset
@@ -251,7 +440,11 @@ bool decode_attn_fold_supported(const AttnParams& p, int head_dim) {
 
 int launch_decode_attn(const AttnParams& p, hipStream_t stream) {
     const dim3 grid(p.nsplit, p.H, p.B);
-    if (p.qkv_part) {
+    if (p.K8) {
+        if (!decode_attn8_supported(p, HD)) return CR_ERR_ARG;
+        if (p.s_div != 1.0f) hipLaunchKernelGGL((decode_attn8_kernel<true>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((decode_attn8_kernel<false>), grid, dim3(256), 0, stream, p);
+    } else if (p.qkv_part) {
         if (!decode_attn_fold_supported(p, HD)) return CR_ERR_ARG;
         if (p.s_div != 1.0f) hipLaunchKernelGGL((decode_attn_kernel<true, true>), grid, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((decode_attn_kernel<false, true>), grid, dim3(256), 0, stream, p);

@@ -24,8 +24,14 @@
 struct cr_kv {
     cr_ctx* ctx;
     int n_seqs, max_tokens, gen_cap, layers;
-    bf16* k;             // [layers][n_seqs][8][max_tokens][128]
+    int fmt;             // CR_KV_BF16 | CR_KV_E4M3 (cr_kv_alloc_ex), fixed for the cache's lifetime
+    bf16* k;             // [layers][n_seqs][8][max_tokens][128]  (bf16 caches only)
     bf16* v;
+    // e4m3 caches: one row = the 128 values of (layer, seq, KV head, position) as OCP e4m3fn bytes + one fp32 scale (max|x| / 448, 1 for a zero row)
+    unsigned char* k8;   // [layers][n_seqs][8][max_tokens][128]
+    unsigned char* v8;
+    float* ks;           // [layers][n_seqs][8][max_tokens]: a wave's 64 keys read 256 contiguous bytes of scales
+    float* vs;
     int32_t* d_len;      // [n_seqs] tokens cached
     int32_t* d_ngen;     // [n_seqs] ids generated
     int64_t* d_gen;      // [n_seqs][gen_cap]
@@ -41,7 +47,8 @@ struct cr_kv {
     std::vector<int> len, ngen;
     // batched decode as a hipGraph (CR_DECODE_GRAPH=1): a step is ~290 short launches whose parameters only change with
     // the row count and the number of attention splits (positions, ids and cache lengths live in device memory), so the
-    // launch sequence is captured once per (rows, splits, penalty) and replayed.  OFF by default: on ROCm 7.2 / MI355X the
+    // launch sequence is captured once per (rows, splits, penalty) and replayed.  The captures live in the cache object, whose format never
+    // changes: a bf16 capture can never be replayed on an e4m3 cache.  OFF by default: on ROCm 7.2 / MI355X the
     // replay measured 0.3 % slower than plain launches at 64 pages per step (6.86 vs 6.88 pages/s) and 5 % slower for a
     // single page (0.711 vs 0.678 s) -- the ~3 us gaps between dependent kernels are not launch overhead the graph removes
     struct DecodeGraph { int n, nsplit; float penalty; char* ws; const int32_t* seqs; uint64_t weight_gen; hipGraphExec_t exec; int warm; };
@@ -128,15 +135,31 @@ __global__ __launch_bounds__(256) void move_rows_kernel(const bf16* __restrict__
     dp[threadIdx.x + 256] = sp[threadIdx.x + 256];
 }
 
+// maximum over the 16 lanes of a DPP row, left in every lane
+__device__ __forceinline__ float row_max16(float v) {
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, true)));      // row_ror:8
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, true)));      // row_ror:4
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, true)));      // row_ror:2
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, true)));      // row_ror:1
+    return v;
+}
+
 // RoPE + split of the fused wqkv output (modeling_internlm2.py:359-388, 233-247).
 // qkv row = [8 groups][4 q | k | v][128].  q_embed = bf16(bf16(q*cos) + bf16(rotate_half(q)*sin)), same for k.
 // grid (rows, 8 groups), 128 threads: thread = (slot 0..7 [6 used], 16-B chunk 0..15).
+// Q8 (e4m3 cache): the K / V rows go to the cache as e4m3 bytes + one fp32 scale each (the rule of quant_fp8_rows_kernel below; a slot's 16 chunks
+// are one DPP row, so the row maximum is four rotate-max steps), and -- when kc / vc are given (prefill) -- as bf16 into the prefill's staging
+// [pages][8][stage_T][128] at (row_page[row], pos), which the prefill attention reads instead of the cache.
+template <bool Q8 = false>
 __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ cosT,
                                                          const bf16* __restrict__ sinT, bf16* __restrict__ q_out,
                                                          bf16* __restrict__ kc, bf16* __restrict__ vc, int pos0, int seq0,
                                                          const int32_t* __restrict__ seqs, const int32_t* __restrict__ lens,
                                                          const int32_t* __restrict__ row_pos, int max_tokens,
-                                                         const float* __restrict__ part, int splits) {
+                                                         const float* __restrict__ part, int splits,
+                                                         unsigned char* __restrict__ k8 = nullptr, unsigned char* __restrict__ v8 = nullptr,
+                                                         float* __restrict__ ks = nullptr, float* __restrict__ vs = nullptr,
+                                                         const int32_t* __restrict__ row_page = nullptr, int stage_T = 0) {
     // part != nullptr (decode): the wqkv output arrives as `splits` fp32 K-slices [s][rows][QKV]; their sum in slice
     // order, rounded once, is the bf16 linear output the reference rotates
     const int row = blockIdx.x, grp = blockIdx.y;
@@ -171,6 +194,27 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
             y[e] = f2bf(rbf(bf2f(x[e]) * bf2f(cs[e])) + rbf(sign * bf2f(xp[e]) * bf2f(sn[e])));
     } else {
         y = x;
+    }
+    if (Q8 && slot >= 4) {
+        float mx = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) mx = fmaxf(mx, fabsf(bf2f(y[e])));
+        mx = row_max16(mx);
+        const float sc = mx > 0.f ? mx / 448.0f : 1.0f;
+        const float inv = 1.0f / sc;
+        unsigned lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[0]) * inv, bf2f(y[1]) * inv, lo, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[2]) * inv, bf2f(y[3]) * inv, lo, true);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[4]) * inv, bf2f(y[5]) * inv, hi, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[6]) * inv, bf2f(y[7]) * inv, hi, true);
+        const int64_t r8 = ((int64_t)seq * NKV + grp) * max_tokens + pos;
+        *(uint2*)((slot == 4 ? k8 : v8) + r8 * HD + c * 8) = make_uint2(lo, hi);
+        if (c == 0) (slot == 4 ? ks : vs)[r8] = sc;
+        if (kc) {
+            bf16* base = slot == 4 ? kc : vc;
+            *(bf16x8*)(base + (((int64_t)row_page[row] * NKV + grp) * stage_T + pos) * HD + c * 8) = y;
+        }
+        return;
     }
     bf16* dst;
     if (slot < 4) dst = q_out + (int64_t)row * D + (grp * 4 + slot) * HD;
@@ -360,13 +404,23 @@ int layer_weights(cr_ctx* c, int l, LayerW& w) {
 
 struct Segment { int seq, row0, S, pos0; };     // a page's rows inside a batched prefill
 
+// Prefill into an e4m3 cache: the prompts' bf16 K / V of the current layer go to a staging buffer [pages][8][T][128] (T = the longest prompt) that the
+// prefill attention reads; the cache gets the e4m3 rows.  row_page: page index of every prompt row; seg / seg_last: d_seg / d_seg_last with the page
+// index in place of the cache slot.
+struct PrefillStage { int T; const int32_t* row_page; const int32_t* seg; const int32_t* seg_last; };
+size_t prefill_stage_bytes(int n_pages, int T) { return (size_t)2 * n_pages * NKV * T * HD * 2; }
+
 // The decoder stack over M rows (prefill: M = all prompt rows of the pages in `segs`; decode: M = n sequences, one row each).
 // d_last / d_seg_last (prefill): the pages' last rows and, as attention segments, the rows that share a wave with them -- see the final layer below.
 int run_layers(cr_ctx* c, cr_kv* kv, bf16* x, int M, bool decode, const std::vector<Segment>& segs, const int32_t* d_row_seq,
                const int32_t* d_row_pos, const int32_t* d_seqs, int nsplit, hipStream_t st, const int32_t* d_seg = nullptr,
-               const int32_t* d_last = nullptr, const int32_t* d_seg_last = nullptr) {
+               const int32_t* d_last = nullptr, const int32_t* d_seg_last = nullptr, const PrefillStage* stg = nullptr) {
     const int ff = (int)WT(c, "derived.w13.0")->shape[0] / 2;
+    const bool kv8 = kv->fmt == CR_KV_E4M3;
+    if (kv8 && !decode && !stg) return cr_fail(CR_ERR_STATE, "e4m3 cache: prefill without its bf16 staging");
     Arena ar(c->ws);
+    bf16* stage = kv8 && !decode ? ar.take<bf16>(prefill_stage_bytes((int)segs.size(), stg->T) / 2) : nullptr;
+    const int64_t stage_half = kv8 && !decode ? (int64_t)segs.size() * NKV * stg->T * HD : 0;
     float* part = decode ? ar.take<float>(attn_split_ws_floats(M, NKV, NH / NKV, nsplit, HD)) : nullptr;
     bf16* h = ar.take<bf16>((size_t)M * D);
     bf16* qkv = ar.take<bf16>((size_t)M * QKV);
@@ -402,7 +456,8 @@ int run_layers(cr_ctx* c, cr_kv* kv, bf16* x, int M, bool decode, const std::vec
     // small batches (<= DECODE_FUSED_MAX_ROWS = 8 rows): gemm_decode.hip folds the norms, RoPE + split and the residual adds into the five GEMMs -- six launches
     // per layer instead of nine, every sum in the order of the kernels below (a row's bits do not depend on its batch): its virtual slices are
     // compiled in, so the path is only taken while the K-sliced kernels' geometry (cost model or CR_PARTIAL_GEOM) is the one they reproduce
-    const bool fused = sliced && c->fused_decode && !c->fp8_decode && decode_fused_supported(M, ff) &&
+    // (an e4m3 cache takes the separate kernels: the fused wqkv epilogue writes bf16 cache rows)
+    const bool fused = sliced && c->fused_decode && !c->fp8_decode && !kv8 && decode_fused_supported(M, ff) &&
                        s_qkv == DEC_SLICES_WQKV && s_o == DEC_SLICES_WO && s_2 == DEC_SLICES_W2;
     // cr_llm_hidden_probe (parity tooling): rows [row0, row0 + rows) of the residual stream before layer 0 and after every layer
     auto probe = [&](int slot) -> int {
@@ -415,8 +470,12 @@ int run_layers(cr_ctx* c, cr_kv* kv, bf16* x, int M, bool decode, const std::vec
     for (int l = 0; l < c->d.llm_layers; l++) {
         LayerW w;
         CR_TRY(layer_weights(c, l, w));
-        bf16* kc = kv->k + l * per_layer;
-        bf16* vc = kv->v + l * per_layer;
+        bf16* kc = kv8 ? stage : kv->k + l * per_layer;                 // e4m3 cache: the prefill's bf16 staging (nullptr in decode)
+        bf16* vc = kv8 ? (stage ? stage + stage_half : nullptr) : kv->v + l * per_layer;
+        unsigned char* k8 = kv8 ? kv->k8 + l * per_layer : nullptr;
+        unsigned char* v8 = kv8 ? kv->v8 + l * per_layer : nullptr;
+        float* ks8 = kv8 ? kv->ks + l * (per_layer / HD) : nullptr;
+        float* vs8 = kv8 ? kv->vs + l * (per_layer / HD) : nullptr;
         // prefill on the fp8 matrix-core path: both norms emit e4m3 rows + scales, wqkv and w1|w3 take them (gemm256 F8)
         if (fused) {
             DecodeGemmParams dp{};
@@ -464,22 +523,34 @@ int run_layers(cr_ctx* c, cr_kv* kv, bf16* x, int M, bool decode, const std::vec
         ap.K = kc; ap.V = vc; ap.Q = q; ap.O = ao;
         ap.k_bs = ap.v_bs = (int64_t)NKV * kv->max_tokens * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)kv->max_tokens * HD;
         ap.q_prescale = 1.0f; ap.s_div = 11.313708498984761f;      // math.sqrt(128)
+        if (kv8 && !decode) {                                      // the prefill attends over its staging
+            ap.k_bs = ap.v_bs = (int64_t)NKV * stg->T * HD; ap.k_hs = ap.v_hs = (int64_t)stg->T * HD;
+        } else if (kv8) {                                          // the decode over the e4m3 cache (attention_decode.hip, decode_attn8_kernel)
+            ap.K = ap.V = nullptr;
+            ap.K8 = k8; ap.V8 = v8; ap.k_scale = ks8; ap.v_scale = vs8;
+            ap.s_bs = (int64_t)NKV * kv->max_tokens; ap.s_hs = kv->max_tokens;
+        }
         // decode, 9..64 rows: RoPE + split + the new token's cache row are folded into the attention kernel (attention_decode.hip, FOLD) where it qualifies
+        // (not on an e4m3 cache: rope_split_kernel<true> quantises the new rows, decode_attn8_kernel reads them back from the cache)
         bool rope_folded = false;
-        if (sliced && c->fold_rope) {
+        if (sliced && c->fold_rope && !kv8) {
             AttnParams fp = ap;
             fp.q_bs = D; fp.q_rs = HD; fp.q_hs = 4 * HD; fp.B = M; fp.H = NKV; fp.Sq = NH / NKV; fp.kv_group = 1; fp.sk_arr = kv->d_len; fp.sk_add = 1;
             fp.nsplit = nsplit; fp.part_ml = part; fp.part_o = part + (size_t)M * NKV * nsplit * (NH / NKV) * 2;
             fp.qkv_part = pbuf; fp.qkv_splits = s_qkv; fp.qkv_ld = QKV; fp.rope_cos = cosT; fp.rope_sin = sinT;
             rope_folded = decode_attn_fold_supported(fp, HD);
         }
-        if (!rope_folded)
-            hipLaunchKernelGGL(rope_split_kernel, dim3(M, NKV), dim3(128), 0, st, qkv, cosT, sinT, q, kc, vc, 0, 0,
+        if (kv8)
+            hipLaunchKernelGGL(rope_split_kernel<true>, dim3(M, NKV), dim3(128), 0, st, qkv, cosT, sinT, q, kc, vc, 0, 0,
                                decode ? d_seqs : d_row_seq, decode ? kv->d_len : nullptr, decode ? nullptr : d_row_pos, kv->max_tokens,
-                               (const float*)(sliced ? pbuf : nullptr), s_qkv);
+                               (const float*)(sliced ? pbuf : nullptr), s_qkv, k8, v8, ks8, vs8, decode ? nullptr : stg->row_page, decode ? 0 : stg->T);
+        else if (!rope_folded)
+            hipLaunchKernelGGL(rope_split_kernel<false>, dim3(M, NKV), dim3(128), 0, st, qkv, cosT, sinT, q, kc, vc, 0, 0,
+                               decode ? d_seqs : d_row_seq, decode ? kv->d_len : nullptr, decode ? nullptr : d_row_pos, kv->max_tokens,
+                               (const float*)(sliced ? pbuf : nullptr), s_qkv, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
         if (last_rows_only && l + 1 == c->d.llm_layers) {
             ap.q_bs = 0; ap.q_rs = D; ap.q_hs = HD; ap.o_bs = 0; ap.o_rs = D; ap.o_hs = HD;
-            ap.H = NH; ap.kv_group = NH / NKV; ap.B = n_pages; ap.seg = d_seg_last; ap.Sq = 32;
+            ap.H = NH; ap.kv_group = NH / NKV; ap.B = n_pages; ap.seg = kv8 ? stg->seg_last : d_seg_last; ap.Sq = 32;
             if (launch_flash_attn(ap, HD, true, st) != CR_OK) return cr_fail(CR_ERR_HIP, "prefill attention launch failed");
             hipLaunchKernelGGL(move_rows_kernel<true>, dim3(n_pages), dim3(256), 0, st, ao, d_last, aol);
             hipLaunchKernelGGL(move_rows_kernel<true>, dim3(n_pages), dim3(256), 0, st, x, d_last, xl);
@@ -497,7 +568,7 @@ int run_layers(cr_ctx* c, cr_kv* kv, bf16* x, int M, bool decode, const std::vec
             // causal attention is per page, the linear layers see all pages at once; the pages' query blocks go out as ONE launch
             // (segments: first row, rows, first position, cache slot), longest blocks first: a launch per page left its 800
             // workgroups of 2..50 key tiles each a ragged tail on 512 slots
-            ap.B = (int)segs.size(); ap.seg = d_seg; ap.Sq = 0;
+            ap.B = (int)segs.size(); ap.seg = kv8 ? stg->seg : d_seg; ap.Sq = 0;
             for (const Segment& sg : segs) ap.Sq = sg.S > ap.Sq ? sg.S : ap.Sq;
             if (launch_flash_attn(ap, HD, true, st) != CR_OK) return cr_fail(CR_ERR_HIP, "prefill attention launch failed");
         } else {
@@ -549,11 +620,12 @@ int run_layers(cr_ctx* c, cr_kv* kv, bf16* x, int M, bool decode, const std::vec
     return CR_OK;
 }
 
-size_t layers_ws(cr_ctx* c, int M, int nsplit = 0, int n_pages = 0) {
+size_t layers_ws(cr_ctx* c, int M, int nsplit = 0, int n_pages = 0, size_t stage = 0) {
     const size_t ff = (size_t)WT(c, "derived.w13.0")->shape[0] / 2;
     const size_t last_rows = (size_t)n_pages * (3 * D + ff) * 2 + 4 * 256;      // the final layer's compact rows (prefill)
     const size_t sliced = nsplit > 0 && M <= 64 ? (size_t)8 * QKV * M * 4 : 0;       // K-slice partial sums of the decode GEMMs
-    return ((size_t)M * D * 4 + (size_t)M * QKV + (size_t)M * ff) * 2 + attn_split_ws_floats(M, NKV, NH / NKV, nsplit, HD) * 4 + sliced + (size_t)M * 4 + (size_t)M * ff + last_rows + 8192;
+    return ((size_t)M * D * 4 + (size_t)M * QKV + (size_t)M * ff) * 2 + attn_split_ws_floats(M, NKV, NH / NKV, nsplit, HD) * 4 + sliced + (size_t)M * 4 + (size_t)M * ff + last_rows + 8192 +
+           (stage ? stage + 256 : 0);       // an e4m3 cache's prefill staging (PrefillStage)
 }
 
 }  // namespace
@@ -824,14 +896,23 @@ int cr_embed_splice(cr_ctx* c, const int64_t* ids, int S, const void* vit, int n
     return CR_OK;
 }
 
-int cr_kv_alloc(cr_ctx* c, int n_seqs, int max_tokens, cr_kv** out) {
-    if (!c || !out || n_seqs <= 0 || max_tokens <= 0) return cr_fail(CR_ERR_ARG, "cr_kv_alloc: bad argument");
+int cr_kv_alloc(cr_ctx* c, int n_seqs, int max_tokens, cr_kv** out) { return cr_kv_alloc_ex(c, n_seqs, max_tokens, CR_KV_BF16, out); }
+
+int cr_kv_alloc_ex(cr_ctx* c, int n_seqs, int max_tokens, int format, cr_kv** out) {
+    if (format != CR_KV_BF16 && format != CR_KV_E4M3)
+        return cr_fail(CR_ERR_ARG, "cr_kv_alloc_ex: unknown cache format %d (CR_KV_BF16 = 0, CR_KV_E4M3 = 1)", format);
+    if (!c || !out || n_seqs <= 0 || max_tokens <= 0) return cr_fail(CR_ERR_ARG, "cr_kv_alloc: bad argument (null context or output, or a size <= 0)");
     if (max_tokens > c->d.max_pos) return cr_fail(CR_ERR_ARG, "cr_kv_alloc: max_tokens %d exceeds the RoPE table (%d rows)", max_tokens, c->d.max_pos);
     CR_HIP(hipSetDevice(c->device));
     cr_kv* kv = new cr_kv();
-    kv->ctx = c; kv->n_seqs = n_seqs; kv->max_tokens = max_tokens; kv->gen_cap = 4096; kv->layers = c->d.llm_layers;
-    const size_t bytes = (size_t)kv->layers * n_seqs * NKV * max_tokens * HD * 2;
-    if (hipMalloc((void**)&kv->k, bytes) != hipSuccess || hipMalloc((void**)&kv->v, bytes) != hipSuccess ||
+    kv->ctx = c; kv->n_seqs = n_seqs; kv->max_tokens = max_tokens; kv->gen_cap = 4096; kv->layers = c->d.llm_layers; kv->fmt = format;
+    const size_t rows = (size_t)kv->layers * n_seqs * NKV * max_tokens;
+    const size_t bytes = rows * HD * (format == CR_KV_E4M3 ? 1 : 2);
+    const bool data_ok = format == CR_KV_E4M3
+        ? hipMalloc((void**)&kv->k8, bytes) == hipSuccess && hipMalloc((void**)&kv->v8, bytes) == hipSuccess &&
+          hipMalloc((void**)&kv->ks, rows * 4) == hipSuccess && hipMalloc((void**)&kv->vs, rows * 4) == hipSuccess
+        : hipMalloc((void**)&kv->k, bytes) == hipSuccess && hipMalloc((void**)&kv->v, bytes) == hipSuccess;
+    if (!data_ok ||
         hipMalloc((void**)&kv->d_len, n_seqs * 4) != hipSuccess || hipMalloc((void**)&kv->d_ngen, n_seqs * 4) != hipSuccess ||
         hipMalloc((void**)&kv->d_stop, ((size_t)4 * n_seqs + 1) * 4) != hipSuccess ||
         hipMalloc((void**)&kv->d_samp, (size_t)n_seqs * 24) != hipSuccess ||
@@ -858,6 +939,10 @@ int cr_kv_free(cr_kv* kv) {
     hipDeviceSynchronize();
     if (kv->k) hipFree(kv->k);
     if (kv->v) hipFree(kv->v);
+    if (kv->k8) hipFree(kv->k8);
+    if (kv->v8) hipFree(kv->v8);
+    if (kv->ks) hipFree(kv->ks);
+    if (kv->vs) hipFree(kv->vs);
     if (kv->d_len) hipFree(kv->d_len);
     if (kv->d_ngen) hipFree(kv->d_ngen);
     if (kv->d_stop) hipFree(kv->d_stop);
@@ -869,6 +954,8 @@ int cr_kv_free(cr_kv* kv) {
 }
 
 int cr_kv_length(const cr_kv* kv, int seq) { return (kv && seq >= 0 && seq < kv->n_seqs) ? kv->len[seq] : -1; }
+
+int cr_kv_format(const cr_kv* kv) { return kv ? kv->fmt : cr_fail(CR_ERR_ARG, "cr_kv_format: null cache"); }
 
 int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
     if (!kv || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_reset: bad sequence");
@@ -925,9 +1012,22 @@ int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream) {
 int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, void* stream) {
     if (!kv || !out || layer < 0 || layer >= kv->layers || seq < 0 || seq >= kv->n_seqs || pos < 0 || pos >= kv->max_tokens || (which != 0 && which != 1))
         return cr_fail(CR_ERR_ARG, "cr_kv_read: bad argument");
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_read: the cache holds e4m3 rows, not bf16 (format %d): read them with cr_kv_read_e4m3", kv->fmt);
     CR_HIP(hipSetDevice(kv->ctx->device));
     const bf16* base = (which ? kv->v : kv->k) + (((int64_t)layer * kv->n_seqs + seq) * NKV * kv->max_tokens + pos) * HD;
     CR_HIP(hipMemcpy2DAsync(out, HD * 2, base, (size_t)kv->max_tokens * HD * 2, HD * 2, NKV, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return CR_OK;
+}
+
+int cr_kv_read_e4m3(cr_kv* kv, int layer, int seq, int pos, int which, uint8_t* q_out, float* s_out, void* stream) {
+    if (!kv || !q_out || !s_out || layer < 0 || layer >= kv->layers || seq < 0 || seq >= kv->n_seqs || pos < 0 || pos >= kv->max_tokens ||
+        (which != 0 && which != 1))
+        return cr_fail(CR_ERR_ARG, "cr_kv_read_e4m3: bad argument");
+    if (kv->fmt != CR_KV_E4M3) return cr_fail(CR_ERR_ARG, "cr_kv_read_e4m3: the cache holds bf16 rows (format %d): read them with cr_kv_read", kv->fmt);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    const int64_t row = ((int64_t)layer * kv->n_seqs + seq) * NKV * kv->max_tokens + pos;
+    CR_HIP(hipMemcpy2DAsync(q_out, HD, (which ? kv->v8 : kv->k8) + row * HD, (size_t)kv->max_tokens * HD, HD, NKV, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    CR_HIP(hipMemcpy2DAsync(s_out, 4, (which ? kv->vs : kv->ks) + row, (size_t)kv->max_tokens * 4, 4, NKV, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return CR_OK;
 }
 
@@ -952,14 +1052,20 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_prefill_batch: sequence %d listed twice", s);
         if (kv->len[s] + lens[i] > kv->max_tokens)
             return cr_fail(CR_ERR_ARG, "cr_llm_prefill: %d + %d tokens exceed the cache (%d)", kv->len[s], lens[i], kv->max_tokens);
+        if (kv->fmt == CR_KV_E4M3 && kv->len[s] != 0)
+            return cr_fail(CR_ERR_ARG, "cr_llm_prefill: sequence %d of an e4m3 cache already holds %d tokens (the prefill attends in bf16 and an e4m3 cache "
+                           "keeps no bf16 copy of a prefix: cr_kv_reset it first)", s, kv->len[s]);
         segs.push_back({s, M, lens[i], kv->len[s]});
         M += lens[i];
     }
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const int V = c->d.vocab;
-    const size_t lw = layers_ws(c, M, 0, n);
-    CR_TRY(ws_ensure(c, lw + (size_t)M * D * 2 + (size_t)n * D * 2 + (size_t)n * V * 4 + (size_t)M * 8 + (size_t)n * 36 + 8192));
+    const bool kv8 = kv->fmt == CR_KV_E4M3;
+    int stage_T = 0;
+    for (const Segment& sg : segs) stage_T = sg.S > stage_T ? sg.S : stage_T;
+    const size_t lw = layers_ws(c, M, 0, n, kv8 ? prefill_stage_bytes(n, stage_T) : 0);
+    CR_TRY(ws_ensure(c, lw + (size_t)M * D * 2 + (size_t)n * D * 2 + (size_t)n * V * 4 + (size_t)M * 12 + (size_t)n * 68 + 8192));
     bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
     bf16* hl = x + (size_t)M * D;
     float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
@@ -968,8 +1074,11 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     int32_t* d_seg = d_row_pos + M;                 // 4 per page: first row, rows, first position, cache slot (the attention launch's segments)
     int32_t* d_seg_last = d_seg + 4 * n;            // the final layer's segments: the rows that share a 32-row wave with the page's last row
     int32_t* d_last = d_seg_last + 4 * n;           // and that last row
+    int32_t* d_seg8 = d_last + n;                   // e4m3 cache (PrefillStage): d_seg and d_seg_last with the page index as the slot, the rows' page indices
+    int32_t* d_seg_last8 = d_seg8 + 4 * n;
+    int32_t* d_row_page = d_seg_last8 + 4 * n;
     {
-        std::vector<int32_t> h(2 * (size_t)M + 9 * segs.size());
+        std::vector<int32_t> h(2 * (size_t)M + 9 * segs.size() + (kv8 ? 8 * segs.size() + (size_t)M : 0));
         for (const Segment& sg : segs)
             for (int r = 0; r < sg.S; r++) { h[sg.row0 + r] = sg.seq; h[(size_t)M + sg.row0 + r] = sg.pos0 + r; }
         for (size_t i = 0; i < segs.size(); i++) {
@@ -980,12 +1089,19 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
             int32_t* f = h.data() + 2 * (size_t)M + 4 * segs.size() + 4 * i;
             f[0] = segs[i].row0 + w0; f[1] = segs[i].S - w0; f[2] = segs[i].pos0 + w0; f[3] = segs[i].seq;
             h[2 * (size_t)M + 8 * segs.size() + i] = segs[i].row0 + segs[i].S - 1;
+            if (kv8) {
+                int32_t* g = h.data() + 2 * (size_t)M + 9 * segs.size() + 4 * i;
+                for (int k = 0; k < 4; k++) { g[k] = e[k]; g[4 * segs.size() + k] = f[k]; }
+                g[3] = g[4 * segs.size() + 3] = (int32_t)i;
+                for (int r = 0; r < segs[i].S; r++) h[2 * (size_t)M + 17 * segs.size() + segs[i].row0 + r] = (int32_t)i;
+            }
         }
         CR_HIP(hipMemcpyAsync(d_row_seq, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
     }
     CR_TRY(stage_seqs(c, seqs, n, st, true));
     CR_HIP(hipMemcpyAsync(x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
-    CR_TRY(run_layers(c, kv, x, M, false, segs, d_row_seq, d_row_pos, nullptr, 0, st, d_seg, d_last, d_seg_last));
+    const PrefillStage stg{stage_T, d_row_page, d_seg8, d_seg_last8};
+    CR_TRY(run_layers(c, kv, x, M, false, segs, d_row_seq, d_row_pos, nullptr, 0, st, d_seg, d_last, d_seg_last, kv8 ? &stg : nullptr));
     const bf16 *nw = W(c, "language_model.model.norm.weight"), *ow = W(c, "language_model.output.weight");
     if (!nw || !ow) return CR_ERR_STATE;
     // only each page's last row feeds the LM head (the reference computes all S rows and reads the last, :1081 + _sample)
@@ -1032,6 +1148,9 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         if (!force_tokens && kv->ngen[s] == 0) return cr_fail(CR_ERR_STATE, "cr_llm_decode: sequence %d has no generated id to feed", s);
         for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_decode: sequence %d listed twice", s);
     }
+    if (kv->fmt == CR_KV_E4M3 && !decode_attn8_available())
+        return cr_fail(CR_ERR_ARG, "cr_llm_decode: an e4m3 cache is read by attention_decode.hip's e4m3 kernel only, and CR_DECODE_ATTN=0 selects the matrix-core "
+                       "split kernel, which reads bf16 caches");
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const int V = c->d.vocab;

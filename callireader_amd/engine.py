@@ -213,9 +213,12 @@ class Engine:
                                       _p(r), 0 if r is None else r.shape[0], ref_id, _p(out), _stream()), 'cr_embed_splice')
         return out
 
-    def kv_alloc(self, n_seqs, max_tokens):
+    def kv_alloc(self, n_seqs, max_tokens, dtype='bf16'):
+        """cr_kv_alloc_ex.  dtype 'bf16' (default: the reference's cache) or 'e4m3' (cr_kv_alloc_ex CR_KV_E4M3: e4m3 rows + one fp32 scale each, 0.52x
+        the bytes; a throughput option, not parity-preserving -- include/callireader_hip.h)."""
+        fmt = kv_format(dtype)
         h = C.c_void_p()
-        B.check(B.lib.cr_kv_alloc(self._h, n_seqs, max_tokens, C.byref(h)), 'cr_kv_alloc')
+        B.check(B.lib.cr_kv_alloc_ex(self._h, n_seqs, max_tokens, fmt, C.byref(h)), 'cr_kv_alloc')
         return KVCache(self, h, n_seqs, max_tokens)
 
     def prefill(self, kv, seq, embeds, penalty=1.0, want_logits=False):
@@ -256,9 +259,21 @@ class Engine:
         return logits
 
 
+KV_DTYPES = {'bf16': B.CR_KV_BF16, 'e4m3': B.CR_KV_E4M3}
+
+
+def kv_format(dtype):
+    """'bf16' | 'e4m3' -> the cache format of cr_kv_alloc_ex (ValueError otherwise)."""
+    if dtype not in KV_DTYPES:
+        raise ValueError(f"kv cache dtype must be one of {sorted(KV_DTYPES)}, got {dtype!r}")
+    return KV_DTYPES[dtype]
+
+
 class KVCache:
     def __init__(self, eng, h, n_seqs, max_tokens):
         self.eng, self._h, self.n_seqs, self.max_tokens = eng, h, n_seqs, max_tokens
+        fmt = B.lib.cr_kv_format(h)
+        self.format = {v: k for k, v in KV_DTYPES.items()}[fmt]      # 'bf16' | 'e4m3'
 
     def length(self, seq):
         return B.lib.cr_kv_length(self._h, seq)
@@ -272,6 +287,13 @@ class KVCache:
         out = torch.empty(8, 128, device=self.eng.device, dtype=torch.bfloat16)
         B.check(B.lib.cr_kv_read(self._h, layer, seq, pos, which, _p(out), _stream()), 'cr_kv_read')
         return out
+
+    def read_e4m3(self, layer, seq, pos, which=0):
+        """e4m3 caches: ((8, 128) uint8 e4m3 bytes, (8,) fp32 scales) of one cached position, all KV heads."""
+        q = torch.empty(8, 128, device=self.eng.device, dtype=torch.uint8)
+        s = torch.empty(8, device=self.eng.device, dtype=torch.float32)
+        B.check(B.lib.cr_kv_read_e4m3(self._h, layer, seq, pos, which, _p(q), _p(s), _stream()), 'cr_kv_read_e4m3')
+        return q, s
 
     def set_stop(self, seq, eos_id=None, max_new=0):
         """cr_kv_set_stop on the current stream: from now on the greedy pick records the sequence's stop (its first `eos_id`, or its
@@ -460,6 +482,22 @@ def op_decode_attention(q, kc, vc, seqs, lens, s_div=11.313708498984761, which=0
         out = torch.empty(Bn, 4096, device=q.device, dtype=torch.bfloat16)
     B.check(B.lib.cr_op_decode_attention(which, _p(q), _p(kc), _p(vc), max_tokens, _p(seqs), _p(lens), Bn, max_keys, float(s_div), _p(scratch), _p(out), _stream()),
             'cr_op_decode_attention')
+    return out
+
+
+def op_decode_attention_e4m3(q, kc, vc, ks, vs, seqs, lens, s_div=11.313708498984761, max_keys=None, scratch=None, out=None):
+    """cr_op_decode_attention_e4m3: as op_decode_attention over an e4m3 cache -- kc / vc (n_slots, 8, max_tokens, 128) uint8 e4m3 bytes, ks / vs
+    (n_slots, 8, max_tokens) fp32 row scales; returns (B, 4096) bf16."""
+    Bn = q.shape[0]
+    max_tokens = kc.shape[2]
+    if max_keys is None:
+        max_keys = int(lens.max().item()) + 1
+    if scratch is None:
+        scratch = torch.empty(int(B.lib.cr_op_decode_attention_scratch_floats(Bn, max_keys)), device=q.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(Bn, 4096, device=q.device, dtype=torch.bfloat16)
+    B.check(B.lib.cr_op_decode_attention_e4m3(0, _p(q), _p(kc), _p(vc), _p(ks), _p(vs), max_tokens, _p(seqs), _p(lens), Bn, max_keys, float(s_div),
+                                              _p(scratch), _p(out), _stream()), 'cr_op_decode_attention_e4m3')
     return out
 
 

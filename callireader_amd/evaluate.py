@@ -316,7 +316,19 @@ def compare_reports(bf16_rows, fp8_rows):
     return out
 
 
-def main(argv=None):
+def fp8_switches(args):
+    """The fp8 switches of a run (under --compare_fp8: of its fp8 arm): --fp8_mfma / --fp8_decode as given, both when --compare_fp8 gets neither;
+    'fp8_kv' (the e4m3 KV cache) only when --fp8_kv is given, so a run without it reports exactly the switches it always did."""
+    want_mfma, want_dec = args.fp8_mfma, args.fp8_decode
+    if args.compare_fp8 and not (want_mfma or want_dec):
+        want_mfma, want_dec = 1, True
+    sw = {'fp8_mfma': want_mfma, 'fp8_decode': want_dec}
+    if getattr(args, 'fp8_kv', False):
+        sw['fp8_kv'] = True
+    return sw
+
+
+def build_parser():
     parser = argparse.ArgumentParser(description='args for inference task')
     parser.add_argument('--type', type=str, choices=['full_page', 'region_wise', 'choice', 'bilingual', 'intent'], default='full_page',
                         help='Evaluation Type (full_page, region_wise, choice, bilingual, intent)')
@@ -334,10 +346,16 @@ def main(argv=None):
     parser.add_argument('--fp8_decode', action='store_true', help='BASELINE config 5: e4m3 weights for the batched decode (cr_enable_fp8_decode)')
     parser.add_argument('--fp8_mfma', type=int, nargs='?', const=1, default=0, choices=(0, 1, 2),
                         help='BASELINE config 5: e4m3 x e4m3 matrix-core linears (cr_enable_fp8_mfma): 1 = the norm-fed linears of the ViT / projector / prefill, 2 = also ViT fc2 and the prefill\'s wo / w2')
-    parser.add_argument('--compare_fp8', action='store_true', help='run every file twice -- bf16, then with --fp8_decode / --fp8_mfma (both when neither is given) -- and '
+    parser.add_argument('--fp8_kv', action='store_true', help='e4m3 KV cache for the decode (kv_cache_dtype="e4m3"; a throughput option, not parity-preserving)')
+    parser.add_argument('--compare_fp8', action='store_true', help='run every file twice -- bf16, then with --fp8_decode / --fp8_mfma (both when neither is given) and '
+                                                                   '--fp8_kv when it is given -- and '
                                                                    'write full_page_<level>_fp8_vs_bf16.json: identical outputs, NED between them, F1 / NED deltas')
     parser.add_argument('--allow_no_t2s', action='store_true', help='run without opencc (responses stay unconverted: scores not comparable with the reference\'s)')
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if cc._cc is None and not args.allow_no_t2s:
         raise SystemExit('opencc is not installed: the reference converts every response traditional -> simplified before scoring (evaluate.py:127-132). '
                          'Install opencc, or pass --allow_no_t2s to score unconverted text (not comparable with the reference\'s numbers).')
@@ -365,15 +383,16 @@ def main(argv=None):
             dist.all_gather_object(out, rows)
             return out
     model = InternVLChatModel.from_pretrained(args.model, params_dir=args.params, torch_dtype=torch.bfloat16, max_pages=args.batch_pages, device=local).eval().cuda()
-    want_mfma, want_dec = args.fp8_mfma, args.fp8_decode
-    if args.compare_fp8 and not (want_mfma or want_dec):
-        want_mfma, want_dec = 1, True
+    switches = fp8_switches(args)
+    want_mfma, want_dec, want_kv = switches['fp8_mfma'], switches['fp8_decode'], switches.get('fp8_kv', False)
 
     def fp8(on):
         if want_mfma:
             model.engine.enable_fp8_mfma(on, level=want_mfma)
         if want_dec:
             model.engine.enable_fp8_decode(on)
+        if want_kv:
+            model.kv_cache_dtype = 'e4m3' if on else 'bf16'
     if not args.compare_fp8:
         fp8(True)
     tokenizer = InternLM2Tokenizer.from_pretrained(args.model)
@@ -416,7 +435,7 @@ def main(argv=None):
                 fp8(False)
             if rank == 0:
                 cmp = compare_reports(json.load(open(save_json_path, encoding='utf-8'))['detailed'], json.load(open(fp8_path, encoding='utf-8'))['detailed'])
-                cmp['switches'] = {'fp8_mfma': want_mfma, 'fp8_decode': want_dec}
+                cmp['switches'] = switches
                 with open(os.path.join(save_dir, f'full_page_{level}_fp8_vs_bf16.json'), 'w', encoding='utf-8') as f:
                     json.dump(cmp, f, ensure_ascii=False, indent=4)
                 print(level, 'fp8', avg8, 'identical outputs', cmp['identical_outputs'], 'of', cmp['pages'], 'delta F1', cmp['delta_f1'], 'delta NED', cmp['delta_ned'])

@@ -161,7 +161,7 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
     return results
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser(description='args for inference task')
     parser.add_argument('--tgt', type=str, help='Recognition target')
     parser.add_argument('--prompt', type=str, default='这幅书法作品内容是什么？', help='Prompt for recognition')
@@ -187,13 +187,20 @@ def main(argv=None):
     parser.add_argument('--top_k', type=int, default=None, help='with --do_sample (default 50; 0: off)')
     parser.add_argument('--top_p', type=float, default=None, help='with --do_sample (default 1.0: off)')
     parser.add_argument('--seed', type=int, default=None, help='torch.manual_seed before the run: --do_sample output becomes reproducible')
-    args = parser.parse_args(argv)
+    parser.add_argument('--fp8_kv', action='store_true',
+                        help='e4m3 KV cache for the decode (kv_cache_dtype="e4m3": 0.52x the cache bytes; off by default; a throughput option, not parity-preserving)')
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if not isinstance(args.tgt, str):
         raise ValueError(f'The target should a string, not a instance of {type(args.tgt)}!')
     from .tokenization_internlm2 import InternLM2Tokenizer
     folder = os.path.isdir(args.tgt) and args.batch_pages > 1
     model = InternVLChatModel.from_pretrained(args.model, params_dir=args.params, torch_dtype=torch.bfloat16,
-                                              **(dict(max_pages=args.batch_pages) if folder else {})).eval().cuda()
+                                              **(dict(max_pages=args.batch_pages) if folder else {}),
+                                              **(dict(kv_cache_dtype='e4m3') if args.fp8_kv else {})).eval().cuda()
     if args.fp8_mfma:
         model.engine.enable_fp8_mfma(True, level=args.fp8_mfma)
     if args.fp8_decode:

@@ -16,6 +16,7 @@ import json
 import os
 import sys
 import time
+import weakref
 
 import numpy as np
 import torch
@@ -31,7 +32,11 @@ from .sampling import base_seed, page_seeds, parse as sampling_parse, splitmix64
 class InternVLChatModel:
     main_input_name = 'pixel_values'
 
-    def __init__(self, dims: ModelDims = None, device=0, max_tokens=8192, max_pages=1):
+    def __init__(self, dims: ModelDims = None, device=0, max_tokens=8192, max_pages=1, kv_cache_dtype='bf16'):
+        from .engine import kv_format
+        kv_format(kv_cache_dtype)                                            # ValueError for anything but 'bf16' / 'e4m3'
+        self._kv_cache_dtype = kv_cache_dtype
+        self._pipes = weakref.WeakSet()          # pipelines made from this model that are not closed yet (their caches follow kv_cache_dtype)
         self.dims = dims or ModelDims.full()
         self.engine = Engine(self.dims, device=device, max_pos=min(self.dims.max_pos, max(max_tokens, 64)))
         self.device = self.engine.device
@@ -81,7 +86,7 @@ class InternVLChatModel:
         from .weights import load_checkpoint
         if torch_dtype not in (torch.bfloat16, None, 'auto', 'bfloat16'):
             raise ValueError('the engine computes in bf16, the dtype the reference loads the model in (inference.py:87)')
-        ours = {k: kw.pop(k) for k in ('device', 'max_tokens', 'max_pages') if k in kw}
+        ours = {k: kw.pop(k) for k in ('device', 'max_tokens', 'max_pages', 'kv_cache_dtype') if k in kw}
         dims = kw.pop('dims', None)
         if dims is None:
             dims = ModelDims.from_hf_config(path) if os.path.exists(os.path.join(path, 'config.json')) else ModelDims.full()
@@ -122,11 +127,34 @@ class InternVLChatModel:
             self._kv = None
         self.engine.close()
 
+    @property
+    def kv_cache_dtype(self):
+        """Format of every KV cache this model allocates (its own, generate_pages', PagePipeline's, ContinuousPipeline's): 'bf16' (default, the
+        reference's) or 'e4m3' (Engine.kv_alloc: e4m3 rows + one fp32 scale each, 0.52x the bytes; a throughput option, not parity-preserving)."""
+        return self._kv_cache_dtype
+
+    @kv_cache_dtype.setter
+    def kv_cache_dtype(self, dtype):
+        from .engine import kv_format
+        kv_format(dtype)
+        if dtype == self._kv_cache_dtype:
+            return
+        live = [p for p in list(self._pipes) if not getattr(p, 'closed', False)]
+        if live:
+            raise RuntimeError(f'kv_cache_dtype: {len(live)} pipeline(s) made from this model are still open (close them first: their caches keep their format)')
+        if self._kv is not None:                  # the model's own cache is re-made in the new format on next use
+            self._kv.free()
+            self._kv = None
+        self._kv_cache_dtype = dtype
+
+    def _kv_alloc(self, n_seqs, max_tokens):
+        return self.engine.kv_alloc(n_seqs, max_tokens, dtype=self._kv_cache_dtype)
+
     def kv(self, n_seqs=None):
         """The model's own KV cache (the pipeline of chat_ocr_stream has two of its own): `n_seqs` sequences when none exists yet (default: max_pages).  The one-page
         calls ask for ONE sequence -- 1 GB at max_tokens 8192, where a 64-page cache is 69 GB that folder mode's per-image fallback would hold beside the pipeline's."""
         if self._kv is None:
-            self._kv = self.engine.kv_alloc(n_seqs or self.max_pages, self.max_tokens)
+            self._kv = self._kv_alloc(n_seqs or self.max_pages, self.max_tokens)
         return self._kv
 
     # ---- the * stages --------------------------------------------------------------------------
@@ -817,7 +845,7 @@ class InternVLChatModel:
             if self._kv is not None:
                 self._kv.free()
             self.max_pages = max(P, self.max_pages)
-            self._kv = self.engine.kv_alloc(self.max_pages, self.max_tokens)
+            self._kv = self._kv_alloc(self.max_pages, self.max_tokens)
         kv = self._kv
         kv.reset()
         _set_sampling(kv, per_page)
@@ -872,6 +900,8 @@ class PagePipeline:
         import threading
         from .engine import Engine
         self.m, self.eng = model, model.engine
+        self.closed = False
+        model._pipes.add(self)                        # the model refuses a kv_cache_dtype change while this is open
         self.max_new_tokens, self.eos, self.penalty = max_new_tokens, eos_token_id, repetition_penalty
         self.check_every, self.prefill_batch = int(os.environ.get('CR_PIPE_CHECK_EVERY', check_every)), prefill_batch      # (env: development aid, how often the decode thread looks for EOS)
         self.dec = Engine(self.eng.dims, device=self.eng.device.index, max_pos=self.eng.max_pos)
@@ -892,7 +922,7 @@ class PagePipeline:
         if kv is None or kv.n_seqs < P:
             if kv is not None:
                 kv.free()
-            kv = self.kvs[slot] = self.eng.kv_alloc(max(P, self.m.max_pages), self.m.max_tokens)
+            kv = self.kvs[slot] = self.m._kv_alloc(max(P, self.m.max_pages), self.m.max_tokens)
         return kv
 
     def _decode_loop(self):
@@ -1002,6 +1032,7 @@ class PagePipeline:
         if self.dec is not None:
             self.dec.close()
             self.dec = None
+        self.closed = True
 
 
 def _per_page_sampling(sampling, seeds, P):

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 12  /* 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 13  /* 13: cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -131,6 +131,21 @@ int cr_embed_splice(cr_ctx* ctx, const int64_t* ids, int S, const void* vit_embe
  * far — what transformers' generate() carries as `input_ids` when only inputs_embeds is given — so that the
  * repetition penalty and the next step's input never leave the device. */
 int cr_kv_alloc(cr_ctx* ctx, int n_seqs, int max_tokens, cr_kv** out);
+/* The same with a cache format (cr_kv_alloc is CR_KV_BF16); an unknown format is CR_ERR_ARG, checked before ctx.
+ * CR_KV_E4M3 (an option, OFF by default; a THROUGHPUT option that does not preserve the reference's tokens, like the fp8 weight paths): every cached
+ * row -- the 128 values of one (layer, seq, KV head, position), K after RoPE, V as projected -- is kept as OCP e4m3fn bytes with one fp32 scale,
+ * quantised from the bf16 row a bf16 cache would hold by the rule of cr_op_quantize_fp8: s = max|x| / 448 (1 for a zero row), q = e4m3fn_rne(x * (1 / s)).
+ * 67 584 bytes per cached token instead of 131 072; no bf16 K / V is kept.
+ *   - prefill: the prompt attends over its exact bf16 K / V (a per-context staging buffer, one layer at a time) -- its logits and first id are
+ *     bit-identical to a bf16 cache's -- and only the e4m3 rows go to the cache.  Hence a prefill into a sequence that already holds tokens is CR_ERR_ARG
+ *     on an e4m3 cache (there is no bf16 copy of the prefix): cr_kv_reset the sequence first.
+ *   - decode attends over the dequantised cache, the new token's own row included (quantised before it is attended to): score = bf16(bf16(s_k * (q . k^))
+ *     / sqrt(128)) with the dot in fp32, output = sum_t bf16(p_t) * s_v,t * v^_t in fp32.  A row's result still depends only on its own key count.
+ *   - everything else (ids, lengths, stop tracking, sampling, cr_kv_reset, sharing between contexts) is the format-independent state of the cache; any
+ *     context that decodes the cache reads it in its format.  A process run with CR_DECODE_ATTN=0 refuses to decode an e4m3 cache (CR_ERR_ARG). */
+enum { CR_KV_BF16 = 0, CR_KV_E4M3 = 1 };
+int cr_kv_alloc_ex(cr_ctx* ctx, int n_seqs, int max_tokens, int format, cr_kv** out);
+int cr_kv_format(const cr_kv* kv);                     /* CR_KV_BF16 | CR_KV_E4M3, or < 0 */
 int cr_kv_free(cr_kv* kv);
 int cr_kv_length(const cr_kv* kv, int seq);           /* tokens currently cached (host-side bookkeeping) */
 /* Forget sequence `seq` (length 0, no generated ids), or every sequence when seq < 0.  Enqueued on `stream`, no
@@ -139,6 +154,8 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream);
 /* One cached position as the reference's tuple cache holds it (InternVL/modeling_internlm2.py:383-388, K after RoPE):
  * out [8 kv heads][128] bf16 (device) = past_key_values[layer][which][seq, :, pos, :]; which 0 = K, 1 = V.  Parity tests. */
 int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, void* stream);
+/* The same position of an e4m3 cache (cr_kv_read refuses one): q_out [8 kv heads][128] e4m3 bytes, s_out [8] fp32 scales (both device).  Parity tests. */
+int cr_kv_read_e4m3(cr_kv* kv, int layer, int seq, int pos, int which, uint8_t* q_out, float* s_out, void* stream);
 /* Copy the ids generated so far for `seq` into host memory (at most `max`); returns the count, or < 0.
  * Synchronises `stream`. */
 int cr_kv_generated(cr_kv* kv, int seq, int64_t* out_host, int max, void* stream);
@@ -305,6 +322,10 @@ int cr_op_attention(const void* q, const void* k, const void* v, void* o, const 
 int64_t cr_op_decode_attention_scratch_floats(int B, int max_keys);
 int cr_op_decode_attention(int which, const void* q, const void* kc, const void* vc, int max_tokens, const int32_t* seqs, const int32_t* lens, int B, int max_keys,
                            float s_div, float* scratch, void* out, void* stream);
+/* The same over an e4m3 cache (the reader cr_llm_decode uses on a CR_KV_E4M3 cache): kc / vc [n_slots][8][max_tokens][128] e4m3 bytes, ks / vs
+ * [n_slots][8][max_tokens] fp32 row scales, arithmetic as under cr_kv_alloc_ex.  which = 0 only (1, the matrix-core kernel, reads bf16: CR_ERR_ARG).  ABI v13. */
+int cr_op_decode_attention_e4m3(int which, const void* q, const void* kc, const void* vc, const float* ks, const float* vs, int max_tokens, const int32_t* seqs,
+                                const int32_t* lens, int B, int max_keys, float s_div, float* scratch, void* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -86,11 +86,14 @@ def main():
     ap.add_argument('--slots', type=int, default=64)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--out', type=str, default=None)
+    ap.add_argument('--fp8_kv', action='store_true', help='e4m3 KV caches (kv_cache_dtype="e4m3") for both paths')
+    ap.add_argument('--workload', choices=('ragged', 'equal', 'both'), default='both')
     args = ap.parse_args()
     from callireader_amd import build, _binding as B
     from callireader_amd.modeling_internvl_chat import InternVLChatModel
     S = PAGE_TILES * 256 + CHAR_TILES * 3 + TEXT_TOKENS
-    model = InternVLChatModel.from_synthetic(ModelDims.full(), seed=0, parts=('llm',), max_tokens=S + MAX_NEW + 64, max_pages=64)
+    model = InternVLChatModel.from_synthetic(ModelDims.full(), seed=0, parts=('llm',), max_tokens=S + MAX_NEW + 64, max_pages=64,
+                                             kv_cache_dtype='e4m3' if args.fp8_kv else 'bf16')
     g = torch.Generator(device=model.device).manual_seed(args.seed)
     embeds = [(torch.randn(S, 4096, generator=g, device=model.device) * 0.02).to(torch.bfloat16) for _ in range(args.pages)]
     # warm-up: both paths once on a few pages (workspaces grow to their steady size, kernels load)
@@ -98,7 +101,7 @@ def main():
     run_batch(model, embeds[:16], wb)
     run_continuous(model, embeds[:16], wb, args.slots)
     res = {}
-    for workload in ('ragged', 'equal'):
+    for workload in (('ragged', 'equal') if args.workload == 'both' else (args.workload,)):
         budgets = budgets_for(workload, args.pages, args.seed)
         ob, rb = run_batch(model, embeds, budgets)
         oc, rc = run_continuous(model, embeds, budgets, args.slots)
@@ -106,9 +109,13 @@ def main():
                              batch=rb, continuous=rc, continuous_over_batch=round(rc['pages_per_s'] / rb['pages_per_s'], 3),
                              ids_equal=ob == oc, ids_match_budgets=all(len(o) == b for o, b in zip(oc, budgets)))
         print(json.dumps({workload: res[workload]}), file=sys.stderr, flush=True)
+    argv = sys.argv[1:]
+    if '--out' in argv:                                   # the run's arguments, not where its report was saved
+        i = argv.index('--out')
+        argv = argv[:i] + argv[i + 2:]
     doc = dict(what='continuous batching (ContinuousPipeline) vs batch-granular (PagePipeline) on the same pages; see scripts/continuous_bench.py',
-               cmd='python scripts/continuous_bench.py ' + ' '.join(sys.argv[1:]), build_id=B.lib.cr_build_id().decode(),
-               sources=build.source_hash(), device=torch.cuda.get_device_name(0), pages=args.pages, slots=args.slots, prompt_tokens=S,
+               cmd=' '.join(['python scripts/continuous_bench.py'] + argv), build_id=B.lib.cr_build_id().decode(),
+               sources=build.source_hash(), device=torch.cuda.get_device_name(0), pages=args.pages, slots=args.slots, prompt_tokens=S, kv_cache_dtype=model.kv_cache_dtype,
                max_new_tokens=MAX_NEW, results=res)
     txt = json.dumps(doc, indent=1)
     print(txt)
