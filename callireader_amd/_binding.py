@@ -58,6 +58,8 @@ SIGNATURES = {
     'cr_kv_set_stop': (i32, [vp, i32, i32, i32, vp]),
     'cr_kv_poll_finished': (i32, [vp, vp, i32, vp]),
     'cr_kv_set_sampling': (i32, [vp, i32, f32, i32, f32, C.c_uint64, vp]),
+    'cr_kv_set_logprobs': (i32, [vp, i32, i32, vp]),
+    'cr_kv_logprobs': (i32, [vp, i32, vp, vp, vp, i32, vp]),
     'cr_llm_prefill': (i32, [vp, vp, i32, vp, i32, f32, vp, vp]),
     'cr_llm_prefill_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), f32, vp, vp]),
     'cr_llm_hidden_probe': (i32, [vp, vp, i32, i32]),
@@ -79,6 +81,7 @@ SIGNATURES = {
     'cr_op_attention': (i32, [vp, vp, vp, vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp]),
     'cr_op_decode_attention_scratch_floats': (i64, [i32, i32]),
     'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'cr_op_logprobs': (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     'cr_op_decode_attention': (i32, [i32, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
     'cr_op_decode_attention_e4m3': (i32, [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
 }

@@ -24,6 +24,10 @@ depend on the other rows of its steps.
     done = pipe.ready()                                 # [(ticket, ids)] finished so far, without waiting
     for ticket, ids in pipe.results(): ...              # the rest, in the order they finish
     pipe.close()
+
+Token scores (scores.py): submit(..., logprobs=n) with n in 1..8 switches the page's scores on (cr_kv_set_logprobs after its sequence's reset, before
+its prefill); its result is then (ticket, (ids, TokenScores)) instead of (ticket, ids), the scores read where the ids are read, on the read-back
+stream, and cut at the same stop count.  Pages submitted with logprobs=0 (the default) are returned exactly as before.
 """
 import collections
 import threading
@@ -32,6 +36,7 @@ import time
 import torch
 
 from .config import EOS_TOKEN_ID
+from .scores import TokenScores, check_top_n
 
 
 class _TorchOps:
@@ -105,6 +110,7 @@ class ContinuousPipeline:
         self.waiting = collections.deque()                # (ticket, embeds, budget) not yet prefilled
         self.free = collections.deque(range(self.n_seqs))
         self.owner = {}                                   # sequence -> ticket of the page in it
+        self.scored = {}                                  # sequence -> alternatives per id, for the pages that asked for token scores
         self.to_read = collections.deque()                # (sequence, stop count, release event) handed back by the worker
         self.finished = collections.deque()               # (ticket, ids) not yet handed to the caller
         self.outstanding = 0                              # submitted, not yet handed to the caller
@@ -119,13 +125,14 @@ class ContinuousPipeline:
         self.worker.start()
 
     # ---- caller side ----------------------------------------------------------------------------
-    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None):
+    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None, logprobs=0):
         """Queue one page's prompt embeddings ([S, hidden] on the device) with its budget of new ids (default, and at most, the pipeline's);
         returns its ticket.  Prefills a group when one is complete.  ValueError for a budget the pipeline cannot take.  sampling (a
         sampling.SamplingParams) with a 64-bit `seed`: the page samples (its sequence's state is set after its reset, before its prefill);
-        None: greedy."""
+        None: greedy.  logprobs: 0, or the number of alternatives (1..8) to record per generated id: the page's result is (ids, TokenScores)."""
         t0 = time.perf_counter()
         self._raise_worker_error()
+        logprobs = check_top_n(logprobs, 'logprobs', allow_zero=True)
         budget = self.max_new_tokens if max_new_tokens is None else int(max_new_tokens)
         S = int(embeds.shape[0])
         if not 1 <= budget <= self.max_new_tokens:
@@ -136,7 +143,7 @@ class ContinuousPipeline:
         self.next_ticket += 1
         if sampling is not None and seed is None:
             raise ValueError('a sampled page needs its seed')
-        self.waiting.append((ticket, embeds, budget, sampling, seed))
+        self.waiting.append((ticket, embeds, budget, sampling, seed, logprobs))
         self.outstanding += 1
         self._pump(flush=False, block=False)
         self.stats['caller_host_s'] += time.perf_counter() - t0
@@ -164,7 +171,7 @@ class ContinuousPipeline:
                 yield item
 
     def map(self, items, errors='raise'):
-        """items: an iterable of (key, embeds, budget or None[, sampling, seed]), consumed as pages are admitted (a generator can compute the next pages' embeddings
+        """items: an iterable of (key, embeds, budget or None[, sampling, seed[, logprobs]]), consumed as pages are admitted (a generator can compute the next pages' embeddings
         meanwhile); yields (key, ids) as pages finish.  errors='return': a page whose budget the pipeline refuses yields (key, that ValueError) and
         the others run; 'raise': the ValueError propagates."""
         keys = {}
@@ -213,9 +220,10 @@ class ContinuousPipeline:
             with self.ops.use(self.rb):
                 self.ops.wait(self.rb, ev)
                 ids = self.kv.generated(seq, stop)        # synchronises the read-back stream only: the event and this copy
-            if len(ids) != stop:
+                ts = TokenScores(*self.kv.logprobs(seq, stop)) if self.scored.pop(seq, 0) else None
+            if len(ids) != stop or (ts is not None and len(ts) != stop):
                 raise RuntimeError(f'sequence {seq}: {len(ids)} ids read back, stop count {stop}')
-            self.finished.append((self.owner.pop(seq), ids))
+            self.finished.append((self.owner.pop(seq), ids if ts is None else (ids, ts)))
             self.free.append(seq)                         # its last decode step has completed: a reset on any stream comes after it
             block = False
 
@@ -227,10 +235,13 @@ class ContinuousPipeline:
                 return
             group = [self.waiting.popleft() for _ in range(k)]
             seqs = [self.free.popleft() for _ in range(k)]
-            for s, (_, _, _, sp, seed) in zip(seqs, group):
+            for s, (_, _, _, sp, seed, lpn) in zip(seqs, group):
                 self.kv.reset(s)
                 if sp is not None:
                     self.kv.set_sampling(s, sp.temperature, sp.top_k, sp.top_p, seed)
+                if lpn:
+                    self.kv.set_logprobs(s, lpn)
+                    self.scored[s] = lpn
             self.eng.prefill_batch(self.kv, seqs, [g[1] for g in group], penalty=self.penalty)
             ready = self.ops.record(self.ops.current())
             for s, (ticket, *_) in zip(seqs, group):

@@ -19,6 +19,7 @@
 #include "decode.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
+#include "logprobs.hpp"
 #include "pick.hpp"
 
 struct cr_kv {
@@ -44,6 +45,12 @@ struct cr_kv {
     char* d_samp;
     float* d_temp; int32_t* d_topk; float* d_topp; uint64_t* d_seed;
     std::vector<char> sampled;
+    // token scores (cr_kv_set_logprobs; logprobs.hip), allocated by the first call that switches a sequence on: d_lpn int32[n] = alternatives per sequence
+    // (0: off), d_lpdone int32[n] = slots written, d_lp [n][gen_cap] fp32, d_top_id [n][gen_cap][8] int32, d_top_lp [n][gen_cap][8] fp32, indexed like
+    // d_gen.  `scored` mirrors d_lpn on the host: a launch whose rows are all off launches nothing new (and keeps the graph path)
+    int32_t *d_lpn = nullptr, *d_lpdone = nullptr, *d_top_id = nullptr;
+    float *d_lp = nullptr, *d_top_lp = nullptr;
+    std::vector<char> scored;
     std::vector<int> len, ngen;
     // batched decode as a hipGraph (CR_DECODE_GRAPH=1): a step is ~290 short launches whose parameters only change with
     // the row count and the number of attention splits (positions, ids and cache lengths live in device memory), so the
@@ -778,6 +785,18 @@ static bool any_sampled(const cr_kv* kv, const int32_t* seqs, int n) {
     return false;
 }
 
+static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
+    if (!kv->d_lpn) return false;
+    for (int i = 0; i < n; i++) if (kv->scored[seqs[i]]) return true;
+    return false;
+}
+
+// the scores of the rows the pick has just chosen from (lg: the penalised rows it left), into the sequences' slots; scratch follows lg in the workspace
+static int score_rows(cr_kv* kv, const float* lg, int V, int n, const int32_t* d_seqs, hipStream_t st) {
+    return launch_logprobs(lg, V, V, n, d_seqs, kv->d_lpn, 0, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_lpdone, (void*)(lg + (size_t)n * V), kv->d_lp,
+                           kv->d_top_id, kv->d_top_lp, st);
+}
+
 extern "C" {
 
 int cr_op_quantize_fp8(const void* w, int64_t ldw, int N, int K, void* q, float* scale, void* stream) {
@@ -929,6 +948,7 @@ int cr_kv_alloc_ex(cr_ctx* c, int n_seqs, int max_tokens, int format, cr_kv** ou
     kv->d_topp = (float*)(kv->d_topk + n_seqs);
     CR_HIP(hipMemset(kv->d_samp, 0, (size_t)n_seqs * 24));                           // greedy
     kv->sampled.assign(n_seqs, 0);
+    kv->scored.assign(n_seqs, 0);
     kv->len.assign(n_seqs, 0); kv->ngen.assign(n_seqs, 0);
     *out = kv;
     return CR_OK;
@@ -948,6 +968,10 @@ int cr_kv_free(cr_kv* kv) {
     if (kv->d_stop) hipFree(kv->d_stop);
     if (kv->d_samp) hipFree(kv->d_samp);
     if (kv->d_gen) hipFree(kv->d_gen);
+    if (kv->d_lpn) hipFree(kv->d_lpn);
+    if (kv->d_lp) hipFree(kv->d_lp);
+    if (kv->d_top_id) hipFree(kv->d_top_id);
+    if (kv->d_top_lp) hipFree(kv->d_top_lp);
     for (auto& e : kv->graphs) if (e.exec) hipGraphExecDestroy(e.exec);
     delete kv;
     return CR_OK;
@@ -970,7 +994,11 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
     CR_HIP(hipMemsetAsync(kv->d_stop + 1 + 3 * N + s0, 0, (size_t)n * 4, st));          // no budget
     if (seq < 0) CR_HIP(hipMemsetAsync(kv->d_stop, 0, 4, st));                          // every sequence: the finished ring starts over
     CR_HIP(hipMemsetAsync(kv->d_temp + s0, 0, (size_t)n * 4, st));                      // greedy
-    for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; kv->sampled[s] = 0; }
+    if (kv->d_lpn) {                                                                    // scores off
+        CR_HIP(hipMemsetAsync(kv->d_lpn + s0, 0, (size_t)n * 4, st));
+        CR_HIP(hipMemsetAsync(kv->d_lpdone + s0, 0, (size_t)n * 4, st));
+    }
+    for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; }
     return CR_OK;
 }
 
@@ -998,6 +1026,52 @@ int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float t
     CR_HIP(hipGetLastError());
     kv->sampled[seq] = temperature > 0.f;
     return CR_OK;
+}
+
+int cr_kv_set_logprobs(cr_kv* kv, int seq, int top_n, void* stream) {
+    if (top_n < 0 || top_n > LOGPROBS_MAX_TOP) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: top_n %d (want 0 = off, or 1..%d)", top_n, LOGPROBS_MAX_TOP);
+    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: bad sequence");
+    if (top_n > 0 && kv->ngen[seq] != 0)
+        return cr_fail(CR_ERR_STATE, "cr_kv_set_logprobs: sequence %d has generated %d ids already (switch scores on after cr_kv_reset and before the prefill)",
+                       seq, kv->ngen[seq]);
+    if (!kv->d_lpn && top_n == 0) return CR_OK;                                         // never switched on: nothing to switch off
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    if (!kv->d_lpn) {
+        const size_t N = kv->n_seqs, slots = N * kv->gen_cap;
+        if (hipMalloc((void**)&kv->d_lpn, N * 8) != hipSuccess || hipMalloc((void**)&kv->d_lp, slots * 4) != hipSuccess ||
+            hipMalloc((void**)&kv->d_top_id, slots * LOGPROBS_MAX_TOP * 4) != hipSuccess ||
+            hipMalloc((void**)&kv->d_top_lp, slots * LOGPROBS_MAX_TOP * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            if (kv->d_lpn) hipFree(kv->d_lpn);
+            if (kv->d_lp) hipFree(kv->d_lp);
+            if (kv->d_top_id) hipFree(kv->d_top_id);
+            if (kv->d_top_lp) hipFree(kv->d_top_lp);
+            kv->d_lpn = nullptr; kv->d_lp = nullptr; kv->d_top_id = nullptr; kv->d_top_lp = nullptr;
+            return cr_fail(CR_ERR_NOMEM, "cr_kv_set_logprobs: %zu bytes of token scores", slots * (4 + 8 * LOGPROBS_MAX_TOP));
+        }
+        kv->d_lpdone = kv->d_lpn + N;
+        CR_HIP(hipMemsetAsync(kv->d_lpn, 0, N * 8, (hipStream_t)stream));
+        CR_HIP(hipStreamSynchronize((hipStream_t)stream));                              // once per cache: in place before a call on any other stream
+    }
+    CR_TRY(launch_set_logprobs(kv->d_lpn, kv->d_lpdone, seq, top_n, (hipStream_t)stream));
+    kv->scored[seq] = top_n > 0;
+    return CR_OK;
+}
+
+int cr_kv_logprobs(cr_kv* kv, int seq, float* lp, int32_t* top_ids, float* top_lp, int max, void* stream) {
+    if (!kv || !lp || !top_ids || !top_lp || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_logprobs: bad argument");
+    if (!kv->d_lpn || !kv->scored[seq]) return cr_fail(CR_ERR_STATE, "cr_kv_logprobs: sequence %d has token scores switched off (cr_kv_set_logprobs)", seq);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int n = kv->ngen[seq] < max ? kv->ngen[seq] : max;
+    const size_t at = (size_t)seq * kv->gen_cap;
+    if (n > 0) {
+        CR_HIP(hipMemcpyAsync(lp, kv->d_lp + at, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        CR_HIP(hipMemcpyAsync(top_ids, kv->d_top_id + at * LOGPROBS_MAX_TOP, (size_t)n * LOGPROBS_MAX_TOP * 4, hipMemcpyDeviceToHost, st));
+        CR_HIP(hipMemcpyAsync(top_lp, kv->d_top_lp + at * LOGPROBS_MAX_TOP, (size_t)n * LOGPROBS_MAX_TOP * 4, hipMemcpyDeviceToHost, st));
+    }
+    CR_HIP(hipStreamSynchronize(st));
+    return n;
 }
 
 int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream) {
@@ -1065,11 +1139,13 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     int stage_T = 0;
     for (const Segment& sg : segs) stage_T = sg.S > stage_T ? sg.S : stage_T;
     const size_t lw = layers_ws(c, M, 0, n, kv8 ? prefill_stage_bytes(n, stage_T) : 0);
-    CR_TRY(ws_ensure(c, lw + (size_t)M * D * 2 + (size_t)n * D * 2 + (size_t)n * V * 4 + (size_t)M * 12 + (size_t)n * 68 + 8192));
+    const bool scored = any_scored(kv, seqs, n);
+    CR_TRY(ws_ensure(c, lw + (size_t)M * D * 2 + (size_t)n * D * 2 + (size_t)n * V * 4 + (size_t)M * 12 + (size_t)n * 68 + 8192 +
+                        (scored ? logprobs_scratch_bytes(n, V) : 0)));
     bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
     bf16* hl = x + (size_t)M * D;
     float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
-    int32_t* d_row_seq = (int32_t*)(((uintptr_t)(lg + (size_t)n * V) + 255) & ~(uintptr_t)255);
+    int32_t* d_row_seq = (int32_t*)(((uintptr_t)(lg + (size_t)n * V) + (scored ? logprobs_scratch_bytes(n, V) : 0) + 255) & ~(uintptr_t)255);
     int32_t* d_row_pos = d_row_seq + M;
     int32_t* d_seg = d_row_pos + M;                 // 4 per page: first row, rows, first position, cache slot (the attention launch's segments)
     int32_t* d_seg_last = d_seg + 4 * n;            // the final layer's segments: the rows that share a 32-row wave with the page's last row
@@ -1115,6 +1191,7 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     else
         hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, c->d_seqs, kv->d_gen, kv->d_ngen,
                            kv->d_len, kv->gen_cap, 0, kv->d_stop, kv->n_seqs);
+    if (scored) CR_TRY(score_rows(kv, lg, V, n, c->d_seqs, st));
     hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, d_seg, n, kv->d_len);
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
@@ -1158,7 +1235,8 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     for (int i = 0; i < n; i++) max_len = kv->len[seqs[i]] > max_len ? kv->len[seqs[i]] : max_len;
     const int nsplit = ((max_len + 1 + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
     const size_t lw = layers_ws(c, n, nsplit);
-    CR_TRY(ws_ensure(c, lw + (size_t)n * D * 4 + (size_t)n * V * 4 + 4096));
+    const bool scored = any_scored(kv, seqs, n);
+    CR_TRY(ws_ensure(c, lw + (size_t)n * D * 4 + (size_t)n * V * 4 + 4096 + (scored ? logprobs_scratch_bytes(n, V) : 0)));
     bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
     bf16* hl = x + (size_t)n * D;
     float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
@@ -1190,11 +1268,12 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         else
             hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
                                kv->d_len, kv->gen_cap, 1, kv->d_stop, kv->n_seqs);
+        if (scored) CR_TRY(score_rows(kv, lg, V, n, d_seqs, st));
         return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
     };
     // graph path: the plain generation loop (no forced ids, no logits copy), nothing recording events on these launches
-    // (a step with a sampled row launches the sampling pick: it is left out of the graph path)
-    const bool graphable = c->decode_graph && !force_tokens && !logits && !sampled && !(c->prof && c->prof_mode != 2);
+    // (a step with a sampled row launches the sampling pick, one with a scored row the score kernels: both are left out of the graph path)
+    const bool graphable = c->decode_graph && !force_tokens && !logits && !sampled && !scored && !(c->prof && c->prof_mode != 2);
     bool done = false;
     hipStream_t gs = st;                               // the null stream cannot be captured: use the context's blocking side stream
     if (graphable && !st) {

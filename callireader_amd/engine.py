@@ -2,6 +2,7 @@
 all compute goes through libcallireader_hip.so.  No torch math on the hot path."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _binding as B
@@ -274,6 +275,7 @@ class KVCache:
         self.eng, self._h, self.n_seqs, self.max_tokens = eng, h, n_seqs, max_tokens
         fmt = B.lib.cr_kv_format(h)
         self.format = {v: k for k, v in KV_DTYPES.items()}[fmt]      # 'bf16' | 'e4m3'
+        self._top_n = {}                                             # seq -> alternatives recorded per id (set_logprobs)
 
     def length(self, seq):
         return B.lib.cr_kv_length(self._h, seq)
@@ -281,6 +283,10 @@ class KVCache:
     def reset(self, seq=-1):
         """Forget one sequence, or all of them (seq < 0); enqueued on the current stream."""
         B.check(B.lib.cr_kv_reset(self._h, seq, _stream()), 'cr_kv_reset')
+        if seq < 0:
+            self._top_n.clear()
+        else:
+            self._top_n.pop(seq, None)
 
     def read(self, layer, seq, pos, which=0):
         """(8, 128) bf16: K (which=0, after RoPE) or V (which=1) of one cached position, all KV heads."""
@@ -319,6 +325,27 @@ class KVCache:
         if n < 0:
             B.check(n, 'cr_kv_generated')
         return list(buf[:n])
+
+    def set_logprobs(self, seq, top_n):
+        """cr_kv_set_logprobs on the current stream: record the log-probability and the `top_n` (1..8) best alternatives of every id the sequence
+        generates from now on; 0 switches the scores off (the default, what reset restores).  Call after reset(seq) and before the sequence's prefill."""
+        top_n = int(top_n)
+        if not 0 <= top_n <= 8:
+            raise ValueError(f'top_n has to be 0 (off) or 1..8, got {top_n}')
+        B.check(B.lib.cr_kv_set_logprobs(self._h, seq, top_n, _stream()), 'cr_kv_set_logprobs')
+        self._top_n[seq] = top_n
+
+    def logprobs(self, seq, max_tokens=4096):
+        """cr_kv_logprobs: (lp [T] float32, top_ids [T, n] int32, top_lp [T, n] float32) numpy arrays for the T ids generated so far (generated()'s
+        count), n the sequence's top_n.  Synchronises the current stream.  CalliReaderError for a sequence whose scores are off."""
+        lp = np.empty(max_tokens, dtype=np.float32)
+        ti = np.empty((max_tokens, 8), dtype=np.int32)
+        tl = np.empty((max_tokens, 8), dtype=np.float32)
+        n = B.lib.cr_kv_logprobs(self._h, seq, C.c_void_p(lp.ctypes.data), C.c_void_p(ti.ctypes.data), C.c_void_p(tl.ctypes.data), max_tokens, _stream())
+        if n < 0:
+            B.check(n, 'cr_kv_logprobs')
+        k = self._top_n.get(seq) or 8
+        return lp[:n].copy(), ti[:n, :k].copy(), tl[:n, :k].copy()
 
     def free(self):
         if self._h:
@@ -522,3 +549,20 @@ def op_sample(eng, logits, temperature, top_k, top_p, seed, step, history=None, 
     B.check(B.lib.cr_op_sample(eng._h, _p(lg), n, V, _p(hist), cap, _p(hl), float(penalty), _p(t), _p(k), _p(p), _p(sd), _p(st), _p(ids), _p(kept),
                                _stream()), 'cr_op_sample')
     return ids, kept
+
+
+def op_logprobs(logits, ids, top_n=1):
+    """cr_op_logprobs: the score kernels on given fp32 rows z [n, vocab] and the id scored in each row.  Returns (lp [n] float32, top_ids [n, top_n] int32,
+    top_lp [n, top_n] float32) on the device."""
+    top_n = int(top_n)
+    if not 1 <= top_n <= 8:
+        raise ValueError(f'top_n has to be 1..8, got {top_n}')
+    lg = logits.to(torch.float32).contiguous()
+    n, V = lg.shape
+    idt = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).to(lg.device).contiguous()
+    assert idt.numel() == n and lg.is_cuda
+    lp = torch.empty(n, dtype=torch.float32, device=lg.device)
+    ti = torch.empty(n, 8, dtype=torch.int32, device=lg.device)
+    tl = torch.empty(n, 8, dtype=torch.float32, device=lg.device)
+    B.check(B.lib.cr_op_logprobs(_p(lg), n, V, _p(idt), top_n, _p(lp), _p(ti), _p(tl), _stream()), 'cr_op_logprobs')
+    return lp, ti[:, :top_n].contiguous(), tl[:, :top_n].contiguous()

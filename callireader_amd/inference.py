@@ -61,37 +61,53 @@ def boxes_for(image_path, boxes_arg=None, required=True):
 
 
 def single_rec(model, tokenizer, detect_model, generation_config, image_path, prompt, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
-               boxes=None, quiet=False):
+               boxes=None, quiet=False, scores=0):
+    """scores = n > 0 (--scores): the page's token scores are taken with n alternatives; prints one more line (`confidence <c> min <p> at token <k>
+    (<piece>)`) and returns (response, scores.ResponseScores)."""
     bx = None
     if use_p and (boxes is not None or detect_model is None):
         bx = boxes_for(image_path, boxes)
-    response, history = model.chat_ocr(tokenizer, detect_model, image_path, prompt, generation_config, use_p=use_p, hard_vq=hard_vq,
-                                       drop_zero=drop_zero, repetition_penalty=repetition_penalty, return_history=True,
-                                       verbose=verbose, boxes=bx)
+    out = model.chat_ocr(tokenizer, detect_model, image_path, prompt, generation_config, use_p=use_p, hard_vq=hard_vq,
+                         drop_zero=drop_zero, repetition_penalty=repetition_penalty, return_history=True,
+                         verbose=verbose, boxes=bx, **(dict(return_scores=scores) if scores else {}))
+    response = out[0]
     if not quiet:
         print(f'User: {prompt}\nAssistant: {response}')
-    return response
+        if scores:
+            print(out[2].summary_line())
+    return (response, out[2]) if scores else response
 
 
 DEFAULT_BATCH_PAGES = 64       # pages per decode batch in folder mode: the most rows the batched decode kernels take, and the batch the headline is measured on
 
 
 def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, prompt, save_name, use_p, hard_vq, drop_zero, repetition_penalty,
-               verbose, batch_pages=DEFAULT_BATCH_PAGES, continuous=False):
+               verbose, batch_pages=DEFAULT_BATCH_PAGES, continuous=False, scores=0):
     """inference.py:47-62: every image of the folder -> results JSON [{imagePath, prompt, response}], an image that fails -> "ERROR!" for that entry only.
     The reference calls chat_ocr image after image; here the images go through `chat_ocr_stream` in batches of `batch_pages` (two batches in flight, files
     decoded ahead on threads): each response is the one the image's own chat_ocr call gives, pages/s is what changes (batch_pages <= 1: the serial loop).
     Failures stay per image: a page that cannot be read, has no boxes JSON / no box, or whose prompt is too long is reported alone; if a batch fails as a whole
     its pages are run one by one, each in its own try/except, as the reference does.
     continuous=True: the images go through `chat_ocr_continuous` instead (`batch_pages` decode rows, a row refilled as soon as its page stops);
-    the same responses, JSON and console lines."""
+    the same responses, JSON and console lines.
+    scores = n > 0 (--scores): a second file, the results JSON's name with `.scores.json` in place of its `json` ending, holds per image
+    {imagePath, scores: ResponseScores.to_json() with n alternatives per token, or null for an image whose entry is "ERROR!"}; the results JSON itself is
+    byte-identical to a run without it."""
     paths = get_image_paths(folder_path)
-    responses = {}
+    responses, page_scores = {}, {}
+    skw = dict(return_scores=scores) if scores else {}
+
+    def put(pic_path, r, sc=None):
+        """one page's outcome: a response, an exception, or with scores the pair (response, ResponseScores)"""
+        if scores and isinstance(r, tuple):
+            r, sc = r
+        responses[pic_path] = r
+        page_scores[pic_path] = sc
 
     def one(pic_path):
         try:
             return single_rec(model, tokenizer, detect_model, generation_config, pic_path, prompt, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
-                              quiet=True)
+                              quiet=True, scores=scores)
         except Exception as e:                               # inference.py:55-57
             return e
 
@@ -111,21 +127,22 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
             except Exception as e:
                 responses[pic_path] = e
         try:
-            for i, r in model.chat_ocr_continuous(tokenizer, detect_model, ready, prompt, generation_config,
+            for i, r, *sc in model.chat_ocr_continuous(tokenizer, detect_model, ready, prompt, generation_config,
                                                   boxes_list=[boxes[p] for p in ready] if (use_p and detect_model is None) else None, use_p=use_p,
                                                   drop_zero=drop_zero, hard_vq=hard_vq, repetition_penalty=repetition_penalty, slots=batch_pages,
-                                                  errors='return'):
-                responses[ready[i]] = r
+                                                  errors='return', **skw):
+                put(ready[i], r, *sc)
         except Exception as e:
             left = [p for p in ready if p not in responses]
             print(f'[folder_rec] continuous batching failed ({e}); its {len(left)} remaining pages run one by one')
             for pic_path in left:
-                responses[pic_path] = one(pic_path)
+                put(pic_path, one(pic_path))
         for pic_path in paths:
             record(pic_path, responses[pic_path])
     elif batch_pages <= 1 or not hasattr(model, 'chat_ocr_stream'):
         for pic_path in paths:
-            record(pic_path, one(pic_path))
+            put(pic_path, one(pic_path))
+            record(pic_path, responses[pic_path])
     else:
         # boxes from JSON where there is no detector (single_rec's rule); a page without them fails alone, before the batch is formed
         boxes, ready = {}, []
@@ -140,16 +157,17 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
         while done < len(batches):
             stream = model.chat_ocr_stream(tokenizer, detect_model, batches[done:], prompt, generation_config,
                                            boxes_batches=[[boxes[p] for p in b] for b in batches[done:]] if (use_p and detect_model is None) else None,
-                                           use_p=use_p, drop_zero=drop_zero, hard_vq=hard_vq, repetition_penalty=repetition_penalty, errors='return')
+                                           use_p=use_p, drop_zero=drop_zero, hard_vq=hard_vq, repetition_penalty=repetition_penalty, errors='return', **skw)
             try:
                 for res in stream:
-                    for pic_path, r in zip(batches[done], res):
-                        responses[pic_path] = r
+                    res, scs = res if scores else (res, [None] * len(batches[done]))
+                    for pic_path, r, sc in zip(batches[done], res, scs):
+                        put(pic_path, r, sc)
                     done += 1
             except Exception as e:
                 print(f'[folder_rec] a batch failed as a whole ({e}); its {len(batches[done])} pages run one by one')
                 for pic_path in batches[done]:
-                    responses[pic_path] = one(pic_path)
+                    put(pic_path, one(pic_path))
                 done += 1
         for pic_path in paths:                               # the reference's console output and order
             record(pic_path, responses[pic_path])
@@ -158,7 +176,16 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
         save_name += '_result.json'
     with open(save_name, 'w', encoding='utf-8') as f:
         json.dump(results, f, ensure_ascii=False, indent=4)           # utils/utils.py:59-62 save_json
+    if scores:
+        doc = [{'imagePath': p, 'scores': None if (responses[p] == 'ERROR!' or page_scores.get(p) is None) else page_scores[p].to_json()} for p in paths]
+        with open(scores_name(save_name), 'w', encoding='utf-8') as f:
+            json.dump(doc, f, ensure_ascii=False, indent=4)
     return results
+
+
+def scores_name(save_name):
+    """The scores file of a results file: `.scores.json` in place of the name's `json` ending (recognition.json -> recognition.scores.json)."""
+    return save_name[:-len('json')].rstrip('.') + '.scores.json'
 
 
 def build_parser():
@@ -189,6 +216,9 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=None, help='torch.manual_seed before the run: --do_sample output becomes reproducible')
     parser.add_argument('--fp8_kv', action='store_true',
                         help='e4m3 KV cache for the decode (kv_cache_dtype="e4m3": 0.52x the cache bytes; off by default; a throughput option, not parity-preserving)')
+    parser.add_argument('--scores', type=int, nargs='?', const=1, default=0, choices=range(0, 9), metavar='N',
+                        help='per-token log-probabilities with the N (default 1, at most 8) most likely alternatives: single image prints one more line '
+                             '(confidence, the least certain token); folder mode writes <save_name minus json>.scores.json next to the results JSON, which does not change')
     return parser
 
 
@@ -223,13 +253,13 @@ def main(argv=None):
     if is_image(args.tgt):
         print('Single image recognition mode.')
         single_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, args.use_p, args.hard_vq, args.drop_zero,
-                   args.repetition_penalty, args.verbose, args.boxes)
+                   args.repetition_penalty, args.verbose, args.boxes, scores=args.scores)
     elif os.path.isdir(args.tgt):
         print('Multiple images recognition mode')
         os.makedirs('results', exist_ok=True)
         folder_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, os.path.join('results', args.save_name),
                    args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose, batch_pages=args.batch_pages,
-                   continuous=args.continuous)
+                   continuous=args.continuous, scores=args.scores)
     else:
         raise ValueError('The target should be either a image path or a folder that contain images!')
 

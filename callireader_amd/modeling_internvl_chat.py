@@ -27,6 +27,7 @@ from .conversation import get_conv_template
 from .engine import Engine
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
 from .sampling import base_seed, page_seeds, parse as sampling_parse, splitmix64
+from .scores import ResponseScores, TokenScores, generate_output, parse as scores_parse, per_page as scores_per_page
 
 
 class InternVLChatModel:
@@ -240,16 +241,18 @@ class InternVLChatModel:
         return self.sorter
 
     # ---- generation ----------------------------------------------------------------------------
-    def _generate(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, sampling=None, check_every=16):
+    def _generate(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, sampling=None, check_every=16, logprobs=0):
         """transformers 4.45.2 GenerationMixin._sample with num_beams=1 for ONE sequence: greedy (sampling None), or do_sample=True with
         `sampling` (a sampling.SamplingParams; the page's seed is page_seeds(1)[0]); returns only the new ids, EOS included (oracle/generate.py
-        documents the semantics)."""
+        documents the semantics).  logprobs = n > 0: returns (ids, scores.TokenScores with n alternatives per id, cut like the ids)."""
         kv = self.kv(1)
         kv.reset(0)
         if input_embeds.shape[0] + max_new_tokens > self.max_tokens:
             raise ValueError(f'prompt of {input_embeds.shape[0]} tokens + {max_new_tokens} new exceeds max_tokens={self.max_tokens}')
         if sampling is not None:
             kv.set_sampling(0, sampling.temperature, sampling.top_k, sampling.top_p, page_seeds(1)[0])
+        if logprobs:
+            kv.set_logprobs(0, logprobs)
         self.engine.prefill(kv, 0, input_embeds, penalty=repetition_penalty)
         n = 1
         while n < max_new_tokens:
@@ -262,12 +265,41 @@ class InternVLChatModel:
         ids = kv.generated(0)[:max_new_tokens]
         if eos_token_id is not None and eos_token_id in ids:
             ids = ids[:ids.index(eos_token_id) + 1]       # ids past EOS were speculative; the reference stops here
-        return torch.tensor([ids], dtype=torch.long, device=self.device)
+        out = torch.tensor([ids], dtype=torch.long, device=self.device)
+        return (out, TokenScores.read(kv, 0, len(ids))) if logprobs else out
+
+    def _generate_kw(self, input_embeds, repetition_penalty, generate_kwargs):
+        """_generate driven by transformers' keyword arguments: the new ids, or under return_dict_in_generate=True a scores.GenerateOutput."""
+        max_new, eos, sp = self._gen_args(generate_kwargs)
+        n = scores_parse(generate_kwargs)
+        if not generate_kwargs.get('return_dict_in_generate', False):
+            return self._generate(input_embeds, max_new, eos, repetition_penalty, sp)
+        if not n:
+            return generate_output(self._generate(input_embeds, max_new, eos, repetition_penalty, sp))
+        return generate_output(*self._generate(input_embeds, max_new, eos, repetition_penalty, sp, logprobs=n))
 
     @staticmethod
     def _gen_args(generate_kwargs):
         """(max_new_tokens, eos_token_id, SamplingParams or None for greedy): transformers' defaults and validation (sampling.parse)."""
         return generate_kwargs.get('max_new_tokens', 1024), generate_kwargs.get('eos_token_id', EOS_TOKEN_ID), sampling_parse(generate_kwargs)
+
+    @staticmethod
+    def _score_args(generation_config, return_scores):
+        """(generation_config with the score keywords set, n) for a chat entry point called with return_scores: True records the
+        generation_config's `top_logprobs` alternatives per token (default 1), an int 1..8 that many."""
+        gc = dict(generation_config)
+        if not return_scores:
+            return gc, 0
+        n = (gc.get('top_logprobs') or 1) if return_scores is True else return_scores
+        gc.update(return_dict_in_generate=True, output_scores=True, top_logprobs=n)
+        return gc, scores_parse(gc)
+
+    @staticmethod
+    def _with_scores(tokenizer, out):
+        """(ids tensor, ResponseScores or None) of what a generate_* call returned."""
+        if hasattr(out, 'sequences'):
+            return out.sequences, ResponseScores.build(tokenizer, out.sequences[0].tolist(), out.scores)
+        return out, None
 
     @torch.no_grad()
     def generate_ocr(self, pixel_values=None, input_ids=None, attention_mask=None, visual_features=None,
@@ -287,8 +319,7 @@ class InternVLChatModel:
                                                     img_id=self.img_context_token_id, ref_id=self.aligned_token_id)
         else:
             input_embeds = self.engine.embed_splice(input_ids.reshape(-1))  # :1107
-        max_new, eos, sp = self._gen_args(generate_kwargs)
-        return self._generate(input_embeds, max_new, eos, repetition_penalty, sp)
+        return self._generate_kw(input_embeds, repetition_penalty, generate_kwargs)
 
     @torch.no_grad()
     def generate_origin(self, pixel_values=None, input_ids=None, attention_mask=None, visual_features=None,
@@ -318,8 +349,7 @@ class InternVLChatModel:
             input_embeds = self.engine.embed_splice(ids, vit_embeds, None, img_id=self.img_context_token_id)
         else:
             input_embeds = self.engine.embed_splice(input_ids.reshape(-1))  # :1172
-        max_new, eos, sp = self._gen_args(generate_kwargs)
-        return self._generate(input_embeds, max_new, eos, penalty, sp)
+        return self._generate_kw(input_embeds, penalty, generate_kwargs)
 
     # ---- chat API ------------------------------------------------------------------------------
     def _build_query(self, question, history, num_patches_list, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN):
@@ -339,8 +369,9 @@ class InternVLChatModel:
 
     def chat(self, tokenizer, pixel_values, question, generation_config, history=None, return_history=False,
              num_patches_list=None, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
-             verbose=False):
-        """:955-1018"""
+             verbose=False, return_scores=False):
+        """:955-1018.  return_scores (True, or the number of alternatives per token): a scores.ResponseScores is returned after the response
+        (after `history` when that is returned)."""
         if history is None and pixel_values is not None and '<image>' not in question:
             question = '<image>\n' + question
         if num_patches_list is None:
@@ -350,21 +381,25 @@ class InternVLChatModel:
         query, template, history = self._build_query(question, history, num_patches_list, IMG_START_TOKEN,
                                                      IMG_END_TOKEN, IMG_CONTEXT_TOKEN)
         model_inputs = tokenizer(query, return_tensors='pt')
-        generation_config = dict(generation_config)
+        generation_config, _ = self._score_args(generation_config, return_scores)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
         out = self.generate_origin(pixel_values=pixel_values, input_ids=model_inputs['input_ids'],
                                    attention_mask=model_inputs['attention_mask'], **generation_config)
+        out, sc = self._with_scores(tokenizer, out)
         response = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
         response = response.split(template.sep)[0].strip()
         history.append((question, response))
+        if return_scores:
+            return (response, history, sc) if return_history else (response, sc)
         return (response, history) if return_history else response
 
     def chat_ocr(self, tokenizer, detect_model, img_path, questions, generation_config, num_patches_list=None,
                  history=None, return_history=False, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
                  IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', verbose=False, image_counts=None,
                  batch=False, use_p=True, drop_zero=False, hard_vq=False, repetition_penalty=1.5, region_wise=False,
-                 boxes=None):
-        """:649-762"""
+                 boxes=None, return_scores=False):
+        """:649-762.  return_scores (True, or the number of alternatives per token): a scores.ResponseScores is returned after the response
+        (after `history` when that is returned); a detection failure still returns its message alone."""
         pixel_values = None
         sub_img = None
         page = None                       # the decoded page, handed on to calli_align (the reference opens the file a second time there, :558: 14.5 ms of JPEG decode on the example page)
@@ -407,28 +442,32 @@ class InternVLChatModel:
         query, template, history = self._build_query(question, history, num_patches_list, IMG_START_TOKEN,
                                                      IMG_END_TOKEN, IMG_CONTEXT_TOKEN)
         model_inputs = tokenizer(query, return_tensors='pt')
-        generation_config = dict(generation_config)
+        generation_config, _ = self._score_args(generation_config, return_scores)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)   # :709,732
         out = self.generate_ocr(pixel_values=pixel_values, input_ids=model_inputs['input_ids'],
                                 attention_mask=model_inputs['attention_mask'],
                                 reference_embeds=out_tokens if use_p else None,
                                 repetition_penalty=repetition_penalty, **generation_config)
+        out, sc = self._with_scores(tokenizer, out)
         response = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
         response = response.split(template.sep)[0].strip()                      # :752-753
         history.append((question, response))
+        if return_scores:
+            return (response, history, sc) if return_history else (response, sc)
         return (response, history) if return_history else response
 
     def dynamic_chat(self, tokenizer, pixel_values, questions, generation_config, num_patches_list=None, history=None,
                      return_history=False, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
-                     verbose=False, image_counts=None, batch=False, use_p=True):
+                     verbose=False, image_counts=None, batch=False, use_p=True, return_scores=False):
         """:765-901.  `use_p` switches every tile to 3 pseudo-tokens (and, as upstream, leaves num_image_token at 3 on
         the object afterwards).  batch=True: a list of questions, one answer each (the reference pads them into one
         batch; here every row runs at its own length and the rows decode together).  batch=False: the reference's
-        hard-wired single-turn prompt (:857-866), history only feeds the returned list."""
+        hard-wired single-turn prompt (:857-866), history only feeds the returned list.  return_scores: a scores.ResponseScores after the
+        response (after `history` when returned); batch=True: (responses, [ResponseScores per question])."""
         if use_p:
             self.num_image_token = 3                                        # :768-769
         gen = self.generate if use_p else self.generate_origin
-        generation_config = dict(generation_config)
+        generation_config, _ = self._score_args(generation_config, return_scores)
         self.img_context_token_id = tokenizer.convert_tokens_to_ids(IMG_CONTEXT_TOKEN)
         if batch:
             assert isinstance(questions, list) and len(questions) > 0 and isinstance(questions[0], str)
@@ -442,7 +481,7 @@ class InternVLChatModel:
                 print(f'dynamic ViT batch size: {pixel_values.shape[0]}')
             template = get_conv_template(self.template)
             generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
-            responses, off = [], 0
+            responses, all_sc, off = [], [], 0
             for idx, num_patches in enumerate(num_patches_list):
                 question = questions[idx]
                 if pixel_values is not None and '<image>' not in question:
@@ -454,9 +493,10 @@ class InternVLChatModel:
                 ids = tokenizer(query, return_tensors='pt')['input_ids']
                 px = pixel_values[off:off + num_patches] if pixel_values is not None else None
                 off += num_patches
-                out = gen(pixel_values=px, input_ids=ids, **generation_config)
+                out, sc = self._with_scores(tokenizer, gen(pixel_values=px, input_ids=ids, **generation_config))
+                all_sc.append(sc)
                 responses.append(tokenizer.batch_decode(out, skip_special_tokens=True)[0].split(template.sep)[0].strip())
-            return responses
+            return (responses, all_sc) if return_scores else responses
         assert isinstance(questions, str)
         if num_patches_list is None:
             num_patches_list = [pixel_values.shape[0]] if pixel_values is not None else []
@@ -477,27 +517,44 @@ class InternVLChatModel:
         model_inputs = tokenizer(query, return_tensors='pt')
         out = gen(pixel_values=pixel_values, input_ids=model_inputs['input_ids'], attention_mask=model_inputs['attention_mask'],
                   **generation_config)
+        out, sc = self._with_scores(tokenizer, out)
         response = tokenizer.batch_decode(out, skip_special_tokens=True)[0].split(template.sep)[0].strip()
         history.append((questions, response))
         if return_history:
-            return response, history
+            return (response, history, sc) if return_scores else (response, history)
+        if return_scores:
+            return response, sc
         if verbose:
             print(query.replace(IMG_CONTEXT_TOKEN, '').replace(f'{IMG_START_TOKEN}{IMG_END_TOKEN}', '<image>'), response)
         return response
 
     def chat_ocr_pages(self, tokenizer, detect_model, images, question, generation_config, boxes_list=None, use_p=True,
                        drop_zero=False, hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
-                       IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise'):
+                       IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise', return_scores=False):
         """Many pages at once (new: the reference's chat_ocr is one page per call, evaluate.py loops over it).  The
         character tiles of ALL pages go through the visual stage as one batch, the prompts are prefilled together and
         the pages decode as one batch; every page gets exactly the response its own chat_ocr call would produce.
         errors='return': a page whose own chat_ocr call would raise before generation (unreadable image, detector failure, no box, prompt too long) gets that
-        exception object in its slot and the other pages run -- what folder mode's per-image try/except needs (inference.py:55-57)."""
+        exception object in its slot and the other pages run -- what folder mode's per-image try/except needs (inference.py:55-57).
+        return_scores (True, or the number of alternatives per token): returns (responses, scores) with one scores.ResponseScores per page (None for a
+        page that failed)."""
+        _, lpn = self._score_args(generation_config, return_scores)
         embeds, meta = self._ocr_embeds(tokenizer, detect_model, images, question, generation_config, boxes_list, use_p, drop_zero,
                                         hard_vq, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, errors=errors)
         outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, sampling=meta['sampling'],
-                                   seeds=self._ok_seeds(meta)) if embeds else []
-        return self._responses(tokenizer, outs, meta)
+                                   seeds=self._ok_seeds(meta), logprobs=lpn) if embeds else []
+        return self._answer(tokenizer, outs, meta, return_scores)
+
+    def _answer(self, tokenizer, outs, meta, return_scores):
+        """_responses of a batch, or with return_scores (outs = (ids, TokenScores) lists, or empty) the pair (responses, ResponseScores per page: None for
+        a page that did not run)."""
+        if not return_scores:
+            return self._responses(tokenizer, outs, meta)
+        outs, tss = outs if outs else ([], [])
+        sc = [None] * meta['n']
+        for i, o, ts in zip(meta['ok'], outs, tss):
+            sc[i] = ResponseScores.build(tokenizer, o, ts)
+        return self._responses(tokenizer, outs, meta), sc
 
     @staticmethod
     def _ok_seeds(meta):
@@ -520,12 +577,14 @@ class InternVLChatModel:
 
     def chat_ocr_stream(self, tokenizer, detect_model, image_batches, question, generation_config, boxes_batches=None, use_p=True,
                         drop_zero=False, hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
-                        IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise', stats=None):
+                        IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise', stats=None, return_scores=False):
         """chat_ocr_pages over a sequence of page batches with two batches in flight (PagePipeline): a generator that yields one
         list of responses per batch, in order; batch i decodes on a second stream while batch i+1 is detected, tiled, encoded and
         prefilled, and the image files of batch i+2 are being decoded on the feeder's threads (pageio.PageFeeder).  Every page gets the
         response of its own chat_ocr call.  stats (a dict) receives the host seconds per stage and, per batch, how long the compute stream
-        sat between the previous batch's prefill and this batch's first kernel."""
+        sat between the previous batch's prefill and this batch's first kernel.  return_scores: every batch is yielded as (responses, scores), as
+        chat_ocr_pages returns it."""
+        _, lpn = self._score_args(generation_config, return_scores)
         pipe, pending = None, None
         sampled = sampling_parse(generation_config) is not None
         base, page0, n_prev = (base_seed() if sampled else 0), 0, 0           # page j of the call (over all batches) samples with splitmix64(base + j)
@@ -575,7 +634,7 @@ class InternVLChatModel:
                     # they are handed out first, then the failure surfaces (folder mode re-runs exactly the failing batch page by page)
                     if pending is not None:
                         done, pending = pending, None
-                        yield self._responses(tokenizer, pipe.finish(), done)
+                        yield self._answer(tokenizer, pipe.finish(), done, return_scores)
                     raise
                 # batch i+1's tiles BEFORE this thread blocks for batch i-1's decode: when it comes back the compute stream is close to the end of batch i's
                 # prefill, and the first kernel of batch i+1 must not wait for 64 uploads to be issued (measured: 40-60 ms of idle compute stream per batch)
@@ -584,24 +643,24 @@ class InternVLChatModel:
                 fill()                                          # batch i+2: its files start decoding
                 if not embeds:                                  # nothing of this batch reached the language model
                     if pending is not None:
-                        yield self._responses(tokenizer, pipe.finish(), pending)
+                        yield self._answer(tokenizer, pipe.finish(), pending, return_scores)
                         pending = None
-                    yield self._responses(tokenizer, [], meta)
+                    yield self._answer(tokenizer, [], meta, return_scores)
                     continue
                 if pipe is None:
                     pipe = self.page_pipeline(max_new_tokens=meta['max_new'], eos_token_id=meta['eos'], repetition_penalty=repetition_penalty)
                 prev = pipe.start(embeds, sampling=meta['sampling'],
-                                  seeds=[splitmix64(base + page0 + i) for i in meta['ok']] if sampled else None)
+                                  seeds=[splitmix64(base + page0 + i) for i in meta['ok']] if sampled else None, logprobs=lpn)
                 if stats is not None:
                     e = torch.cuda.Event(enable_timing=True)
                     e.record(torch.cuda.current_stream())
                     marks.append(('end', e))
                 if pending is not None:
-                    yield self._responses(tokenizer, prev, pending)
+                    yield self._answer(tokenizer, prev, pending, return_scores)
                 pending = meta
             if pending is not None:
                 done, pending = pending, None
-                yield self._responses(tokenizer, pipe.finish(), done)
+                yield self._answer(tokenizer, pipe.finish(), done, return_scores)
         finally:
             for item in ahead:
                 if item is not None:
@@ -622,15 +681,18 @@ class InternVLChatModel:
 
     def chat_ocr_continuous(self, tokenizer, detect_model, images, question, generation_config, boxes_list=None, use_p=True, drop_zero=False,
                             hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
-                            ALIGNED_TOKEN='[UNUSED_TOKEN_140]', slots=64, admit_group=16, visual_group=16, errors='raise', stats=None):
+                            ALIGNED_TOKEN='[UNUSED_TOKEN_140]', slots=64, admit_group=16, visual_group=16, errors='raise', stats=None,
+                            return_scores=False):
         """chat_ocr_pages over any number of pages with continuous batching (continuous.ContinuousPipeline): a generator that yields
         (index into `images`, response) as pages finish -- a page that stops early frees its decode row for the next page at once, instead of
         waiting for the longest page of a batch.  The visual stage runs `visual_group` pages at a time ahead of admission (the next group's files
         are decoded on pageio.PageFeeder's threads meanwhile); prefill admits up to `admit_group` pages at once into `slots` decode rows.  Every
         response is the one the page's own chat_ocr call gives.  errors='return': a page whose own chat_ocr call would raise before generation
         yields that exception (chat_ocr_pages' semantics; when a group's visual stage fails as a whole, its pages are retried one by one).
-        stats (a dict) receives the pipeline's counters."""
+        stats (a dict) receives the pipeline's counters.  return_scores (True, or the number of alternatives per token): yields
+        (index, response, scores.ResponseScores), the scores None for a page that failed."""
         from .continuous import ContinuousPipeline
+        _, lpn = self._score_args(generation_config, return_scores)
         images = list(images)
         feeder = self._feeder()
         groups = [list(range(i, min(len(images), i + visual_group))) for i in range(0, len(images), visual_group)]
@@ -667,7 +729,7 @@ class InternVLChatModel:
                 for sub, (embeds, meta) in parts:
                     failed.extend((sub[k], e) for k, e in meta['failed'].items())
                     for k, emb in zip(meta['ok'], embeds):
-                        yield sub[k], emb, None, sp, (seeds[sub[k]] if sp is not None else None)
+                        yield sub[k], emb, None, sp, (seeds[sub[k]] if sp is not None else None), lpn
 
         def response(ids):
             return tokenizer.batch_decode(torch.tensor([ids]), skip_special_tokens=True)[0].split(template.sep)[0].strip()
@@ -676,12 +738,18 @@ class InternVLChatModel:
         pipe = ContinuousPipeline(self, slots=slots, max_new_tokens=max_new, eos_token_id=eos, repetition_penalty=repetition_penalty,
                                   admit_group=admit_group)
         try:
+            fail = (lambda f: tuple(f) + (None,)) if return_scores else (lambda f: f)
             for i, ids in pipe.map(items(), errors=errors):
                 while failed:
-                    yield failed.pop(0)
-                yield i, (ids if isinstance(ids, BaseException) else response(ids))
+                    yield fail(failed.pop(0))
+                if isinstance(ids, BaseException):
+                    yield fail((i, ids))
+                elif return_scores:
+                    yield i, response(ids[0]), ResponseScores.build(tokenizer, *ids)
+                else:
+                    yield i, response(ids)
             while failed:
-                yield failed.pop(0)
+                yield fail(failed.pop(0))
         finally:
             if stats is not None:
                 stats.update(pipe.stats)
@@ -800,8 +868,8 @@ class InternVLChatModel:
 
     def batch_chat(self, tokenizer, pixel_values, questions, generation_config, num_patches_list=None, history=None,
                    return_history=False, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
-                   verbose=False, image_counts=None):
-        """:903-951.  The reference left-pads and runs one padded batch; here every query is prefilled at its own
+                   verbose=False, image_counts=None, return_scores=False):
+        """:903-951.  return_scores: returns (responses, [scores.ResponseScores per question]).  The reference left-pads and runs one padded batch; here every query is prefilled at its own
         length and the pages then decode together (cr_llm_decode), which gives each row exactly its unpadded result."""
         if history is not None or return_history:
             print('Now multi-turn chat is not supported in batch_chat.')
@@ -809,7 +877,7 @@ class InternVLChatModel:
         if image_counts is not None:
             num_patches_list = image_counts
         self.img_context_token_id = tokenizer.convert_tokens_to_ids(IMG_CONTEXT_TOKEN)
-        generation_config = dict(generation_config)
+        generation_config, lpn = self._score_args(generation_config, return_scores)
         embeds, off = [], 0
         feats = self.extract_feature(pixel_values) if pixel_values is not None else None
         for idx, num_patches in enumerate(num_patches_list):
@@ -824,9 +892,11 @@ class InternVLChatModel:
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
         max_new, eos, sp = self._gen_args(generation_config)
         outs = self.generate_pages(embeds, max_new, eos, generation_config.get('repetition_penalty', 1.0), sampling=sp,
-                                   seeds=page_seeds(len(embeds)) if sp is not None else None)
+                                   seeds=page_seeds(len(embeds)) if sp is not None else None, logprobs=lpn)
+        outs, tss = outs if lpn else (outs, None)
         responses = [tokenizer.batch_decode(torch.tensor([o]), skip_special_tokens=True)[0] for o in outs]
-        return [r.split(template.sep)[0].strip() for r in responses]
+        responses = [r.split(template.sep)[0].strip() for r in responses]
+        return (responses, [ResponseScores.build(tokenizer, o, ts) for o, ts in zip(outs, tss)]) if return_scores else responses
 
     # ---- page-parallel generation (new: the reference decodes one page at a time) ---------------
     def page_pipeline(self, **kw):
@@ -834,13 +904,17 @@ class InternVLChatModel:
         return PagePipeline(self, **kw)
 
     def generate_pages(self, embeds_list, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0,
-                       check_every=16, prefill_batch=16, sampling=None, seeds=None):
+                       check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0):
         """Prefill every page, then decode all unfinished pages as ONE batch per step: the 14.7 GB of LLM weights are
         streamed once per step for all pages.  Per page the ids equal the single-page greedy result.
         sampling: None (every page greedy), one sampling.SamplingParams for every page, or a list with one entry (or None: greedy) per page;
-        seeds: one 64-bit seed per page (default page_seeds(P)).  A sampled page's ids depend only on its prompt, its parameters and its seed."""
+        seeds: one 64-bit seed per page (default page_seeds(P)).  A sampled page's ids depend only on its prompt, its parameters and its seed.
+        logprobs: 0 (the return value is the list of id lists), an int n in 1..8 for every page, or one int per page.  When any is non-zero the
+        return value is (ids, scores): scores[i] is the page's scores.TokenScores with its n alternatives per id, cut like its ids, or None for a
+        page with 0.  A page's scores, like its ids, do not depend on the batch it decodes in."""
         P = len(embeds_list)
         per_page = _per_page_sampling(sampling, seeds, P)
+        lpn = scores_per_page(logprobs, P)
         if self._kv is None or self._kv.n_seqs < P:
             if self._kv is not None:
                 self._kv.free()
@@ -849,6 +923,7 @@ class InternVLChatModel:
         kv = self._kv
         kv.reset()
         _set_sampling(kv, per_page)
+        _set_logprobs(kv, lpn)
         for i0 in range(0, P, prefill_batch):                       # prompts of several pages share the linear layers' GEMMs
             idx = list(range(i0, min(P, i0 + prefill_batch)))
             self.engine.prefill_batch(kv, idx, [embeds_list[i] for i in idx], penalty=repetition_penalty)
@@ -874,7 +949,7 @@ class InternVLChatModel:
                 if eos_token_id is not None and eos_token_id in ids:
                     ids = ids[:ids.index(eos_token_id) + 1]
             outs.append(ids)
-        return outs
+        return (outs, _read_scores(kv, lpn, outs)) if any(lpn) else outs
 
 
 class PagePipeline:
@@ -931,7 +1006,7 @@ class PagePipeline:
             job = self.jobs.get()
             if job is None:
                 return
-            kv, P, ready, budgets = job
+            kv, P, ready, budgets, lpn = job
             try:
                 with torch.cuda.stream(self.side):
                     self.side.wait_event(ready)                        # the prefill that filled this cache, on the caller's stream
@@ -976,6 +1051,8 @@ class PagePipeline:
                             if self.eos is not None and self.eos in ids:
                                 ids = ids[:ids.index(self.eos) + 1]
                         outs.append(ids)
+                    if any(lpn):
+                        outs = (outs, _read_scores(kv, lpn, outs))
                 self.results.put(outs)
             except BaseException as e:                                 # hand the failure to the caller's thread
                 self.results.put(e)
@@ -989,13 +1066,14 @@ class PagePipeline:
             raise out
         return out
 
-    def start(self, embeds_list, budgets=None, sampling=None, seeds=None):
+    def start(self, embeds_list, budgets=None, sampling=None, seeds=None, logprobs=0):
         """Prefill a batch on the caller's stream and hand it to the decode thread; returns the previous batch's ids (None if there
         was none), waiting for them if they are not there yet.  budgets: optional per-page max_new_tokens (<= the pipeline's): a page
         leaves the batch at the first EOS check at or past its budget and its ids are cut there, as its own generate_pages call would.
-        sampling / seeds: as generate_pages takes them."""
+        sampling / seeds / logprobs: as generate_pages takes them; a batch started with a non-zero logprobs is returned as (ids, scores)."""
         P = len(embeds_list)
         per_page = _per_page_sampling(sampling, seeds, P)
+        lpn = scores_per_page(logprobs, P)
         # The OTHER slot may be under the worker's decode right now (the previous batch, not collected yet): it is only ever
         # CREATED here, on the first batch (28 GB at 64 pages: not inside a later step), never regrown -- a batch larger than it
         # holds regrows it when that slot's turn comes, i.e. after _collect() has returned the batch that last used it.
@@ -1005,13 +1083,14 @@ class PagePipeline:
         self.turn ^= 1
         kv.reset()
         _set_sampling(kv, per_page)
+        _set_logprobs(kv, lpn)
         for i0 in range(0, P, self.prefill_batch):
             idx = list(range(i0, min(P, i0 + self.prefill_batch)))
             self.eng.prefill_batch(kv, idx, [embeds_list[i] for i in idx], penalty=self.penalty)
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream())
         prev = self._collect()
-        self.jobs.put((kv, P, ready, None if budgets is None else [min(int(b), self.max_new_tokens) for b in budgets]))
+        self.jobs.put((kv, P, ready, None if budgets is None else [min(int(b), self.max_new_tokens) for b in budgets], lpn))
         self.in_flight += 1
         return prev
 
@@ -1054,6 +1133,18 @@ def _set_sampling(kv, per_page):
     for i, e in enumerate(per_page or ()):
         if e is not None:
             kv.set_sampling(i, e[0].temperature, e[0].top_k, e[0].top_p, e[1])
+
+
+def _set_logprobs(kv, lpn):
+    """The scored pages' state, after the cache's reset and before the prefill (whose pick is every page's step 0)."""
+    for i, n in enumerate(lpn):
+        if n:
+            kv.set_logprobs(i, n)
+
+
+def _read_scores(kv, lpn, outs):
+    """TokenScores of the scored pages (None for the others), cut to the ids returned; on the current stream."""
+    return [TokenScores.read(kv, i, len(ids)) if n else None for i, (n, ids) in enumerate(zip(lpn, outs))]
 
 
 def load_boxes_json(path):

@@ -434,7 +434,7 @@ def plan_even(n_pages, world, page_tiles, char_tiles, prompt_tokens, new_tokens,
 
 def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, generation_config, boxes_list=None, hard_vq=False, repetition_penalty=1.5,
                            plan=None, cost=None, group=None, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
-                           ALIGNED_TOKEN='[UNUSED_TOKEN_140]'):
+                           ALIGNED_TOKEN='[UNUSED_TOKEN_140]', return_scores=False):
     """`model.chat_ocr_pages` over the ranks of `group`: every rank calls it with the same pages (paths or PIL images) and gets every page's response -- the one
     its own single-GPU `chat_ocr(..., use_p=True, drop_zero=False)` call gives (modeling_internvl_chat.py:649-763 per page; the reference has no multi-GPU form).
 
@@ -442,6 +442,9 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     `sharded_generate`: each rank crops and encodes ITS contiguous shard of the flat character-box list (GPU resize / pad / normalise, ViT -> mlp1 -> resampler ->
     VQ -> de-norm), one all-gather of the pseudo-token rows, and the owners of a page (plan_balanced over the pages' real sizes, or `plan`) encode its own
     tiles, splice, prefill and decode.  drop_zero is not offered here: it makes a page's prompt length depend on the VQ result of tiles another rank encodes."""
+    if return_scores or dict(generation_config).get('return_dict_in_generate', False):
+        raise NotImplementedError('chat_ocr_pages_sharded: token scores (return_scores=True) are not implemented across GPUs (a page\'s scores stay on the '
+                                  'rank that decodes it); use chat_ocr_pages / chat_ocr_continuous on one GPU')
     if dict(generation_config).get('do_sample', False):
         raise NotImplementedError('chat_ocr_pages_sharded: do_sample=True is not implemented across GPUs yet (it needs the per-call seed broadcast '
                                   'to every rank); use chat_ocr_pages / chat_ocr_continuous on one GPU')

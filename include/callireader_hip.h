@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 13  /* 13: cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -181,6 +181,29 @@ int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream);
  * sequence's first pick: call this after cr_kv_reset and BEFORE the sequence's prefill (cr_kv_set_stop may come after it).  A launch whose rows
  * are all greedy runs the greedy pick exactly as before.  Enqueued on `stream`. */
 int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
+/* Token scores of `seq`: top_n = 0 switches them off (the default, and what cr_kv_reset restores), 1..8 on with that many alternatives.  While on, every
+ * pick of the sequence (the prefill's is t = 0) is followed by the score kernels (csrc/logprobs.hip), which record for the t-th generated id
+ *     z           = the fp32 score row the pick chose from: the LM-head logits AFTER the repetition penalty and before anything else.  For a greedy
+ *                   sequence that is transformers' scores[t]; for a sampled one (cr_kv_set_sampling) it is the SAME row, i.e. before temperature /
+ *                   top-k / top-p, whereas transformers' scores under do_sample=True are the warped ones: a confidence describes the model, not the warper
+ *     lse         = m + log(sum_i exp(z_i - m)), m = max_i z_i, -inf entries contributing 0
+ *     logprob[t]  = z[id_t] - lse                        (what compute_transition_scores(normalize_logits=True) returns for greedy search)
+ *     top_ids[t][0..n), top_logprobs[t][0..n) = the n largest entries of z, descending, an exact tie broken towards the LOWER id (the greedy pick's
+ *                   rule: top_ids[t][0] == id_t for a greedy sequence), as id and z - lse; entries n..8 of a step hold id -1 and -inf
+ * A row is summed in an order that depends on vocab alone (fixed chunks of 4096 scores, merged in chunk order, no float atomics): the scores of a
+ * sequence are bit-equal whatever batch, row, slot, stream or pipeline computes them.  Accuracy: within 5e-6 absolute of the float64 log-softmax for
+ * |z| <= 32 (double accumulation, one fp32 rounding of the result).  A row holding NaN or +inf gives NaN log-probabilities for that step (ids
+ * unspecified).  With scores off for every row of a launch nothing is launched or changed; ids and logits never depend on the setting.  A decode step
+ * with a scored row stays out of the CR_DECODE_GRAPH replay, as a sampled one does.  The blocks (cr_kv_logprobs' layout, 68 bytes per generated id,
+ * 4096 ids per sequence) are allocated by the first call that switches a sequence of the cache on.  CR_ERR_ARG for top_n outside 0..8 (checked
+ * before the cache and sequence), CR_ERR_STATE when switching on a sequence that has generated ids already: call after cr_kv_reset and BEFORE the
+ * sequence's prefill.  Cache state like the stop criteria and the sampling state: any cache format, any decode option, a cache shared between
+ * contexts.  Enqueued on `stream` (the first switching-on call of a cache also synchronises it).  Added within ABI v13. */
+int cr_kv_set_logprobs(cr_kv* kv, int seq, int top_n, void* stream);
+/* The twin of cr_kv_generated: copy the scores of the ids generated so far for `seq` into host memory (at most `max` steps): lp [max] fp32, top_ids
+ * [max][8] int32, top_lp [max][8] fp32.  Returns the count (cr_kv_generated's), or < 0: CR_ERR_STATE for a sequence whose scores are off.
+ * Synchronises `stream`.  Added within ABI v13. */
+int cr_kv_logprobs(cr_kv* kv, int seq, float* lp, int32_t* top_ids, float* top_lp, int max, void* stream);
 /* Enqueue on `stream` an asynchronous copy of the finished queue into host_out (caller-owned PINNED memory of max >= 1 + 2 n_seqs
  * int32): host_out[0] = sequences pushed since the last cr_kv_reset(kv, -1) (a running count c), host_out[1 + k % n_seqs] = the
  * k-th of them (the ring holds the last n_seqs: a sequence is pushed again only after a reset, so a caller that releases a sequence
@@ -309,6 +332,10 @@ int cr_op_decode_swizzle(int which, const void* W, int64_t ldw, int N, int K, vo
 int cr_op_sample(cr_ctx* ctx, const float* logits, int n, int vocab, const int64_t* history, int hist_cap, const int32_t* hist_len, float penalty,
                  const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed, const int32_t* step, int64_t* out_ids,
                  int32_t* out_kept, void* stream);
+/* The score kernels of cr_kv_set_logprobs alone (test entry; the prefill and decode launch the same kernels): logits [n][vocab] fp32 = the rows z
+ * (not modified), ids [n] int64 = the id scored in each row; lp [n], top_ids [n][8], top_lp [n][8] as above with top_n alternatives (1..8, CR_ERR_ARG
+ * otherwise; vocab >= 8, n <= 65535).  All pointers are DEVICE arrays.  Synchronises `stream`.  Added within ABI v13. */
+int cr_op_logprobs(const float* logits, int n, int vocab, const int64_t* ids, int top_n, float* lp, int32_t* top_ids, float* top_lp, void* stream);
 /* q/k/v/o addressed as base + b*bs + row*rs + head*hs (elements) */
 int cr_op_attention(const void* q, const void* k, const void* v, void* o, const int64_t* strides12, int B, int H,
                     int Sq, int Sk, int head_dim, int kv_group, int causal, int q_pos0, float q_prescale, float s_div,
