@@ -87,8 +87,8 @@ class ContinuousPipeline:
                  poll_depth=3, ops=None):
         if slots < 1 or admit_group < 1 or poll_depth < 1:
             raise ValueError('slots, admit_group and poll_depth must be >= 1')
-        if not 1 <= max_new_tokens <= 4096:
-            raise ValueError(f'max_new_tokens={max_new_tokens}: 1 .. 4096 (the cache keeps at most 4096 generated ids per sequence)')
+        if not 1 <= max_new_tokens <= model.max_tokens:
+            raise ValueError(f'max_new_tokens={max_new_tokens}: 1 .. {model.max_tokens} (the cache holds max_tokens tokens per sequence, prompt included)')
         self.m, self.eng = model, model.engine
         self.ops = ops or _TorchOps(model.device)
         self.slots, self.admit_group, self.poll_depth = slots, admit_group, poll_depth

@@ -35,7 +35,7 @@ struct cr_kv {
     float* vs;
     int32_t* d_len;      // [n_seqs] tokens cached
     int32_t* d_ngen;     // [n_seqs] ids generated
-    int64_t* d_gen;      // [n_seqs][gen_cap]
+    int64_t* d_gen;      // [n_seqs][gen_cap]; gen_cap = max_tokens: every generated id costs a cached token, so the cache fills first
     // stop tracking (cr_kv_set_stop / cr_kv_poll_finished), one block of 1 + 4 n_seqs int32:
     //   [0] finished count (monotonic), [1, 1 + n) ring of finished sequence indices (entry k at 1 + k % n),
     //   [1 + n, 1 + 2n) stop count per sequence (0 = not stopped), [1 + 2n, 1 + 3n) EOS id (< 0: none), [1 + 3n, 1 + 4n) budget (<= 0: none)
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
 __global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty,
                                                     int seq0, const int32_t* __restrict__ seqs, int64_t* __restrict__ gen,
                                                     int32_t* __restrict__ ngen, int32_t* __restrict__ lens, int gen_cap, int len_add,
-                                                    int32_t* __restrict__ stop, int n_seqs) {
+                                                    int32_t* __restrict__ stop, int n_seqs, const float* __restrict__ orig) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, 
     float* lg = logits + (int64_t)row * ld;
     const int ng = ngen[seq];
     int64_t* g = gen + (int64_t)seq * gen_cap;
-    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid);
+    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid, orig ? orig + (int64_t)row * ld : nullptr);
     argmax_row(lg, vocab, tid, bv, bi);
     if (tid == 0) {
         if (ng < gen_cap) {
@@ -785,6 +785,13 @@ static bool any_sampled(const cr_kv* kv, const int32_t* seqs, int n) {
     return false;
 }
 
+// a row whose history is longer than the 4096 ids apply_penalty gathers in registers: the pick then needs an untouched copy of the rows (pick.hpp)
+static bool long_history(const cr_kv* kv, const int32_t* seqs, int n, float penalty) {
+    if (penalty == 1.0f) return false;
+    for (int i = 0; i < n; i++) if (kv->ngen[seqs[i]] > 4096) return true;
+    return false;
+}
+
 static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
     if (!kv->d_lpn) return false;
     for (int i = 0; i < n; i++) if (kv->scored[seqs[i]]) return true;
@@ -924,7 +931,7 @@ int cr_kv_alloc_ex(cr_ctx* c, int n_seqs, int max_tokens, int format, cr_kv** ou
     if (max_tokens > c->d.max_pos) return cr_fail(CR_ERR_ARG, "cr_kv_alloc: max_tokens %d exceeds the RoPE table (%d rows)", max_tokens, c->d.max_pos);
     CR_HIP(hipSetDevice(c->device));
     cr_kv* kv = new cr_kv();
-    kv->ctx = c; kv->n_seqs = n_seqs; kv->max_tokens = max_tokens; kv->gen_cap = 4096; kv->layers = c->d.llm_layers; kv->fmt = format;
+    kv->ctx = c; kv->n_seqs = n_seqs; kv->max_tokens = max_tokens; kv->gen_cap = max_tokens; kv->layers = c->d.llm_layers; kv->fmt = format;
     const size_t rows = (size_t)kv->layers * n_seqs * NKV * max_tokens;
     const size_t bytes = rows * HD * (format == CR_KV_E4M3 ? 1 : 2);
     const bool data_ok = format == CR_KV_E4M3
@@ -1004,7 +1011,6 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
 
 int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream) {
     if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: bad sequence");
-    if (max_new > kv->gen_cap) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: budget %d exceeds the generated-id capacity (%d)", max_new, kv->gen_cap);
     if (max_new > kv->max_tokens - kv->len[seq])
         return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: budget %d exceeds what the cache leaves after %d tokens (%d)", max_new, kv->len[seq], kv->max_tokens);
     if (eos_id >= kv->ctx->d.vocab) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: EOS id %d outside the vocabulary", eos_id);
@@ -1140,8 +1146,11 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     for (const Segment& sg : segs) stage_T = sg.S > stage_T ? sg.S : stage_T;
     const size_t lw = layers_ws(c, M, 0, n, kv8 ? prefill_stage_bytes(n, stage_T) : 0);
     const bool scored = any_scored(kv, seqs, n);
-    CR_TRY(ws_ensure(c, lw + (size_t)M * D * 2 + (size_t)n * D * 2 + (size_t)n * V * 4 + (size_t)M * 12 + (size_t)n * 68 + 8192 +
-                        (scored ? logprobs_scratch_bytes(n, V) : 0)));
+    const bool deep = long_history(kv, seqs, n, penalty);
+    const size_t need = lw + (size_t)M * D * 2 + (size_t)n * D * 2 + (size_t)n * V * 4 + (size_t)M * 12 + (size_t)n * 68 + 8192 +
+                        (scored ? logprobs_scratch_bytes(n, V) : 0);
+    CR_TRY(ws_ensure(c, need + (deep ? (size_t)n * V * 4 + 256 : 0)));
+    float* lg0 = deep ? (float*)(c->ws + ((need + 255) & ~(size_t)255)) : nullptr;      // the rows before the penalty, for the pick
     bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
     bf16* hl = x + (size_t)M * D;
     float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
@@ -1185,12 +1194,13 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         CR_TRY(rms(x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, D, hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
     CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st));
     if (last_logits) CR_HIP(hipMemcpyAsync(last_logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
+    if (lg0) CR_HIP(hipMemcpyAsync(lg0, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
     if (any_sampled(kv, seqs, n))
         CR_TRY(launch_sample(lg, V, V, penalty, n, c->d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
-                             nullptr, 1, kv->d_len, 0, kv->d_stop, kv->n_seqs, nullptr, nullptr, st));
+                             nullptr, 1, kv->d_len, 0, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, lg0));
     else
         hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, c->d_seqs, kv->d_gen, kv->d_ngen,
-                           kv->d_len, kv->gen_cap, 0, kv->d_stop, kv->n_seqs);
+                           kv->d_len, kv->gen_cap, 0, kv->d_stop, kv->n_seqs, lg0);
     if (scored) CR_TRY(score_rows(kv, lg, V, n, c->d_seqs, st));
     hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, d_seg, n, kv->d_len);
     CR_HIP(hipGetLastError());
@@ -1236,7 +1246,10 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     const int nsplit = ((max_len + 1 + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
     const size_t lw = layers_ws(c, n, nsplit);
     const bool scored = any_scored(kv, seqs, n);
-    CR_TRY(ws_ensure(c, lw + (size_t)n * D * 4 + (size_t)n * V * 4 + 4096 + (scored ? logprobs_scratch_bytes(n, V) : 0)));
+    const bool deep = long_history(kv, seqs, n, penalty);
+    const size_t need = lw + (size_t)n * D * 4 + (size_t)n * V * 4 + 4096 + (scored ? logprobs_scratch_bytes(n, V) : 0);
+    CR_TRY(ws_ensure(c, need + (deep ? (size_t)n * V * 4 + 256 : 0)));
+    float* lg0 = deep ? (float*)(c->ws + ((need + 255) & ~(size_t)255)) : nullptr;      // the rows before the penalty, for the pick
     bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
     bf16* hl = x + (size_t)n * D;
     float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
@@ -1262,18 +1275,19 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         else CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st, false, opt(c, "declayout.language_model.output.weight")));
         }
         if (logits) CR_HIP(hipMemcpyAsync(logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
+        if (lg0) CR_HIP(hipMemcpyAsync(lg0, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
         if (sampled)
             CR_TRY(launch_sample(lg, V, V, penalty, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
-                                 nullptr, 1, kv->d_len, 1, kv->d_stop, kv->n_seqs, nullptr, nullptr, st));
+                                 nullptr, 1, kv->d_len, 1, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, lg0));
         else
             hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
-                               kv->d_len, kv->gen_cap, 1, kv->d_stop, kv->n_seqs);
+                               kv->d_len, kv->gen_cap, 1, kv->d_stop, kv->n_seqs, lg0);
         if (scored) CR_TRY(score_rows(kv, lg, V, n, d_seqs, st));
         return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
     };
     // graph path: the plain generation loop (no forced ids, no logits copy), nothing recording events on these launches
     // (a step with a sampled row launches the sampling pick, one with a scored row the score kernels: both are left out of the graph path)
-    const bool graphable = c->decode_graph && !force_tokens && !logits && !sampled && !scored && !(c->prof && c->prof_mode != 2);
+    const bool graphable = c->decode_graph && !force_tokens && !logits && !sampled && !scored && !deep && !(c->prof && c->prof_mode != 2);
     bool done = false;
     hipStream_t gs = st;                               // the null stream cannot be captured: use the context's blocking side stream
     if (graphable && !st) {

@@ -15,9 +15,22 @@ __device__ inline void stop_check(int32_t* __restrict__ stop, int n_seqs, int se
     }
 }
 
-// RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) in place over the `ng` ids of history g (ng <= 4096).  Every thread of a
-// 1024-thread workgroup calls it.  The scores are gathered first, then scattered: duplicates of an id all see the ORIGINAL score.
-__device__ __forceinline__ void apply_penalty(float* __restrict__ lg, const int64_t* __restrict__ g, int ng, float penalty, int tid) {
+// RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) in place over the `ng` ids of history g.  Every thread of a 1024-thread workgroup
+// calls it.  The scores are gathered first, then scattered: duplicates of an id all see the ORIGINAL score.  Up to 4096 ids the gather stays in
+// registers; a longer history (a cache of more than 4096 tokens) needs `orig`, an untouched copy of the row that the caller made before the
+// launch: every id then reads its original score from there, whatever has been scattered into lg already (duplicates write the same value).
+// orig == NULL with ng > 4096 penalises the first 4096 ids only -- the callers pass a copy whenever a history can be that long.
+__device__ __forceinline__ void apply_penalty(float* __restrict__ lg, const int64_t* __restrict__ g, int ng, float penalty, int tid,
+                                              const float* __restrict__ orig = nullptr) {
+    if (ng > 4096 && orig) {
+        for (int h = tid; h < ng; h += 1024) {
+            const int64_t id = g[h];
+            const float v = orig[id];
+            lg[id] = v < 0.f ? v * penalty : v / penalty;
+        }
+        __syncthreads();
+        return;
+    }
     float sv[4]; int64_t si[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -54,6 +67,7 @@ __device__ __forceinline__ void argmax_row(const float* __restrict__ lg, int voc
 // history (gen [.][gen_cap], ngen) and the sampling state (temp / topk / topp / seed); a row whose temperature is not > 0 is greedy (pick_kernel's
 // result).  step NULL: step = ngen[seq]; else step[row].  append != 0: the id is appended to the sequence's history with pick_kernel's stop check and
 // lens update (lens[seq] += len_add).  out_ids / out_kept (may be NULL): the id and the size of the kept set of each row (0 for a greedy row).
+// orig (may be NULL): a copy of the rows made before the launch, for histories of more than 4096 ids (apply_penalty).
 int launch_sample(float* logits, int64_t ld, int vocab, float penalty, int rows, const int32_t* seqs, int64_t* gen, int32_t* ngen, int gen_cap,
                   const float* temp, const int32_t* topk, const float* topp, const uint64_t* seed, const int32_t* step, int append, int32_t* lens,
-                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st);
+                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig = nullptr);

@@ -218,7 +218,8 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
                                                       int64_t* __restrict__ gen, int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_,
                                                       const int32_t* __restrict__ topk_, const float* __restrict__ topp_, const uint64_t* __restrict__ seed_,
                                                       const int32_t* __restrict__ step_, int append, int32_t* __restrict__ lens, int len_add,
-                                                      int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_kept) {
+                                                      int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_kept,
+                                                      const float* __restrict__ orig) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     __shared__ SelShared s;
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
     float* lg = logits + (int64_t)row * ld;
     const int ng = ngen[seq] < gen_cap ? ngen[seq] : gen_cap;       // (a KV cache never holds more; cr_op_sample's hist_len may)
     int64_t* g = gen + (int64_t)seq * gen_cap;
-    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid);
+    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid, orig ? orig + (int64_t)row * ld : nullptr);
     const float temp = temp_[seq];
     int64_t id;
     int kept = 0;
@@ -321,9 +322,9 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
 
 int launch_sample(float* logits, int64_t ld, int vocab, float penalty, int rows, const int32_t* seqs, int64_t* gen, int32_t* ngen, int gen_cap,
                   const float* temp, const int32_t* topk, const float* topp, const uint64_t* seed, const int32_t* step, int append, int32_t* lens,
-                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st) {
+                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig) {
     hipLaunchKernelGGL(sample_kernel, dim3(rows), dim3(1024), 0, st, logits, ld, vocab, penalty, seqs, gen, ngen, gen_cap, temp, topk, topp, seed,
-                       step, append, lens, len_add, stop, n_seqs, out_ids, out_kept);
+                       step, append, lens, len_add, stop, n_seqs, out_ids, out_kept, orig);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }

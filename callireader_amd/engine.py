@@ -319,7 +319,9 @@ class KVCache:
         assert out.dtype == torch.int32 and not out.is_cuda and out.is_contiguous()
         B.check(B.lib.cr_kv_poll_finished(self._h, C.c_void_p(out.data_ptr()), out.numel(), _stream()), 'cr_kv_poll_finished')
 
-    def generated(self, seq, max_tokens=4096):
+    def generated(self, seq, max_tokens=None):
+        """The ids generated so far (all of them by default: a sequence never holds more ids than the cache holds tokens)."""
+        max_tokens = self.max_tokens if max_tokens is None else max_tokens
         buf = (C.c_int64 * max_tokens)()
         n = B.lib.cr_kv_generated(self._h, seq, buf, max_tokens, _stream())
         if n < 0:
@@ -335,9 +337,10 @@ class KVCache:
         B.check(B.lib.cr_kv_set_logprobs(self._h, seq, top_n, _stream()), 'cr_kv_set_logprobs')
         self._top_n[seq] = top_n
 
-    def logprobs(self, seq, max_tokens=4096):
+    def logprobs(self, seq, max_tokens=None):
         """cr_kv_logprobs: (lp [T] float32, top_ids [T, n] int32, top_lp [T, n] float32) numpy arrays for the T ids generated so far (generated()'s
         count), n the sequence's top_n.  Synchronises the current stream.  CalliReaderError for a sequence whose scores are off."""
+        max_tokens = self.max_tokens if max_tokens is None else max_tokens
         lp = np.empty(max_tokens, dtype=np.float32)
         ti = np.empty((max_tokens, 8), dtype=np.int32)
         tl = np.empty((max_tokens, 8), dtype=np.float32)

@@ -156,7 +156,8 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream);
 int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, void* stream);
 /* The same position of an e4m3 cache (cr_kv_read refuses one): q_out [8 kv heads][128] e4m3 bytes, s_out [8] fp32 scales (both device).  Parity tests. */
 int cr_kv_read_e4m3(cr_kv* kv, int layer, int seq, int pos, int which, uint8_t* q_out, float* s_out, void* stream);
-/* Copy the ids generated so far for `seq` into host memory (at most `max`); returns the count, or < 0.
+/* Copy the ids generated so far for `seq` into host memory (at most `max`); returns the count, or < 0.  A sequence never holds more than
+ * the cache's max_tokens ids (every id costs a cached token; a full cache is cr_llm_decode's CR_ERR_ARG), so max = max_tokens reads them all.
  * Synchronises `stream`. */
 int cr_kv_generated(cr_kv* kv, int seq, int64_t* out_host, int max, void* stream);
 /* Stop criteria of `seq`, checked by the greedy pick of every later prefill / decode of it (and, at this call, against the ids it has
@@ -165,7 +166,8 @@ int cr_kv_generated(cr_kv* kv, int seq, int64_t* out_host, int max, void* stream
  * finished queue.  Nothing else changes: ids, lengths and the host-side counts keep advancing with every step that includes the
  * sequence; ids past the stop are speculative and are the caller's to cut.  Without criteria a step computes exactly what it did
  * before.  cr_kv_reset clears a sequence's criteria and stop; call this once per sequence after it.  CR_ERR_ARG when max_new exceeds
- * the generated-id capacity (4096) or what the cache leaves after the tokens cached so far (max_tokens - cr_kv_length(seq)).
+ * what the cache leaves after the tokens cached so far (max_tokens - cr_kv_length(seq)); there is no other limit: a sequence keeps one
+ * generated id per prefill / decode call, every call caches at least one token, so the id buffer is sized by max_tokens.
  * Enqueued on `stream`. */
 int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream);
 /* Sampling state of `seq` (transformers 4.45.2 _sample with do_sample=True): every later pick of the sequence applies the repetition penalty,
@@ -195,7 +197,7 @@ int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float t
  * |z| <= 32 (double accumulation, one fp32 rounding of the result).  A row holding NaN or +inf gives NaN log-probabilities for that step (ids
  * unspecified).  With scores off for every row of a launch nothing is launched or changed; ids and logits never depend on the setting.  A decode step
  * with a scored row stays out of the CR_DECODE_GRAPH replay, as a sampled one does.  The blocks (cr_kv_logprobs' layout, 68 bytes per generated id,
- * 4096 ids per sequence) are allocated by the first call that switches a sequence of the cache on.  CR_ERR_ARG for top_n outside 0..8 (checked
+ * max_tokens ids per sequence) are allocated by the first call that switches a sequence of the cache on.  CR_ERR_ARG for top_n outside 0..8 (checked
  * before the cache and sequence), CR_ERR_STATE when switching on a sequence that has generated ids already: call after cr_kv_reset and BEFORE the
  * sequence's prefill.  Cache state like the stop criteria and the sampling state: any cache format, any decode option, a cache shared between
  * contexts.  Enqueued on `stream` (the first switching-on call of a cache also synchronises it).  Added within ABI v13. */
