@@ -142,7 +142,6 @@ int cr_create(int device, const cr_model_desc* desc, cr_ctx** out) {
     c->device = device;
     c->d = *desc;
     { const char* e = getenv("CR_NO_SLICED_DECODE"); c->no_sliced_decode = e && atoi(e) != 0; }
-    { const char* e = getenv("CR_DECODE_GRAPH"); if (e) c->decode_graph = atoi(e) != 0; }
     { const char* e = getenv("CR_DECODE_FUSED"); if (e) c->fused_decode = atoi(e) != 0; }
     { const char* e = getenv("CR_DECODE_FOLD_ROPE"); if (e) c->fold_rope = atoi(e) != 0; }
     { const char* e = getenv("CR_PERCEIVER_ATTN_V1"); if (e) c->perceiver_v1 = atoi(e) != 0; }
@@ -167,7 +166,6 @@ int cr_destroy(cr_ctx* c) {
         if (h.host) hipHostFree(h.host);
         if (h.copied) hipEventDestroy(h.copied);
     }
-    if (c->side) hipStreamDestroy(c->side);
     for (auto& r : c->prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto e : c->prof_pool) hipEventDestroy(e);
     delete c;

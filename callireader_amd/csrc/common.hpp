@@ -124,6 +124,18 @@ __device__ __forceinline__ void store16_e4m3(unsigned char* dst, const float* y,
     }
     *(u32x4_*)dst = w;
 }
+// The e4m3 row rule (weight copies: quant_fp8_rows_kernel; e4m3 KV cache rows: rope_split_kernel<true>): scale = max|x| / 448, the largest e4m3
+// magnitude; an all-zero row keeps scale 1
+__device__ __forceinline__ float e4m3_row_scale(float mx) { return mx > 0.f ? mx / 448.0f : 1.0f; }
+// 8 bf16 values times `inv` -> 8 e4m3 bytes (same conversion as store16_e4m3)
+__device__ __forceinline__ uint2 pack8_e4m3(const bf16x8& v, float inv) {
+    unsigned lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]) * inv, bf2f(v[1]) * inv, lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]) * inv, bf2f(v[3]) * inv, lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]) * inv, bf2f(v[5]) * inv, hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]) * inv, bf2f(v[7]) * inv, hi, true);
+    return make_uint2(lo, hi);
+}
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
 

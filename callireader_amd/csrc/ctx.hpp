@@ -23,11 +23,8 @@ struct cr_ctx {
     int device = 0;
     cr_model_desc d{};
     bool finalized = false;
-    int prof_mode = 0;                  // cr_profile: 1 = every GEMM launch, 2 = only the tiled class (M >= 1024): leaves decode free to run as a graph
-    int decode_graph = 0;               // CR_DECODE_GRAPH=1 replays the decode step as a captured hipGraph (measured slower here, see llm.hip); reset to 0 after a capture failure
-    hipStream_t side = nullptr;         // blocking stream the decode graph is captured into and replayed on when the caller's stream is the
-                                        // null stream (which cannot be captured); implicitly ordered with it
-    uint64_t weight_gen = 0;            // bumped by cr_load_weight / cr_finalize: captured graphs hold weight pointers
+    int prof_mode = 0;                  // cr_profile: 1 = every GEMM launch, 2 = only the tiled class (M >= 1024): no events around the decode steps' launches
+    uint64_t weight_gen = 0;            // bumped by cr_load_weight / cr_finalize / the fp8 switches: contexts that borrow these weights watch it (ctx_share_ok)
     bool fp8_decode = false;            // cr_enable_fp8_decode: batched decode streams e4m3 copies of the LLM's linear weights (half the bytes)
     int fp8_mfma = 0;                   // cr_enable_fp8_mfma level: 1 = the norm-fed linears of the ViT, the projector and the LLM prefill run e4m3 x e4m3 on the
                                         // matrix cores; 2 = also the linears whose input no norm produces (ViT fc2 via fc1's e4m3 epilogue, LLM wo / w2 via a quantiser pass)
@@ -101,14 +98,18 @@ const bf16* W(cr_ctx* c, const std::string& name);
 const DevTensor* WT(cr_ctx* c, const std::string& name);
 int ws_ensure(cr_ctx* c, size_t bytes);
 
-// simple bump allocator over the workspace
+// simple bump allocator over the workspace.  Without a base it only measures: the takes return null and bytes() is what they need.  With a capacity,
+// a take that would pass it returns null and clears ok(); the caller checks ok() before it launches anything (llm.hip's ws_carve).  A caller that
+// passes no capacity (the other stages, which size the workspace by their own formulas) gets no check.
 struct Arena {
-    char* base; size_t off = 0;
-    explicit Arena(char* b) : base(b) {}
+    char* base; size_t cap; size_t off = 0; bool fits = true;
+    explicit Arena(char* b = nullptr, size_t capacity = ~(size_t)0) : base(b), cap(capacity) {}
     template <typename T> T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = (T*)(base + off);
-        off += n * sizeof(T);
-        return p;
+        const size_t at = (off + 255) & ~(size_t)255;
+        off = at + n * sizeof(T);
+        if (off > cap) fits = false;
+        return base && fits ? (T*)(base + at) : nullptr;
     }
+    size_t bytes() const { return off; }
+    bool ok() const { return fits; }
 };

@@ -41,25 +41,17 @@ struct cr_kv {
     //   [1 + n, 1 + 2n) stop count per sequence (0 = not stopped), [1 + 2n, 1 + 3n) EOS id (< 0: none), [1 + 3n, 1 + 4n) budget (<= 0: none)
     int32_t* d_stop;
     // sampling state (cr_kv_set_sampling), one block: temperature float[n] (<= 0: greedy), top_k int32[n], top_p float[n], seed uint64[n];
-    // `sampled` mirrors "temperature > 0" on the host: a launch whose rows are all greedy keeps pick_kernel (and the graph path)
+    // `sampled` mirrors "temperature > 0" on the host: a launch whose rows are all greedy keeps pick_kernel
     char* d_samp;
     float* d_temp; int32_t* d_topk; float* d_topp; uint64_t* d_seed;
     std::vector<char> sampled;
     // token scores (cr_kv_set_logprobs; logprobs.hip), allocated by the first call that switches a sequence on: d_lpn int32[n] = alternatives per sequence
     // (0: off), d_lpdone int32[n] = slots written, d_lp [n][gen_cap] fp32, d_top_id [n][gen_cap][8] int32, d_top_lp [n][gen_cap][8] fp32, indexed like
-    // d_gen.  `scored` mirrors d_lpn on the host: a launch whose rows are all off launches nothing new (and keeps the graph path)
+    // d_gen.  `scored` mirrors d_lpn on the host: a launch whose rows are all off launches nothing new
     int32_t *d_lpn = nullptr, *d_lpdone = nullptr, *d_top_id = nullptr;
     float *d_lp = nullptr, *d_top_lp = nullptr;
     std::vector<char> scored;
     std::vector<int> len, ngen;
-    // batched decode as a hipGraph (CR_DECODE_GRAPH=1): a step is ~290 short launches whose parameters only change with
-    // the row count and the number of attention splits (positions, ids and cache lengths live in device memory), so the
-    // launch sequence is captured once per (rows, splits, penalty) and replayed.  The captures live in the cache object, whose format never
-    // changes: a bf16 capture can never be replayed on an e4m3 cache.  OFF by default: on ROCm 7.2 / MI355X the
-    // replay measured 0.3 % slower than plain launches at 64 pages per step (6.86 vs 6.88 pages/s) and 5 % slower for a
-    // single page (0.711 vs 0.678 s) -- the ~3 us gaps between dependent kernels are not launch overhead the graph removes
-    struct DecodeGraph { int n, nsplit; float penalty; char* ws; const int32_t* seqs; uint64_t weight_gen; hipGraphExec_t exec; int warm; };
-    std::vector<DecodeGraph> graphs;
 };
 
 namespace {
@@ -154,7 +146,7 @@ __device__ __forceinline__ float row_max16(float v) {
 // RoPE + split of the fused wqkv output (modeling_internlm2.py:359-388, 233-247).
 // qkv row = [8 groups][4 q | k | v][128].  q_embed = bf16(bf16(q*cos) + bf16(rotate_half(q)*sin)), same for k.
 // grid (rows, 8 groups), 128 threads: thread = (slot 0..7 [6 used], 16-B chunk 0..15).
-// Q8 (e4m3 cache): the K / V rows go to the cache as e4m3 bytes + one fp32 scale each (the rule of quant_fp8_rows_kernel below; a slot's 16 chunks
+// Q8 (e4m3 cache): the K / V rows go to the cache as e4m3 bytes + one fp32 scale each (common.hpp's e4m3 row rule, as quant_fp8_rows_kernel; a slot's 16 chunks
 // are one DPP row, so the row maximum is four rotate-max steps), and -- when kc / vc are given (prefill) -- as bf16 into the prefill's staging
 // [pages][8][stage_T][128] at (row_page[row], pos), which the prefill attention reads instead of the cache.
 template <bool Q8 = false>
@@ -207,15 +199,10 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
 #pragma unroll
         for (int e = 0; e < 8; e++) mx = fmaxf(mx, fabsf(bf2f(y[e])));
         mx = row_max16(mx);
-        const float sc = mx > 0.f ? mx / 448.0f : 1.0f;
-        const float inv = 1.0f / sc;
-        unsigned lo = 0, hi = 0;
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[0]) * inv, bf2f(y[1]) * inv, lo, false);
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[2]) * inv, bf2f(y[3]) * inv, lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[4]) * inv, bf2f(y[5]) * inv, hi, false);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(y[6]) * inv, bf2f(y[7]) * inv, hi, true);
+        const float sc = e4m3_row_scale(mx);
+        const uint2 y8 = pack8_e4m3(y, 1.0f / sc);
         const int64_t r8 = ((int64_t)seq * NKV + grp) * max_tokens + pos;
-        *(uint2*)((slot == 4 ? k8 : v8) + r8 * HD + c * 8) = make_uint2(lo, hi);
+        *(uint2*)((slot == 4 ? k8 : v8) + r8 * HD + c * 8) = y8;
         if (c == 0) (slot == 4 ? ks : vs)[r8] = sc;
         if (kc) {
             bf16* base = slot == 4 ? kc : vc;
@@ -307,8 +294,7 @@ __global__ __launch_bounds__(256) void interleave8_kernel(const bf16* __restrict
     dp[threadIdx.x + 256] = sp[threadIdx.x + 256];
 }
 
-// One weight row -> e4m3 bytes + its scale: scale = max|w| / 448 (the largest e4m3 magnitude), q = round-to-nearest-even
-// (w / scale); an all-zero row keeps scale 1.  One workgroup per row, K % 8 == 0.
+// One weight row -> e4m3 bytes + its scale (common.hpp's e4m3 row rule): q = round-to-nearest-even (w / scale).  One workgroup per row, K % 8 == 0.
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* __restrict__ w, int64_t ldw, int K, unsigned char* __restrict__ q,
                                                               float* __restrict__ scale) {
     __shared__ float red[4];
@@ -325,18 +311,10 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* __restr
     if ((tid & 63) == 0) red[tid >> 6] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float sc = mx > 0.f ? mx / 448.0f : 1.0f;
+    const float sc = e4m3_row_scale(mx);
     const float inv = 1.0f / sc;
     if (tid == 0) scale[r] = sc;
-    for (int k = tid * 8; k < K; k += 256 * 8) {
-        const bf16x8 v = *(const bf16x8*)(wr + k);
-        unsigned lo = 0, hi = 0;
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]) * inv, bf2f(v[1]) * inv, lo, false);
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]) * inv, bf2f(v[3]) * inv, lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]) * inv, bf2f(v[5]) * inv, hi, false);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]) * inv, bf2f(v[7]) * inv, hi, true);
-        *(uint2*)(q + r * (int64_t)K + k) = make_uint2(lo, hi);
-    }
+    for (int k = tid * 8; k < K; k += 256 * 8) *(uint2*)(q + r * (int64_t)K + k) = pack8_e4m3(*(const bf16x8*)(wr + k), inv);
 }
 
 // out[0] = max over rows of ||w_row||_2, out[1] = max |b| (positive floats order like their bit patterns: atomicMax on the bits)
@@ -355,284 +333,370 @@ __global__ __launch_bounds__(256) void row_norm_max_kernel(const bf16* __restric
     }
 }
 
-int gemm(cr_ctx* c, int epi, const bf16* A, int64_t lda, const bf16* Wt, int64_t ldw, void* C, int64_t ldc, const bf16* res, int64_t ldr,
-         int M, int N, int K, hipStream_t st, bool prefill_rows = false, const DevTensor* dl = nullptr, int dl_kind = 1) {
-    GemmParams p{};
-    p.A = A; p.lda = lda; p.W = Wt; p.ldw = ldw; p.C = C; p.ldc = ldc; p.res = res; p.ldr = ldr; p.M = M; p.N = N; p.K = K;
-    // decode (<= 64 rows): the weight-streaming kernels take the decode-layout copy where llm_finalize made one (a contiguous KiB per load instruction)
-    if (dl && !prefill_rows && M <= 64) { p.W = (const bf16*)dl->ptr; p.wsw = dl_kind; }
-    // a prompt row's result must not depend on what it is prefilled with: prompts of <= 64 rows in all stay on the tiled kernel, whose K
-    // order is that of every longer prefill (the weight-streaming kernel the dispatcher would pick splits K over its waves)
-    if (prefill_rows && M <= 64) p.kernel = 128;
-    return ctx_gemm(c, epi, p, st);
-}
-
-int rms(const bf16* in, int64_t ld_in, bf16* out, const bf16* w, int64_t rows, float eps, hipStream_t st, float* row_scale = nullptr) {
+int rms(const bf16* in, bf16* out, const bf16* w, int64_t rows, float eps, hipStream_t st, float* row_scale = nullptr) {
     NormParams np{};
-    np.in = in; np.ld_in = ld_in; np.out = out; np.ld_out = D; np.gamma = w; np.rows = rows; np.eps = eps;
+    np.in = in; np.ld_in = D; np.out = out; np.ld_out = D; np.gamma = w; np.rows = rows; np.eps = eps;
     if (row_scale) { np.out8 = (unsigned char*)out; np.out8_scale = row_scale; }     // e4m3 rows in the first half of `out`
     return launch_rmsnorm(np, D, st);
 }
-
-// the same GEMM on the e4m3 copy of a weight (decode only): C = (A . W8^T) * wscale
-int gemm8(cr_ctx* c, int epi, const bf16* A, int64_t lda, const DevTensor* w8, const DevTensor* ws, void* C, int64_t ldc, const bf16* res,
-          int64_t ldr, int M, int N, int K, hipStream_t st, const DevTensor* dl = nullptr) {
-    GemmParams p{};
-    p.A = A; p.lda = lda; p.W = (const bf16*)w8->ptr; p.ldw = K; p.C = C; p.ldc = ldc; p.res = res; p.ldr = ldr; p.M = M; p.N = N; p.K = K;
-    p.w8 = 1; p.wscale = (const float*)ws->ptr;
-    if (dl && M <= 64) { p.W = (const bf16*)dl->ptr; p.wsw = 1; }       // the e4m3 copy in its decode layout (cr_enable_fp8_decode): a contiguous KiB per load instruction
-    return ctx_gemm(c, epi, p, st);
-}
-
-struct LayerW { const bf16 *an, *fn, *wqkv, *wo, *w13, *w2; const DevTensor *d_qkv, *d_o, *d_13, *d_2;      // d_*: decode-layout copies (llm_finalize), may be null
-                const DevTensor *q_qkv, *s_qkv, *q_o, *s_o, *q_13, *s_13, *q_2, *s_2;
-                const DevTensor *l_qkv, *l_o, *l_13, *l_2; };      // l_*: the e4m3 copies in their decode layout (cr_enable_fp8_decode), may be null
 
 const DevTensor* opt(cr_ctx* c, const std::string& name) {
     auto it = c->w.find(name);
     return it == c->w.end() ? nullptr : &it->second;
 }
 
-int layer_weights(cr_ctx* c, int l, LayerW& w) {
+// One linear layer's weight [N][K] in the forms the GEMM kernels take; all but `w` may be null
+struct LinW {
+    const bf16* w;                // bf16 as loaded (nn.Linear's layout; w1|w3: the interleaved derived tensor)
+    int N, K;
+    const DevTensor* dl;          // its decode-layout copy (llm_finalize)
+    int dl_kind;                  // GemmParams::wsw of that copy: 1 plain tiles, 2 wqkv's RoPE tile order (only the K-sliced kernel reads it)
+    const DevTensor *q8, *s8;     // e4m3 copy + one fp32 scale per row (cr_enable_fp8_mfma / cr_enable_fp8_decode)
+    const DevTensor* dl8;         // the e4m3 copy in its decode layout (cr_enable_fp8_decode)
+    bool e4m3() const { return q8 && s8; }
+};
+struct LayerW { const bf16 *an, *fn; LinW qkv, o, w13, w2; };
+
+LinW lin_weight(cr_ctx* c, const std::string& nm, int N, int K, int dl_kind = 1) {
+    return {W(c, nm), N, K, opt(c, "declayout." + nm), dl_kind, opt(c, "fp8." + nm), opt(c, "fp8s." + nm), opt(c, "fp8dl." + nm)};
+}
+
+int layer_weights(cr_ctx* c, int l, int ff, LayerW& w) {
     const std::string p = "language_model.model.layers." + std::to_string(l) + ".";
     w.an = W(c, p + "attention_norm.weight"); w.fn = W(c, p + "ffn_norm.weight");
-    w.wqkv = W(c, p + "attention.wqkv.weight"); w.wo = W(c, p + "attention.wo.weight");
-    w.w13 = W(c, "derived.w13." + std::to_string(l)); w.w2 = W(c, p + "feed_forward.w2.weight");
-    w.d_qkv = opt(c, "declayout." + p + "attention.wqkv.weight"); w.d_o = opt(c, "declayout." + p + "attention.wo.weight");
-    w.d_13 = opt(c, "declayout.derived.w13." + std::to_string(l)); w.d_2 = opt(c, "declayout." + p + "feed_forward.w2.weight");
-    w.q_qkv = opt(c, "fp8." + p + "attention.wqkv.weight"); w.s_qkv = opt(c, "fp8s." + p + "attention.wqkv.weight");
-    w.q_o = opt(c, "fp8." + p + "attention.wo.weight"); w.s_o = opt(c, "fp8s." + p + "attention.wo.weight");
-    w.q_13 = opt(c, "fp8.derived.w13." + std::to_string(l)); w.s_13 = opt(c, "fp8s.derived.w13." + std::to_string(l));
-    w.q_2 = opt(c, "fp8." + p + "feed_forward.w2.weight"); w.s_2 = opt(c, "fp8s." + p + "feed_forward.w2.weight");
-    w.l_qkv = opt(c, "fp8dl." + p + "attention.wqkv.weight"); w.l_o = opt(c, "fp8dl." + p + "attention.wo.weight");
-    w.l_13 = opt(c, "fp8dl.derived.w13." + std::to_string(l)); w.l_2 = opt(c, "fp8dl." + p + "feed_forward.w2.weight");
-    return (w.an && w.fn && w.wqkv && w.wo && w.w13 && w.w2) ? CR_OK : CR_ERR_STATE;
+    w.qkv = lin_weight(c, p + "attention.wqkv.weight", QKV, D, 2); w.o = lin_weight(c, p + "attention.wo.weight", D, D);
+    w.w13 = lin_weight(c, "derived.w13." + std::to_string(l), 2 * ff, D); w.w2 = lin_weight(c, p + "feed_forward.w2.weight", D, ff);
+    return (w.an && w.fn && w.qkv.w && w.o.w && w.w13.w && w.w2.w) ? CR_OK : CR_ERR_STATE;
 }
+
+enum LinForm {
+    LIN_PREFILL,    // bf16 as loaded; a prompt row's result must not depend on what it is prefilled with: prompts of <= 64 rows in all stay on the tiled kernel,
+                    // whose K order is that of every longer prefill (the weight-streaming kernel the dispatcher would pick splits K over its waves)
+    LIN_LOADED,     // bf16 as loaded, the dispatcher's choice of kernel
+    LIN_DECODE,     // <= 64 rows: the weight-streaming kernels take the decode-layout copy where llm_finalize made one (a contiguous KiB per load instruction)
+    LIN_E4M3        // the e4m3 copy (decode only: C = (A . W8^T) * wscale), <= 64 rows in its decode layout where cr_enable_fp8_decode made one
+};
+
+// C = epi(A . W^T) on dense rows: lda = ldw = K, ldc = the width the epilogue writes; EPI_RES adds into C in place
+int linear(cr_ctx* c, int epi, const bf16* A, const LinW& w, LinForm form, void* C, int M, hipStream_t st) {
+    GemmParams p{};
+    p.A = A; p.lda = w.K; p.W = w.w; p.ldw = w.K; p.C = C; p.ldc = epi == EPI_SWIGLU ? w.N / 2 : w.N; p.M = M; p.N = w.N; p.K = w.K;
+    if (epi == EPI_RES) { p.res = (const bf16*)C; p.ldr = p.ldc; }
+    if (form == LIN_E4M3) {
+        if (!w.e4m3()) return cr_fail(CR_ERR_STATE, "linear: no e4m3 copy of this weight (cr_enable_fp8_decode)");
+        p.W = (const bf16*)w.q8->ptr; p.w8 = 1; p.wscale = (const float*)w.s8->ptr;
+        if (w.dl8 && M <= 64) { p.W = (const bf16*)w.dl8->ptr; p.wsw = 1; }
+    } else if (form == LIN_DECODE && w.dl && M <= 64) { p.W = (const bf16*)w.dl->ptr; p.wsw = w.dl_kind; }
+    else if (form == LIN_PREFILL && M <= 64) p.kernel = 128;
+    return ctx_gemm(c, epi, p, st);
+}
+
+// the same on the fp8 matrix cores (prefill): A as e4m3 rows with one scale each, the weight's e4m3 copy
+int linear_f8(cr_ctx* c, int epi, const void* a8, const float* ascale, const LinW& w, void* C, int M, hipStream_t st) {
+    const bool res = epi == EPI_RES;
+    return ctx_gemm_f8(c, epi, a8, ascale, w.q8, w.s8, C, epi == EPI_SWIGLU ? w.N / 2 : w.N, nullptr, M, w.N, w.K, st, res ? (const bf16*)C : nullptr, res ? w.N : 0);
+}
+
+// One layer of the cache: bf16 rows [n_seqs][8][max_tokens][128], or e4m3 rows of that shape + one scale per row (the other pointers null)
+struct LayerKV { bf16 *k, *v; unsigned char *k8, *v8; float *ks, *vs; };
+LayerKV layer_kv(const cr_kv* kv, int l) {
+    const int64_t per_layer = (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD;
+    if (kv->fmt == CR_KV_E4M3) return {nullptr, nullptr, kv->k8 + l * per_layer, kv->v8 + l * per_layer, kv->ks + l * (per_layer / HD), kv->vs + l * (per_layer / HD)};
+    return {kv->k + l * per_layer, kv->v + l * per_layer, nullptr, nullptr, nullptr, nullptr};
+}
+
+// what every attention launch of the stage shares: K / V rows [slot][8][T][128], bf16-rounded scores divided by sqrt(128)
+AttnParams attn_params(const LayerKV& lk, int T, bf16* q, bf16* ao) {
+    AttnParams ap{};
+    ap.K = lk.k; ap.V = lk.v; ap.Q = q; ap.O = ao;
+    ap.k_bs = ap.v_bs = (int64_t)NKV * T * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)T * HD;
+    ap.q_prescale = 1.0f; ap.s_div = 11.313708498984761f;      // math.sqrt(128)
+    return ap;
+}
+
+// Causal prefill attention, the pages' query blocks as ONE launch of `n_segs` segments {first row, rows, first position, slot} whose longest has Sq rows:
+// causal attention is per page, the linear layers see all pages at once (a launch per page left its 800 workgroups of 2..50 key tiles each a ragged
+// tail on 512 slots).  q / ao rows are [row][32 heads][128].
+AttnParams prefill_attn_params(const LayerKV& lk, int T, bf16* q, bf16* ao, int n_segs, const int32_t* seg, int Sq) {
+    AttnParams ap = attn_params(lk, T, q, ao);
+    ap.q_bs = 0; ap.q_rs = D; ap.q_hs = HD; ap.o_bs = 0; ap.o_rs = D; ap.o_hs = HD;
+    ap.H = NH; ap.kv_group = NH / NKV; ap.B = n_segs; ap.seg = seg; ap.Sq = Sq;
+    return ap;
+}
+
+// Runs the call's carve twice: on an Arena without a base to measure what the call needs, then -- the workspace grown to that -- on the workspace itself.
+// The bytes reserved and the pointers handed out come from the same takes.
+template <class Bufs> int ws_carve(cr_ctx* c, const char* who, Bufs& b) {
+    Arena measure;
+    b.carve(measure);
+    CR_TRY(ws_ensure(c, measure.bytes()));
+    Arena ar(c->ws, c->ws_bytes);
+    b.carve(ar);
+    return ar.ok() ? CR_OK : cr_fail(CR_ERR_STATE, "%s: the carve passed the %zu bytes of workspace (%zu measured)", who, c->ws_bytes, measure.bytes());
+}
+
+// The LM head's n rows of a prefill / decode call, carved after the layer buffers
+struct HeadBufs {
+    int n, V;
+    bool scored, deep;      // a row of the launch has token scores on / a history of more than 4096 ids under a penalty
+    bf16* hl;               // the normalised rows
+    float* lg;              // their logits [n][V]
+    void* score;            // scored: logprobs.hip's scratch
+    float* lg0;             // deep: the rows before the penalty, for the pick
+    void carve(Arena& ar) {
+        hl = ar.take<bf16>((size_t)n * D);
+        lg = ar.take<float>((size_t)n * V);
+        score = scored ? ar.take<char>(logprobs_scratch_bytes(n, V)) : nullptr;
+        lg0 = deep ? ar.take<float>((size_t)n * V) : nullptr;
+    }
+};
 
 struct Segment { int seq, row0, S, pos0; };     // a page's rows inside a batched prefill
 
-// Prefill into an e4m3 cache: the prompts' bf16 K / V of the current layer go to a staging buffer [pages][8][T][128] (T = the longest prompt) that the
-// prefill attention reads; the cache gets the e4m3 rows.  row_page: page index of every prompt row; seg / seg_last: d_seg / d_seg_last with the page
-// index in place of the cache slot.
-struct PrefillStage { int T; const int32_t* row_page; const int32_t* seg; const int32_t* seg_last; };
-size_t prefill_stage_bytes(int n_pages, int T) { return (size_t)2 * n_pages * NKV * T * HD * 2; }
+// The index arrays of a batched prefill (M rows, n pages): one block of ints, laid out the same on the host and on the device
+struct PrefillRows {
+    int32_t *row_seq, *row_pos;      // per row: cache slot, position
+    int32_t* seg;                    // per page, 4 ints: first row, rows, first position, cache slot (the attention launch's segments)
+    int32_t* seg_last;               // per page, 4 ints: the final layer's segment, the rows that share a 32-row wave with the page's last row
+    int32_t* last;                   // per page: that last row
+    int32_t *seg8, *seg_last8;       // e4m3 cache only: seg and seg_last with the page index as the slot (they address the staging)
+    int32_t* row_page;               // e4m3 cache only: page index of every row
+};
+size_t prefill_rows_ints(int M, int n, bool kv8) { return 2 * (size_t)M + 9 * (size_t)n + (kv8 ? 8 * (size_t)n + (size_t)M : 0); }
+PrefillRows prefill_rows(int32_t* p, int M, int n) {
+    int32_t* g = p + 2 * (size_t)M;
+    return {p, p + M, g, g + 4 * n, g + 8 * n, g + 9 * n, g + 13 * n, g + 17 * n};
+}
 
-// The decoder stack over M rows (prefill: M = all prompt rows of the pages in `segs`; decode: M = n sequences, one row each).
-// d_last / d_seg_last (prefill): the pages' last rows and, as attention segments, the rows that share a wave with them -- see the final layer below.
-int run_layers(cr_ctx* c, cr_kv* kv, bf16* x, int M, bool decode, const std::vector<Segment>& segs, const int32_t* d_row_seq,
-               const int32_t* d_row_pos, const int32_t* d_seqs, int nsplit, hipStream_t st, const int32_t* d_seg = nullptr,
-               const int32_t* d_last = nullptr, const int32_t* d_seg_last = nullptr, const PrefillStage* stg = nullptr) {
-    const int ff = (int)WT(c, "derived.w13.0")->shape[0] / 2;
-    const bool kv8 = kv->fmt == CR_KV_E4M3;
-    if (kv8 && !decode && !stg) return cr_fail(CR_ERR_STATE, "e4m3 cache: prefill without its bf16 staging");
-    Arena ar(c->ws);
-    bf16* stage = kv8 && !decode ? ar.take<bf16>(prefill_stage_bytes((int)segs.size(), stg->T) / 2) : nullptr;
-    const int64_t stage_half = kv8 && !decode ? (int64_t)segs.size() * NKV * stg->T * HD : 0;
-    float* part = decode ? ar.take<float>(attn_split_ws_floats(M, NKV, NH / NKV, nsplit, HD)) : nullptr;
-    bf16* h = ar.take<bf16>((size_t)M * D);
-    bf16* qkv = ar.take<bf16>((size_t)M * QKV);
-    bf16* q = ar.take<bf16>((size_t)M * D);
-    bf16* ao = ar.take<bf16>((size_t)M * D);
-    bf16* act = ar.take<bf16>((size_t)M * ff);
-    float* hs = ar.take<float>((size_t)M);          // fp8 matrix-core path: one scale per normalised row
-    const bool any8 = !decode && c->fp8_mfma && M >= 256;
-    unsigned char* a8 = any8 ? ar.take<unsigned char>((size_t)M * ff) : nullptr;     // e4m3 rows of the attention output / the SwiGLU output
-    // Prefill, FINAL layer: only each page's last row is ever read again (the LM head, :1081-1082 + _sample; the reference computes every row).  K / V of
-    // every row still go to the cache, so the norm, wqkv and RoPE + split run on all rows; attention, wo, the second norm, w1|w3 and w2 run on the n last rows
-    // only -- 88 % of that layer's linear work.  Bit-exact: the tiled kernels give a row the same sum whatever it is batched with (pinned, as for short
-    // prompts), and the attention launch keeps a last row in the company of the rows that share its WAVE in the full launch (the kernel's deferred-rescale vote
-    // is wave-wide): segment = {first row of that 32-row group, rows up to the last, their first position}.  CR_PREFILL_LAST_ROWS=0: every row (A/B aid).
-    const int n_pages = (int)segs.size();
-    const bool last_rows_only = !decode && c->prefill_last_rows && d_last && d_seg_last && !any8 && !c->probe_dst && n_pages > 0;
-    bf16 *xl = nullptr, *aol = nullptr, *hl2 = nullptr, *actl = nullptr;
-    if (last_rows_only) {
-        xl = ar.take<bf16>((size_t)n_pages * D); aol = ar.take<bf16>((size_t)n_pages * D); hl2 = ar.take<bf16>((size_t)n_pages * D);
-        actl = ar.take<bf16>((size_t)n_pages * ff);
+// What a batched prefill (M prompt rows of n_pages pages, the longest max_S rows) takes from the workspace
+struct PrefillBufs {
+    int M, n_pages, max_S, ff;
+    bool kv8;           // prefill into an e4m3 cache: the prompts' bf16 K / V of the current layer go to a staging [pages][8][max_S][128] that the prefill attention
+                        // reads; the cache gets the e4m3 rows
+    bool any8;          // fp8 matrix-core path (cr_enable_fp8_mfma): both norms emit e4m3 rows + scales, wqkv and w1|w3 take them (gemm256 F8)
+    bool last_rows;     // the final layer on the pages' last rows only, see prefill_layers
+    bf16 *x, *stage_k, *stage_v, *h, *qkv, *q, *ao, *act, *xl, *aol, *hl2, *actl;
+    float* hs;          // any8: one scale per normalised row
+    unsigned char* a8;  // any8: e4m3 rows of the attention output / the SwiGLU output
+    PrefillRows rows;
+    HeadBufs head;
+
+    PrefillBufs(cr_ctx* c, const cr_kv* kv, int M, int n_pages, int max_S, bool scored, bool deep)
+        : M(M), n_pages(n_pages), max_S(max_S), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), any8(c->fp8_mfma && M >= 256),
+          last_rows(c->prefill_last_rows && !any8 && !c->probe_dst), head{n_pages, c->d.vocab, scored, deep} {}
+
+    void carve(Arena& ar) {
+        x = ar.take<bf16>((size_t)M * D);
+        stage_k = kv8 ? ar.take<bf16>((size_t)n_pages * NKV * max_S * HD) : nullptr;
+        stage_v = kv8 ? ar.take<bf16>((size_t)n_pages * NKV * max_S * HD) : nullptr;
+        h = ar.take<bf16>((size_t)M * D); qkv = ar.take<bf16>((size_t)M * QKV); q = ar.take<bf16>((size_t)M * D); ao = ar.take<bf16>((size_t)M * D);
+        act = ar.take<bf16>((size_t)M * ff);
+        hs = any8 ? ar.take<float>((size_t)M) : nullptr;
+        a8 = any8 ? ar.take<unsigned char>((size_t)M * ff) : nullptr;
+        xl = aol = hl2 = actl = nullptr;
+        if (last_rows) {
+            xl = ar.take<bf16>((size_t)n_pages * D); aol = ar.take<bf16>((size_t)n_pages * D); hl2 = ar.take<bf16>((size_t)n_pages * D);
+            actl = ar.take<bf16>((size_t)n_pages * ff);
+        }
+        rows = prefill_rows(ar.take<int32_t>(prefill_rows_ints(M, n_pages, kv8)), M, n_pages);
+        head.carve(ar);
     }
-    const bf16 *cosT = W(c, "rope.cos"), *sinT = W(c, "rope.sin");
+};
+
+// The decoder stack over the prompt rows b.x of a batched prefill.
+int prefill_layers(cr_ctx* c, cr_kv* kv, const PrefillBufs& b, hipStream_t st) {
+    const PrefillRows& r = b.rows;
+    const int M = b.M, ff = b.ff, n_pages = b.n_pages, layers = c->d.llm_layers;
+    const float eps = c->d.rms_eps;
+    const bf16 *cosT = W(c, "rope.cos"), *sinT = W(c, "rope.sin");      // [max_pos][128] each
     if (!cosT || !sinT) return CR_ERR_STATE;
-    const int64_t per_layer = (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD;
-    // decode (M <= 64): wqkv, wo and w2 run as K-sliced partial-sum GEMMs (gemm_skinny.hip: tall workgroups re-read X
-    // once per 64 weight rows); the slices are summed by the kernel that consumes the result anyway -- RoPE/split for
-    // wqkv, the residual add fused with the NEXT RMSNorm for wo and w2 -- in slice order, so a row's result is the same
-    // whatever it is batched with.
-    const int s_qkv = decode ? gemm_partial_splits(QKV, D) : 0, s_o = decode ? gemm_partial_splits(D, D) : 0,
-              s_2 = decode ? gemm_partial_splits(D, ff) : 0;
-    const bool sliced = decode && M <= 64 && s_qkv > 0 && s_o > 0 && s_2 > 0 && !c->no_sliced_decode;
-    float* pbuf = sliced ? ar.take<float>((size_t)std::max(s_qkv * QKV, std::max(s_o, s_2) * D) * M) : nullptr;
-    // small batches (<= DECODE_FUSED_MAX_ROWS = 8 rows): gemm_decode.hip folds the norms, RoPE + split and the residual adds into the five GEMMs -- six launches
-    // per layer instead of nine, every sum in the order of the kernels below (a row's bits do not depend on its batch): its virtual slices are
-    // compiled in, so the path is only taken while the K-sliced kernels' geometry (cost model or CR_PARTIAL_GEOM) is the one they reproduce
-    // (an e4m3 cache takes the separate kernels: the fused wqkv epilogue writes bf16 cache rows)
-    const bool fused = sliced && c->fused_decode && !c->fp8_decode && !kv8 && decode_fused_supported(M, ff) &&
-                       s_qkv == DEC_SLICES_WQKV && s_o == DEC_SLICES_WO && s_2 == DEC_SLICES_W2;
     // cr_llm_hidden_probe (parity tooling): rows [row0, row0 + rows) of the residual stream before layer 0 and after every layer
     auto probe = [&](int slot) -> int {
-        if (!c->probe_dst || decode || c->probe_row0 + c->probe_rows > M) return CR_OK;
-        CR_HIP(hipMemcpyAsync(c->probe_dst + (size_t)slot * c->probe_rows * D, x + (size_t)c->probe_row0 * D, (size_t)c->probe_rows * D * 2,
+        if (!c->probe_dst || c->probe_row0 + c->probe_rows > M) return CR_OK;
+        CR_HIP(hipMemcpyAsync(c->probe_dst + (size_t)slot * c->probe_rows * D, b.x + (size_t)c->probe_row0 * D, (size_t)c->probe_rows * D * 2,
                               hipMemcpyDeviceToDevice, st));
         return CR_OK;
     };
     CR_TRY(probe(0));
-    for (int l = 0; l < c->d.llm_layers; l++) {
+    for (int l = 0; l < layers; l++) {
         LayerW w;
-        CR_TRY(layer_weights(c, l, w));
-        bf16* kc = kv8 ? stage : kv->k + l * per_layer;                 // e4m3 cache: the prefill's bf16 staging (nullptr in decode)
-        bf16* vc = kv8 ? (stage ? stage + stage_half : nullptr) : kv->v + l * per_layer;
-        unsigned char* k8 = kv8 ? kv->k8 + l * per_layer : nullptr;
-        unsigned char* v8 = kv8 ? kv->v8 + l * per_layer : nullptr;
-        float* ks8 = kv8 ? kv->ks + l * (per_layer / HD) : nullptr;
-        float* vs8 = kv8 ? kv->vs + l * (per_layer / HD) : nullptr;
-        // prefill on the fp8 matrix-core path: both norms emit e4m3 rows + scales, wqkv and w1|w3 take them (gemm256 F8)
-        if (fused) {
-            DecodeGemmParams dp{};
-            dp.M = M; dp.eps = c->d.rms_eps;
-            dp.W = w.wqkv; dp.ldw = D; dp.N = QKV; dp.K = D; dp.xres = x; dp.gamma = w.an;
-            if (w.d_qkv) { dp.W = (const bf16*)w.d_qkv->ptr; dp.swizzled = 1; }
-            dp.cosT = cosT; dp.sinT = sinT; dp.q_out = q; dp.kc = kc; dp.vc = vc; dp.seqs = d_seqs; dp.lens = kv->d_len; dp.max_tokens = kv->max_tokens;
-            CR_TRY(launch_decode_gemm(DEC_WQKV, dp, st));
-            AttnParams ap{};
-            ap.K = kc; ap.V = vc; ap.Q = q; ap.O = ao;
-            ap.k_bs = ap.v_bs = (int64_t)NKV * kv->max_tokens * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)kv->max_tokens * HD;
-            ap.q_prescale = 1.0f; ap.s_div = 11.313708498984761f;
-            ap.q_bs = D; ap.q_rs = HD; ap.q_hs = 4 * HD; ap.o_bs = D; ap.o_rs = HD; ap.o_hs = 4 * HD;
-            ap.B = M; ap.H = NKV; ap.Sq = NH / NKV; ap.Sk = 0; ap.kv_group = 1; ap.q_pos0 = 0;
-            ap.seq_map = d_seqs; ap.sk_arr = kv->d_len; ap.sk_add = 1;
-            ap.nsplit = nsplit; ap.part_ml = part; ap.part_o = part + (size_t)M * NKV * nsplit * (NH / NKV) * 2;
-            if (launch_flash_attn_split(ap, HD, st) != CR_OK) return cr_fail(CR_ERR_HIP, "decode attention launch failed");
-            DecodeGemmParams dq{};
-            dq.M = M; dq.eps = c->d.rms_eps;
-            dq.W = w.wo; dq.ldw = D; dq.N = D; dq.K = D; dq.X = ao; dq.ldx = D; dq.xio = x;
-            if (w.d_o) { dq.W = (const bf16*)w.d_o->ptr; dq.swizzled = 1; }
-            CR_TRY(launch_decode_gemm(DEC_WO, dq, st));
-            dq = DecodeGemmParams{};
-            dq.M = M; dq.eps = c->d.rms_eps;
-            dq.W = w.w13; dq.ldw = D; dq.N = 2 * ff; dq.K = D; dq.xres = x; dq.gamma = w.fn; dq.C = act; dq.ldc = ff;
-            if (w.d_13) { dq.W = (const bf16*)w.d_13->ptr; dq.swizzled = 1; }
-            CR_TRY(launch_decode_gemm(DEC_W13, dq, st));
-            dq = DecodeGemmParams{};
-            dq.M = M; dq.eps = c->d.rms_eps;
-            dq.W = w.w2; dq.ldw = ff; dq.N = D; dq.K = ff; dq.X = act; dq.ldx = ff; dq.xio = x;
-            if (w.d_2) { dq.W = (const bf16*)w.d_2->ptr; dq.swizzled = 1; }
-            CR_TRY(launch_decode_gemm(DEC_W2, dq, st));
+        CR_TRY(layer_weights(c, l, ff, w));
+        LayerKV lk = layer_kv(kv, l);
+        if (b.kv8) { lk.k = b.stage_k; lk.v = b.stage_v; }
+        const int T = b.kv8 ? b.max_S : kv->max_tokens;      // rows per (slot, head) of what the attention reads
+        const bool m8 = b.any8 && w.qkv.e4m3() && w.w13.e4m3();
+        const bool m8all = m8 && c->fp8_mfma >= 2 && w.o.e4m3() && w.w2.e4m3();      // level 2: wo and w2 as well (their inputs take a quantiser pass)
+        // x += in . W^T for wo and w2.  Level 2: their inputs are activations no norm produced, so one quantiser pass each (row maximum, then the e4m3 row)
+        auto add_linear = [&](const bf16* in, const LinW& lw) -> int {
+            if (!m8all) return linear(c, EPI_RES, in, lw, LIN_PREFILL, b.x, M, st);
+            hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, in, (int64_t)lw.K, lw.K, b.a8, b.hs);
+            return linear_f8(c, EPI_RES, b.a8, b.hs, lw, b.x, M, st);
+        };
+        CR_TRY(rms(b.x, b.h, w.an, M, eps, st, m8 ? b.hs : nullptr));
+        CR_TRY(m8 ? linear_f8(c, EPI_STORE, b.h, b.hs, w.qkv, b.qkv, M, st) : linear(c, EPI_STORE, b.h, w.qkv, LIN_PREFILL, b.qkv, M, st));
+        // (bf16 cache: lk's e4m3 pointers are null, and the kernel takes no staging)
+        hipLaunchKernelGGL(b.kv8 ? rope_split_kernel<true> : rope_split_kernel<false>, dim3(M, NKV), dim3(128), 0, st, b.qkv, cosT, sinT, b.q, lk.k, lk.v, 0, 0,
+                           r.row_seq, nullptr, r.row_pos, kv->max_tokens, nullptr, 0, lk.k8, lk.v8, lk.ks, lk.vs, b.kv8 ? r.row_page : nullptr, b.kv8 ? b.max_S : 0);
+        // FINAL layer: only each page's last row is ever read again (the LM head, :1081-1082 + _sample; the reference computes every row).  K / V of
+        // every row still go to the cache, so the norm, wqkv and RoPE + split run on all rows; attention, wo, the second norm, w1|w3 and w2 run on the n last rows
+        // only -- 88 % of that layer's linear work.  Bit-exact: the tiled kernels give a row the same sum whatever it is batched with (LIN_PREFILL pins rows <= 64;
+        // more pages than that take the tiled kernel by the dispatcher's own rule), and the attention launch keeps a last row in the company of the rows that share
+        // its WAVE in the full launch (the kernel's deferred-rescale vote is wave-wide): segment = {first row of that 32-row group, rows up to the last, their first
+        // position}.  CR_PREFILL_LAST_ROWS=0: every row (A/B aid).
+        if (b.last_rows && l + 1 == layers) {
+            if (launch_flash_attn(prefill_attn_params(lk, T, b.q, b.ao, n_pages, b.kv8 ? r.seg_last8 : r.seg_last, 32), HD, true, st) != CR_OK)
+                return cr_fail(CR_ERR_HIP, "prefill attention launch failed");
+            hipLaunchKernelGGL(move_rows_kernel<true>, dim3(n_pages), dim3(256), 0, st, b.ao, r.last, b.aol);
+            hipLaunchKernelGGL(move_rows_kernel<true>, dim3(n_pages), dim3(256), 0, st, b.x, r.last, b.xl);
+            CR_TRY(linear(c, EPI_RES, b.aol, w.o, LIN_PREFILL, b.xl, n_pages, st));
+            CR_TRY(rms(b.xl, b.hl2, w.fn, n_pages, eps, st));
+            CR_TRY(linear(c, EPI_SWIGLU, b.hl2, w.w13, LIN_PREFILL, b.actl, n_pages, st));
+            CR_TRY(linear(c, EPI_RES, b.actl, w.w2, LIN_PREFILL, b.xl, n_pages, st));
+            hipLaunchKernelGGL(move_rows_kernel<false>, dim3(n_pages), dim3(256), 0, st, b.xl, r.last, b.x);
             continue;
         }
-        const bool m8 = any8 && w.q_qkv && w.s_qkv && w.q_13 && w.s_13;
-        const bool m8all = m8 && c->fp8_mfma >= 2 && w.q_o && w.s_o && w.q_2 && w.s_2;      // level 2: wo and w2 as well (their inputs take a quantiser pass)
-        if (!sliced || l == 0) CR_TRY(rms(x, D, h, w.an, M, c->d.rms_eps, st, m8 ? hs : nullptr));
-        const bool f8 = decode && M <= 64 && c->fp8_decode && w.q_qkv && w.s_qkv && w.q_o && w.s_o && w.q_13 && w.s_13 && w.q_2 && w.s_2;
-        if (m8) CR_TRY(ctx_gemm_f8(c, EPI_STORE, h, hs, w.q_qkv, w.s_qkv, qkv, QKV, nullptr, M, QKV, D, st));
-        else if (sliced) CR_TRY(f8 ? gemm8(c, EPI_PARTIAL, h, D, w.q_qkv, w.s_qkv, pbuf, QKV, nullptr, 0, M, QKV, D, st, w.l_qkv)
-                               : gemm(c, EPI_PARTIAL, h, D, w.wqkv, D, pbuf, QKV, nullptr, 0, M, QKV, D, st, false, w.d_qkv, 2));
-        else CR_TRY(f8 ? gemm8(c, EPI_STORE, h, D, w.q_qkv, w.s_qkv, qkv, QKV, nullptr, 0, M, QKV, D, st, w.l_qkv)
-                        : gemm(c, EPI_STORE, h, D, w.wqkv, D, qkv, QKV, nullptr, 0, M, QKV, D, st, !decode));
-        AttnParams ap{};
-        ap.K = kc; ap.V = vc; ap.Q = q; ap.O = ao;
-        ap.k_bs = ap.v_bs = (int64_t)NKV * kv->max_tokens * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)kv->max_tokens * HD;
-        ap.q_prescale = 1.0f; ap.s_div = 11.313708498984761f;      // math.sqrt(128)
-        if (kv8 && !decode) {                                      // the prefill attends over its staging
-            ap.k_bs = ap.v_bs = (int64_t)NKV * stg->T * HD; ap.k_hs = ap.v_hs = (int64_t)stg->T * HD;
-        } else if (kv8) {                                          // the decode over the e4m3 cache (attention_decode.hip, decode_attn8_kernel)
-            ap.K = ap.V = nullptr;
-            ap.K8 = k8; ap.V8 = v8; ap.k_scale = ks8; ap.v_scale = vs8;
-            ap.s_bs = (int64_t)NKV * kv->max_tokens; ap.s_hs = kv->max_tokens;
-        }
-        // decode, 9..64 rows: RoPE + split + the new token's cache row are folded into the attention kernel (attention_decode.hip, FOLD) where it qualifies
-        // (not on an e4m3 cache: rope_split_kernel<true> quantises the new rows, decode_attn8_kernel reads them back from the cache)
-        bool rope_folded = false;
-        if (sliced && c->fold_rope && !kv8) {
-            AttnParams fp = ap;
-            fp.q_bs = D; fp.q_rs = HD; fp.q_hs = 4 * HD; fp.B = M; fp.H = NKV; fp.Sq = NH / NKV; fp.kv_group = 1; fp.sk_arr = kv->d_len; fp.sk_add = 1;
-            fp.nsplit = nsplit; fp.part_ml = part; fp.part_o = part + (size_t)M * NKV * nsplit * (NH / NKV) * 2;
-            fp.qkv_part = pbuf; fp.qkv_splits = s_qkv; fp.qkv_ld = QKV; fp.rope_cos = cosT; fp.rope_sin = sinT;
-            rope_folded = decode_attn_fold_supported(fp, HD);
-        }
-        if (kv8)
-            hipLaunchKernelGGL(rope_split_kernel<true>, dim3(M, NKV), dim3(128), 0, st, qkv, cosT, sinT, q, kc, vc, 0, 0,
-                               decode ? d_seqs : d_row_seq, decode ? kv->d_len : nullptr, decode ? nullptr : d_row_pos, kv->max_tokens,
-                               (const float*)(sliced ? pbuf : nullptr), s_qkv, k8, v8, ks8, vs8, decode ? nullptr : stg->row_page, decode ? 0 : stg->T);
-        else if (!rope_folded)
-            hipLaunchKernelGGL(rope_split_kernel<false>, dim3(M, NKV), dim3(128), 0, st, qkv, cosT, sinT, q, kc, vc, 0, 0,
-                               decode ? d_seqs : d_row_seq, decode ? kv->d_len : nullptr, decode ? nullptr : d_row_pos, kv->max_tokens,
-                               (const float*)(sliced ? pbuf : nullptr), s_qkv, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-        if (last_rows_only && l + 1 == c->d.llm_layers) {
-            ap.q_bs = 0; ap.q_rs = D; ap.q_hs = HD; ap.o_bs = 0; ap.o_rs = D; ap.o_hs = HD;
-            ap.H = NH; ap.kv_group = NH / NKV; ap.B = n_pages; ap.seg = kv8 ? stg->seg_last : d_seg_last; ap.Sq = 32;
-            if (launch_flash_attn(ap, HD, true, st) != CR_OK) return cr_fail(CR_ERR_HIP, "prefill attention launch failed");
-            hipLaunchKernelGGL(move_rows_kernel<true>, dim3(n_pages), dim3(256), 0, st, ao, d_last, aol);
-            hipLaunchKernelGGL(move_rows_kernel<true>, dim3(n_pages), dim3(256), 0, st, x, d_last, xl);
-            // (rows <= 64 are pinned to the tiled kernel by `prefill_rows`; more pages than that take it by the dispatcher's own rule)
-            CR_TRY(gemm(c, EPI_RES, aol, D, w.wo, D, xl, D, xl, D, n_pages, D, D, st, true));
-            CR_TRY(rms(xl, D, hl2, w.fn, n_pages, c->d.rms_eps, st));
-            CR_TRY(gemm(c, EPI_SWIGLU, hl2, D, w.w13, D, actl, ff, nullptr, 0, n_pages, 2 * ff, D, st, true));
-            CR_TRY(gemm(c, EPI_RES, actl, ff, w.w2, ff, xl, D, xl, D, n_pages, D, ff, st, true));
-            hipLaunchKernelGGL(move_rows_kernel<false>, dim3(n_pages), dim3(256), 0, st, xl, d_last, x);
-            continue;
-        }
-        if (!decode) {
-            ap.q_bs = 0; ap.q_rs = D; ap.q_hs = HD; ap.o_bs = 0; ap.o_rs = D; ap.o_hs = HD;
-            ap.B = 1; ap.H = NH; ap.kv_group = NH / NKV;
-            // causal attention is per page, the linear layers see all pages at once; the pages' query blocks go out as ONE launch
-            // (segments: first row, rows, first position, cache slot), longest blocks first: a launch per page left its 800
-            // workgroups of 2..50 key tiles each a ragged tail on 512 slots
-            ap.B = (int)segs.size(); ap.seg = kv8 ? stg->seg : d_seg; ap.Sq = 0;
-            for (const Segment& sg : segs) ap.Sq = sg.S > ap.Sq ? sg.S : ap.Sq;
-            if (launch_flash_attn(ap, HD, true, st) != CR_OK) return cr_fail(CR_ERR_HIP, "prefill attention launch failed");
-        } else {
-            // rows = the 4 query heads of one KV group, all at the same position: no mask needed
-            ap.q_bs = D; ap.q_rs = HD; ap.q_hs = 4 * HD; ap.o_bs = D; ap.o_rs = HD; ap.o_hs = 4 * HD;
-            ap.B = M; ap.H = NKV; ap.Sq = NH / NKV; ap.Sk = 0; ap.kv_group = 1; ap.q_pos0 = 0;
-            ap.seq_map = d_seqs; ap.sk_arr = kv->d_len; ap.sk_add = 1;
-            ap.nsplit = nsplit; ap.part_ml = part; ap.part_o = part + (size_t)M * NKV * nsplit * (NH / NKV) * 2;
-            if (rope_folded) { ap.qkv_part = pbuf; ap.qkv_splits = s_qkv; ap.qkv_ld = QKV; ap.rope_cos = cosT; ap.rope_sin = sinT; }
-            if (launch_flash_attn_split(ap, HD, st) != CR_OK) return cr_fail(CR_ERR_HIP, "decode attention launch failed");
-        }
-        if (sliced) {
-            CR_TRY(f8 ? gemm8(c, EPI_PARTIAL, ao, D, w.q_o, w.s_o, pbuf, D, nullptr, 0, M, D, D, st, w.l_o)
-                      : gemm(c, EPI_PARTIAL, ao, D, w.wo, D, pbuf, D, nullptr, 0, M, D, D, st, false, w.d_o));
-            CR_TRY(launch_add_rmsnorm(x, pbuf, s_o, M, w.fn, h, c->d.rms_eps, st));
-        } else {
-            if (m8all) {    // wo and w2 take activations no norm produced: one quantiser pass each (row maximum, then the e4m3 row)
-                hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, ao, (int64_t)D, D, a8, hs);
-                CR_TRY(ctx_gemm_f8(c, EPI_RES, a8, hs, w.q_o, w.s_o, x, D, nullptr, M, D, D, st, x, D));
-            } else {
-                CR_TRY(f8 ? gemm8(c, EPI_RES, ao, D, w.q_o, w.s_o, x, D, x, D, M, D, D, st, w.l_o)
-                          : gemm(c, EPI_RES, ao, D, w.wo, D, x, D, x, D, M, D, D, st, !decode));
-            }
-            CR_TRY(rms(x, D, h, w.fn, M, c->d.rms_eps, st, m8 ? hs : nullptr));
-        }
-        if (m8) CR_TRY(ctx_gemm_f8(c, EPI_SWIGLU, h, hs, w.q_13, w.s_13, act, ff, nullptr, M, 2 * ff, D, st));
-        else CR_TRY(f8 ? gemm8(c, EPI_SWIGLU, h, D, w.q_13, w.s_13, act, ff, nullptr, 0, M, 2 * ff, D, st, w.l_13)
-                       : gemm(c, EPI_SWIGLU, h, D, w.w13, D, act, ff, nullptr, 0, M, 2 * ff, D, st, !decode, decode ? w.d_13 : nullptr));
-        if (sliced) {
-            CR_TRY(f8 ? gemm8(c, EPI_PARTIAL, act, ff, w.q_2, w.s_2, pbuf, D, nullptr, 0, M, D, ff, st, w.l_2)
-                      : gemm(c, EPI_PARTIAL, act, ff, w.w2, ff, pbuf, D, nullptr, 0, M, D, ff, st, false, w.d_2));
-            const bf16* next_norm = nullptr;             // the last layer's sum only lands in x: the caller norms what it needs
-            if (l + 1 < c->d.llm_layers) {
-                LayerW wn;
-                CR_TRY(layer_weights(c, l + 1, wn));
-                next_norm = wn.an;
-            }
-            CR_TRY(launch_add_rmsnorm(x, pbuf, s_2, M, next_norm, h, c->d.rms_eps, st));
-        } else if (m8all) {
-            hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, act, (int64_t)ff, ff, a8, hs);
-            CR_TRY(ctx_gemm_f8(c, EPI_RES, a8, hs, w.q_2, w.s_2, x, D, nullptr, M, D, ff, st, x, D));
-        } else {
-            CR_TRY(f8 ? gemm8(c, EPI_RES, act, ff, w.q_2, w.s_2, x, D, x, D, M, D, ff, st, w.l_2)
-                      : gemm(c, EPI_RES, act, ff, w.w2, ff, x, D, x, D, M, D, ff, st, !decode));
-        }
+        if (launch_flash_attn(prefill_attn_params(lk, T, b.q, b.ao, n_pages, b.kv8 ? r.seg8 : r.seg, b.max_S), HD, true, st) != CR_OK)
+            return cr_fail(CR_ERR_HIP, "prefill attention launch failed");
+        CR_TRY(add_linear(b.ao, w.o));
+        CR_TRY(rms(b.x, b.h, w.fn, M, eps, st, m8 ? b.hs : nullptr));
+        CR_TRY(m8 ? linear_f8(c, EPI_SWIGLU, b.h, b.hs, w.w13, b.act, M, st) : linear(c, EPI_SWIGLU, b.h, w.w13, LIN_PREFILL, b.act, M, st));
+        CR_TRY(add_linear(b.act, w.w2));
         CR_TRY(probe(l + 1));
     }
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
 
-size_t layers_ws(cr_ctx* c, int M, int nsplit = 0, int n_pages = 0, size_t stage = 0) {
-    const size_t ff = (size_t)WT(c, "derived.w13.0")->shape[0] / 2;
-    const size_t last_rows = (size_t)n_pages * (3 * D + ff) * 2 + 4 * 256;      // the final layer's compact rows (prefill)
-    const size_t sliced = nsplit > 0 && M <= 64 ? (size_t)8 * QKV * M * 4 : 0;       // K-slice partial sums of the decode GEMMs
-    return ((size_t)M * D * 4 + (size_t)M * QKV + (size_t)M * ff) * 2 + attn_split_ws_floats(M, NKV, NH / NKV, nsplit, HD) * 4 + sliced + (size_t)M * 4 + (size_t)M * ff + last_rows + 8192 +
-           (stage ? stage + 256 : 0);       // an e4m3 cache's prefill staging (PrefillStage)
+// What a decode step (M rows, one per sequence; the longest sequence's keys in nsplit attention splits) takes from the workspace
+struct DecodeBufs {
+    int M, nsplit, ff;
+    bool kv8;
+    // <= 64 rows: wqkv, wo and w2 run as K-sliced partial-sum GEMMs (gemm_skinny.hip: tall workgroups re-read X once per 64 weight rows); the slices are
+    // summed by the kernel that consumes the result anyway -- RoPE/split for wqkv, the residual add fused with the NEXT RMSNorm for wo and w2 -- in slice
+    // order, so a row's result is the same whatever it is batched with.  CR_NO_SLICED_DECODE=1, or > 64 rows: the one-tile GEMMs.
+    int s_qkv, s_o, s_2;
+    bool sliced;
+    // <= DECODE_FUSED_MAX_ROWS = 8 rows: gemm_decode.hip folds the norms, RoPE + split and the residual adds into the five GEMMs -- six launches per layer instead
+    // of nine, every sum in the order of the separate kernels (a row's bits do not depend on its batch): its virtual slices are compiled in, so the path is only
+    // taken while the K-sliced kernels' geometry (cost model or CR_PARTIAL_GEOM) is the one they reproduce (an e4m3 cache takes the separate kernels: the fused
+    // wqkv epilogue writes bf16 cache rows)
+    bool fused;
+    bf16 *x, *h, *qkv, *q, *ao, *act;
+    float *part, *pbuf;      // the attention splits' partials; the K-slices of one GEMM ([slices][M][N] fp32, the largest of the three)
+    HeadBufs head;
+
+    DecodeBufs(cr_ctx* c, const cr_kv* kv, int M, int nsplit, bool scored, bool deep)
+        : M(M), nsplit(nsplit), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), s_qkv(gemm_partial_splits(QKV, D)),
+          s_o(gemm_partial_splits(D, D)), s_2(gemm_partial_splits(D, ff)), sliced(M <= 64 && s_qkv > 0 && s_o > 0 && s_2 > 0 && !c->no_sliced_decode),
+          fused(sliced && c->fused_decode && !c->fp8_decode && !kv8 && decode_fused_supported(M, ff) && s_qkv == DEC_SLICES_WQKV && s_o == DEC_SLICES_WO &&
+                s_2 == DEC_SLICES_W2), head{M, c->d.vocab, scored, deep} {}
+
+    void carve(Arena& ar) {
+        x = ar.take<bf16>((size_t)M * D);
+        part = ar.take<float>(attn_split_ws_floats(M, NKV, NH / NKV, nsplit, HD));
+        h = ar.take<bf16>((size_t)M * D); q = ar.take<bf16>((size_t)M * D); ao = ar.take<bf16>((size_t)M * D); act = ar.take<bf16>((size_t)M * ff);
+        qkv = sliced ? nullptr : ar.take<bf16>((size_t)M * QKV);
+        pbuf = sliced ? ar.take<float>((size_t)std::max(s_qkv * QKV, std::max(s_o, s_2) * D) * M) : nullptr;
+        head.carve(ar);
+    }
+};
+
+// The decode attention launch: rows = the 4 query heads of one KV group, all at the same position (no mask needed), the keys of cache slot seqs[row]
+// in nsplit splits.  The one description of it: the fused path, decode_attn_fold_supported and the launch itself all start from this.
+AttnParams decode_attn_params(const cr_kv* kv, const LayerKV& lk, const DecodeBufs& b, const int32_t* d_seqs) {
+    AttnParams ap = attn_params(lk, kv->max_tokens, b.q, b.ao);
+    if (b.kv8) {      // attention_decode.hip, decode_attn8_kernel
+        ap.K8 = lk.k8; ap.V8 = lk.v8; ap.k_scale = lk.ks; ap.v_scale = lk.vs;
+        ap.s_bs = (int64_t)NKV * kv->max_tokens; ap.s_hs = kv->max_tokens;
+    }
+    ap.q_bs = D; ap.q_rs = HD; ap.q_hs = 4 * HD; ap.o_bs = D; ap.o_rs = HD; ap.o_hs = 4 * HD;
+    ap.B = b.M; ap.H = NKV; ap.Sq = NH / NKV; ap.Sk = 0; ap.kv_group = 1; ap.q_pos0 = 0;
+    ap.seq_map = d_seqs; ap.sk_arr = kv->d_len; ap.sk_add = 1;
+    ap.nsplit = b.nsplit; ap.part_ml = b.part; ap.part_o = b.part + (size_t)b.M * NKV * b.nsplit * (NH / NKV) * 2;
+    return ap;
+}
+
+// gemm_decode.hip's parameters for one weight: the decode-layout copy where there is one
+DecodeGemmParams fused_gemm_params(cr_ctx* c, const LinW& w, int M) {
+    DecodeGemmParams dp{};
+    dp.M = M; dp.eps = c->d.rms_eps; dp.W = w.w; dp.ldw = w.K; dp.N = w.N; dp.K = w.K;
+    if (w.dl) { dp.W = (const bf16*)w.dl->ptr; dp.swizzled = 1; }
+    return dp;
+}
+
+// The decoder stack over the rows b.x of a decode step (row i = the next token of sequence d_seqs[i]).
+int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_seqs, hipStream_t st) {
+    const int M = b.M, layers = c->d.llm_layers;
+    const float eps = c->d.rms_eps;
+    const bf16 *cosT = W(c, "rope.cos"), *sinT = W(c, "rope.sin");      // [max_pos][128] each
+    if (!cosT || !sinT) return CR_ERR_STATE;
+    auto fused_layer = [&](const LayerW& w, const LayerKV& lk) -> int {
+        DecodeGemmParams dp = fused_gemm_params(c, w.qkv, M);
+        dp.xres = b.x; dp.gamma = w.an;
+        dp.cosT = cosT; dp.sinT = sinT; dp.q_out = b.q; dp.kc = lk.k; dp.vc = lk.v; dp.seqs = d_seqs; dp.lens = kv->d_len; dp.max_tokens = kv->max_tokens;
+        CR_TRY(launch_decode_gemm(DEC_WQKV, dp, st));
+        if (launch_flash_attn_split(decode_attn_params(kv, lk, b, d_seqs), HD, st) != CR_OK) return cr_fail(CR_ERR_HIP, "decode attention launch failed");
+        dp = fused_gemm_params(c, w.o, M);
+        dp.X = b.ao; dp.ldx = D; dp.xio = b.x;
+        CR_TRY(launch_decode_gemm(DEC_WO, dp, st));
+        dp = fused_gemm_params(c, w.w13, M);
+        dp.xres = b.x; dp.gamma = w.fn; dp.C = b.act; dp.ldc = b.ff;
+        CR_TRY(launch_decode_gemm(DEC_W13, dp, st));
+        dp = fused_gemm_params(c, w.w2, M);
+        dp.X = b.act; dp.ldx = b.ff; dp.xio = b.x;
+        return launch_decode_gemm(DEC_W2, dp, st);
+    };
+    for (int l = 0; l < layers; l++) {
+        LayerW w;
+        CR_TRY(layer_weights(c, l, b.ff, w));
+        const LayerKV lk = layer_kv(kv, l);
+        if (b.fused) {
+            CR_TRY(fused_layer(w, lk));
+            continue;
+        }
+        const bool f8 = M <= 64 && c->fp8_decode && w.qkv.e4m3() && w.o.e4m3() && w.w13.e4m3() && w.w2.e4m3();
+        const LinForm dec = f8 ? LIN_E4M3 : LIN_DECODE;
+        // the one-tile fallback takes bf16 wqkv, wo and w2 as loaded (wqkv's decode-layout copy is in RoPE tile order, which only the K-sliced kernel reads)
+        const LinForm plain = f8 ? LIN_E4M3 : LIN_LOADED;
+        if (b.sliced) {
+            if (l == 0) CR_TRY(rms(b.x, b.h, w.an, M, eps, st));      // later layers: the add + norm after the previous layer's w2 left h
+            CR_TRY(linear(c, EPI_PARTIAL, b.h, w.qkv, dec, b.pbuf, M, st));
+        } else {
+            CR_TRY(rms(b.x, b.h, w.an, M, eps, st));
+            CR_TRY(linear(c, EPI_STORE, b.h, w.qkv, plain, b.qkv, M, st));
+        }
+        AttnParams ap = decode_attn_params(kv, lk, b, d_seqs);
+        // 9..64 rows: RoPE + split + the new token's cache row are folded into the attention kernel (attention_decode.hip, FOLD) where it qualifies
+        // (not on an e4m3 cache: rope_split_kernel<true> quantises the new rows, decode_attn8_kernel reads them back from the cache)
+        AttnParams fp = ap;
+        fp.qkv_part = b.pbuf; fp.qkv_splits = b.s_qkv; fp.qkv_ld = QKV; fp.rope_cos = cosT; fp.rope_sin = sinT;
+        const bool rope_folded = b.sliced && c->fold_rope && !b.kv8 && decode_attn_fold_supported(fp, HD);
+        if (rope_folded) ap = fp;
+        // (b.pbuf: wqkv's K-slices when sliced, else null and the kernel reads b.qkv; of lk either the bf16 or the e4m3 pointers are null)
+        else
+            hipLaunchKernelGGL(b.kv8 ? rope_split_kernel<true> : rope_split_kernel<false>, dim3(M, NKV), dim3(128), 0, st, b.qkv, cosT, sinT, b.q, lk.k, lk.v, 0, 0,
+                               d_seqs, kv->d_len, nullptr, kv->max_tokens, (const float*)b.pbuf, b.s_qkv, lk.k8, lk.v8, lk.ks, lk.vs, nullptr, 0);
+        if (launch_flash_attn_split(ap, HD, st) != CR_OK) return cr_fail(CR_ERR_HIP, "decode attention launch failed");
+        if (b.sliced) {
+            CR_TRY(linear(c, EPI_PARTIAL, b.ao, w.o, dec, b.pbuf, M, st));
+            CR_TRY(launch_add_rmsnorm(b.x, b.pbuf, b.s_o, M, w.fn, b.h, eps, st));
+        } else {
+            CR_TRY(linear(c, EPI_RES, b.ao, w.o, plain, b.x, M, st));
+            CR_TRY(rms(b.x, b.h, w.fn, M, eps, st));
+        }
+        CR_TRY(linear(c, EPI_SWIGLU, b.h, w.w13, dec, b.act, M, st));
+        if (b.sliced) {
+            CR_TRY(linear(c, EPI_PARTIAL, b.act, w.w2, dec, b.pbuf, M, st));
+            // the last layer's sum only lands in x: the caller norms what it needs
+            const bf16* next_norm = l + 1 < layers ? W(c, "language_model.model.layers." + std::to_string(l + 1) + ".attention_norm.weight") : nullptr;
+            if (l + 1 < layers && !next_norm) return CR_ERR_STATE;
+            CR_TRY(launch_add_rmsnorm(b.x, b.pbuf, b.s_2, M, next_norm, b.h, eps, st));
+        } else {
+            CR_TRY(linear(c, EPI_RES, b.act, w.w2, plain, b.x, M, st));
+        }
+    }
+    CR_HIP(hipGetLastError());
+    return CR_OK;
 }
 
 }  // namespace
@@ -798,10 +862,22 @@ static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
     return false;
 }
 
-// the scores of the rows the pick has just chosen from (lg: the penalised rows it left), into the sequences' slots; scratch follows lg in the workspace
-static int score_rows(cr_kv* kv, const float* lg, int V, int n, const int32_t* d_seqs, hipStream_t st) {
-    return launch_logprobs(lg, V, V, n, d_seqs, kv->d_lpn, 0, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_lpdone, (void*)(lg + (size_t)n * V), kv->d_lp,
-                           kv->d_top_id, kv->d_top_lp, st);
+// What follows the LM head in a prefill and in a decode step: the logits out, then the pick (greedy or sampled) appends every row's id and adds len_add
+// to its cached length, then the scores of the rows the pick has just chosen from (h.lg: the penalised rows it left) go into the sequences' slots
+static int pick_rows(cr_kv* kv, const HeadBufs& h, const int32_t* seqs, const int32_t* d_seqs, float penalty, int len_add, float* out, hipStream_t st) {
+    const int n = h.n, V = h.V;
+    if (out) CR_HIP(hipMemcpyAsync(out, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
+    if (h.lg0) CR_HIP(hipMemcpyAsync(h.lg0, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
+    if (any_sampled(kv, seqs, n))
+        CR_TRY(launch_sample(h.lg, V, V, penalty, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
+                             nullptr, 1, kv->d_len, len_add, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, h.lg0));
+    else
+        hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, h.lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
+                           kv->d_len, kv->gen_cap, len_add, kv->d_stop, kv->n_seqs, h.lg0);
+    if (h.scored)
+        CR_TRY(launch_logprobs(h.lg, V, V, n, d_seqs, kv->d_lpn, 0, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_lpdone, h.score, kv->d_lp, kv->d_top_id,
+                               kv->d_top_lp, st));
+    return CR_OK;
 }
 
 extern "C" {
@@ -815,7 +891,7 @@ int cr_op_quantize_fp8(const void* w, int64_t ldw, int N, int K, void* q, float*
 
 int cr_enable_fp8_mfma(cr_ctx* c, int enable, void* stream) {
     if (!c) return cr_fail(CR_ERR_ARG, "cr_enable_fp8_mfma: null context");
-    if (!enable) { if (c->fp8_mfma) cr_bump_gen(c); c->fp8_mfma = 0; return CR_OK; }      // captured decode graphs are keyed on weight_gen
+    if (!enable) { if (c->fp8_mfma) cr_bump_gen(c); c->fp8_mfma = 0; return CR_OK; }      // borrowers of these weights watch weight_gen (ctx_share_ok)
     if (c->borrowed) return cr_fail(CR_ERR_STATE, "cr_enable_fp8_mfma: enable it on the context that owns the weights, then share again");
     if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_enable_fp8_mfma: call cr_finalize first");
     CR_HIP(hipSetDevice(c->device));
@@ -979,7 +1055,6 @@ int cr_kv_free(cr_kv* kv) {
     if (kv->d_lp) hipFree(kv->d_lp);
     if (kv->d_top_id) hipFree(kv->d_top_id);
     if (kv->d_top_lp) hipFree(kv->d_top_lp);
-    for (auto& e : kv->graphs) if (e.exec) hipGraphExecDestroy(e.exec);
     delete kv;
     return CR_OK;
 }
@@ -1142,67 +1217,42 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     hipStream_t st = (hipStream_t)stream;
     const int V = c->d.vocab;
     const bool kv8 = kv->fmt == CR_KV_E4M3;
-    int stage_T = 0;
-    for (const Segment& sg : segs) stage_T = sg.S > stage_T ? sg.S : stage_T;
-    const size_t lw = layers_ws(c, M, 0, n, kv8 ? prefill_stage_bytes(n, stage_T) : 0);
-    const bool scored = any_scored(kv, seqs, n);
-    const bool deep = long_history(kv, seqs, n, penalty);
-    const size_t need = lw + (size_t)M * D * 2 + (size_t)n * D * 2 + (size_t)n * V * 4 + (size_t)M * 12 + (size_t)n * 68 + 8192 +
-                        (scored ? logprobs_scratch_bytes(n, V) : 0);
-    CR_TRY(ws_ensure(c, need + (deep ? (size_t)n * V * 4 + 256 : 0)));
-    float* lg0 = deep ? (float*)(c->ws + ((need + 255) & ~(size_t)255)) : nullptr;      // the rows before the penalty, for the pick
-    bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
-    bf16* hl = x + (size_t)M * D;
-    float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
-    int32_t* d_row_seq = (int32_t*)(((uintptr_t)(lg + (size_t)n * V) + (scored ? logprobs_scratch_bytes(n, V) : 0) + 255) & ~(uintptr_t)255);
-    int32_t* d_row_pos = d_row_seq + M;
-    int32_t* d_seg = d_row_pos + M;                 // 4 per page: first row, rows, first position, cache slot (the attention launch's segments)
-    int32_t* d_seg_last = d_seg + 4 * n;            // the final layer's segments: the rows that share a 32-row wave with the page's last row
-    int32_t* d_last = d_seg_last + 4 * n;           // and that last row
-    int32_t* d_seg8 = d_last + n;                   // e4m3 cache (PrefillStage): d_seg and d_seg_last with the page index as the slot, the rows' page indices
-    int32_t* d_seg_last8 = d_seg8 + 4 * n;
-    int32_t* d_row_page = d_seg_last8 + 4 * n;
+    int max_S = 0;
+    for (const Segment& sg : segs) max_S = sg.S > max_S ? sg.S : max_S;
+    PrefillBufs b(c, kv, M, n, max_S, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty));
+    CR_TRY(ws_carve(c, "cr_llm_prefill_batch", b));
     {
-        std::vector<int32_t> h(2 * (size_t)M + 9 * segs.size() + (kv8 ? 8 * segs.size() + (size_t)M : 0));
-        for (const Segment& sg : segs)
-            for (int r = 0; r < sg.S; r++) { h[sg.row0 + r] = sg.seq; h[(size_t)M + sg.row0 + r] = sg.pos0 + r; }
-        for (size_t i = 0; i < segs.size(); i++) {
-            int32_t* e = h.data() + 2 * (size_t)M + 4 * i;
-            e[0] = segs[i].row0; e[1] = segs[i].S; e[2] = segs[i].pos0; e[3] = segs[i].seq;
+        std::vector<int32_t> h(prefill_rows_ints(M, n, kv8));
+        const PrefillRows hr = prefill_rows(h.data(), M, n);
+        for (int i = 0; i < n; i++) {
+            const Segment& sg = segs[i];
+            int32_t *e = hr.seg + 4 * i, *f = hr.seg_last + 4 * i;
+            e[0] = sg.row0; e[1] = sg.S; e[2] = sg.pos0; e[3] = sg.seq;
             // the attention kernel's query blocks are 128 rows of a segment, its waves 32: rows [32 k, 32 k + 32) of a page meet in one wave
-            const int w0 = (segs[i].S - 1) / 32 * 32;
-            int32_t* f = h.data() + 2 * (size_t)M + 4 * segs.size() + 4 * i;
-            f[0] = segs[i].row0 + w0; f[1] = segs[i].S - w0; f[2] = segs[i].pos0 + w0; f[3] = segs[i].seq;
-            h[2 * (size_t)M + 8 * segs.size() + i] = segs[i].row0 + segs[i].S - 1;
+            const int w0 = (sg.S - 1) / 32 * 32;
+            f[0] = sg.row0 + w0; f[1] = sg.S - w0; f[2] = sg.pos0 + w0; f[3] = sg.seq;
+            hr.last[i] = sg.row0 + sg.S - 1;
+            for (int r = 0; r < sg.S; r++) { hr.row_seq[sg.row0 + r] = sg.seq; hr.row_pos[sg.row0 + r] = sg.pos0 + r; }
             if (kv8) {
-                int32_t* g = h.data() + 2 * (size_t)M + 9 * segs.size() + 4 * i;
-                for (int k = 0; k < 4; k++) { g[k] = e[k]; g[4 * segs.size() + k] = f[k]; }
-                g[3] = g[4 * segs.size() + 3] = (int32_t)i;
-                for (int r = 0; r < segs[i].S; r++) h[2 * (size_t)M + 17 * segs.size() + segs[i].row0 + r] = (int32_t)i;
+                for (int k = 0; k < 3; k++) { hr.seg8[4 * i + k] = e[k]; hr.seg_last8[4 * i + k] = f[k]; }
+                hr.seg8[4 * i + 3] = hr.seg_last8[4 * i + 3] = i;
+                for (int r = 0; r < sg.S; r++) hr.row_page[sg.row0 + r] = i;
             }
         }
-        CR_HIP(hipMemcpyAsync(d_row_seq, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
+        CR_HIP(hipMemcpyAsync(b.rows.row_seq, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
     }
     CR_TRY(stage_seqs(c, seqs, n, st, true));
-    CR_HIP(hipMemcpyAsync(x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
-    const PrefillStage stg{stage_T, d_row_page, d_seg8, d_seg_last8};
-    CR_TRY(run_layers(c, kv, x, M, false, segs, d_row_seq, d_row_pos, nullptr, 0, st, d_seg, d_last, d_seg_last, kv8 ? &stg : nullptr));
-    const bf16 *nw = W(c, "language_model.model.norm.weight"), *ow = W(c, "language_model.output.weight");
-    if (!nw || !ow) return CR_ERR_STATE;
+    CR_HIP(hipMemcpyAsync(b.x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
+    CR_TRY(prefill_layers(c, kv, b, st));
+    const bf16* nw = W(c, "language_model.model.norm.weight");
+    const LinW head = lin_weight(c, "language_model.output.weight", V, D);
+    if (!nw || !head.w) return CR_ERR_STATE;
     // only each page's last row feeds the LM head (the reference computes all S rows and reads the last, :1081 + _sample)
     for (int i = 0; i < n; i++)
-        CR_TRY(rms(x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, D, hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
-    CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st));
-    if (last_logits) CR_HIP(hipMemcpyAsync(last_logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-    if (lg0) CR_HIP(hipMemcpyAsync(lg0, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-    if (any_sampled(kv, seqs, n))
-        CR_TRY(launch_sample(lg, V, V, penalty, n, c->d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
-                             nullptr, 1, kv->d_len, 0, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, lg0));
-    else
-        hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, c->d_seqs, kv->d_gen, kv->d_ngen,
-                           kv->d_len, kv->gen_cap, 0, kv->d_stop, kv->n_seqs, lg0);
-    if (scored) CR_TRY(score_rows(kv, lg, V, n, c->d_seqs, st));
-    hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, d_seg, n, kv->d_len);
+        CR_TRY(rms(b.x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, b.head.hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
+    CR_TRY(linear(c, EPI_F32, b.head.hl, head, LIN_LOADED, b.head.lg, n, st));
+    CR_TRY(pick_rows(kv, b.head, seqs, c->d_seqs, penalty, 0, last_logits, st));
+    hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, b.rows.seg, n, kv->d_len);
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
         kv->len[sg.seq] += sg.S;
@@ -1244,99 +1294,26 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     int max_len = 0;
     for (int i = 0; i < n; i++) max_len = kv->len[seqs[i]] > max_len ? kv->len[seqs[i]] : max_len;
     const int nsplit = ((max_len + 1 + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
-    const size_t lw = layers_ws(c, n, nsplit);
-    const bool scored = any_scored(kv, seqs, n);
-    const bool deep = long_history(kv, seqs, n, penalty);
-    const size_t need = lw + (size_t)n * D * 4 + (size_t)n * V * 4 + 4096 + (scored ? logprobs_scratch_bytes(n, V) : 0);
-    CR_TRY(ws_ensure(c, need + (deep ? (size_t)n * V * 4 + 256 : 0)));
-    float* lg0 = deep ? (float*)(c->ws + ((need + 255) & ~(size_t)255)) : nullptr;      // the rows before the penalty, for the pick
-    bf16* x = (bf16*)(c->ws + ((lw + 255) & ~(size_t)255));
-    bf16* hl = x + (size_t)n * D;
-    float* lg = (float*)(((uintptr_t)(hl + (size_t)n * D) + 255) & ~(uintptr_t)255);
+    DecodeBufs b(c, kv, n, nsplit, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty));
+    CR_TRY(ws_carve(c, "cr_llm_decode", b));
     CR_TRY(stage_seqs(c, seqs, n, st, false));
     const int32_t* d_seqs = c->d_seqs;
     const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
-    const bf16 *nw = W(c, "language_model.model.norm.weight"), *ow = W(c, "language_model.output.weight");
-    if (!table || !nw || !ow) return CR_ERR_STATE;
-    const bool sampled = any_sampled(kv, seqs, n);
-    auto enqueue_step = [&](hipStream_t st) -> int {
-        hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(256), 0, st, table, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, x);
-        CR_TRY(run_layers(c, kv, x, n, true, {}, nullptr, nullptr, d_seqs, nsplit, st));
-        const DevTensor *q_out = opt(c, "fp8.language_model.output.weight"), *s_out = opt(c, "fp8s.language_model.output.weight");
-        const int ff_ = (int)WT(c, "derived.w13.0")->shape[0] / 2;
-        if (c->fused_decode && !c->fp8_decode && !c->no_sliced_decode && decode_fused_supported(n, ff_)) {
-            DecodeGemmParams dh{};                                // final RMSNorm folded into the LM head (gemm_decode.hip)
-            dh.M = n; dh.eps = c->d.rms_eps; dh.W = ow; dh.ldw = D; dh.N = V; dh.K = D; dh.xres = x; dh.gamma = nw; dh.C = lg; dh.ldc = V;
-            if (const DevTensor* dl = opt(c, "declayout.language_model.output.weight")) { dh.W = (const bf16*)dl->ptr; dh.swizzled = 1; }
-            CR_TRY(launch_decode_gemm(DEC_HEAD, dh, st));
-        } else {
-        CR_TRY(rms(x, D, hl, nw, n, c->d.rms_eps, st));
-        if (c->fp8_decode && n <= 64 && q_out && s_out) CR_TRY(gemm8(c, EPI_F32, hl, D, q_out, s_out, lg, V, nullptr, 0, n, V, D, st, opt(c, "fp8dl.language_model.output.weight")));
-        else CR_TRY(gemm(c, EPI_F32, hl, D, ow, D, lg, V, nullptr, 0, n, V, D, st, false, opt(c, "declayout.language_model.output.weight")));
-        }
-        if (logits) CR_HIP(hipMemcpyAsync(logits, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-        if (lg0) CR_HIP(hipMemcpyAsync(lg0, lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-        if (sampled)
-            CR_TRY(launch_sample(lg, V, V, penalty, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
-                                 nullptr, 1, kv->d_len, 1, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, lg0));
-        else
-            hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
-                               kv->d_len, kv->gen_cap, 1, kv->d_stop, kv->n_seqs, lg0);
-        if (scored) CR_TRY(score_rows(kv, lg, V, n, d_seqs, st));
-        return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
-    };
-    // graph path: the plain generation loop (no forced ids, no logits copy), nothing recording events on these launches
-    // (a step with a sampled row launches the sampling pick, one with a scored row the score kernels: both are left out of the graph path)
-    const bool graphable = c->decode_graph && !force_tokens && !logits && !sampled && !scored && !deep && !(c->prof && c->prof_mode != 2);
-    bool done = false;
-    hipStream_t gs = st;                               // the null stream cannot be captured: use the context's blocking side stream
-    if (graphable && !st) {
-        if (!c->side && hipStreamCreate(&c->side) != hipSuccess) { (void)hipGetLastError(); c->decode_graph = 0; }
-        gs = c->side;
+    const bf16* nw = W(c, "language_model.model.norm.weight");
+    const LinW head = lin_weight(c, "language_model.output.weight", V, D);
+    if (!table || !nw || !head.w) return CR_ERR_STATE;
+    hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(256), 0, st, table, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.x);
+    CR_TRY(decode_layers(c, kv, b, d_seqs, st));
+    if (c->fused_decode && !c->fp8_decode && !c->no_sliced_decode && decode_fused_supported(n, b.ff)) {
+        DecodeGemmParams dh = fused_gemm_params(c, head, n);      // final RMSNorm folded into the LM head (gemm_decode.hip)
+        dh.xres = b.x; dh.gamma = nw; dh.C = b.head.lg; dh.ldc = V;
+        CR_TRY(launch_decode_gemm(DEC_HEAD, dh, st));
+    } else {
+        CR_TRY(rms(b.x, b.head.hl, nw, n, c->d.rms_eps, st));
+        CR_TRY(linear(c, EPI_F32, b.head.hl, head, c->fp8_decode && n <= 64 && head.e4m3() ? LIN_E4M3 : LIN_DECODE, b.head.lg, n, st));
     }
-    if (getenv("CR_GRAPH_DEBUG") && !graphable) fprintf(stderr, "[cr] decode not graphable: flag %d force %d logits %d prof %d/%d\n", c->decode_graph, force_tokens != nullptr, logits != nullptr, (int)c->prof, c->prof_mode);
-    if (graphable && c->decode_graph && gs) {
-        cr_kv::DecodeGraph* g = nullptr;
-        for (auto& e : kv->graphs)
-            if (e.n == n && e.nsplit == nsplit && e.penalty == penalty && e.ws == c->ws && e.seqs == d_seqs && e.weight_gen == c->weight_gen) { g = &e; break; }
-        if (!g) {
-            if (kv->graphs.size() >= 24) {                       // stale keys (grown workspace, reloaded weights, old split counts)
-                for (auto& e : kv->graphs) if (e.exec) hipGraphExecDestroy(e.exec);
-                kv->graphs.clear();
-            }
-            kv->graphs.push_back({n, nsplit, penalty, c->ws, d_seqs, c->weight_gen, nullptr, 0});
-            g = &kv->graphs.back();
-        }
-        if (g->exec) {
-            if (hipGraphLaunch(g->exec, gs) == hipSuccess) done = true;
-            else { (void)hipGetLastError(); c->decode_graph = 0; }
-        } else if (g->warm >= 1) {
-            // second step with this key: one-time attribute set-up and workspace growth happened in the eager first one
-            hipGraph_t graph = nullptr;
-            if (hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rc = enqueue_step(gs);
-                const hipError_t ee = hipStreamEndCapture(gs, &graph);
-                if (rc == CR_OK && ee == hipSuccess && graph && hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) == hipSuccess &&
-                    hipGraphLaunch(g->exec, gs) == hipSuccess) {
-                    done = true;
-                    if (getenv("CR_GRAPH_DEBUG")) fprintf(stderr, "[cr] decode graph captured: rows %d, splits %d\n", n, nsplit);
-                } else {
-                    if (getenv("CR_GRAPH_DEBUG")) fprintf(stderr, "[cr] decode graph capture FAILED (rc %d, end %d): %s\n", rc, (int)ee, hipGetErrorString(hipGetLastError()));
-                    (void)hipGetLastError();
-                    if (g->exec) { hipGraphExecDestroy(g->exec); g->exec = nullptr; }
-                    c->decode_graph = 0;                          // fall back to plain launches for good
-                }
-                if (graph) hipGraphDestroy(graph);
-            } else {
-                if (getenv("CR_GRAPH_DEBUG")) fprintf(stderr, "[cr] hipStreamBeginCapture failed: %s\n", hipGetErrorString(hipGetLastError()));
-                (void)hipGetLastError();
-                c->decode_graph = 0;
-            }
-        } else {
-            g->warm++;
-        }
-    }
-    if (!done) CR_TRY(enqueue_step(st));
+    CR_TRY(pick_rows(kv, b.head, seqs, d_seqs, penalty, 1, logits, st));
+    CR_HIP(hipGetLastError());
     for (int i = 0; i < n; i++) {
         kv->len[seqs[i]] += 1;
         if (kv->ngen[seqs[i]] < kv->gen_cap) kv->ngen[seqs[i]] += 1;

@@ -195,8 +195,7 @@ int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float t
  * A row is summed in an order that depends on vocab alone (fixed chunks of 4096 scores, merged in chunk order, no float atomics): the scores of a
  * sequence are bit-equal whatever batch, row, slot, stream or pipeline computes them.  Accuracy: within 5e-6 absolute of the float64 log-softmax for
  * |z| <= 32 (double accumulation, one fp32 rounding of the result).  A row holding NaN or +inf gives NaN log-probabilities for that step (ids
- * unspecified).  With scores off for every row of a launch nothing is launched or changed; ids and logits never depend on the setting.  A decode step
- * with a scored row stays out of the CR_DECODE_GRAPH replay, as a sampled one does.  The blocks (cr_kv_logprobs' layout, 68 bytes per generated id,
+ * unspecified).  With scores off for every row of a launch nothing is launched or changed; ids and logits never depend on the setting.  The blocks (cr_kv_logprobs' layout, 68 bytes per generated id,
  * max_tokens ids per sequence) are allocated by the first call that switches a sequence of the cache on.  CR_ERR_ARG for top_n outside 0..8 (checked
  * before the cache and sequence), CR_ERR_STATE when switching on a sequence that has generated ids already: call after cr_kv_reset and BEFORE the
  * sequence's prefill.  Cache state like the stop criteria and the sampling state: any cache format, any decode option, a cache shared between
@@ -266,8 +265,8 @@ int cr_enable_fp8_mfma(cr_ctx* ctx, int enable, void* stream);
  * HIP events on the launch stream.  cr_profile_read synchronises and returns, for the compute-bound class
  * (M >= 1024 rows) in out[0..3] = {launches, summed kernel ms, summed algorithmic FLOPs (2*M*N*K), algorithmic bytes} and for the
  * weight-streaming class (M < 1024) in out[4..7] = {launches, ms, FLOPs, algorithmic bytes (W + A + C)}; then clears. */
-/* enable: 0 off, 1 every GEMM launch, 2 only the compute-bound class (batched decode then runs as a captured hipGraph,
- * whose launches cannot carry events). */
+/* enable: 0 off, 1 every GEMM launch, 2 only the compute-bound class (the decode steps' many short launches then
+ * carry no events). */
 int cr_profile(cr_ctx* ctx, int enable);
 int cr_profile_read(cr_ctx* ctx, double* out8);
 /* Bookkeeping of the above since cr_create: out[0] = launches bracketed, out[1] = launches accounted for (retired into

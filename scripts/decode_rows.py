@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Decode step time against the number of rows: 1 / 8 / 16 / 64 pages of the bench's prompt length, plain launches
-and hipGraph replay (CR_DECODE_GRAPH is read when the context is created, so the parent starts one child per setting).
+"""Decode step time against the number of rows: 1 / 8 / 16 / 64 pages of the bench's prompt length, the separate kernels
+and the fused small-batch path (CR_DECODE_FUSED is read when the context is created, so the parent starts one child per setting).
    python scripts/decode_rows.py            -> gpurun_out/decode_rows.json
    python scripts/decode_rows.py child      (one setting, rows swept in-process; under rocprofv3 --kernel-trace --stats with ROWS=1 for the per-kernel view)"""
 import json, os, subprocess, sys, time
@@ -39,16 +39,15 @@ def child():
             ts.append((time.perf_counter() - t0) / STEPS * 1e3)
         res[n] = min(ts)
         ctx = kv.length(0) if hasattr(kv, 'length') else -1
-        print(f'rows {n:3d}: {min(ts):.3f} ms per step (runs {", ".join(f"{t:.3f}" for t in ts)}), graph {os.environ.get("CR_DECODE_GRAPH", "0")} fused {os.environ.get("CR_DECODE_FUSED", "1")}', flush=True)
+        print(f'rows {n:3d}: {min(ts):.3f} ms per step (runs {", ".join(f"{t:.3f}" for t in ts)}), fused {os.environ.get("CR_DECODE_FUSED", "1")}', flush=True)
     print('RESULT ' + json.dumps(res), flush=True)
 
 if len(sys.argv) > 1 and sys.argv[1] == 'child':
     child()
 else:
     out = {}
-    for name, graph, fused in (('separate kernels (CR_DECODE_FUSED=0), plain launches', '0', '0'), ('fused small-batch path, plain launches', '0', '1'),
-                               ('fused small-batch path, hipGraph replay', '1', '1')):
-        env = dict(os.environ, CR_DECODE_GRAPH=graph, CR_DECODE_FUSED=fused)
+    for name, fused in (('separate kernels (CR_DECODE_FUSED=0)', '0'), ('fused small-batch path', '1')):
+        env = dict(os.environ, CR_DECODE_FUSED=fused)
         p = subprocess.run([sys.executable, os.path.abspath(__file__), 'child'], env=env, capture_output=True, text=True)
         sys.stdout.write(p.stdout); sys.stderr.write(p.stderr[-2000:])
         for line in p.stdout.splitlines():
