@@ -378,6 +378,17 @@ int cr_op_attention(const void* q, const void* k, const void* v, void* o, const 
     return CR_OK;
 }
 
+int cr_op_attention_segments(const void* q, const void* kc, const void* vc, void* o, const int32_t* seg, int n, int Sq, int H, int kv_group, int max_tokens,
+                             float s_div, void* stream) {
+    if (!q || !kc || !vc || !o || !seg || n <= 0 || Sq <= 0 || Sq > max_tokens || H <= 0 || kv_group <= 0 || H % kv_group != 0)
+        return cr_fail(CR_ERR_ARG, "cr_op_attention_segments: bad argument");
+    // the fill is the LLM stage's own (attention.hpp: prefill_attn_params of llm.hip calls the same function)
+    const AttnParams ap = segment_attn_params((const bf16*)kc, (const bf16*)vc, max_tokens, (const bf16*)q, (bf16*)o, H, kv_group, n, seg, Sq, s_div);
+    const int r = launch_flash_attn(ap, 128, true, (hipStream_t)stream);
+    if (r != CR_OK) return cr_fail(r, "cr_op_attention_segments(n=%d, Sq=%d, H=%d) rejected or failed", n, Sq, H);
+    return CR_OK;
+}
+
 int64_t cr_op_decode_attention_scratch_floats(int B, int max_keys) {
     const int nsplit = ((max_keys + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
     return (int64_t)attn_split_ws_floats(B, 8, 4, nsplit, 128);

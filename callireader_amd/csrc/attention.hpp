@@ -48,7 +48,21 @@ bool decode_attn_fold_supported(const AttnParams& p, int head_dim);
 bool decode_attn8_available();
 bool decode_attn8_supported(const AttnParams& p, int head_dim);
 
-constexpr int ATTN_SPLIT_TILES = 4;      // 256 keys per split: depends only on the row's own key count
+// The segment launch of the causal d = 128 kernel (AttnParams::seg above), filled in ONE place for the LLM stage's prefill (llm.hip, prefill_attn_params) and for
+// the test entry cr_op_attention_segments (api.hip): q / o rows [row][H][128], K / V [slot][H / kv_group][T][128], bf16-rounded scores divided by s_div.
+inline AttnParams segment_attn_params(const bf16* k, const bf16* v, int T, const bf16* q, bf16* o, int H, int kv_group, int n_segs, const int32_t* seg, int Sq,
+                                      float s_div) {
+    constexpr int HD = 128;
+    AttnParams ap{};
+    ap.K = k; ap.V = v; ap.Q = q; ap.O = o;
+    ap.k_bs = ap.v_bs = (int64_t)(H / kv_group) * T * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)T * HD;
+    ap.q_prescale = 1.0f; ap.s_div = s_div;
+    ap.q_bs = 0; ap.q_rs = (int64_t)H * HD; ap.q_hs = HD; ap.o_bs = 0; ap.o_rs = (int64_t)H * HD; ap.o_hs = HD;
+    ap.H = H; ap.kv_group = kv_group; ap.B = n_segs; ap.seg = seg; ap.Sq = Sq;
+    return ap;
+}
+
+constexpr int ATTN_SPLIT_TILES = 4;     // 256 keys per split: depends only on the row's own key count
 
 int launch_flash_attn(const AttnParams& p, int head_dim, bool causal, hipStream_t stream);
 // decode: Sq <= 32 query rows per (batch, head), non-causal over each sequence's own keys, split over the keys

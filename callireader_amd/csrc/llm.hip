@@ -418,10 +418,8 @@ AttnParams attn_params(const LayerKV& lk, int T, bf16* q, bf16* ao) {
 // causal attention is per page, the linear layers see all pages at once (a launch per page left its 800 workgroups of 2..50 key tiles each a ragged
 // tail on 512 slots).  q / ao rows are [row][32 heads][128].
 AttnParams prefill_attn_params(const LayerKV& lk, int T, bf16* q, bf16* ao, int n_segs, const int32_t* seg, int Sq) {
-    AttnParams ap = attn_params(lk, T, q, ao);
-    ap.q_bs = 0; ap.q_rs = D; ap.q_hs = HD; ap.o_bs = 0; ap.o_rs = D; ap.o_hs = HD;
-    ap.H = NH; ap.kv_group = NH / NKV; ap.B = n_segs; ap.seg = seg; ap.Sq = Sq;
-    return ap;
+    static_assert(HD == 128 && D == NH * HD, "segment_attn_params lays rows out as [row][NH][128]");
+    return segment_attn_params(lk.k, lk.v, T, q, ao, NH, NH / NKV, n_segs, seg, Sq, attn_params(lk, T, q, ao).s_div);      // (attention.hpp; cr_op_attention_segments fills its launch there too)
 }
 
 // Runs the call's carve twice: on an Arena without a base to measure what the call needs, then -- the workspace grown to that -- on the workspace itself.

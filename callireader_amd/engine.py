@@ -477,6 +477,28 @@ def op_attention(q, k, v, o, strides, Bn, H, Sq, Sk, head_dim, kv_group=1, causa
     return o
 
 
+def op_attention_segments(q, kc, vc, o, segs, s_div=11.313708498984761, Sq=None):
+    """cr_op_attention_segments: the prefill attention's segment launch alone.  q / o (rows, H, 128) bf16, kc / vc (n_slots, H_kv, max_tokens, 128) bf16 caches
+    holding every segment's keys / values, segs = [(first row, rows, first position, cache slot), ...] on the host; Sq = the grid's longest segment (default: the
+    longest of segs).  The ranges are checked here, where the shapes are known: the C entry only sees a device array."""
+    rows, H, hd = q.shape
+    n_slots, n_kv, max_tokens, _ = kc.shape
+    if hd != 128 or kc.shape[3] != 128 or vc.shape != kc.shape or o.shape != q.shape or H % n_kv or not segs:
+        raise ValueError('op_attention_segments: q / o (rows, H, 128), kc / vc (n_slots, H_kv, max_tokens, 128)')
+    for t in (q, kc, vc, o):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError('op_attention_segments: contiguous bf16 tensors')
+    if Sq is None:
+        Sq = max(s[1] for s in segs)
+    for row0, S, pos0, slot in segs:
+        if not (0 <= row0 and 0 < S <= Sq and row0 + S <= rows and 0 <= pos0 and pos0 + S <= max_tokens and 0 <= slot < n_slots):
+            raise ValueError(f'op_attention_segments: segment {(row0, S, pos0, slot)} outside q / o ({rows} rows), the cache ({n_slots} x {max_tokens}) or Sq = {Sq}')
+    d_seg = torch.tensor([int(x) for s in segs for x in s], dtype=torch.int32).to(q.device)
+    B.check(B.lib.cr_op_attention_segments(_p(q), _p(kc), _p(vc), _p(o), _p(d_seg), len(segs), int(Sq), H, H // n_kv, max_tokens, float(s_div), _stream()),
+            'cr_op_attention_segments')
+    return o
+
+
 def op_decode_swizzle(which, W):
     """cr_op_decode_swizzle: the decode layout of a [N, K] weight for op_decode_gemm's `which` (1 KiB per 16-row tile and 32-deep k-step)."""
     N, K = W.shape

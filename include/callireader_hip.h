@@ -217,7 +217,13 @@ int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream);
  * for ONE sequence `seq`, appended at its current length; then the first greedy pick of
  * transformers 4.45.2 GenerationMixin._sample (RepetitionPenaltyLogitsProcessor over the ids generated so far,
  * argmax with first-max-wins), appended to the sequence's generated ids.
- * embeds [S,4096]; last_logits [vocab] fp32 = raw last-row logits before the penalty (may be NULL). */
+ * embeds [S,4096]; last_logits [vocab] fp32 = raw last-row logits before the penalty (may be NULL).
+ * Continued prefill: a sequence that already holds n tokens (an earlier prefill, decode steps) takes the S rows at positions n .. n + S - 1 (RoPE and
+ * the causal mask count from n; the rows attend over the n cached tokens and themselves) and holds n + S afterwards: prefill(A) then prefill(B) caches
+ * what one prefill of A followed by B caches.  EVERY prefill appends one pick to the generated ids (cr_kv_generated): after two prefills the sequence
+ * holds two ids, the first made at the end of A, the second at the end of B with the penalty applied over the first; the stop criteria, the sampling
+ * step and the scores count both.  A caller that wants one id per prompt calls cr_kv_reset and prefills the whole prompt, as the chat code does.
+ * An e4m3 cache refuses a sequence that already holds tokens (CR_ERR_ARG: it keeps no bf16 prefix for the prefill attention to read). */
 int cr_llm_prefill(cr_ctx* ctx, cr_kv* kv, int seq, const void* embeds, int S, float penalty, float* last_logits,
                    void* stream);
 /* The same for n sequences at once: embeds is the concatenation [sum(lens), 4096] of the prompts in seqs[] order
@@ -341,6 +347,14 @@ int cr_op_logprobs(const float* logits, int n, int vocab, const int64_t* ids, in
 int cr_op_attention(const void* q, const void* k, const void* v, void* o, const int64_t* strides12, int B, int H,
                     int Sq, int Sk, int head_dim, int kv_group, int causal, int q_pos0, float q_prescale, float s_div,
                     void* stream);
+/* The prefill attention's segment launch alone (test entry; cr_llm_prefill_batch fills its launch through the same function and drives the same kernel,
+ * flash_attn_kernel<128, causal, divisor>): q / o [rows][H][128] bf16, kc / vc [n_slots][H / kv_group][max_tokens][128] bf16 caches that already hold every
+ * segment's keys / values, seg = n x {first row, rows S, position of the first row pos0, cache slot} int32 (DEVICE array), Sq = the longest segment's rows
+ * (the grid).  Row r of a segment attends causally over cache positions 0 .. pos0 + r of its slot: scores bf16 -> / s_div -> bf16, fp32 softmax, bf16
+ * probabilities (modeling_internlm2.py:393-410).  Only rows first row .. first row + S - 1 of o are written and only positions < pos0 + S of the slot are
+ * read; the caller guarantees first row + S <= rows, pos0 + S <= max_tokens and slot < n_slots (the entry cannot see the device array).  Added within ABI v13. */
+int cr_op_attention_segments(const void* q, const void* kc, const void* vc, void* o, const int32_t* seg, int n, int Sq, int H, int kv_group, int max_tokens,
+                             float s_div, void* stream);
 
 /* Batched decode attention alone (test / tuning entry; cr_llm_decode drives the same launcher): row b = one new token of cache slot seqs[b], its H_kv x 4 query heads x 128 at
  * q + b * 4096 (InternLM2's GQA layout: the 4 query heads of KV head h at (4 h .. 4 h + 3) * 128), keys / values [n_slots][8][max_tokens][128] bf16, lens[slot] + 1 keys per row

@@ -435,3 +435,161 @@ def test_embed_splice(setup):
         eng.embed_splice(ids, vit[:1].cuda(), ref.cuda(), img_id=IMG, ref_id=REF)     # count mismatch
     with pytest.raises(CalliReaderError):
         eng.embed_splice(torch.zeros(1, 8, dtype=torch.long), vit.cuda(), None, img_id=IMG)   # no <IMG_CONTEXT>
+
+
+# ---- continued prefill: a sequence that already holds tokens takes more prompt rows (cr_llm_prefill "appended at its current length") ----
+CONTINUED = [(64, 1), (70, 130), (128, 128), (200, 300), (333, 31)]
+
+
+def two_prompts(a, b):
+    """A ‖ B as one prompt of a + b rows, and its two pieces."""
+    whole = prompt(a + b, 4000 + 7 * a + b)
+    return whole, whole[:, :a], whole[:, a:]
+
+
+@pytest.mark.parametrize('a,b', CONTINUED)
+def test_continued_prefill_against_the_oracle(setup, a, b):
+    """prefill(A) then prefill(B) on one sequence against the oracle run on A ‖ B: the second prefill's logits and six teacher-forced decode steps under
+    check_step's rule (ATOL / RTOL_L2 of decode_checks.py, a differing pick only as a measured near-tie).  The sequence's ids are [pick after A, pick
+    after B, ...]: step t of the oracle's stream is generated()[t + 1]."""
+    eng, sd = setup['eng'], setup['sd']
+    whole, A, B = two_prompts(a, b)
+    ref_ids, ref_logits = oracle_run(sd, whole, 7)
+    kv = eng.kv_alloc(2, 640)
+    eng.prefill(kv, 1, A.cuda())
+    assert kv.length(1) == a
+    lg = eng.prefill(kv, 1, B.cuda(), want_logits=True)
+    torch.cuda.synchronize()
+    assert kv.length(1) == a + b
+    diverged = []
+    for t in range(7):
+        got = lg.float().cpu().reshape(-1)
+        print(f'  ({a}, {b}) step {t}: rel-L2 {rel_l2(got, ref_logits[t]):.3e}, max |diff| {float((got - ref_logits[t]).abs().max()):.3e}')
+        if check_step(t, got, ref_logits[t], kv.generated(1)[t + 1], ref_ids):
+            diverged.append(t)
+        if t < 6:
+            lg = eng.decode(kv, [1], force_tokens=torch.tensor([ref_ids[t]]), want_logits=True)
+            torch.cuda.synchronize()
+    assert kv.length(1) == a + b + 6 and kv.length(0) == 0
+    if diverged:
+        print(f'({a}, {b}): greedy picks differed from the oracle at measured near-ties, steps {diverged}')
+    kv.free()
+
+
+@pytest.mark.parametrize('a,b', [(64, 1), (70, 130), (333, 31)])
+def test_continued_prefill_writes_the_single_prefills_layer0_rows(setup, a, b):
+    """Layer 0's K / V of a position depend only on the embedding row and its RoPE position, and LIN_PREFILL pins the linears row-independent: the
+    layer-0 cache rows of B's positions after prefill(A), prefill(B) are those of one prefill(A ‖ B), bit for bit -- any difference is a position or
+    row-mapping error.  (Deeper layers see other company in their attention waves and are not required to match in bits.)"""
+    eng = setup['eng']
+    whole, A, B = two_prompts(a, b)
+    kv = eng.kv_alloc(2, 512)
+    eng.prefill(kv, 0, whole.cuda())
+    eng.prefill(kv, 1, A.cuda())
+    eng.prefill(kv, 1, B.cuda())
+    assert kv.length(0) == kv.length(1) == a + b
+    for pos in range(a, a + b):
+        for which in (0, 1):
+            one, two = kv.read(0, 0, pos, which), kv.read(0, 1, pos, which)
+            assert torch.equal(one, two), (pos, which, float((one.float() - two.float()).abs().max()))
+    assert float(kv.read(0, 1, a + b - 1, 0).float().abs().max()) > 0
+    kv.free()
+
+
+def test_prefill_batch_with_mixed_first_positions_equals_single(setup):
+    """test_prefill_batch_equals_single with one sequence of the batch continuing (it holds 70 tokens) beside two fresh ones: every sequence's logits
+    and its following three decode ids are the bits of the same call made for that sequence alone."""
+    eng = setup['eng']
+    _, A, B = two_prompts(70, 130)
+    fresh = [prompt(300, 41), prompt(77, 42)]
+    single_logits, single_ids = [], []
+    for first, e in ((A, B), (None, fresh[0]), (None, fresh[1])):
+        kv = eng.kv_alloc(1, 512)
+        if first is not None:
+            eng.prefill(kv, 0, first.cuda())
+        single_logits.append(eng.prefill(kv, 0, e.cuda(), want_logits=True).clone())
+        for _ in range(3):
+            eng.decode(kv, [0])
+        single_ids.append(kv.generated(0))
+        kv.free()
+    kv = eng.kv_alloc(4, 512)
+    eng.prefill(kv, 2, A.cuda())
+    lg = eng.prefill_batch(kv, [0, 2, 3], [fresh[0].cuda(), B.cuda(), fresh[1].cuda()], want_logits=True)
+    torch.cuda.synchronize()
+    for row, i in ((1, 0), (0, 1), (2, 2)):
+        assert torch.equal(lg[row], single_logits[i]), (row, float((lg[row] - single_logits[i]).abs().max()))
+    for _ in range(3):
+        eng.decode(kv, [3, 0, 2])
+    assert [kv.generated(s) for s in (2, 0, 3)] == single_ids
+    assert len(single_ids[0]) == 5 and len(single_ids[1]) == 4                  # the continuing sequence holds one pick per prefill
+    assert [kv.length(s) for s in (2, 0, 3)] == [203, 303, 80] and kv.length(1) == 0
+    kv.free()
+
+
+def test_continued_prefill_final_layer_on_the_last_rows_only_gives_the_same_bits(setup):
+    """test_final_layer_on_the_last_rows_only_gives_the_same_bits for pages that continue a sequence: the last-rows segment starts at position
+    pos0 + w0.  A CR_PREFILL_LAST_ROWS=0 engine on the same weights gives the same logits, decode steps, ids and final-layer cache rows."""
+    import os
+    from callireader_amd.engine import Engine
+    eng = setup['eng']
+    os.environ['CR_PREFILL_LAST_ROWS'] = '0'
+    try:
+        ref = Engine(setup['dims'], max_pos=2048)
+    finally:
+        del os.environ['CR_PREFILL_LAST_ROWS']
+    ref.share_weights_from(eng)
+    pairs = [(70, 130), (200, 300), (333, 31), (64, 1)]
+    pieces = [two_prompts(a, b) for a, b in pairs]
+    outs = []
+    for e in (eng, ref):
+        kv = e.kv_alloc(len(pairs) + 1, 640)
+        seqs = list(range(1, len(pairs) + 1))
+        e.prefill_batch(kv, seqs, [p[1].cuda() for p in pieces], penalty=1.1)
+        lg = e.prefill_batch(kv, seqs, [p[2].cuda() for p in pieces], penalty=1.1, want_logits=True).clone()
+        kv1 = e.kv_alloc(1, 640)
+        e.prefill(kv1, 0, pieces[1][1].cuda(), penalty=1.1)
+        alone = e.prefill(kv1, 0, pieces[1][2].cuda(), penalty=1.1, want_logits=True).clone()
+        kv1.free()
+        steps = [e.decode(kv, seqs, penalty=1.1, want_logits=True).clone() for _ in range(3)]
+        torch.cuda.synchronize()
+        cache = [kv.read(1, i + 1, a + b - 1, which) for i, (a, b) in enumerate(pairs) for which in (0, 1)]
+        outs.append((lg, alone, steps, [kv.generated(s) for s in seqs], cache))
+        kv.free()
+    x, y = outs
+    assert torch.equal(x[0], y[0]), float((x[0] - y[0]).abs().max())
+    assert torch.equal(x[1], y[1]) and torch.equal(x[0][1], x[1])
+    for p, q in zip(x[2] + x[4], y[2] + y[4]):
+        assert torch.equal(p, q)
+    assert x[3] == y[3] and all(len(g) == 5 for g in x[3])
+    ref.close()
+
+
+def test_every_prefill_appends_one_pick(setup):
+    """What a sequence's generated ids hold across two prefills (include/callireader_hip.h, cr_llm_prefill): each prefill appends one pick, the second
+    made with the penalty over the first; the stop criteria count both; the decode that follows feeds the second."""
+    from oracle.generate import apply_repetition_penalty
+    eng = setup['eng']
+    _, A, B = two_prompts(70, 130)
+    kv = eng.kv_alloc(1, 256)
+    la = eng.prefill(kv, 0, A.cuda(), penalty=1.5, want_logits=True).clone()
+    first = kv.generated(0)
+    assert len(first) == 1 and first[0] == int(torch.argmax(la))
+    kv.set_stop(0, max_new=2)
+    lb = eng.prefill(kv, 0, B.cuda(), penalty=1.5, want_logits=True).clone()
+    both = kv.generated(0)
+    assert len(both) == 2 and both[0] == first[0]
+    assert both[1] == int(torch.argmax(apply_repetition_penalty(lb.float().cpu().reshape(-1), first, 1.5)))
+    out = torch.zeros(1 + 2 * 1, dtype=torch.int32).pin_memory()
+    kv.poll_finished(out)
+    torch.cuda.synchronize()
+    assert out.tolist() == [1, 0, 2]                                  # pushed once, sequence 0, stop count 2: the second prefill's pick reached max_new
+    eng.decode(kv, [0], penalty=1.5)
+    fed = kv.generated(0)
+    assert len(fed) == 3 and fed[:2] == both and kv.length(0) == 201
+    # the same ids as a forced decode of the second pick gives: the decode fed generated()[1]
+    kv.reset(0)
+    eng.prefill(kv, 0, A.cuda(), penalty=1.5)
+    eng.prefill(kv, 0, B.cuda(), penalty=1.5)
+    eng.decode(kv, [0], penalty=1.5, force_tokens=torch.tensor([both[1]]))
+    assert kv.generated(0) == fed
+    kv.free()

@@ -11,6 +11,8 @@ import math
 import pytest
 import torch
 
+from attn_ref import attn_ref as _attn_ref      # shared with test_gpu_prefill_attention.py
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1.6e-2
@@ -486,21 +488,6 @@ def test_rmsnorm(E):
     xf = x.float()
     h = rb(xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-5))
     torch.testing.assert_close(out.float(), rb(w.float() * h), rtol=RTOL, atol=1e-2)
-
-
-def _attn_ref(q, k, v, causal, q_pos0, prescale, s_div):
-    """q (B,H,Sq,D), k/v (B,H,Sk,D) float tensors holding bf16 values; reference rounding points."""
-    if prescale != 1.0:
-        q = rb(q * prescale)
-    s = rb(q @ k.transpose(-1, -2))
-    if s_div != 1.0:
-        s = rb(s / s_div)
-    if causal:
-        Sq, Sk = s.shape[-2:]
-        qpos = q_pos0 + torch.arange(Sq, device=s.device)[:, None]
-        s = s.masked_fill(torch.arange(Sk, device=s.device)[None, :] > qpos, float('-inf'))
-    p = rb(torch.softmax(s, dim=-1))
-    return rb(p @ v)
 
 
 def test_attention_vit_shape(E):
