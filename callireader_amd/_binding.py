@@ -60,6 +60,9 @@ SIGNATURES = {
     'cr_kv_set_sampling': (i32, [vp, i32, f32, i32, f32, C.c_uint64, vp]),
     'cr_kv_set_logprobs': (i32, [vp, i32, i32, vp]),
     'cr_kv_logprobs': (i32, [vp, i32, vp, vp, vp, i32, vp]),
+    'cr_kv_set_beam': (i32, [vp, i32, i32, f32, i32, i32, i32, vp]),
+    'cr_kv_beam_result': (i32, [vp, i32, C.POINTER(i64), i32, C.POINTER(f32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]),
+    'cr_kv_beam_reorder': (i32, [vp, i32, i32, C.POINTER(C.c_int32), i32, vp]),
     'cr_llm_prefill': (i32, [vp, vp, i32, vp, i32, f32, vp, vp]),
     'cr_llm_prefill_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), f32, vp, vp]),
     'cr_llm_hidden_probe': (i32, [vp, vp, i32, i32]),
@@ -83,6 +86,7 @@ SIGNATURES = {
     'cr_op_decode_attention_scratch_floats': (i64, [i32, i32]),
     'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'cr_op_logprobs': (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
+    'cr_op_beam_step': (i32, [vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp]),
     'cr_op_decode_attention': (i32, [i32, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
     'cr_op_decode_attention_e4m3': (i32, [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
 }

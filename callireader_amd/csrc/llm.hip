@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "attention.hpp"
+#include "beam.hpp"
 #include "ctx.hpp"
 #include "decode.hpp"
 #include "misc.hpp"
@@ -51,6 +52,13 @@ struct cr_kv {
     int32_t *d_lpn = nullptr, *d_lpdone = nullptr, *d_top_id = nullptr;
     float *d_lp = nullptr, *d_top_lp = nullptr;
     std::vector<char> scored;
+    // beam groups (cr_kv_set_beam; beam.hip), allocated by the first call: d_beam BeamState[n] (a group's state at its first sequence), d_bgrp int32[n] = first
+    // sequence of the sequence's group (< 0: none), d_bfin [n][gen_cap] ids of the finished slots.  `bgrp` / `bnum` mirror the group and its size on the host:
+    // a launch without a group launches nothing new
+    BeamState* d_beam = nullptr;
+    int32_t* d_bgrp = nullptr;
+    int64_t* d_bfin = nullptr;
+    std::vector<int> bgrp, bnum;
     std::vector<int> len, ngen;
 };
 
@@ -224,11 +232,13 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
 __global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty,
                                                     int seq0, const int32_t* __restrict__ seqs, int64_t* __restrict__ gen,
                                                     int32_t* __restrict__ ngen, int32_t* __restrict__ lens, int gen_cap, int len_add,
-                                                    int32_t* __restrict__ stop, int n_seqs, const float* __restrict__ orig) {
+                                                    int32_t* __restrict__ stop, int n_seqs, const float* __restrict__ orig,
+                                                    const int32_t* __restrict__ bgrp) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     const int row = blockIdx.x, tid = threadIdx.x;
     const int seq = seqs ? seqs[row] : seq0;
+    if (bgrp && bgrp[seq] >= 0) return;                       // a beam row: beam.hip picks for it
     float* lg = logits + (int64_t)row * ld;
     const int ng = ngen[seq];
     int64_t* g = gen + (int64_t)seq * gen_cap;
@@ -437,15 +447,18 @@ template <class Bufs> int ws_carve(cr_ctx* c, const char* who, Bufs& b) {
 struct HeadBufs {
     int n, V;
     bool scored, deep;      // a row of the launch has token scores on / a history of more than 4096 ids under a penalty
+    bool beam;              // a row of the launch belongs to a beam group: beam.hip's candidate scratch
     bf16* hl;               // the normalised rows
     float* lg;              // their logits [n][V]
     void* score;            // scored: logprobs.hip's scratch
     float* lg0;             // deep: the rows before the penalty, for the pick
+    char* cand;             // beam: the rows' candidates
     void carve(Arena& ar) {
         hl = ar.take<bf16>((size_t)n * D);
         lg = ar.take<float>((size_t)n * V);
         score = scored ? ar.take<char>(logprobs_scratch_bytes(n, V)) : nullptr;
         lg0 = deep ? ar.take<float>((size_t)n * V) : nullptr;
+        cand = beam ? ar.take<char>(beam_scratch_bytes(n)) : nullptr;
     }
 };
 
@@ -479,9 +492,9 @@ struct PrefillBufs {
     PrefillRows rows;
     HeadBufs head;
 
-    PrefillBufs(cr_ctx* c, const cr_kv* kv, int M, int n_pages, int max_S, bool scored, bool deep)
+    PrefillBufs(cr_ctx* c, const cr_kv* kv, int M, int n_pages, int max_S, bool scored, bool deep, bool beam)
         : M(M), n_pages(n_pages), max_S(max_S), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), any8(c->fp8_mfma && M >= 256),
-          last_rows(c->prefill_last_rows && !any8 && !c->probe_dst), head{n_pages, c->d.vocab, scored, deep} {}
+          last_rows(c->prefill_last_rows && !any8 && !c->probe_dst), head{n_pages, c->d.vocab, scored, deep, beam} {}
 
     void carve(Arena& ar) {
         x = ar.take<bf16>((size_t)M * D);
@@ -583,11 +596,11 @@ struct DecodeBufs {
     float *part, *pbuf;      // the attention splits' partials; the K-slices of one GEMM ([slices][M][N] fp32, the largest of the three)
     HeadBufs head;
 
-    DecodeBufs(cr_ctx* c, const cr_kv* kv, int M, int nsplit, bool scored, bool deep)
+    DecodeBufs(cr_ctx* c, const cr_kv* kv, int M, int nsplit, bool scored, bool deep, bool beam)
         : M(M), nsplit(nsplit), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), s_qkv(gemm_partial_splits(QKV, D)),
           s_o(gemm_partial_splits(D, D)), s_2(gemm_partial_splits(D, ff)), sliced(M <= 64 && s_qkv > 0 && s_o > 0 && s_2 > 0 && !c->no_sliced_decode),
           fused(sliced && c->fused_decode && !c->fp8_decode && !kv8 && decode_fused_supported(M, ff) && s_qkv == DEC_SLICES_WQKV && s_o == DEC_SLICES_WO &&
-                s_2 == DEC_SLICES_W2), head{M, c->d.vocab, scored, deep} {}
+                s_2 == DEC_SLICES_W2), head{M, c->d.vocab, scored, deep, beam} {}
 
     void carve(Arena& ar) {
         x = ar.take<bf16>((size_t)M * D);
@@ -854,6 +867,28 @@ static bool long_history(const cr_kv* kv, const int32_t* seqs, int n, float pena
     return false;
 }
 
+// rows of the launch that belong to a beam group
+static int beam_row_count(const cr_kv* kv, const int32_t* seqs, int n) {
+    if (!kv->d_beam) return 0;
+    int k = 0;
+    for (int i = 0; i < n; i++) if (kv->bgrp[seqs[i]] >= 0) k++;
+    return k;
+}
+
+// The beam step of the launch's groups, after the picks of its other rows: candidates and select on the logits rows (first_only: a prefill, which holds a
+// group's first sequence only), and in a decode step the re-order behind them (the prefill's follows its set_len_kernel)
+static BeamLaunch beam_launch(cr_kv* kv, const HeadBufs& h, const int32_t* d_seqs, float penalty, int len_add, int first_only) {
+    BeamLaunch p{};
+    p.logits = h.lg; p.ld = h.V; p.vocab = h.V; p.penalty = penalty; p.rows = h.n; p.seqs = d_seqs; p.grp = kv->d_bgrp; p.state = kv->d_beam;
+    p.gen = kv->d_gen; p.ngen = kv->d_ngen; p.gen_cap = kv->gen_cap; p.lens = kv->d_len; p.len_add = len_add; p.orig = h.lg0;
+    p.cand_v = (float*)h.cand; p.cand_i = (int32_t*)(h.cand + (size_t)h.n * 2 * BEAM_MAX * 4); p.fin_ids = kv->d_bfin; p.stop = kv->d_stop; p.n_seqs = kv->n_seqs;
+    p.first_only = first_only;
+    return p;
+}
+static BeamCache beam_cache(const cr_kv* kv) {
+    return {kv->k, kv->v, (int64_t)kv->n_seqs * 8 * kv->max_tokens * 128, kv->layers, kv->max_tokens};
+}
+
 static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
     if (!kv->d_lpn) return false;
     for (int i = 0; i < n; i++) if (kv->scored[seqs[i]]) return true;
@@ -862,19 +897,22 @@ static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
 
 // What follows the LM head in a prefill and in a decode step: the logits out, then the pick (greedy or sampled) appends every row's id and adds len_add
 // to its cached length, then the scores of the rows the pick has just chosen from (h.lg: the penalised rows it left) go into the sequences' slots
-static int pick_rows(cr_kv* kv, const HeadBufs& h, const int32_t* seqs, const int32_t* d_seqs, float penalty, int len_add, float* out, hipStream_t st) {
+static int pick_rows(cr_kv* kv, const HeadBufs& h, const int32_t* seqs, const int32_t* d_seqs, float penalty, int len_add, float* out, hipStream_t st, bool prefill) {
     const int n = h.n, V = h.V;
     if (out) CR_HIP(hipMemcpyAsync(out, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
     if (h.lg0) CR_HIP(hipMemcpyAsync(h.lg0, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-    if (any_sampled(kv, seqs, n))
+    const int32_t* bgrp = h.beam ? kv->d_bgrp : nullptr;      // beam rows are skipped by the picks and taken by beam_rows below
+    if (beam_row_count(kv, seqs, n) == n) {}                 // nothing but beams: no pick at all
+    else if (any_sampled(kv, seqs, n))
         CR_TRY(launch_sample(h.lg, V, V, penalty, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
-                             nullptr, 1, kv->d_len, len_add, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, h.lg0));
+                             nullptr, 1, kv->d_len, len_add, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, h.lg0, bgrp));
     else
         hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, h.lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
-                           kv->d_len, kv->gen_cap, len_add, kv->d_stop, kv->n_seqs, h.lg0);
+                           kv->d_len, kv->gen_cap, len_add, kv->d_stop, kv->n_seqs, h.lg0, bgrp);
     if (h.scored)
         CR_TRY(launch_logprobs(h.lg, V, V, n, d_seqs, kv->d_lpn, 0, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_lpdone, h.score, kv->d_lp, kv->d_top_id,
                                kv->d_top_lp, st));
+    if (h.beam) CR_TRY(launch_beam_step(beam_launch(kv, h, d_seqs, penalty, len_add, prefill ? 1 : 0), st));
     return CR_OK;
 }
 
@@ -1030,6 +1068,7 @@ int cr_kv_alloc_ex(cr_ctx* c, int n_seqs, int max_tokens, int format, cr_kv** ou
     CR_HIP(hipMemset(kv->d_samp, 0, (size_t)n_seqs * 24));                           // greedy
     kv->sampled.assign(n_seqs, 0);
     kv->scored.assign(n_seqs, 0);
+    kv->bgrp.assign(n_seqs, -1); kv->bnum.assign(n_seqs, 0);
     kv->len.assign(n_seqs, 0); kv->ngen.assign(n_seqs, 0);
     *out = kv;
     return CR_OK;
@@ -1053,6 +1092,9 @@ int cr_kv_free(cr_kv* kv) {
     if (kv->d_lp) hipFree(kv->d_lp);
     if (kv->d_top_id) hipFree(kv->d_top_id);
     if (kv->d_top_lp) hipFree(kv->d_top_lp);
+    if (kv->d_beam) hipFree(kv->d_beam);
+    if (kv->d_bgrp) hipFree(kv->d_bgrp);
+    if (kv->d_bfin) hipFree(kv->d_bfin);
     delete kv;
     return CR_OK;
 }
@@ -1079,6 +1121,16 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
         CR_HIP(hipMemsetAsync(kv->d_lpdone + s0, 0, (size_t)n * 4, st));
     }
     for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; }
+    if (kv->d_beam)                                                                     // a beam group goes as a whole with any of its sequences
+        for (int s = s0; s < s0 + n; s++) {
+            const int f = kv->bgrp[s];
+            if (f < 0) continue;
+            const int B = kv->bnum[f];
+            CR_HIP(hipMemsetAsync(kv->d_bgrp + f, 0xff, (size_t)B * 4, st));
+            CR_HIP(hipMemsetAsync(kv->d_stop + 1 + N + f, 0, 4, st));                   // the group's stop record sits at its first sequence
+            for (int j = 0; j < B; j++) kv->bgrp[f + j] = -1;
+            kv->bnum[f] = 0;
+        }
     return CR_OK;
 }
 
@@ -1099,6 +1151,7 @@ int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float t
         return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: temperature %g, top_k %d, top_p %g (want a finite temperature >= 0, top_k >= 0, 0 <= top_p <= 1)",
                        temperature, top_k, top_p);
     if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: bad sequence");
+    if (temperature > 0.f && kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: sequence %d belongs to a beam group (no beam sampling)", seq);
     CR_HIP(hipSetDevice(kv->ctx->device));
     hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed, seq,
                        temperature, top_k, top_p, seed);
@@ -1110,6 +1163,7 @@ int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float t
 int cr_kv_set_logprobs(cr_kv* kv, int seq, int top_n, void* stream) {
     if (top_n < 0 || top_n > LOGPROBS_MAX_TOP) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: top_n %d (want 0 = off, or 1..%d)", top_n, LOGPROBS_MAX_TOP);
     if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: bad sequence");
+    if (top_n > 0 && kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: sequence %d belongs to a beam group (no token scores with beams)", seq);
     if (top_n > 0 && kv->ngen[seq] != 0)
         return cr_fail(CR_ERR_STATE, "cr_kv_set_logprobs: sequence %d has generated %d ids already (switch scores on after cr_kv_reset and before the prefill)",
                        seq, kv->ngen[seq]);
@@ -1151,6 +1205,98 @@ int cr_kv_logprobs(cr_kv* kv, int seq, float* lp, int32_t* top_ids, float* top_l
     }
     CR_HIP(hipStreamSynchronize(st));
     return n;
+}
+
+// The beam blocks of a cache, allocated by the first call that needs them (that call also synchronises `st`: in place before a call on any other stream)
+static int beam_alloc(cr_kv* kv, hipStream_t st) {
+    if (!kv->d_beam) {
+        const size_t N = kv->n_seqs;
+        if (hipMalloc((void**)&kv->d_beam, N * sizeof(BeamState)) != hipSuccess || hipMalloc((void**)&kv->d_bgrp, N * 4) != hipSuccess ||
+            hipMalloc((void**)&kv->d_bfin, N * kv->gen_cap * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            if (kv->d_beam) hipFree(kv->d_beam);
+            if (kv->d_bgrp) hipFree(kv->d_bgrp);
+            if (kv->d_bfin) hipFree(kv->d_bfin);
+            kv->d_beam = nullptr; kv->d_bgrp = nullptr; kv->d_bfin = nullptr;
+            return cr_fail(CR_ERR_NOMEM, "beam search: %zu bytes of beam state", N * (sizeof(BeamState) + 4 + (size_t)kv->gen_cap * 8));
+        }
+        CR_HIP(hipMemsetAsync(kv->d_beam, 0, N * sizeof(BeamState), st));
+        CR_HIP(hipMemsetAsync(kv->d_bgrp, 0xff, N * 4, st));
+        CR_HIP(hipStreamSynchronize(st));                                               // once per cache: in place before a call on any other stream
+    }
+    return CR_OK;
+}
+
+int cr_kv_set_beam(cr_kv* kv, int first_seq, int num_beams, float length_penalty, int early_stopping, int eos_id, int max_new, void* stream) {
+    if (num_beams < 2 || num_beams > BEAM_MAX) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: num_beams %d (want 2..%d)", num_beams, BEAM_MAX);
+    if (early_stopping < 0 || early_stopping > 2 || !(length_penalty >= -3.402823466e38f && length_penalty <= 3.402823466e38f))
+        return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: early_stopping %d (0 False, 1 True, 2 'never') / length_penalty %g (finite)", early_stopping, length_penalty);
+    if (!kv || first_seq < 0 || first_seq + num_beams > kv->n_seqs)
+        return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: a group of %d from sequence %d runs past the cache's sequences", num_beams, first_seq);
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: beam search needs a bf16 cache (the re-order does not move e4m3 rows and scales)");
+    if (eos_id >= kv->ctx->d.vocab) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: EOS id %d outside the vocabulary", eos_id);
+    if (kv->ctx->d.vocab < 2 * BEAM_MAX) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: vocabulary of %d ids", kv->ctx->d.vocab);
+    if (max_new < 1 || max_new > kv->max_tokens) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: max_new %d (want 1..max_tokens = %d)", max_new, kv->max_tokens);
+    for (int j = 0; j < num_beams; j++) {
+        const int s = first_seq + j;
+        if (kv->sampled[s] || kv->scored[s]) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: sequence %d samples or records token scores", s);
+        if (kv->bgrp[s] >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: sequence %d already belongs to the group of %d (cr_kv_reset first)", s, kv->bgrp[s]);
+        if (kv->len[s] != 0 || kv->ngen[s] != 0) return cr_fail(CR_ERR_STATE, "cr_kv_set_beam: sequence %d holds tokens (call after cr_kv_reset, before the prefill)", s);
+    }
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    CR_TRY(beam_alloc(kv, st));
+    CR_TRY(launch_set_beam(kv->d_beam, kv->d_bgrp, first_seq, num_beams, length_penalty, early_stopping, eos_id < 0 ? -1 : eos_id, max_new, st));
+    for (int j = 0; j < num_beams; j++) kv->bgrp[first_seq + j] = first_seq;
+    kv->bnum[first_seq] = num_beams;
+    return CR_OK;
+}
+
+int cr_kv_beam_result(cr_kv* kv, int first_seq, int64_t* out_host, int max, float* score, int32_t* length, int32_t* done, void* stream) {
+    if (!kv || !out_host || !score || !length || !done || first_seq < 0 || first_seq >= kv->n_seqs || max < 0) return cr_fail(CR_ERR_ARG, "cr_kv_beam_result: bad argument");
+    if (!kv->d_beam || kv->bgrp[first_seq] != first_seq) return cr_fail(CR_ERR_STATE, "cr_kv_beam_result: sequence %d is not the first of a beam group", first_seq);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    BeamState s;
+    CR_HIP(hipMemcpyAsync(&s, kv->d_beam + first_seq, sizeof(s), hipMemcpyDeviceToHost, st));
+    CR_HIP(hipStreamSynchronize(st));
+    *done = s.done;
+    *score = s.n_fin > 0 ? s.fin_score[0] : -1.0e9f;
+    *length = s.n_fin > 0 ? s.fin_len[0] : 0;
+    const int n = *length < max ? *length : max;
+    if (n > 0) {
+        CR_HIP(hipMemcpyAsync(out_host, kv->d_bfin + (size_t)(first_seq + s.fin_phys[0]) * kv->gen_cap, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        CR_HIP(hipStreamSynchronize(st));
+    }
+    return n;
+}
+
+int cr_kv_beam_reorder(cr_kv* kv, int first_seq, int num_beams, const int32_t* src_host, int from, void* stream) {
+    if (num_beams < 2 || num_beams > BEAM_MAX) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: num_beams %d (want 2..%d)", num_beams, BEAM_MAX);
+    if (!kv || !src_host || first_seq < 0 || first_seq + num_beams > kv->n_seqs || from < 0) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: bad argument");
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: the re-order moves bf16 rows only");
+    BeamState tmp{};
+    tmp.B = num_beams; tmp.prompt = from;
+    for (int j = 0; j < BEAM_MAX; j++) {
+        tmp.next_src[j] = j < num_beams ? src_host[j] : j;
+        if (tmp.next_src[j] < 0 || (j < num_beams && tmp.next_src[j] >= num_beams)) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: source %d of beam %d", tmp.next_src[j], j);
+    }
+    for (int j = 0; j < num_beams; j++) {
+        if (kv->bgrp[first_seq + j] >= 0)
+            return cr_fail(CR_ERR_STATE, "cr_kv_beam_reorder: sequence %d belongs to a live beam group (the entry is for plain sequences: it would overwrite the group's state)", first_seq + j);
+        if (kv->len[first_seq + j] != kv->len[first_seq] || kv->ngen[first_seq + j] != kv->ngen[first_seq])
+            return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: sequences %d and %d hold different counts of tokens or ids", first_seq, first_seq + j);
+    }
+    if (from > kv->len[first_seq]) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: from %d past the %d cached tokens", from, kv->len[first_seq]);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    CR_TRY(beam_alloc(kv, st));
+    // the slot of a sequence that is in no group is free: cr_kv_set_beam initialises it whole (pageable source: staged before the call returns)
+    CR_HIP(hipMemcpyAsync(kv->d_beam + first_seq, &tmp, sizeof(tmp), hipMemcpyHostToDevice, st));
+    BeamLaunch p{};
+    p.rows = 1; p.seqs = nullptr; p.grp = kv->d_bgrp; p.state = kv->d_beam; p.gen = kv->d_gen; p.ngen = kv->d_ngen; p.gen_cap = kv->gen_cap; p.lens = kv->d_len;
+    const int row = first_seq;                 // seqs NULL: a row is its sequence
+    return launch_beam_reorder(p, beam_cache(kv), &row, 1, kv->len[first_seq] - from, 0, st);
 }
 
 int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream) {
@@ -1208,16 +1354,20 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         if (kv->fmt == CR_KV_E4M3 && kv->len[s] != 0)
             return cr_fail(CR_ERR_ARG, "cr_llm_prefill: sequence %d of an e4m3 cache already holds %d tokens (the prefill attends in bf16 and an e4m3 cache "
                            "keeps no bf16 copy of a prefix: cr_kv_reset it first)", s, kv->len[s]);
+        if (kv->bgrp[s] >= 0 && (kv->bgrp[s] != s || kv->len[s] != 0 || kv->ngen[s] != 0))
+            return cr_fail(CR_ERR_ARG, "cr_llm_prefill: sequence %d belongs to the beam group of sequence %d: prefill the group's FIRST sequence, once, after "
+                           "cr_kv_reset and cr_kv_set_beam", s, kv->bgrp[s]);
         segs.push_back({s, M, lens[i], kv->len[s]});
         M += lens[i];
     }
+    const bool beams = beam_row_count(kv, seqs, n) > 0;
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const int V = c->d.vocab;
     const bool kv8 = kv->fmt == CR_KV_E4M3;
     int max_S = 0;
     for (const Segment& sg : segs) max_S = sg.S > max_S ? sg.S : max_S;
-    PrefillBufs b(c, kv, M, n, max_S, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty));
+    PrefillBufs b(c, kv, M, n, max_S, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty), beams);
     CR_TRY(ws_carve(c, "cr_llm_prefill_batch", b));
     {
         std::vector<int32_t> h(prefill_rows_ints(M, n, kv8));
@@ -1249,12 +1399,19 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     for (int i = 0; i < n; i++)
         CR_TRY(rms(b.x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, b.head.hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
     CR_TRY(linear(c, EPI_F32, b.head.hl, head, LIN_LOADED, b.head.lg, n, st));
-    CR_TRY(pick_rows(kv, b.head, seqs, c->d_seqs, penalty, 0, last_logits, st));
+    CR_TRY(pick_rows(kv, b.head, seqs, c->d_seqs, penalty, 0, last_logits, st, true));
     hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, b.rows.seg, n, kv->d_len);
+    if (beams) {    // the fan-out: the prompt's cache rows, the first id and the length go from a group's first sequence to its others
+        std::vector<int> firsts;
+        for (int i = 0; i < n; i++) if (kv->bgrp[seqs[i]] == seqs[i]) firsts.push_back(i);
+        CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, c->d_seqs, penalty, 0, 1), beam_cache(kv), firsts.data(), (int)firsts.size(), max_S, 1, st));
+    }
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
         kv->len[sg.seq] += sg.S;
         if (kv->ngen[sg.seq] < kv->gen_cap) kv->ngen[sg.seq] += 1;
+        if (kv->bgrp[sg.seq] == sg.seq)
+            for (int j = 1; j < kv->bnum[sg.seq]; j++) { kv->len[sg.seq + j] = kv->len[sg.seq]; kv->ngen[sg.seq + j] = kv->ngen[sg.seq]; }
     }
     return CR_OK;
 }
@@ -1283,6 +1440,20 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         if (!force_tokens && kv->ngen[s] == 0) return cr_fail(CR_ERR_STATE, "cr_llm_decode: sequence %d has no generated id to feed", s);
         for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_decode: sequence %d listed twice", s);
     }
+    int beam_span = 0;                                        // > 0: the launch holds beam groups; the most cache positions their re-order moves
+    std::vector<int> beam_firsts;                             // the rows of the groups' first sequences
+    for (int i = 0; i < n && kv->d_beam; i++) {
+        const int f = kv->bgrp[seqs[i]];
+        if (f < 0) continue;
+        const int B = kv->bnum[f];
+        if (seqs[i] != f || i + B > n) return cr_fail(CR_ERR_ARG, "cr_llm_decode: a beam group decodes whole: its %d sequences from %d on, consecutive in seqs[]", B, f);
+        for (int j = 1; j < B; j++)
+            if (seqs[i + j] != f + j) return cr_fail(CR_ERR_ARG, "cr_llm_decode: a beam group decodes whole: its %d sequences from %d on, consecutive in seqs[]", B, f);
+        if (force_tokens) return cr_fail(CR_ERR_ARG, "cr_llm_decode: force_tokens with a beam group (sequence %d)", f);
+        beam_span = std::max(beam_span, kv->ngen[f] + 1);
+        beam_firsts.push_back(i);
+        i += B - 1;
+    }
     if (kv->fmt == CR_KV_E4M3 && !decode_attn8_available())
         return cr_fail(CR_ERR_ARG, "cr_llm_decode: an e4m3 cache is read by attention_decode.hip's e4m3 kernel only, and CR_DECODE_ATTN=0 selects the matrix-core "
                        "split kernel, which reads bf16 caches");
@@ -1292,7 +1463,7 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     int max_len = 0;
     for (int i = 0; i < n; i++) max_len = kv->len[seqs[i]] > max_len ? kv->len[seqs[i]] : max_len;
     const int nsplit = ((max_len + 1 + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
-    DecodeBufs b(c, kv, n, nsplit, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty));
+    DecodeBufs b(c, kv, n, nsplit, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty), beam_span > 0);
     CR_TRY(ws_carve(c, "cr_llm_decode", b));
     CR_TRY(stage_seqs(c, seqs, n, st, false));
     const int32_t* d_seqs = c->d_seqs;
@@ -1310,7 +1481,9 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         CR_TRY(rms(b.x, b.head.hl, nw, n, c->d.rms_eps, st));
         CR_TRY(linear(c, EPI_F32, b.head.hl, head, c->fp8_decode && n <= 64 && head.e4m3() ? LIN_E4M3 : LIN_DECODE, b.head.lg, n, st));
     }
-    CR_TRY(pick_rows(kv, b.head, seqs, d_seqs, penalty, 1, logits, st));
+    CR_TRY(pick_rows(kv, b.head, seqs, d_seqs, penalty, 1, logits, st, false));
+    if (beam_span > 0)
+        CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, d_seqs, penalty, 1, 0), beam_cache(kv), beam_firsts.data(), (int)beam_firsts.size(), beam_span, 1, st));
     CR_HIP(hipGetLastError());
     for (int i = 0; i < n; i++) {
         kv->len[seqs[i]] += 1;

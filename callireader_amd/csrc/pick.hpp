@@ -68,6 +68,7 @@ __device__ __forceinline__ void argmax_row(const float* __restrict__ lg, int voc
 // result).  step NULL: step = ngen[seq]; else step[row].  append != 0: the id is appended to the sequence's history with pick_kernel's stop check and
 // lens update (lens[seq] += len_add).  out_ids / out_kept (may be NULL): the id and the size of the kept set of each row (0 for a greedy row).
 // orig (may be NULL): a copy of the rows made before the launch, for histories of more than 4096 ids (apply_penalty).
+// bgrp (may be NULL): [n_seqs] beam group of every sequence; a row whose sequence has one (>= 0) is left untouched (beam.hip picks for it).
 int launch_sample(float* logits, int64_t ld, int vocab, float penalty, int rows, const int32_t* seqs, int64_t* gen, int32_t* ngen, int gen_cap,
                   const float* temp, const int32_t* topk, const float* topp, const uint64_t* seed, const int32_t* step, int append, int32_t* lens,
-                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig = nullptr);
+                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig = nullptr, const int32_t* bgrp = nullptr);

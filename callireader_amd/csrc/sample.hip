@@ -219,7 +219,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
                                                       const int32_t* __restrict__ topk_, const float* __restrict__ topp_, const uint64_t* __restrict__ seed_,
                                                       const int32_t* __restrict__ step_, int append, int32_t* __restrict__ lens, int len_add,
                                                       int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_kept,
-                                                      const float* __restrict__ orig) {
+                                                      const float* __restrict__ orig, const int32_t* __restrict__ bgrp) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     __shared__ SelShared s;
@@ -227,6 +227,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
     __shared__ int ri[16], rk[16];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int seq = seqs ? seqs[row] : row;
+    if (bgrp && bgrp[seq] >= 0) return;                     // a beam row: beam.hip picks for it
     float* lg = logits + (int64_t)row * ld;
     const int ng = ngen[seq] < gen_cap ? ngen[seq] : gen_cap;       // (a KV cache never holds more; cr_op_sample's hist_len may)
     int64_t* g = gen + (int64_t)seq * gen_cap;
@@ -322,9 +323,9 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
 
 int launch_sample(float* logits, int64_t ld, int vocab, float penalty, int rows, const int32_t* seqs, int64_t* gen, int32_t* ngen, int gen_cap,
                   const float* temp, const int32_t* topk, const float* topp, const uint64_t* seed, const int32_t* step, int append, int32_t* lens,
-                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig) {
+                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig, const int32_t* bgrp) {
     hipLaunchKernelGGL(sample_kernel, dim3(rows), dim3(1024), 0, st, logits, ld, vocab, penalty, seqs, gen, ngen, gen_cap, temp, topk, topp, seed,
-                       step, append, lens, len_add, stop, n_seqs, out_ids, out_kept, orig);
+                       step, append, lens, len_add, stop, n_seqs, out_ids, out_kept, orig, bgrp);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }

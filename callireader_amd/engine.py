@@ -328,6 +328,29 @@ class KVCache:
             B.check(n, 'cr_kv_generated')
         return list(buf[:n])
 
+    def set_beam(self, first_seq, num_beams, length_penalty=1.0, early_stopping=False, eos_id=None, max_new=1024):
+        """cr_kv_set_beam on the current stream: sequences first_seq .. first_seq + num_beams - 1 become one beam group (transformers' deterministic beam
+        search; early_stopping False | True | 'never').  Call after reset and before the prefill of `first_seq`, which is the group's step 0."""
+        from .sampling import early_code
+        es = early_code(early_stopping)
+        B.check(B.lib.cr_kv_set_beam(self._h, int(first_seq), int(num_beams), float(length_penalty), es, -1 if eos_id is None else int(eos_id), int(max_new),
+                                     _stream()), 'cr_kv_set_beam')
+
+    def beam_result(self, first_seq):
+        """cr_kv_beam_result: (ids of the group's best finished hypothesis so far, its score, done).  Synchronises the current stream."""
+        buf = (C.c_int64 * self.max_tokens)()
+        score, length, done = C.c_float(), C.c_int32(), C.c_int32()
+        n = B.lib.cr_kv_beam_result(self._h, int(first_seq), buf, self.max_tokens, C.byref(score), C.byref(length), C.byref(done), _stream())
+        if n < 0:
+            B.check(n, 'cr_kv_beam_result')
+        return list(buf[:n]), float(score.value), bool(done.value)
+
+    def beam_reorder(self, first_seq, src, start=0):
+        """cr_kv_beam_reorder (test entry, plain sequences): sequence first_seq + j takes the cache positions [start, length) and the id history of
+        first_seq + src[j], j < len(src)."""
+        B.check(B.lib.cr_kv_beam_reorder(self._h, int(first_seq), len(src), (C.c_int32 * len(src))(*[int(x) for x in src]), int(start), _stream()),
+                'cr_kv_beam_reorder')
+
     def set_logprobs(self, seq, top_n):
         """cr_kv_set_logprobs on the current stream: record the log-probability and the `top_n` (1..8) best alternatives of every id the sequence
         generates from now on; 0 switches the scores off (the default, what reset restores).  Call after reset(seq) and before the sequence's prefill."""
@@ -574,6 +597,21 @@ def op_sample(eng, logits, temperature, top_k, top_p, seed, step, history=None, 
     B.check(B.lib.cr_op_sample(eng._h, _p(lg), n, V, _p(hist), cap, _p(hl), float(penalty), _p(t), _p(k), _p(p), _p(sd), _p(st), _p(ids), _p(kept),
                                _stream()), 'cr_op_sample')
     return ids, kept
+
+
+BEAM_WORDS = 64          # four-byte words of a beam group's device state (include/callireader_hip.h, cr_op_beam_step)
+
+
+def op_beam_step(logits, history, hist_len, group, state, fin_ids, penalty=1.0):
+    """cr_op_beam_step: one beam-search step on given fp32 rows.  logits [n, V] float32 (overwritten with the penalised log-probabilities), history [n, cap]
+    int64 and hist_len [n] int32 (updated), group [n] int32 (first row of each row's group), state [n, 64] int32 (bit patterns; layout in the header),
+    fin_ids [n, cap] int64 -- all contiguous device tensors, modified in place.  Synchronises the current stream."""
+    n, V = logits.shape
+    for t, dt in ((logits, torch.float32), (history, torch.int64), (hist_len, torch.int32), (group, torch.int32), (state, torch.int32), (fin_ids, torch.int64)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt
+    assert history.shape[0] == n and fin_ids.shape == history.shape and state.shape == (n, BEAM_WORDS) and hist_len.numel() == n and group.numel() == n
+    B.check(B.lib.cr_op_beam_step(_p(logits), n, V, _p(history), history.shape[1], _p(hist_len), float(penalty), _p(group), _p(state), _p(fin_ids), _stream()),
+            'cr_op_beam_step')
 
 
 def op_logprobs(logits, ids, top_n=1):

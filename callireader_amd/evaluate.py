@@ -142,8 +142,15 @@ def test_full_page(parquet_path, save_json_path, model, tokenizer, detect_model,
     sums = [0.0, 0.0, 0.0, 0.0]
     count = 0
     step = max(batch_pages, 1)
+    beams = generation_config.get('num_beams', 1) or 1
+    if beams > 1 and batch_pages > 1:
+        step = max(1, min(batch_pages, 64) // beams)          # beam search: every page takes `beams` of the decode rows
     groups = [(images[i0:i0 + step], annotations[i0:i0 + step]) for i0 in range(0, len(images), step)]
-    if batch_pages > 1:
+    if beams > 1 and batch_pages > 1:
+        # the pipeline decodes one row per page: beams go batch after batch through chat_ocr_pages
+        answers = (model.chat_ocr_pages(tokenizer, detect_model, g[0], prompt, generation_config, use_p=use_p, hard_vq=hard_vq, drop_zero=drop_zero,
+                                        repetition_penalty=repetition_penalty) for g in groups)
+    elif batch_pages > 1:
         # two batches in flight: batch i decodes while batch i+1 goes through detection, tiling, the visual stage and the prefill
         answers = model.chat_ocr_stream(tokenizer, detect_model, (g[0] for g in groups), prompt, generation_config, use_p=use_p, hard_vq=hard_vq,
                                         drop_zero=drop_zero, repetition_penalty=repetition_penalty)
@@ -350,6 +357,9 @@ def build_parser():
     parser.add_argument('--compare_fp8', action='store_true', help='run every file twice -- bf16, then with --fp8_decode / --fp8_mfma (both when neither is given) and '
                                                                    '--fp8_kv when it is given -- and '
                                                                    'write full_page_<level>_fp8_vs_bf16.json: identical outputs, NED between them, F1 / NED deltas')
+    parser.add_argument('--num_beams', type=int, default=1, help='beam search with this many beams (2..8); 1: the greedy default')
+    parser.add_argument('--length_penalty', type=float, default=None, help='with --num_beams > 1 (default 1.0)')
+    parser.add_argument('--early_stopping', type=str, default=None, choices=('false', 'true', 'never'), help='with --num_beams > 1 (default false)')
     parser.add_argument('--allow_no_t2s', action='store_true', help='run without opencc (responses stay unconverted: scores not comparable with the reference\'s)')
     return parser
 
@@ -397,6 +407,8 @@ def main(argv=None):
         fp8(True)
     tokenizer = InternLM2Tokenizer.from_pretrained(args.model)
     generation_config = dict(num_beams=1, max_new_tokens=1024, do_sample=False)
+    from .inference import beam_config
+    generation_config.update(beam_config(args))
     detect_model = load_detector(args.params)
     common = (args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose)
     if args.type != 'full_page':

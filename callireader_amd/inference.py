@@ -118,7 +118,35 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
         print(f'User: {prompt}\nAssistant: {response}')
         responses[pic_path] = response
 
-    if continuous and batch_pages > 1:
+    beams = generation_config.get('num_beams', 1) or 1
+    if beams > 1 and batch_pages > 1:
+        # beam search: the pipelines decode one row per page, so the images go through chat_ocr_pages, as many pages per batch as fit the decode rows
+        # with `beams` rows each; a batch that fails as a whole runs page by page, like the other modes
+        boxes, ready = {}, []
+        for pic_path in paths:
+            try:
+                boxes[pic_path] = boxes_for(pic_path) if (use_p and detect_model is None) else None
+                ready.append(pic_path)
+            except Exception as e:
+                responses[pic_path] = e
+        per = max(1, min(batch_pages, DEFAULT_BATCH_PAGES) // beams)
+        for i in range(0, len(ready), per):
+            b = ready[i:i + per]
+            try:
+                res = model.chat_ocr_pages(tokenizer, detect_model, b, prompt, generation_config,
+                                           boxes_list=[boxes[p] for p in b] if (use_p and detect_model is None) else None, use_p=use_p, drop_zero=drop_zero,
+                                           hard_vq=hard_vq, repetition_penalty=repetition_penalty, errors='return', **skw)
+                for pic_path, r in zip(b, res):
+                    put(pic_path, r)
+            except NotImplementedError:
+                raise                                            # an option beams do not take (--scores): not a page's failure
+            except Exception as e:
+                print(f'[folder_rec] a batch failed as a whole ({e}); its {len(b)} pages run one by one')
+                for pic_path in b:
+                    put(pic_path, one(pic_path))
+        for pic_path in paths:
+            record(pic_path, responses[pic_path])
+    elif continuous and batch_pages > 1:
         boxes, ready = {}, []
         for pic_path in paths:
             try:
@@ -188,6 +216,18 @@ def scores_name(save_name):
     return save_name[:-len('json')].rstrip('.') + '.scores.json'
 
 
+def beam_config(args):
+    """The beam entries of generation_config from --num_beams / --length_penalty / --early_stopping; {} without --num_beams (the config stays as it was)."""
+    if args.num_beams == 1:
+        return {}
+    cfg = dict(num_beams=args.num_beams)
+    if args.length_penalty is not None:
+        cfg['length_penalty'] = args.length_penalty
+    if args.early_stopping is not None:
+        cfg['early_stopping'] = {'false': False, 'true': True, 'never': 'never'}[args.early_stopping]
+    return cfg
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description='args for inference task')
     parser.add_argument('--tgt', type=str, help='Recognition target')
@@ -214,6 +254,9 @@ def build_parser():
     parser.add_argument('--top_k', type=int, default=None, help='with --do_sample (default 50; 0: off)')
     parser.add_argument('--top_p', type=float, default=None, help='with --do_sample (default 1.0: off)')
     parser.add_argument('--seed', type=int, default=None, help='torch.manual_seed before the run: --do_sample output becomes reproducible')
+    parser.add_argument('--num_beams', type=int, default=1, help='beam search with this many beams (2..8; transformers\' deterministic beam search, on the device); 1: the greedy default')
+    parser.add_argument('--length_penalty', type=float, default=None, help='with --num_beams > 1: exponent of the hypothesis length a finished score is divided by (default 1.0)')
+    parser.add_argument('--early_stopping', type=str, default=None, choices=('false', 'true', 'never'), help="with --num_beams > 1: generation_config.early_stopping (default false)")
     parser.add_argument('--fp8_kv', action='store_true',
                         help='e4m3 KV cache for the decode (kv_cache_dtype="e4m3": 0.52x the cache bytes; off by default; a throughput option, not parity-preserving)')
     parser.add_argument('--scores', type=int, nargs='?', const=1, default=0, choices=range(0, 9), metavar='N',
@@ -247,6 +290,7 @@ def main(argv=None):
     if args.do_sample:
         generation_config['do_sample'] = True
         generation_config.update({k: getattr(args, k) for k in ('temperature', 'top_k', 'top_p') if getattr(args, k) is not None})
+    generation_config.update(beam_config(args))
     if args.seed is not None:
         torch.manual_seed(args.seed)
     detect_model = load_detector(args.params)

@@ -26,7 +26,7 @@ from .config import ModelDims, IMG_CONTEXT_TOKEN_ID, ALIGNED_TOKEN_ID, EOS_TOKEN
 from .conversation import get_conv_template
 from .engine import Engine
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
-from .sampling import base_seed, page_seeds, parse as sampling_parse, splitmix64
+from .sampling import base_seed, page_seeds, parse as sampling_parse, parse_beams, splitmix64
 from .scores import ResponseScores, TokenScores, generate_output, parse as scores_parse, per_page as scores_per_page
 
 
@@ -270,7 +270,17 @@ class InternVLChatModel:
 
     def _generate_kw(self, input_embeds, repetition_penalty, generate_kwargs):
         """_generate driven by transformers' keyword arguments: the new ids, or under return_dict_in_generate=True a scores.GenerateOutput."""
-        max_new, eos, sp = self._gen_args(generate_kwargs)
+        max_new, eos, sp = self._gen_args(generate_kwargs, allow_beams=True)
+        beams = parse_beams(generate_kwargs)
+        if beams is not None:                      # beam search: the page's beams decode as one batch (generate_pages)
+            ids, sc = self.generate_pages([input_embeds], max_new, eos, repetition_penalty, num_beams=beams.num_beams, length_penalty=beams.length_penalty,
+                                          early_stopping=beams.early_stopping)
+            seq = torch.tensor([ids[0]], dtype=torch.long, device=self.device)
+            if not generate_kwargs.get('return_dict_in_generate', False):
+                return seq
+            out = generate_output(seq)
+            out.sequences_scores = torch.tensor([sc[0]], dtype=torch.float32)
+            return out
         n = scores_parse(generate_kwargs)
         if not generate_kwargs.get('return_dict_in_generate', False):
             return self._generate(input_embeds, max_new, eos, repetition_penalty, sp)
@@ -279,8 +289,13 @@ class InternVLChatModel:
         return generate_output(*self._generate(input_embeds, max_new, eos, repetition_penalty, sp, logprobs=n))
 
     @staticmethod
-    def _gen_args(generate_kwargs):
-        """(max_new_tokens, eos_token_id, SamplingParams or None for greedy): transformers' defaults and validation (sampling.parse)."""
+    def _gen_args(generate_kwargs, allow_beams=False):
+        """(max_new_tokens, eos_token_id, SamplingParams or None for greedy): transformers' defaults and validation (sampling.parse).  These are the
+        arguments of the one-row-per-page loops: a caller that has no beam path (the pipelines, the sharded entry points, chat) gets NotImplementedError for
+        num_beams > 1; the callers that run beams (allow_beams) parse them with sampling.parse_beams."""
+        if not allow_beams and parse_beams(generate_kwargs) is not None:
+            raise NotImplementedError(f"num_beams={generate_kwargs.get('num_beams')}: this entry point decodes one row per page (num_beams=1); beam search runs "
+                                      'through generate / generate_ocr / generate_origin, chat_ocr, dynamic_chat, generate_pages and chat_ocr_pages')
         return generate_kwargs.get('max_new_tokens', 1024), generate_kwargs.get('eos_token_id', EOS_TOKEN_ID), sampling_parse(generate_kwargs)
 
     @staticmethod
@@ -383,6 +398,7 @@ class InternVLChatModel:
         model_inputs = tokenizer(query, return_tensors='pt')
         generation_config, _ = self._score_args(generation_config, return_scores)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
+        self._gen_args(generation_config)           # the plain chat keeps its num_beams=1 contract (beams: chat_ocr, dynamic_chat, generate_*)
         out = self.generate_origin(pixel_values=pixel_values, input_ids=model_inputs['input_ids'],
                                    attention_mask=model_inputs['attention_mask'], **generation_config)
         out, sc = self._with_scores(tokenizer, out)
@@ -539,8 +555,13 @@ class InternVLChatModel:
         return_scores (True, or the number of alternatives per token): returns (responses, scores) with one scores.ResponseScores per page (None for a
         page that failed)."""
         _, lpn = self._score_args(generation_config, return_scores)
+        beams = parse_beams(dict(generation_config, return_scores=return_scores))
         embeds, meta = self._ocr_embeds(tokenizer, detect_model, images, question, generation_config, boxes_list, use_p, drop_zero,
                                         hard_vq, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, errors=errors)
+        if beams is not None:                      # every page's beams in one decode batch; a page gets what its own chat_ocr call gives
+            outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, num_beams=beams.num_beams, length_penalty=beams.length_penalty,
+                                       early_stopping=beams.early_stopping)[0] if embeds else []
+            return self._answer(tokenizer, outs, meta, False)
         outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, sampling=meta['sampling'],
                                    seeds=self._ok_seeds(meta), logprobs=lpn) if embeds else []
         return self._answer(tokenizer, outs, meta, return_scores)
@@ -584,6 +605,8 @@ class InternVLChatModel:
         response of its own chat_ocr call.  stats (a dict) receives the host seconds per stage and, per batch, how long the compute stream
         sat between the previous batch's prefill and this batch's first kernel.  return_scores: every batch is yielded as (responses, scores), as
         chat_ocr_pages returns it."""
+        if parse_beams(generation_config) is not None:
+            raise NotImplementedError('chat_ocr_stream: beam search does not go through PagePipeline (use chat_ocr_pages)')
         _, lpn = self._score_args(generation_config, return_scores)
         pipe, pending = None, None
         sampled = sampling_parse(generation_config) is not None
@@ -691,6 +714,8 @@ class InternVLChatModel:
         yields that exception (chat_ocr_pages' semantics; when a group's visual stage fails as a whole, its pages are retried one by one).
         stats (a dict) receives the pipeline's counters.  return_scores (True, or the number of alternatives per token): yields
         (index, response, scores.ResponseScores), the scores None for a page that failed."""
+        if parse_beams(generation_config) is not None:
+            raise NotImplementedError('chat_ocr_continuous: beam search does not go through ContinuousPipeline (use chat_ocr_pages)')
         from .continuous import ContinuousPipeline
         _, lpn = self._score_args(generation_config, return_scores)
         images = list(images)
@@ -823,7 +848,7 @@ class InternVLChatModel:
         template = get_conv_template(self.template)
         generation_config = dict(generation_config)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
-        max_new, eos, sp = self._gen_args(generation_config)
+        max_new, eos, sp = self._gen_args(generation_config, allow_beams=True)      # (the pipelines that call this have refused beams on entry)
         meta = {'n': len(images), 'ok': [], 'failed': dict(batch.failed), 'max_new': max_new, 'eos': eos, 'template': template, 'sampling': sp}
         if not batch.ok:
             return [], meta
@@ -904,15 +929,23 @@ class InternVLChatModel:
         return PagePipeline(self, **kw)
 
     def generate_pages(self, embeds_list, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0,
-                       check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0):
+                       check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0, num_beams=1, length_penalty=1.0, early_stopping=False):
         """Prefill every page, then decode all unfinished pages as ONE batch per step: the 14.7 GB of LLM weights are
         streamed once per step for all pages.  Per page the ids equal the single-page greedy result.
         sampling: None (every page greedy), one sampling.SamplingParams for every page, or a list with one entry (or None: greedy) per page;
         seeds: one 64-bit seed per page (default page_seeds(P)).  A sampled page's ids depend only on its prompt, its parameters and its seed.
         logprobs: 0 (the return value is the list of id lists), an int n in 1..8 for every page, or one int per page.  When any is non-zero the
         return value is (ids, scores): scores[i] is the page's scores.TokenScores with its n alternatives per id, cut like its ids, or None for a
-        page with 0.  A page's scores, like its ids, do not depend on the batch it decodes in."""
+        page with 0.  A page's scores, like its ids, do not depend on the batch it decodes in.
+        num_beams > 1 (with length_penalty and early_stopping, validated as sampling.parse_beams does): beam search, every page's B beams as B rows of the one decode
+        batch (P * B <= 64).  The return value is then (ids, sequences_scores): per page the best finished hypothesis, EOS included, and its score.  No
+        sampling and no token scores with beams."""
         P = len(embeds_list)
+        beams = parse_beams(dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping))
+        if beams is not None:
+            if sampling is not None or (logprobs and any(scores_per_page(logprobs, P))):
+                raise NotImplementedError('generate_pages: beam search takes neither sampling nor token scores')
+            return self._generate_pages_beams(embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams)
         per_page = _per_page_sampling(sampling, seeds, P)
         lpn = scores_per_page(logprobs, P)
         if self._kv is None or self._kv.n_seqs < P:
@@ -950,6 +983,54 @@ class InternVLChatModel:
                     ids = ids[:ids.index(eos_token_id) + 1]
             outs.append(ids)
         return (outs, _read_scores(kv, lpn, outs)) if any(lpn) else outs
+
+
+    def _generate_pages_beams(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams):
+        """generate_pages with beam search: page i is the beam group of sequences beam_slots(i, B); the done flags are read every check_every steps,
+        where the greedy loop reads EOS."""
+        P, Bn = len(embeds_list), beams.num_beams
+        if P * Bn > 64:
+            raise ValueError(f'{P} pages x {Bn} beams = {P * Bn} decode rows: at most 64 (the batched decode kernels)')
+        if self._kv is None or self._kv.n_seqs < P * Bn:
+            if self._kv is not None:
+                self._kv.free()
+            self.max_pages = max(P * Bn, self.max_pages)
+            self._kv = self._kv_alloc(self.max_pages, self.max_tokens)
+        kv = self._kv
+        for e in embeds_list:
+            if e.shape[0] + max_new_tokens > self.max_tokens:
+                raise ValueError(f'prompt of {e.shape[0]} tokens + {max_new_tokens} new exceeds max_tokens={self.max_tokens}')
+        kv.reset()
+        for i in range(P):
+            kv.set_beam(beam_slots(i, Bn)[0], Bn, beams.length_penalty, beams.early_stopping, eos_token_id, max_new_tokens)
+        for i0 in range(0, P, prefill_batch):
+            idx = list(range(i0, min(P, i0 + prefill_batch)))
+            self.engine.prefill_batch(kv, [beam_slots(i, Bn)[0] for i in idx], [embeds_list[i] for i in idx], penalty=repetition_penalty)
+        live, res, n = list(range(P)), {}, 1
+
+        def collect():
+            for i in list(live):
+                ids, score, done = kv.beam_result(beam_slots(i, Bn)[0])
+                if done:
+                    res[i] = (ids, score)
+                    live.remove(i)
+        if max_new_tokens <= 1:
+            collect()
+        while n < max_new_tokens and live:
+            steps = min(check_every, max_new_tokens - n)
+            rows = [s for i in live for s in beam_slots(i, Bn)]
+            for _ in range(steps):
+                self.engine.decode(kv, rows, penalty=repetition_penalty)
+            n += steps
+            collect()
+        if live:
+            raise RuntimeError(f'beam groups of pages {live} are still running after {max_new_tokens} tokens')
+        return [res[i][0] for i in range(P)], [res[i][1] for i in range(P)]
+
+
+def beam_slots(page, num_beams):
+    """Cache sequences of page `page` when every page of a batch runs `num_beams` beams: consecutive, the group's first sequence first."""
+    return list(range(page * num_beams, (page + 1) * num_beams))
 
 
 class PagePipeline:

@@ -376,6 +376,8 @@ def sharded_generate(model, page_tiles, char_tiles, input_ids, *, img_id, ref_id
     cost: the stage-cost table of that default plan -- None: MI355X_COST, or MI355X_COST_FP8 when the engine's fp8 options are on (`default_cost`); 'measure': measured
     on this GPU once per model (`measure_cost`, ~2 s, rank 0's numbers on every rank); or a table of your own (other hardware).
     Returns {page: ids} for every page (gather_results) or for the pages this rank owns.  Per page the ids are the single-process ids."""
+    if generate_kw.get('num_beams', 1) not in (1, None):
+        raise NotImplementedError('sharded_generate: beam search is not implemented across GPUs (use generate_pages on one)')
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     n_pages = len(input_ids)
@@ -445,6 +447,8 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     if return_scores or dict(generation_config).get('return_dict_in_generate', False):
         raise NotImplementedError('chat_ocr_pages_sharded: token scores (return_scores=True) are not implemented across GPUs (a page\'s scores stay on the '
                                   'rank that decodes it); use chat_ocr_pages / chat_ocr_continuous on one GPU')
+    if dict(generation_config).get('num_beams', 1) not in (1, None):
+        raise NotImplementedError('chat_ocr_pages_sharded: beam search is not implemented across GPUs (use chat_ocr_pages on one)')
     if dict(generation_config).get('do_sample', False):
         raise NotImplementedError('chat_ocr_pages_sharded: do_sample=True is not implemented across GPUs yet (it needs the per-call seed broadcast '
                                   'to every rank); use chat_ocr_pages / chat_ocr_continuous on one GPU')

@@ -42,11 +42,71 @@ class SamplingParams:
             raise ValueError(f'`top_p` has to be a float >= 0 and <= 1, but is {p}')
 
 
+MAX_BEAMS = 8
+
+# beam knobs the device does not implement (name -> the value that means "off")
+BEAM_UNSUPPORTED = {'num_return_sequences': 1, 'num_beam_groups': 1, 'diversity_penalty': 0.0, 'constraints': None, 'force_words_ids': None,
+                    'penalty_alpha': None, 'low_memory': None, 'custom_generate': None}
+
+
+@dataclass(frozen=True)
+class BeamParams:
+    """num_beams > 1 as transformers' deterministic beam search takes it: length_penalty (exponent of the hypothesis length a finished score is divided
+    by), early_stopping False | True | 'never'."""
+    num_beams: int
+    length_penalty: float = 1.0
+    early_stopping: object = False
+
+    def __post_init__(self):
+        b, lp, es = self.num_beams, self.length_penalty, self.early_stopping
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 2:
+            raise ValueError(f'`num_beams` has to be an integer strictly greater than 1, but is {b!r}')
+        if b > MAX_BEAMS:
+            raise NotImplementedError(f'num_beams={b}: the device keeps at most {MAX_BEAMS} beams per page')
+        if isinstance(lp, bool) or not isinstance(lp, (int, float)) or not math.isfinite(lp):
+            raise ValueError(f'`length_penalty` has to be a finite float, but is {lp!r}')
+        if not (es is True or es is False or es == 'never'):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es!r}.")       # transformers' GenerationConfig.validate
+
+    @property
+    def early_code(self):
+        return early_code(self.early_stopping)
+
+
+def early_code(early_stopping):
+    """cr_kv_set_beam's early_stopping: 0 False, 1 True, 2 'never'."""
+    return 2 if early_stopping == 'never' else 1 if early_stopping else 0
+
+
+def parse_beams(kwargs):
+    """BeamParams for num_beams > 1, None for num_beams=1 (length_penalty and early_stopping are then ignored, as transformers does).
+    ValueError for a num_beams that is no integer >= 1; NotImplementedError for num_beams above 8, beam sampling (do_sample=True), more than one
+    returned sequence, group / diverse / constrained beams, and token scores together with beams."""
+    b = kwargs.get('num_beams', 1)
+    if b is None:
+        b = 1
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
+        raise ValueError(f'`num_beams` has to be a positive integer, but is {b!r}')
+    if b == 1:
+        return None
+    if kwargs.get('do_sample', False):
+        raise NotImplementedError(f'num_beams={b} with do_sample=True (beam sampling) is not implemented: beam search is deterministic here')
+    for k, off in BEAM_UNSUPPORTED.items():
+        v = kwargs.get(k, off)
+        if v is not None and v != off:
+            raise NotImplementedError(f'{k}={v!r} is not implemented with num_beams={b} (beam search returns its one best sequence; no group, diverse '
+                                      'or constrained beams)')
+    if kwargs.get('output_scores') or kwargs.get('return_scores') or kwargs.get('output_logits'):
+        raise NotImplementedError(f'token scores (output_scores / return_scores) are not implemented with num_beams={b}: '
+                                  'return_dict_in_generate=True gives sequences_scores')
+    lp, es = kwargs.get('length_penalty'), kwargs.get('early_stopping')
+    return BeamParams(int(b), 1.0 if lp is None else lp, False if es is None else es)
+
+
 def parse(kwargs):
-    """SamplingParams for do_sample=True, None for greedy (do_sample=False ignores temperature, top_k and top_p, as transformers does).
-    Raises NotImplementedError for num_beams > 1 and for any other sampling knob set to a non-default value."""
-    if kwargs.get('num_beams', 1) not in (1, None):
-        raise NotImplementedError('the CalliReader path has no beam search: num_beams=1')
+    """SamplingParams for do_sample=True, None for greedy or beam search (do_sample=False ignores temperature, top_k and top_p, as transformers does).
+    Raises what parse_beams raises for num_beams, and NotImplementedError for any other sampling knob set to a non-default value."""
+    parse_beams(kwargs)
     if not kwargs.get('do_sample', False):
         return None
     for k, off in UNSUPPORTED.items():

@@ -90,6 +90,7 @@ class GenerateOutput:
     top_ids: object
     top_logprobs: object
     scores: Optional[TokenScores] = None          # the same numbers as numpy arrays
+    sequences_scores: object = None               # beam search (num_beams > 1): [1] float32, the returned hypothesis' length-penalised score
 
     def __getitem__(self, k):
         return getattr(self, k)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_set_beam, cr_kv_beam_result, cr_kv_beam_reorder, cr_op_beam_step, cr_kv_reset also dissolves beam groups; cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -205,6 +205,38 @@ int cr_kv_set_logprobs(cr_kv* kv, int seq, int top_n, void* stream);
  * [max][8] int32, top_lp [max][8] fp32.  Returns the count (cr_kv_generated's), or < 0: CR_ERR_STATE for a sequence whose scores are off.
  * Synchronises `stream`.  Added within ABI v13. */
 int cr_kv_logprobs(cr_kv* kv, int seq, float* lp, int32_t* top_ids, float* top_lp, int max, void* stream);
+/* Beam search (csrc/beam.hip): the `num_beams` (2..8) consecutive sequences first_seq .. first_seq + num_beams - 1 become one beam group that runs the
+ * deterministic beam search of transformers 5.x GenerationMixin._beam_search (do_sample=False, one returned sequence, no group / diverse / constrained beams)
+ * as `generate(inputs_embeds=...)` drives it, entirely on the device.  With g = ids generated before a step, B = num_beams, K = 2 B, every step
+ *   1. lp = log_softmax(logits) in fp32 per running beam, then the repetition penalty over that beam's own generated ids ON lp (lp <= 0: a penalised entry
+ *      is lp * penalty) -- not the greedy pick's order (penalty on the raw logits);
+ *   2. acc = running score + lp; the K largest of the flattened [B x vocab] in descending order, an exact tie towards the lower flattened index b * vocab + id
+ *      (torch.topk leaves ties open).  Running scores start as [0, -1e9, ...]: step 0, the prefill's, takes all candidates from the one prompt row;
+ *   3. a candidate finishes when its id is eos_id or g + 1 == max_new;
+ *   4. the first B candidates that do not finish are the next running beams (source beam, id, acc);
+ *   5. a finishing candidate among the first B of the K enters the B finished slots (initially -1e9) with acc / (g + 1) ** length_penalty, unless the slots
+ *      are full and early_stopping is 1, or the early-stop heuristic is already satisfied; the B best are kept;
+ *   6. the group stops when early_stopping is 1 and the slots are full, when running score[0] / L ** length_penalty <= the worst finished score (L = max_new
+ *      for early_stopping 2 ('never') with length_penalty > 0, else g + 1; while a slot is empty the worst is -1e9), or when all K candidates finished (the
+ *      length limit).  A stopped group is pushed onto the finished queue (cr_kv_poll_finished: its first sequence, stop count = the best hypothesis' length);
+ *      later steps that include it keep appending cache rows and change nothing else.
+ * Between two steps sequence j of the group is given the cache rows and the id history of its source beam (in place; after step 0 the prompt's rows fan out from
+ * the first sequence).  A row's bits do not depend on its batch, so a beam whose rows were copied computes what a sequence that generated those ids itself computes.
+ * Call after cr_kv_reset and BEFORE the prefill, like the sampling state; cr_kv_reset of any member dissolves the group.  early_stopping: 0 False, 1 True,
+ * 2 'never'; eos_id < 0: none.  cr_llm_prefill / cr_llm_prefill_batch take the group's FIRST sequence only (any other member: CR_ERR_ARG); cr_llm_decode takes
+ * all num_beams sequences, consecutive and in order in seqs[] (a partial group or force_tokens with a group: CR_ERR_ARG, nothing changes).  Groups and plain greedy
+ * or sampled sequences may share a launch; those keep their bits.  The ids of a group's member sequences (cr_kv_generated) are the running beams': internal.
+ * CR_ERR_ARG for num_beams outside 2..8, a group that runs past n_seqs, a member that samples, records token scores or belongs to a group already, early_stopping
+ * outside 0..2, max_new outside 1..max_tokens, or an e4m3 cache (left out: the re-order moves bf16 rows only); CR_ERR_STATE for a member that holds tokens or ids.
+ * The state blocks (256 bytes + 8 max_tokens bytes per sequence) are allocated by the first call on a cache, which also synchronises `stream`.  Enqueued on `stream`. */
+int cr_kv_set_beam(cr_kv* kv, int first_seq, int num_beams, float length_penalty, int early_stopping, int eos_id, int max_new, void* stream);
+/* The group's best finished hypothesis so far: its ids (EOS included; at most `max`) into host memory, *score = its sequences_scores entry, *length = its id count
+ * (0 and -1e9 while no hypothesis has finished), *done = the group has stopped.  Returns the ids copied, or < 0.  Synchronises `stream` like cr_kv_generated. */
+int cr_kv_beam_result(cr_kv* kv, int first_seq, int64_t* out_host, int max, float* score, int32_t* length, int32_t* done, void* stream);
+/* The re-order kernel alone (test entry), on PLAIN sequences: sequence first_seq + j (j < num_beams) takes cache positions [from, length) and the id history of
+ * first_seq + src_host[j] (host array of num_beams entries, each 0 .. num_beams - 1), every layer, KV head, K and V, in place.  The sequences hold the same
+ * counts of tokens and ids (CR_ERR_ARG otherwise) and belong to no beam group (CR_ERR_STATE: a live group's state is never touched).  Enqueued on `stream`. */
+int cr_kv_beam_reorder(cr_kv* kv, int first_seq, int num_beams, const int32_t* src_host, int from, void* stream);
 /* Enqueue on `stream` an asynchronous copy of the finished queue into host_out (caller-owned PINNED memory of max >= 1 + 2 n_seqs
  * int32): host_out[0] = sequences pushed since the last cr_kv_reset(kv, -1) (a running count c), host_out[1 + k % n_seqs] = the
  * k-th of them (the ring holds the last n_seqs: a sequence is pushed again only after a reset, so a caller that releases a sequence
@@ -343,6 +375,16 @@ int cr_op_sample(cr_ctx* ctx, const float* logits, int n, int vocab, const int64
  * (not modified), ids [n] int64 = the id scored in each row; lp [n], top_ids [n][8], top_lp [n][8] as above with top_n alternatives (1..8, CR_ERR_ARG
  * otherwise; vocab >= 8, n <= 65535).  All pointers are DEVICE arrays.  Synchronises `stream`.  Added within ABI v13. */
 int cr_op_logprobs(const float* logits, int n, int vocab, const int64_t* ids, int top_n, float* lp, int32_t* top_ids, float* top_lp, void* stream);
+/* One beam-search step of cr_kv_set_beam alone (test entry; the prefill and decode launch the same three kernels): logits [n][vocab] fp32 (OVERWRITTEN with the
+ * penalised log-probabilities), history [n][hist_cap] int64 with hist_len[n] ids per row (both updated: re-ordered, the new id appended), group[n] = the first row
+ * of the row's beam group (every row belongs to one; a group's rows are consecutive, in beam order), fin_ids [n][hist_cap] int64 = ids of the finished slots
+ * (row = first row + fin_phys), state [n][64] four-byte words = a group's state at its first row:
+ *   0 num_beams, 1 eos_id, 2 max_new, 3 early_stopping, 4 g, 5 done, 6 skip, 7 heuristic still unsatisfied (start: 1), 8 finished slots in use, 9 prompt length,
+ *   10 length_penalty (float), 16..23 running scores (float; start 0, -1e9, ...), 24..31 finished scores (float; start -1e9), 32..39 their lengths,
+ *   40..47 their rows of fin_ids, 48..55 source beam of each next beam, 56..63 its new id.
+ * All pointers are DEVICE arrays.  vocab >= 16, n <= 65535.  Synchronises `stream`. */
+int cr_op_beam_step(float* logits, int n, int vocab, int64_t* history, int hist_cap, int32_t* hist_len, float penalty, const int32_t* group, void* state,
+                    int64_t* fin_ids, void* stream);
 /* q/k/v/o addressed as base + b*bs + row*rs + head*hs (elements) */
 int cr_op_attention(const void* q, const void* k, const void* v, void* o, const int64_t* strides12, int B, int H,
                     int Sq, int Sk, int head_dim, int kv_group, int causal, int q_pos0, float q_prescale, float s_div,

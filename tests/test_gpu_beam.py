@@ -1,0 +1,324 @@
+"""Beam search on the device (csrc/beam.hip; cr_kv_set_beam, cr_op_beam_step, cr_kv_beam_reorder) against tests/beam_replica.py, the host replica that
+tests/test_beam_cpu.py holds against transformers.
+
+  1. cr_op_beam_step on given fp32 rows: source beams, ids, finished and done state equal the replica's, scores within 5e-6 (logprobs.hip's bound);
+  2. the re-order alone: every (layer, head, position) of every sequence holds its source's bits, everything else keeps its own, histories follow
+     (the cache is filled by prefilling different prompts: there is no cache-write entry; the rows are distinct, and the comparison is of bits);
+  3. end to end, exact: generate_pages(num_beams=B) against the replica driven by the SAME engine through its greedy ABI (reset, prefill, forced decode);
+  4. properties: batch and slot independence, greedy and sampled neighbours keep their ids, 9+ rows and <= 8 rows agree, what is refused changes nothing;
+  5. surface: generate_ocr(num_beams=3) returns what generate_pages returns, with sequences_scores.
+A differing case passes only for a measured tie: the replica's float64 gap between neighbouring candidates <= 1e-5 at some step."""
+import numpy as np
+import pytest
+import torch
+
+from beam_replica import Beam, beam_search
+from callireader_amd import sampling as S
+from callireader_amd import synthetic
+from callireader_amd.config import ModelDims
+
+pytestmark = pytest.mark.gpu
+
+
+def f2i(x):
+    return int(np.float32(x).view(np.int32))
+
+
+def i2f(t):
+    return t.cpu().numpy().view(np.float32)
+
+
+OP_CASES = [(V, B, h, pen) for V in (92553, 9001) for B in (2, 3, 8) for h in (0, 5, 4100) for pen in (1.0, 1.5)]
+# (length_penalty, early_stopping, what the step meets): 'open' = a fresh group far from its limit; 'limit' = its last step (g + 1 == max_new: every candidate
+# finishes); 'heur' = full finished slots whose worst beats anything running (the heuristic stops a group whose beams are alive); 'early' = full slots under
+# early_stopping=True that a better hypothesis may no longer enter
+OP_MODES = [(1.0, False, 'open'), (0.0, True, 'open'), (2.0, 'never', 'open'), (1.0, False, 'limit'), (0.0, False, 'heur'), (1.0, True, 'early')]
+
+
+@pytest.fixture(scope='module')
+def op_tally():
+    t = {'cands': 0, 'excused': 0}
+    yield t
+    assert t['excused'] <= 0.01 * t['cands'], t
+
+
+def spread_rows(B, V, K, g):
+    """B rows of fp32 logits whose candidates are more than 1e-3 apart: every row is its own permutation of ONE set of values (noise in [-7, -1], 2 K peaks
+    0.05 apart from 3.0 down, ten -inf), so the rows share their log-sum-exp and a row's candidates sit on a 0.05 lattice; spread_run() shifts beam b's
+    lattice by 0.05 b / B.  The top K + 1 of [B x V] are then at least 0.05 / B >= 6e-3 apart (asserted on the replica's float64 gaps)."""
+    base = -1.0 - torch.rand(V, generator=g) * 6.0
+    base[:2 * K] = 3.0 - 0.05 * torch.arange(2 * K, dtype=torch.float32)
+    base[2 * K:2 * K + 10] = -float('inf')
+    return torch.stack([base[torch.randperm(V, generator=g)] for _ in range(B)])
+
+
+def spread_run(B):
+    return -(0.5 + torch.arange(B, dtype=torch.float32) * (0.25 + 0.05 / B))
+
+
+def exact_scores(rows, hist, run, pen, picks):
+    """float64 value of acc = run[b] + penalised log-softmax(rows[b])[id] for the (b, id) in picks."""
+    lp = torch.log_softmax(rows.double(), dim=-1)
+    out = []
+    for b, i in picks:
+        v = lp[b, i]
+        if pen != 1.0 and i in hist[b]:
+            v = v * pen if v < 0 else v / pen
+        out.append(float(v + run[b].double()))
+    return out
+
+
+@pytest.mark.parametrize('V,B,h,pen', OP_CASES)
+def test_op_beam_step_matches_replica(V, B, h, pen, op_tally):
+    """Scores: |device - float64 value| <= 5e-6, the bound logprobs.hip documents for its log-softmax against float64 (the issue's figure).  The fp32 torch
+    replica decides ids, sources and state; its OWN scores are fp32 sums over up to 92 553 terms and sit up to ~7e-6 from float64 (measured), so the numbers
+    are held against float64, not against it.  The running scores here are below 4 in magnitude and the penalty (1.5) multiplies an lp of magnitude
+    < 16: the fp32 roundings of the penalty product and of the add (half an ulp below 16 each, ~1e-6 together) and the log-softmax's own one fp32 rounding of
+    a value below 16 after a double-precision sum (~5e-7, scaled by the penalty) stay inside the 5e-6."""
+    from callireader_amd.engine import op_beam_step
+    g = torch.Generator().manual_seed(V + 131 * B + h)
+    K, cap = 2 * B, h + 8
+    for eos_at in (None, 0, B + 1):                   # no EOS; EOS inside the first B candidates; outside them
+        for lp, es, mode in OP_MODES:
+            rows = spread_rows(B, V, K, g)
+            hist = [torch.randint(0, V, (h,), generator=g).tolist() for _ in range(B)]
+            if h:
+                for b in range(B):                    # the penalty meets a candidate: the row's best id is in its history
+                    hist[b][0] = int(rows[b].argmax())
+            run = torch.tensor([0.0] + [-1.0e9] * (B - 1)) if h == 0 else spread_run(B)
+            max_new = h + 1 if mode == 'limit' else h + 3
+            full = mode in ('heur', 'early')
+            fin0 = [5.0 - 0.5 * k for k in range(B)] if mode == 'heur' else [-30.0 - k for k in range(B)]      # 'heur': nothing running reaches 3.0
+
+            def replica(eos):
+                bm = Beam(B, max_new, eos, lp, es, pen)
+                bm.run, bm.seqs, bm.g = run.clone().float(), [list(x) for x in hist], h
+                if full:
+                    bm.fin = [{'score': torch.tensor(fin0[k]), 'ids': [7 + k] * 2} for k in range(B)]
+                bm.step(rows.clone())
+                return bm
+            eos = None if eos_at is None else replica(None).cands[0][eos_at][1]
+            bm = replica(eos)
+            assert bm.min_gap > 1e-3, bm.min_gap                                   # the construction: no candidate pair is near a tie
+            if mode == 'limit':
+                assert bm.done and bm.stopped_by == 'length'
+            if mode == 'heur':
+                assert bm.done and bm.stopped_by == 'heuristic' and bm.alive_at_stop
+            dev = 'cuda'
+            lg = rows.clone().to(dev)
+            H = torch.zeros(B, cap, dtype=torch.int64)
+            for b in range(B):
+                H[b, :h] = torch.tensor(hist[b], dtype=torch.int64)
+            H, hl = H.to(dev), torch.full((B,), h, dtype=torch.int32, device=dev)
+            st = torch.zeros(B, 64, dtype=torch.int32)
+            st[0, :11] = torch.tensor([B, -1 if eos is None else eos, max_new, 2 if es == 'never' else int(es), h, 0, 0, 1, B if full else 0, 0, f2i(lp)],
+                                      dtype=torch.int32)
+            st[0, 16:24] = torch.tensor([f2i(x) for x in run.tolist()] + [f2i(-1.0e9)] * (8 - B), dtype=torch.int32)
+            st[0, 24:32] = f2i(-1.0e9)
+            fin = torch.zeros(B, cap, dtype=torch.int64)
+            if full:
+                st[0, 24:24 + B] = torch.tensor([f2i(x) for x in fin0], dtype=torch.int32)
+                st[0, 32:32 + B] = 2
+                st[0, 40:40 + B] = torch.arange(B, dtype=torch.int32)
+                for k in range(B):
+                    fin[k, :2] = 7 + k
+            st, grp, fin = st.to(dev), torch.zeros(B, dtype=torch.int32, device=dev), fin.to(dev)
+            op_beam_step(lg, H, hl, grp, st, fin, penalty=pen)
+            w = st[0].cpu()
+            got = dict(src=w[48:48 + B].tolist(), ids=w[56:56 + B].tolist(), run=i2f(w[16:16 + B]), n_fin=int(w[8]), done=int(w[5]), heur=int(w[7]),
+                       fin_score=i2f(w[24:24 + B]), fin_len=w[32:32 + B].tolist(), phys=w[40:40 + B].tolist())
+            op_tally['cands'] += K
+            same = (got['src'] == bm.src and got['ids'] == bm.ids and got['n_fin'] == len(bm.fin) and got['done'] == int(bm.done) and
+                    got['heur'] == int(bm.heur) and got['fin_len'][:len(bm.fin)] == [len(hyp['ids']) for hyp in bm.fin])
+            if not same:
+                assert bm.min_gap <= 1e-5, (V, B, h, pen, eos_at, lp, es, mode, got, bm.src, bm.ids, len(bm.fin), bm.done, bm.min_gap)
+                op_tally['excused'] += K
+                continue
+            case = (V, B, h, pen, eos_at, lp, es, mode)
+            if mode != 'limit':                       # (at the limit the "running" beams are finished candidates at acc - 1e9: nothing to compare at 5e-6)
+                want = exact_scores(rows, hist, run, pen, list(zip(bm.src, bm.ids)))
+                err = max(abs(float(a) - b) for a, b in zip(got['run'], want))
+                print('run score error vs float64', case, f'{err:.2e}')
+                assert err <= 5e-6, (case, got['run'], want)
+            for k, hyp in enumerate(bm.fin):
+                assert fin[got['phys'][k], :len(hyp['ids'])].tolist() == hyp['ids'], case
+                if len(hyp['ids']) == h + 1:          # entered in this step: acc / (g + 1) ** lp in float64
+                    b_src = next(b for b in range(B) if hist[b] == hyp['ids'][:-1]) if h else 0
+                    want = exact_scores(rows, hist, run, pen, [(b_src, hyp['ids'][-1])])[0] / float(h + 1) ** lp
+                    err = abs(float(got['fin_score'][k]) - want)
+                    print('finished score error vs float64', case, f'{err:.2e}')
+                    assert err <= 5e-6, (case, got['fin_score'][k], want)
+                else:                                 # an older slot: its bits are untouched
+                    assert float(got['fin_score'][k]) == float(hyp['score']), case
+            assert hl.tolist() == [h + 1] * B
+            assert [H[b, :h + 1].tolist() for b in range(B)] == bm.seqs, case       # the histories followed their sources, the new id appended
+
+
+@pytest.fixture(scope='module')
+def llm():
+    from callireader_amd.modeling_internvl_chat import InternVLChatModel
+    dims = ModelDims.reduced(vit_layers=1, llm_layers=2, rs_depth=1, vocab=9000)
+    m = InternVLChatModel.from_state_dict(synthetic.make_state_dict(dims, seed=3), dims, max_tokens=128, max_pages=24)
+    g = torch.Generator().manual_seed(7)
+    ids = [torch.randint(0, 9000, (n,), generator=g) for n in (5, 64, 70, 33, 21, 48)]
+    pages = [m.engine.embed_splice(i) for i in ids]
+    yield m, pages, ids
+    m.close()
+
+
+def test_reorder_alone(llm):
+    m, pages, _ = llm
+    eng = m.engine
+    kv = eng.kv_alloc(13, 32)
+    try:
+        g = torch.Generator().manual_seed(11)
+        P, steps, Bn = 6, 3, 4
+        for s in range(13):
+            eng.prefill(kv, s, eng.embed_splice(torch.randint(0, 9000, (P,), generator=g)))
+        for _ in range(steps):
+            eng.decode(kv, list(range(13)))
+        L = P + steps
+
+        def snap():
+            return torch.stack([torch.stack([torch.stack([torch.stack([kv.read(l, s, p, w) for w in (0, 1)]) for p in range(L)]) for l in range(2)])
+                                for s in range(13)]).cpu()
+        cur, hist = snap(), [kv.generated(s) for s in range(13)]
+        assert len({tuple(cur[s].flatten().tolist()[:64]) for s in range(13)}) == 13       # distinct rows
+        for start in (0, P):
+            for src in ([0, 1, 2, 3], [1, 2, 3, 0], [2, 2, 2, 2], [1, 0, 0, 3]):
+                kv.beam_reorder(4, src, start)                       # sequences 0..3, 8..12 stand for other groups and plain sequences
+                want, wh = cur.clone(), list(hist)
+                for j in range(Bn):
+                    want[4 + j, :, start:] = cur[4 + src[j], :, start:]
+                    wh[4 + j] = hist[4 + src[j]]
+                got = snap()
+                assert torch.equal(got.view(torch.int16), want.view(torch.int16)), (start, src)
+                assert [kv.generated(s) for s in range(13)] == wh, (start, src)
+                cur, hist = got, wh
+    finally:
+        kv.free()
+
+
+def engine_logits_fn(m, page, pen_unused=None):
+    """The replica's logits callback through the engine's greedy ABI: each beam is rebuilt in a sequence of its own (reset, prefill, forced decodes)."""
+    eng = m.engine
+    kv = eng.kv_alloc(1, m.max_tokens)
+
+    def fn(seqs):
+        out = []
+        for ids in seqs:
+            kv.reset(0)
+            lg = eng.prefill(kv, 0, page, want_logits=True)
+            for t in ids:
+                lg = eng.decode(kv, [0], force_tokens=torch.tensor([t]), want_logits=True)[0]
+            out.append(lg.float().cpu())
+        return torch.stack(out)
+    return fn, kv
+
+
+E2E = [(2, 0, 12, 0.0, False, 1.0, False), (3, 1, 14, 1.0, True, 1.5, True), (4, 2, 12, 1.0, 'never', 1.0, True), (2, 1, 16, 0.0, True, 1.5, True),
+       (3, 0, 20, 1.0, False, 1.5, False), (4, 1, 12, 0.0, 'never', 1.5, True), (3, 2, 13, 1.0, False, 1.0, True), (2, 2, 12, 1.0, True, 1.0, False)]
+
+
+def test_end_to_end_matches_replica(llm):
+    m, pages, _ = llm
+    excused = 0
+    for B, pi, n_new, lp, es, pen, with_eos in E2E:
+        fn, kv1 = engine_logits_fn(m, pages[pi])
+        try:
+            eos = None
+            if with_eos:                                # an EOS id from the replica's own candidates, so that hypotheses finish early
+                eos = beam_search(fn, B, 4, length_penalty=lp, early_stopping=es, repetition_penalty=pen).cands[2][1][1]
+            bm = beam_search(fn, B, n_new, eos_token_id=eos, length_penalty=lp, early_stopping=es, repetition_penalty=pen)
+        finally:
+            kv1.free()
+        ids, sc = m.generate_pages([pages[pi]], n_new, eos, pen, num_beams=B, length_penalty=lp, early_stopping=es)
+        want_ids, want_sc = bm.result()
+        if ids[0] != want_ids or abs(sc[0] - want_sc) > 1e-5:
+            assert bm.min_gap <= 1e-5, ((B, pi, n_new, lp, es, pen, eos), ids[0], want_ids, sc[0], want_sc, bm.min_gap)
+            excused += 1
+    assert excused <= 0.05 * len(E2E), excused
+
+
+def test_batch_slot_and_row_count_independence(llm):
+    m, pages, _ = llm
+    kw = dict(max_new_tokens=12, eos_token_id=None, repetition_penalty=1.3)
+    for B in (3, 8):                                    # alone: 3 / 8 rows (the fused small-batch path); three pages: 9 / 24 rows
+        alone = [m.generate_pages([pages[i]], num_beams=B, **kw) for i in (0, 1, 2)]
+        batch = m.generate_pages([pages[0], pages[1], pages[2]], num_beams=B, **kw)
+        other = m.generate_pages([pages[2], pages[0], pages[1]], num_beams=B, **kw)
+        for j, i in enumerate((0, 1, 2)):
+            assert batch[0][j] == alone[j][0][0] and batch[1][j] == alone[j][1][0]
+        assert other[0] == [batch[0][2], batch[0][0], batch[0][1]] and other[1] == [batch[1][2], batch[1][0], batch[1][1]]
+
+
+def test_greedy_and_sampled_neighbours_keep_their_ids(llm):
+    m, pages, _ = llm
+    eng, pen, n_new = m.engine, 1.3, 10
+    kv = eng.kv_alloc(6, 128)
+    try:
+        def run(with_group):
+            kv.reset()
+            kv.set_sampling(4, 0.9, 40, 0.95, 1234)
+            seqs = [3, 4]
+            if with_group:
+                kv.set_beam(0, 3, 1.0, False, None, n_new)
+                seqs = [0, 3, 4]
+            eng.prefill_batch(kv, seqs, [pages[1], pages[3], pages[4]][-len(seqs):], penalty=pen)
+            rows = ([0, 1, 2] if with_group else []) + [3, 4]
+            for _ in range(n_new - 1):
+                eng.decode(kv, rows, penalty=pen)
+            return kv.generated(3), kv.generated(4), (kv.beam_result(0) if with_group else None)
+        g0, s0, _ = run(False)
+        g1, s1, beam = run(True)
+        assert g1 == g0 and s1 == s0 and len(g0) == n_new
+        ids, sc = m.generate_pages([pages[1]], n_new, None, pen, num_beams=3)
+        assert beam[2] and beam[0] == ids[0] and beam[1] == sc[0]
+    finally:
+        kv.free()
+
+
+def test_refusals_change_nothing(llm):
+    from callireader_amd._binding import CalliReaderError
+    m, pages, _ = llm
+    eng = m.engine
+    kv = eng.kv_alloc(4, 64)
+    try:
+        with pytest.raises(CalliReaderError, match='num_beams'):
+            kv.set_beam(0, 9)
+        with pytest.raises(CalliReaderError, match='past'):
+            kv.set_beam(2, 3)
+        kv.set_beam(0, 3, max_new=8)
+        with pytest.raises(CalliReaderError, match='FIRST'):
+            eng.prefill(kv, 1, pages[0])
+        eng.prefill(kv, 0, pages[0])
+        before = [kv.length(s) for s in range(4)], kv.generated(0)
+        for rows in ([0, 1], [1, 2, 0], [0]):
+            with pytest.raises(CalliReaderError, match='whole'):
+                eng.decode(kv, rows)
+        assert ([kv.length(s) for s in range(4)], kv.generated(0)) == before
+        with pytest.raises(CalliReaderError, match='beam group'):
+            kv.set_sampling(1, 0.8, 0, 1.0, 1)
+    finally:
+        kv.free()
+    kv8 = eng.kv_alloc(4, 64, dtype='e4m3')
+    try:
+        with pytest.raises(CalliReaderError, match='bf16 cache'):
+            kv8.set_beam(0, 2)
+    finally:
+        kv8.free()
+
+
+def test_generate_ocr_surface(llm):
+    m, pages, ids = llm
+    want_ids, want_sc = m.generate_pages([pages[3]], 10, None, 1.5, num_beams=3)
+    m.img_context_token_id = 8990
+    out = m.generate_ocr(input_ids=ids[3].reshape(1, -1), repetition_penalty=1.5, num_beams=3, max_new_tokens=10, eos_token_id=None, do_sample=False)
+    assert out[0].tolist() == want_ids[0]
+    d = m.generate_ocr(input_ids=ids[3].reshape(1, -1), repetition_penalty=1.5, num_beams=3, max_new_tokens=10, eos_token_id=None,
+                       return_dict_in_generate=True)
+    assert d.sequences[0].tolist() == want_ids[0] and float(d.sequences_scores[0]) == want_sc[0]
+    greedy = m.generate_ocr(input_ids=ids[3].reshape(1, -1), repetition_penalty=1.5, num_beams=1, max_new_tokens=10, eos_token_id=None)
+    assert greedy.shape[1] == 10
+    with pytest.raises(NotImplementedError):
+        m.generate_ocr(input_ids=ids[3].reshape(1, -1), num_beams=3, do_sample=True, max_new_tokens=4)
