@@ -18,6 +18,7 @@
 #include "beam.hpp"
 #include "ctx.hpp"
 #include "decode.hpp"
+#include "kvops.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
 #include "logprobs.hpp"
@@ -1131,6 +1132,44 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
             for (int j = 0; j < B; j++) kv->bgrp[f + j] = -1;
             kv->bnum[f] = 0;
         }
+    return CR_OK;
+}
+
+static KvState kv_state(cr_kv* kv) { return {kv->d_len, kv->d_ngen, kv->d_stop, kv->n_seqs, kv->d_temp, kv->d_lpn, kv->d_lpdone}; }
+
+int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream) {
+    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_truncate: bad sequence");
+    if (n_tokens < 0 || n_tokens > kv->len[seq]) return cr_fail(CR_ERR_ARG, "cr_kv_truncate: n_tokens %d outside 0..%d, the tokens sequence %d holds", n_tokens, kv->len[seq], seq);
+    if (kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_truncate: sequence %d belongs to the beam group of sequence %d (cr_kv_reset dissolves the group)", seq, kv->bgrp[seq]);
+    if (n_tokens == 0) return cr_kv_reset(kv, seq, stream);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    KvSeqs one{};
+    one.n = 1; one.seq[0] = seq;
+    CR_TRY(launch_kv_truncate(kv_state(kv), one, n_tokens, (hipStream_t)stream));
+    kv->len[seq] = n_tokens; kv->ngen[seq] = 0; kv->sampled[seq] = 0; kv->scored[seq] = 0;
+    return CR_OK;
+}
+
+int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream) {
+    if (!kv || !dsts_host || src < 0 || src >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_fork: bad argument (null cache or destinations, or a source out of range)");
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_fork: the fork copies bf16 rows only (an e4m3 cache keeps no bf16 prefix for a continued prefill to read)");
+    if (n_dst < 1 || n_dst > kv->n_seqs - 1 || n_dst > KV_FORK_MAX)
+        return cr_fail(CR_ERR_ARG, "cr_kv_fork: %d destinations (want 1..%d)", n_dst, kv->n_seqs - 1 < KV_FORK_MAX ? kv->n_seqs - 1 : KV_FORK_MAX);
+    if (n_tokens < 1 || n_tokens > kv->len[src]) return cr_fail(CR_ERR_ARG, "cr_kv_fork: n_tokens %d outside 1..%d, the tokens sequence %d holds", n_tokens, kv->len[src], src);
+    KvSeqs d{};
+    d.n = n_dst;
+    for (int j = 0; j < n_dst; j++) {
+        const int s = dsts_host[j];
+        if (s < 0 || s >= kv->n_seqs || s == src) return cr_fail(CR_ERR_ARG, "cr_kv_fork: destination %d (want 0..%d, not the source %d)", s, kv->n_seqs - 1, src);
+        for (int i = 0; i < j; i++) if (dsts_host[i] == s) return cr_fail(CR_ERR_ARG, "cr_kv_fork: destination %d listed twice", s);
+        d.seq[j] = s;
+    }
+    if (kv->bgrp[src] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_fork: the source %d belongs to the beam group of sequence %d", src, kv->bgrp[src]);
+    for (int j = 0; j < n_dst; j++)
+        if (kv->bgrp[d.seq[j]] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_fork: destination %d belongs to the beam group of sequence %d", d.seq[j], kv->bgrp[d.seq[j]]);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    CR_TRY(launch_kv_fork(kv_state(kv), kv->k, kv->v, (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD, kv->layers, kv->max_tokens, src, d, n_tokens, (hipStream_t)stream));
+    for (int j = 0; j < n_dst; j++) { const int s = d.seq[j]; kv->len[s] = n_tokens; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; }
     return CR_OK;
 }
 

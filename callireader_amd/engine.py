@@ -288,6 +288,20 @@ class KVCache:
         else:
             self._top_n.pop(seq, None)
 
+    def truncate(self, seq, n):
+        """cr_kv_truncate on the current stream: the sequence keeps its first `n` cached positions and forgets what reset forgets (ids, stop
+        criteria, sampling state, scores).  Cache rows are not touched; n = 0 is reset(seq)."""
+        B.check(B.lib.cr_kv_truncate(self._h, int(seq), int(n), _stream()), 'cr_kv_truncate')
+        self._top_n.pop(seq, None)
+
+    def fork(self, src, dsts, n):
+        """cr_kv_fork on the current stream: every sequence of `dsts` takes the cached positions [0, n) of `src` (one launch, the source read once)
+        and is otherwise as after truncate(dst, n).  bf16 caches only."""
+        dsts = [int(d) for d in dsts]
+        B.check(B.lib.cr_kv_fork(self._h, int(src), (C.c_int32 * len(dsts))(*dsts), len(dsts), int(n), _stream()), 'cr_kv_fork')
+        for d in dsts:
+            self._top_n.pop(d, None)
+
     def read(self, layer, seq, pos, which=0):
         """(8, 128) bf16: K (which=0, after RoPE) or V (which=1) of one cached position, all KV heads."""
         out = torch.empty(8, 128, device=self.eng.device, dtype=torch.bfloat16)

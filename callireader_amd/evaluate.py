@@ -241,8 +241,15 @@ def parse_choice(prompt, letter):
 FIRST_TURN = '这幅书法作品内容是什么？'
 
 
-def _two_turns(model, tokenizer, detect_model, generation_config, img, second_question, use_p, hard_vq, drop_zero, repetition_penalty, verbose):
-    """The reference's reasoning tasks ask for the transcription first and put the actual question as a second turn on that history."""
+def _two_turns(model, tokenizer, detect_model, generation_config, img, second_question, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
+               reuse_page=False):
+    """The reference's reasoning tasks ask for the transcription first and put the actual question as a second turn on that history.
+    reuse_page (--reuse_page): both turns run on one session.PageSession -- the page's visual stage once, the second turn a continued prefill of
+    its new rows over the first turn's cache."""
+    if reuse_page:
+        with model.open_page(tokenizer, detect_model, img, use_p=use_p, drop_zero=drop_zero, hard_vq=hard_vq, verbose=verbose) as page:
+            _, history = page.chat_ocr(FIRST_TURN, generation_config, return_history=True, repetition_penalty=repetition_penalty)
+            return page.chat_ocr(second_question, generation_config, history=history, return_history=True, repetition_penalty=repetition_penalty)[0]
     kw = dict(use_p=use_p, hard_vq=hard_vq, drop_zero=drop_zero, repetition_penalty=repetition_penalty, return_history=True, verbose=verbose)
     _, history = model.chat_ocr(tokenizer, detect_model, img, FIRST_TURN, generation_config, **kw)
     response, history = model.chat_ocr(tokenizer, detect_model, img, second_question, generation_config, history=history, **kw)
@@ -250,7 +257,7 @@ def _two_turns(model, tokenizer, detect_model, generation_config, img, second_qu
 
 
 def test_choice(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p=True, hard_vq=False, drop_zero=True,
-                repetition_penalty=1.0, verbose=False, limit=3):
+                repetition_penalty=1.0, verbose=False, limit=3, reuse_page=False):
     """evaluate.py:216-313 (author / style / layout).  The reference scores the first three samples of each file (:257, :301); limit=0
     scores all."""
     images, annotations = get_parquet(parquet_path)
@@ -261,7 +268,7 @@ def test_choice(parquet_path, save_json_path, model, tokenizer, detect_model, ge
     for img, annot, gt in zip(images, annotations, answers):
         prompt = annot['conversations'][0]['value'].replace('<image>\n', '')
         response = _two_turns(model, tokenizer, detect_model, generation_config, img, prompt + '\n只需要输出问题的答案，禁止输出其他内容！答案：',
-                              use_p, hard_vq, drop_zero, repetition_penalty, verbose)
+                              use_p, hard_vq, drop_zero, repetition_penalty, verbose, reuse_page=reuse_page)
         responses.append(response)
         rows.append({'imgPath': annot['image'], 'output': response, 'reference': gt[0]})
     accuracy = evaluate_accuracy(responses, answers) if responses else 0.0
@@ -272,7 +279,7 @@ def test_choice(parquet_path, save_json_path, model, tokenizer, detect_model, ge
 
 
 def _test_reasoning(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty,
-                    verbose, with_content, limit=None):
+                    verbose, with_content, limit=None, reuse_page=False):
     """evaluate.py:317-386: question = the prompt up to its first option line; the answer is split at "INTENT:" and stored for the
     external judges of eval/ (not run here)."""
     images, annotations = get_parquet(parquet_path)
@@ -283,7 +290,8 @@ def _test_reasoning(parquet_path, save_json_path, model, tokenizer, detect_model
         prompt = annot['conversations'][0]['value']
         m = re.search(r'^(.*?)\n[A-Z]:', prompt, re.DOTALL)
         question = m.group(1).strip() if m else prompt
-        response = _two_turns(model, tokenizer, detect_model, generation_config, img, question, use_p, hard_vq, drop_zero, repetition_penalty, verbose)
+        response = _two_turns(model, tokenizer, detect_model, generation_config, img, question, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
+                              reuse_page=reuse_page)
         row = {'imgPath': annot['image'], 'chinese': response.split('INTENT:')[0], 'answer': response.split('INTENT:')[-1],
                'gt': annot['conversations'][-1]['value']}
         if with_content:
@@ -294,12 +302,16 @@ def _test_reasoning(parquet_path, save_json_path, model, tokenizer, detect_model
     return rows
 
 
-def test_bilingual(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, limit=None):
-    return _test_reasoning(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, False, limit)
+def test_bilingual(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, limit=None,
+                   reuse_page=False):
+    return _test_reasoning(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, False, limit,
+                           reuse_page=reuse_page)
 
 
-def test_intent(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, limit=None):
-    return _test_reasoning(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, True, limit)
+def test_intent(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, limit=None,
+                reuse_page=False):
+    return _test_reasoning(parquet_path, save_json_path, model, tokenizer, detect_model, generation_config, use_p, hard_vq, drop_zero, repetition_penalty, verbose, True, limit,
+                           reuse_page=reuse_page)
 
 
 def compare_reports(bf16_rows, fp8_rows):
@@ -360,6 +372,8 @@ def build_parser():
     parser.add_argument('--num_beams', type=int, default=1, help='beam search with this many beams (2..8); 1: the greedy default')
     parser.add_argument('--length_penalty', type=float, default=None, help='with --num_beams > 1 (default 1.0)')
     parser.add_argument('--early_stopping', type=str, default=None, choices=('false', 'true', 'never'), help='with --num_beams > 1 (default false)')
+    parser.add_argument('--reuse_page', action='store_true', help='choice / bilingual / intent: run both turns of a page on one page session (session.PageSession: the visual '
+                                                                  'stage once, the second turn prefills only its new rows); greedy or sampled, bf16 cache, no beams')
     parser.add_argument('--allow_no_t2s', action='store_true', help='run without opencc (responses stay unconverted: scores not comparable with the reference\'s)')
     return parser
 
@@ -420,14 +434,14 @@ def main(argv=None):
             elif args.type == 'choice':
                 for name in ('author', 'style', 'layout'):
                     acc, _ = test_choice(os.path.join(args.data, f'choice/{name}/{name}.parquet'), os.path.join(save_dir, f'{name}.json'), model, tokenizer,
-                                         detect_model, generation_config, *common, limit=args.choice_limit)
+                                         detect_model, generation_config, *common, limit=args.choice_limit, reuse_page=args.reuse_page)
                     print(name, acc)
             elif args.type == 'bilingual':
                 test_bilingual(os.path.join(args.data, 'reasoning/bilingual/medium/bilingual_medium.parquet'), os.path.join(save_dir, 'bilingual.json'), model,
-                               tokenizer, detect_model, generation_config, *common)
+                               tokenizer, detect_model, generation_config, *common, reuse_page=args.reuse_page)
             else:
                 test_intent(os.path.join(args.data, 'reasoning/intent/intent.parquet'), os.path.join(save_dir, 'intent.json'), model, tokenizer, detect_model,
-                            generation_config, *common)
+                            generation_config, *common, reuse_page=args.reuse_page)
         return
     prompt = '读出图中所有文字。'
     for level in ('easy', 'medium', 'hard'):

@@ -241,37 +241,46 @@ class InternVLChatModel:
         return self.sorter
 
     # ---- generation ----------------------------------------------------------------------------
-    def _generate(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, sampling=None, check_every=16, logprobs=0):
+    def _generate(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, sampling=None, check_every=16, logprobs=0, kv=None, seq=0,
+                  reset=True):
         """transformers 4.45.2 GenerationMixin._sample with num_beams=1 for ONE sequence: greedy (sampling None), or do_sample=True with
         `sampling` (a sampling.SamplingParams; the page's seed is page_seeds(1)[0]); returns only the new ids, EOS included (oracle/generate.py
-        documents the semantics).  logprobs = n > 0: returns (ids, scores.TokenScores with n alternatives per id, cut like the ids)."""
-        kv = self.kv(1)
-        kv.reset(0)
-        if input_embeds.shape[0] + max_new_tokens > self.max_tokens:
-            raise ValueError(f'prompt of {input_embeds.shape[0]} tokens + {max_new_tokens} new exceeds max_tokens={self.max_tokens}')
+        documents the semantics).  logprobs = n > 0: returns (ids, scores.TokenScores with n alternatives per id, cut like the ids).
+        kv / seq: the cache and sequence to run in (default: the model's own, sequence 0).  reset=False (session.PageSession): the sequence keeps the
+        tokens it holds -- the caller has rolled it back with KV.truncate, which leaves no ids and no state -- and `input_embeds` are the rows that
+        continue it."""
+        kv = self.kv(1) if kv is None else kv
+        if reset:
+            kv.reset(seq)
+        S = kv.length(seq) + input_embeds.shape[0]
+        if S + max_new_tokens > self.max_tokens:
+            raise ValueError(f'prompt of {S} tokens + {max_new_tokens} new exceeds max_tokens={self.max_tokens}')
         if sampling is not None:
-            kv.set_sampling(0, sampling.temperature, sampling.top_k, sampling.top_p, page_seeds(1)[0])
+            kv.set_sampling(seq, sampling.temperature, sampling.top_k, sampling.top_p, page_seeds(1)[0])
         if logprobs:
-            kv.set_logprobs(0, logprobs)
-        self.engine.prefill(kv, 0, input_embeds, penalty=repetition_penalty)
+            kv.set_logprobs(seq, logprobs)
+        self.engine.prefill(kv, seq, input_embeds, penalty=repetition_penalty)
         n = 1
         while n < max_new_tokens:
             steps = min(check_every, max_new_tokens - n)
-            if eos_token_id is not None and eos_token_id in kv.generated(0):
+            if eos_token_id is not None and eos_token_id in kv.generated(seq):
                 break
             for _ in range(steps):
-                self.engine.decode(kv, [0], penalty=repetition_penalty)
+                self.engine.decode(kv, [seq], penalty=repetition_penalty)
             n += steps
-        ids = kv.generated(0)[:max_new_tokens]
+        ids = kv.generated(seq)[:max_new_tokens]
         if eos_token_id is not None and eos_token_id in ids:
             ids = ids[:ids.index(eos_token_id) + 1]       # ids past EOS were speculative; the reference stops here
         out = torch.tensor([ids], dtype=torch.long, device=self.device)
-        return (out, TokenScores.read(kv, 0, len(ids))) if logprobs else out
+        return (out, TokenScores.read(kv, seq, len(ids))) if logprobs else out
 
-    def _generate_kw(self, input_embeds, repetition_penalty, generate_kwargs):
-        """_generate driven by transformers' keyword arguments: the new ids, or under return_dict_in_generate=True a scores.GenerateOutput."""
+    def _generate_kw(self, input_embeds, repetition_penalty, generate_kwargs, **where):
+        """_generate driven by transformers' keyword arguments: the new ids, or under return_dict_in_generate=True a scores.GenerateOutput.
+        where: _generate's kv / seq / reset (a session's turn; no beams there)."""
         max_new, eos, sp = self._gen_args(generate_kwargs, allow_beams=True)
         beams = parse_beams(generate_kwargs)
+        if beams is not None and where:
+            raise NotImplementedError(f'num_beams={beams.num_beams} in a page session: cr_kv_set_beam needs empty sequences (use chat_ocr(history=...))')
         if beams is not None:                      # beam search: the page's beams decode as one batch (generate_pages)
             ids, sc = self.generate_pages([input_embeds], max_new, eos, repetition_penalty, num_beams=beams.num_beams, length_penalty=beams.length_penalty,
                                           early_stopping=beams.early_stopping)
@@ -283,10 +292,10 @@ class InternVLChatModel:
             return out
         n = scores_parse(generate_kwargs)
         if not generate_kwargs.get('return_dict_in_generate', False):
-            return self._generate(input_embeds, max_new, eos, repetition_penalty, sp)
+            return self._generate(input_embeds, max_new, eos, repetition_penalty, sp, **where)
         if not n:
-            return generate_output(self._generate(input_embeds, max_new, eos, repetition_penalty, sp))
-        return generate_output(*self._generate(input_embeds, max_new, eos, repetition_penalty, sp, logprobs=n))
+            return generate_output(self._generate(input_embeds, max_new, eos, repetition_penalty, sp, **where))
+        return generate_output(*self._generate(input_embeds, max_new, eos, repetition_penalty, sp, logprobs=n, **where))
 
     @staticmethod
     def _gen_args(generate_kwargs, allow_beams=False):
@@ -446,24 +455,38 @@ class InternVLChatModel:
             else:
                 out_tokens, indices = self.calli_align(page if page is not None else img_path, detect_model, drop_zero=drop_zero,
                                                        use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
+        question, history, template, model_inputs, generation_config = self._ocr_prompt(
+            tokenizer, questions, history, None if pixel_values is None else len(pixel_values), out_tokens, use_p, num_patches_list, generation_config,
+            return_scores, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN)
+        out = self.generate_ocr(pixel_values=pixel_values, input_ids=model_inputs['input_ids'],
+                                attention_mask=model_inputs['attention_mask'],
+                                reference_embeds=out_tokens if use_p else None,
+                                repetition_penalty=repetition_penalty, **generation_config)
+        return self._ocr_reply(tokenizer, out, template, question, history, return_history, return_scores)
+
+    def _ocr_prompt(self, tokenizer, questions, history, n_tiles, out_tokens, use_p, num_patches_list, generation_config, return_scores,
+                    IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]'):
+        """chat_ocr between the visual stage and the language model (:690-732), shared with session.PageSession: the question as the history keeps it,
+        the history list, the template, the tokenised query and the generation_config with the score keywords and the EOS id set.  n_tiles: the page's
+        tiles, None without an image; out_tokens: the pseudo-token rows (their count is appended to a first turn's question)."""
         question = questions
-        if pixel_values is not None and '<image>' not in questions:
+        if n_tiles is not None and '<image>' not in questions:
             question = '<image>\n' + questions                                  # :690-691
         if history is None and use_p and ALIGNED_TOKEN not in question:
             question = question + ALIGNED_TOKEN * out_tokens.shape[0]           # :698-699
         if num_patches_list is None:
-            num_patches_list = [pixel_values.shape[0]] if pixel_values is not None else []
-        assert pixel_values is None or len(pixel_values) == sum(num_patches_list)          # :702
+            num_patches_list = [n_tiles] if n_tiles is not None else []
+        assert n_tiles is None or n_tiles == sum(num_patches_list)              # :702
         self.img_context_token_id = tokenizer.convert_tokens_to_ids(IMG_CONTEXT_TOKEN)
         query, template, history = self._build_query(question, history, num_patches_list, IMG_START_TOKEN,
                                                      IMG_END_TOKEN, IMG_CONTEXT_TOKEN)
         model_inputs = tokenizer(query, return_tensors='pt')
         generation_config, _ = self._score_args(generation_config, return_scores)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)   # :709,732
-        out = self.generate_ocr(pixel_values=pixel_values, input_ids=model_inputs['input_ids'],
-                                attention_mask=model_inputs['attention_mask'],
-                                reference_embeds=out_tokens if use_p else None,
-                                repetition_penalty=repetition_penalty, **generation_config)
+        return question, history, template, model_inputs, generation_config
+
+    def _ocr_reply(self, tokenizer, out, template, question, history, return_history, return_scores):
+        """chat_ocr after the language model (:752-762): the response text, appended to the history, in the shape the caller asked for."""
         out, sc = self._with_scores(tokenizer, out)
         response = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
         response = response.split(template.sep)[0].strip()                      # :752-753
@@ -471,6 +494,13 @@ class InternVLChatModel:
         if return_scores:
             return (response, history, sc) if return_history else (response, sc)
         return (response, history) if return_history else response
+
+    def open_page(self, tokenizer, detect_model, img_path, use_p=True, drop_zero=False, hard_vq=False, boxes=None, max_branches=1, verbose=False):
+        """A session.PageSession on one page: the visual stage of chat_ocr runs once here, and the turns asked through the session
+        (session.chat_ocr, session.ask_many) keep the page's KV cache between them.  A detection failure behaves as chat_ocr's does."""
+        from .session import PageSession
+        return PageSession.open(self, tokenizer, detect_model, img_path, use_p=use_p, drop_zero=drop_zero, hard_vq=hard_vq, boxes=boxes,
+                                max_branches=max_branches, verbose=verbose)
 
     def dynamic_chat(self, tokenizer, pixel_values, questions, generation_config, num_patches_list=None, history=None,
                      return_history=False, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
@@ -960,7 +990,13 @@ class InternVLChatModel:
         for i0 in range(0, P, prefill_batch):                       # prompts of several pages share the linear layers' GEMMs
             idx = list(range(i0, min(P, i0 + prefill_batch)))
             self.engine.prefill_batch(kv, idx, [embeds_list[i] for i in idx], penalty=repetition_penalty)
-        live = list(range(P))
+        outs = self._decode_rows(kv, list(range(P)), max_new_tokens, eos_token_id, repetition_penalty, check_every)
+        return (outs, _read_scores(kv, lpn, outs)) if any(lpn) else outs
+
+    def _decode_rows(self, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, check_every=16):
+        """The batched decode behind a prefill of the sequences `seqs` (each holds its first id): all unfinished ones as one batch per step, EOS looked
+        for every check_every steps; the ids per sequence, in seqs order, cut at EOS / max_new_tokens."""
+        live = list(seqs)
         n = 1
         done = {}
         while n < max_new_tokens and live:
@@ -975,15 +1011,14 @@ class InternVLChatModel:
                         done[i] = ids[:ids.index(eos_token_id) + 1]
                         live.remove(i)
         outs = []
-        for i in range(P):
+        for i in seqs:
             ids = done.get(i)
             if ids is None:
                 ids = kv.generated(i)[:max_new_tokens]
                 if eos_token_id is not None and eos_token_id in ids:
                     ids = ids[:ids.index(eos_token_id) + 1]
             outs.append(ids)
-        return (outs, _read_scores(kv, lpn, outs)) if any(lpn) else outs
-
+        return outs
 
     def _generate_pages_beams(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams):
         """generate_pages with beam search: page i is the beam group of sequences beam_slots(i, B); the done flags are read every check_every steps,

@@ -1,0 +1,195 @@
+"""Page sessions: several turns about ONE page on one KV cache.
+
+The reference's choice / bilingual / intent tasks ask for the transcription and then put the real question as a second chat_ocr call on the
+same image with `history=` (evaluate.py:257-287, 321-342, 357-378).  That second call repeats the page's visual stage and prefills a prompt
+whose first ~3 000 tokens the cache held a moment ago.  A PageSession (InternVLChatModel.open_page) runs the visual stage once, keeps the
+page's ViT embeddings and pseudo-token rows, and owns a bf16 KV cache of 1 + max_branches sequences: sequence 0, the TRUNK, carries the
+conversation from turn to turn; the others are BRANCHES that ask_many forks off it for one batch of questions.
+
+A turn
+    p = longest common prefix of the ids at the trunk's cached positions and the new prompt's ids (at most len(prompt) - 1: a prefill needs a row)
+    KV.truncate(0, p)   cr_kv_truncate: the trunk keeps positions [0, p) and forgets ids, criteria, sampling state and scores -- the
+                        speculative rows behind EOS are cut, and the new turn's repetition penalty sees this turn's ids only, as the
+                        processors of the reference's `generate` call do
+    embed rows [p, S), one continued prefill (cr_llm_prefill appends at the cached length), the decode loop of _generate
+
+Why a common id prefix is a common embedding prefix: within a session row i of the spliced prompt depends only on ids[0..i] -- a plain id takes
+its table row, the k-th <IMG_CONTEXT> takes ViT row k and the k-th aligned token takes pseudo-token row k, k counted from the prompt's start --
+and the rows behind them are the session's own tensors, the same for every turn.  p is computed on IDS, not text: where re-tokenising the
+history's answer does not give back the generated ids the prefix ends, and the rest is prefilled again.  That costs rows, never correctness.
+
+What a session turn is: the reference's chat_ocr(history=...) turn, held to the oracle like every other greedy path (tests/test_gpu_session.py).
+It is deterministic -- the same calls give the same bits -- but it is NOT promised bit-equal to a non-session chat_ocr: a continued prefill puts
+its rows in other company inside the attention waves of deeper layers.  A branch gives the ids the same question gives when asked alone from the
+same trunk state (greedy decoding; sampled branches have their own seeds: ask_many).
+
+Not here (NotImplementedError): num_beams > 1 (cr_kv_set_beam needs empty sequences: use chat_ocr(history=...)), e4m3 caches (no bf16 prefix
+to continue from: use kv_cache_dtype='bf16'), region_wise (one turn), and the pipelines / sharded entry points, which own their caches.
+"""
+import numpy as np
+import torch
+from PIL import Image
+
+from .preprocess import load_image, plan_page
+from .sampling import page_seeds, parse_beams
+
+
+def common_prefix(a, b):
+    """Length of the longest common prefix of two id lists."""
+    n = min(len(a), len(b))
+    i = 0
+    while i < n and a[i] == b[i]:
+        i += 1
+    return i
+
+
+def plan_prefix(cached_ids, prompt_ids):
+    """p of a turn: the cached positions the prompt keeps.  Capped at len(prompt) - 1 -- the prefill that makes the turn's first pick needs a row."""
+    return min(common_prefix(cached_ids, prompt_ids), len(prompt_ids) - 1)
+
+
+def fork_groups(prefixes):
+    """ask_many's forks: {prefix length: [question indices]} in first-seen order, one cr_kv_fork per distinct length."""
+    groups = {}
+    for j, p in enumerate(prefixes):
+        groups.setdefault(p, []).append(j)
+    return groups
+
+
+def _refuse_e4m3(model):
+    if getattr(model, 'kv_cache_dtype', 'bf16') != 'bf16':
+        raise NotImplementedError("a page session continues a cached prefix, and an e4m3 cache keeps no bf16 prefix for a continued prefill to read: "
+                                  "open the page on a model with kv_cache_dtype='bf16', or use chat_ocr(history=...)")
+
+
+class PageSession:
+    """See the module docstring.  Made by InternVLChatModel.open_page; a context manager (close() frees the cache)."""
+
+    def __init__(self, model, tokenizer, vit_embeds, ref_embeds, n_tiles, use_p=True, max_branches=1):
+        _refuse_e4m3(model)
+        if max_branches < 1:
+            raise ValueError(f'max_branches has to be >= 1, got {max_branches}')
+        self.m, self.tokenizer, self.use_p, self.n_tiles, self.max_branches = model, tokenizer, use_p, n_tiles, max_branches
+        self.vit = vit_embeds.reshape(-1, vit_embeds.shape[-1])                               # [n_tiles * 256, hidden]: <IMG_CONTEXT> k takes row k
+        self.ref = ref_embeds.reshape(-1, ref_embeds.shape[-1]).to(torch.bfloat16) if use_p else None           # [n_ref, hidden]: aligned token k takes row k
+        self.kv = model.engine.kv_alloc(1 + max_branches, model.max_tokens, dtype='bf16')
+        self.cached_ids = []                     # the id at every cached position of the trunk
+        self.rows_prefilled = []                 # rows of every prefill the session made (turns and ask_many), in order
+
+    @classmethod
+    def open(cls, model, tokenizer, detect_model, img_path, use_p=True, drop_zero=False, hard_vq=False, boxes=None, max_branches=1, verbose=False):
+        """What chat_ocr does per call before its prompt (:653-688), once: decode the page, its tiles, extract_feature, calli_align."""
+        _refuse_e4m3(model)                                                                   # before any visual work
+        try:
+            page = Image.open(img_path).convert('RGB') if isinstance(img_path, str) else img_path.convert('RGB')
+            if model.gpu_preprocess:
+                jobs, n = plan_page(*page.size)
+                pixel_values = model.engine.preprocess(torch.from_numpy(np.array(page)), jobs, n)
+            else:
+                pixel_values = load_image(page).to(torch.bfloat16).to(model.device)
+        except Exception:
+            raise FileNotFoundError                                                           # :670-671
+        out_tokens = None
+        if use_p:
+            out_tokens, _ = model.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
+        return cls(model, tokenizer, model.extract_feature(pixel_values), out_tokens, pixel_values.shape[0], use_p=use_p, max_branches=max_branches)
+
+    # ---- lifetime ----
+    def close(self):
+        if self.kv is not None:
+            self.kv.free()
+            self.kv = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- prompts ----
+    def _prompt(self, question, history, generation_config, return_scores=False):
+        """chat_ocr's own prompt for this page (InternVLChatModel._ocr_prompt: the lines chat_ocr runs) and its ids as a list."""
+        if parse_beams(dict(generation_config)) is not None:
+            raise NotImplementedError(f"num_beams={generation_config.get('num_beams')} in a page session: cr_kv_set_beam needs empty sequences "
+                                      '(beam search runs through chat_ocr(history=...))')
+        question, history, template, inputs, gc = self.m._ocr_prompt(self.tokenizer, question, history, self.n_tiles, self.ref, self.use_p, None,
+                                                                      generation_config, return_scores)
+        return question, history, template, inputs['input_ids'].reshape(-1).tolist(), gc
+
+    def _embed(self, ids, p):
+        """Embedding rows [p, S) of the prompt `ids`: the ids before p only say how many visual and pseudo-token rows are used up."""
+        img, ref = self.m.img_context_token_id, self.m.aligned_token_id
+        head, tail = ids[:p], torch.tensor(ids[p:], dtype=torch.long)
+        k_img, n_img = head.count(img), int((tail == img).sum())
+        k_ref, n_ref = (head.count(ref), int((tail == ref).sum())) if self.use_p else (0, 0)
+        eng = self.m.engine
+        if n_img:
+            return eng.embed_splice(tail, self.vit[k_img:k_img + n_img], self.ref[k_ref:k_ref + n_ref] if n_ref else None, img_id=img, ref_id=ref)
+        if n_ref:                                # aligned tokens without a visual one before them in the tail: the splice's one-kind form on their rows
+            return eng.embed_splice(tail, self.ref[k_ref:k_ref + n_ref], None, img_id=ref)
+        return eng.embed_splice(tail)
+
+    def _after_turn(self, ids):
+        """cached position S + i holds generated id i (the decode step that fed it cached it); the last id generated is cached nowhere yet"""
+        self.cached_ids = list(ids) + self.kv.generated(0)[:self.kv.length(0) - len(ids)]
+
+    # ---- turns ----
+    @torch.no_grad()
+    def chat_ocr(self, question, generation_config, history=None, return_history=False, repetition_penalty=1.5, return_scores=False):
+        """chat_ocr's arguments after the image, and its return values.  The turn runs on the trunk."""
+        question, history, template, ids, gc = self._prompt(question, history, generation_config, return_scores)
+        p = plan_prefix(self.cached_ids, ids)
+        max_new = self.m._gen_args(gc, allow_beams=True)[0]                                   # validated here: a refused turn leaves the trunk as it was
+        if len(ids) + max_new > self.m.max_tokens:                                            # before the trunk changes
+            raise ValueError(f'prompt of {len(ids)} tokens + {max_new} new exceeds max_tokens={self.m.max_tokens}')
+        self.kv.truncate(0, p)
+        self.cached_ids = self.cached_ids[:p]
+        embeds = self._embed(ids, p)
+        self.rows_prefilled.append(len(ids) - p)
+        out = self.m._generate_kw(embeds, repetition_penalty, gc, kv=self.kv, seq=0, reset=False)
+        self._after_turn(ids)
+        return self.m._ocr_reply(self.tokenizer, out, template, question, history, return_history, return_scores)
+
+    @torch.no_grad()
+    def ask_many(self, questions, generation_config, history=None, repetition_penalty=1.5):
+        """Several questions about the page as ONE decode batch: every question's prompt is built as chat_ocr builds it (the same `history` for all),
+        its branch is forked off the trunk at the prefix the two share, the tails are prefilled together and the branches decode together.  Returns
+        the responses in order.  The trunk is not changed -- except that an EMPTY trunk first takes the part all the prompts share.
+        Greedy: a branch gives the ids its question gives when asked alone from the same trunk state.  do_sample=True: branch j draws with
+        page_seeds(n)[j] (chat_ocr_pages' rule), not with the page_seeds(1)[0] of a lone session.chat_ocr -- reproducible under torch.manual_seed, but
+        not the lone call's draws.  No return_scores here."""
+        questions = list(questions)
+        if not 1 <= len(questions) <= self.max_branches:
+            raise ValueError(f'ask_many: {len(questions)} questions for a session opened with max_branches={self.max_branches}')
+        m, kv = self.m, self.kv
+        built = [self._prompt(q, None if history is None else list(history), generation_config) for q in questions]
+        gc, template = built[0][4], built[0][2]
+        max_new, eos, sp = m._gen_args(gc, allow_beams=True)
+        for _, _, _, ids, _ in built:
+            if len(ids) + max_new > m.max_tokens:
+                raise ValueError(f'prompt of {len(ids)} tokens + {max_new} new exceeds max_tokens={m.max_tokens}')
+        if not self.cached_ids:                  # an empty trunk: what the prompts share goes into it first; the pick that prefill appends is dropped
+            first = built[0][3]
+            shared = min(min(common_prefix(first, b[3]) for b in built), min(len(b[3]) for b in built) - 1)
+            if shared > 0:
+                kv.truncate(0, 0)
+                m.engine.prefill(kv, 0, self._embed(first[:shared], 0), penalty=repetition_penalty)
+                kv.truncate(0, shared)
+                self.rows_prefilled.append(shared)
+                self.cached_ids = first[:shared]
+        prefixes = [plan_prefix(self.cached_ids, b[3]) for b in built]
+        branches = list(range(1, 1 + len(built)))
+        for p, js in fork_groups(prefixes).items():
+            if p > 0:
+                kv.fork(0, [branches[j] for j in js], p)
+            else:
+                for j in js:
+                    kv.truncate(branches[j], 0)
+        if sp is not None:
+            for b, seed in zip(branches, page_seeds(len(branches))):
+                kv.set_sampling(b, sp.temperature, sp.top_k, sp.top_p, seed)
+        tails = [self._embed(b[3], p) for b, p in zip(built, prefixes)]
+        self.rows_prefilled.append(sum(len(b[3]) - p for b, p in zip(built, prefixes)))
+        m.engine.prefill_batch(kv, branches, tails, penalty=repetition_penalty)
+        outs = m._decode_rows(kv, branches, max_new, eos, repetition_penalty)
+        return [self.tokenizer.batch_decode(torch.tensor([o]), skip_special_tokens=True)[0].split(template.sep)[0].strip() for o in outs]

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_set_beam, cr_kv_beam_result, cr_kv_beam_reorder, cr_op_beam_step, cr_kv_reset also dissolves beam groups; cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_truncate, cr_kv_fork; cr_kv_set_beam, cr_kv_beam_result, cr_kv_beam_reorder, cr_op_beam_step, cr_kv_reset also dissolves beam groups; cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -151,6 +151,22 @@ int cr_kv_length(const cr_kv* kv, int seq);           /* tokens currently cached
 /* Forget sequence `seq` (length 0, no generated ids), or every sequence when seq < 0.  Enqueued on `stream`, no
  * device-wide synchronisation: ordered after earlier work on that stream and before what the caller enqueues next. */
 int cr_kv_reset(cr_kv* kv, int seq, void* stream);
+/* Roll `seq` back to its first n_tokens cached positions: it keeps positions [0, n_tokens) and forgets everything else that cr_kv_reset forgets -- its
+ * generated ids, its stop criteria and stop count, its sampling state (greedy again; a later sampled pick's `step` counts from 0) and its token scores (off).
+ * cr_kv_length and the host-side id count follow.  State only: no cache row is touched, rows at positions >= n_tokens are dead and later appends overwrite
+ * them.  n_tokens == 0 is cr_kv_reset of the sequence.  What it is for: the next turn of a conversation whose prompt begins with what the cache holds -- cut
+ * the speculative rows behind EOS, continue with cr_llm_prefill of the new rows; the repetition penalty of the new turn then sees that turn's ids only, as
+ * the processors of a `generate` call do.  Any cache format.  CR_ERR_ARG for n_tokens outside 0..cr_kv_length(seq), CR_ERR_STATE for a member of a live
+ * beam group.  Enqueued on `stream`, no device-wide synchronisation.  Added within ABI v13. */
+int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream);
+/* Give the n_dst sequences dsts_host[] (host array) the prefix of `src`: each becomes a sequence that holds cached positions [0, n_tokens) of src -- every
+ * layer, KV head, K and V -- and is otherwise as after cr_kv_truncate(dst, n_tokens): no ids, no criteria, greedy, scores off.  One launch of the copy kernel
+ * of csrc/kvops.hip, which reads the source once however many destinations there are ((1 + n_dst) * layers * 4096 * n_tokens bytes of traffic); rows of a
+ * destination at positions >= n_tokens are not written; src is unchanged.  A row's bits do not depend on its sequence, so a destination continued by a
+ * prefill computes what src continued by that prefill computes.  CR_ERR_ARG for n_tokens outside 1..cr_kv_length(src), n_dst outside 1..min(n_seqs - 1, 64),
+ * a destination equal to src, repeated or out of range, or an e4m3 cache (left out, as for the beam re-order: it keeps no bf16 prefix for a continued
+ * prefill to read anyway); CR_ERR_STATE for a beam-group member on either side.  Enqueued on `stream`.  Added within ABI v13. */
+int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream);
 /* One cached position as the reference's tuple cache holds it (InternVL/modeling_internlm2.py:383-388, K after RoPE):
  * out [8 kv heads][128] bf16 (device) = past_key_values[layer][which][seq, :, pos, :]; which 0 = K, 1 = V.  Parity tests. */
 int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, void* stream);
