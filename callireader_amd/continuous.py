@@ -1,6 +1,6 @@
 """Continuous batching of pages: a fixed set of decode rows kept full, a finished page's row refilled at once.
 
-PagePipeline (modeling_internvl_chat.py) decodes in batches: a batch runs until its longest page stops, and the slots of pages that stopped
+PagePipeline (pipeline.py) decodes in batches: a batch runs until its longest page stops, and the slots of pages that stopped
 earlier stay empty until then.  ContinuousPipeline keeps up to `slots` pages decoding at every step.  It stops them on the device and reads
 the stops without a stream drain:
   - the greedy pick checks each row's stop criteria (cr_kv_set_stop: EOS id, budget of new ids), records the stop count and pushes the
@@ -9,7 +9,7 @@ the stops without a stream drain:
     once the copy's event has completed; ids past a stop are speculative and are cut at the stop count.
 
 Threads and streams, as in PagePipeline:
-  - the CALLER's thread prefills waiting pages into free KV sequences on its own stream, in groups of up to `admit_group` pages (wide
+  - the CALLER's thread prefills waiting pages into free KV sequences on its own stream (generation.admit), in groups of up to `admit_group` pages (wide
     prefill GEMMs; a partial group once input has run out, i.e. while results() drains), and reads finished pages' ids back;
   - a WORKER thread decodes on a side stream through a second context that shares the weights (Engine.shared_context).
 
@@ -36,6 +36,7 @@ import time
 import torch
 
 from .config import EOS_TOKEN_ID
+from .generation import admit, check_fits
 from .scores import TokenScores, check_top_n
 
 
@@ -137,8 +138,7 @@ class ContinuousPipeline:
         S = int(embeds.shape[0])
         if not 1 <= budget <= self.max_new_tokens:
             raise ValueError(f'max_new_tokens={budget}: a page budget must be 1 .. {self.max_new_tokens} (the pipeline\'s)')
-        if S + budget > self.max_tokens:
-            raise ValueError(f'prompt of {S} tokens + {budget} new exceeds max_tokens={self.max_tokens}')
+        check_fits(S, budget, self.max_tokens)
         ticket = self.next_ticket
         self.next_ticket += 1
         if sampling is not None and seed is None:
@@ -235,14 +235,9 @@ class ContinuousPipeline:
                 return
             group = [self.waiting.popleft() for _ in range(k)]
             seqs = [self.free.popleft() for _ in range(k)]
-            for s, (_, _, _, sp, seed, lpn) in zip(seqs, group):
-                self.kv.reset(s)
-                if sp is not None:
-                    self.kv.set_sampling(s, sp.temperature, sp.top_k, sp.top_p, seed)
-                if lpn:
-                    self.kv.set_logprobs(s, lpn)
-                    self.scored[s] = lpn
-            self.eng.prefill_batch(self.kv, seqs, [g[1] for g in group], penalty=self.penalty)
+            self.scored.update((s, g[5]) for s, g in zip(seqs, group) if g[5])
+            admit(self.eng, self.kv, seqs, [g[1] for g in group], self.penalty, per_page=[None if g[3] is None else (g[3], g[4]) for g in group],
+                  lpn=[g[5] for g in group], prefill_batch=k, reset_each=True)
             ready = self.ops.record(self.ops.current())
             for s, (ticket, *_) in zip(seqs, group):
                 self.owner[s] = ticket

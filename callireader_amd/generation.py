@@ -1,0 +1,105 @@
+"""The host side of generation, once: the prompt-length check, the admission of sequences into a cache, the chunked decode loop of the greedy
+and sampled rows, the EOS / budget cut and the reply text.  Plain functions of an engine and a cache, so the caller's engine (generate_pages,
+_generate, session.PageSession) and a pipeline's second context (pipeline.PagePipeline) run the same code.  ContinuousPipeline admits through
+`admit` too; its worker stops rows on the device and is a different loop (continuous.py).  Beam search keeps its own loop (its finish test is the
+group's done flag: InternVLChatModel._generate_pages_beams)."""
+import time
+
+import torch
+
+from .sampling import page_seeds
+from .scores import TokenScores
+
+
+def check_fits(S, max_new, max_tokens):
+    """A prompt of S tokens and max_new new ones have to fit a sequence of the cache."""
+    if S + max_new > max_tokens:
+        raise ValueError(f'prompt of {S} tokens + {max_new} new exceeds max_tokens={max_tokens}')
+
+
+def cut_ids(ids, eos, budget):
+    """The ids a caller gets: at most `budget` of them, cut behind the first EOS (ids past it were speculative; the reference stops there)."""
+    ids = ids[:budget]
+    return ids[:ids.index(eos) + 1] if eos is not None and eos in ids else ids
+
+
+def per_page_sampling(sampling, seeds, P):
+    """[(SamplingParams, seed) or None] per page from generate_pages' sampling / seeds arguments."""
+    if sampling is None:
+        return None
+    sps = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * P
+    if len(sps) != P:
+        raise ValueError(f'sampling: {len(sps)} entries for {P} pages')
+    if seeds is None:
+        seeds = page_seeds(P)
+    if len(seeds) != P:
+        raise ValueError(f'seeds: {len(seeds)} entries for {P} pages')
+    return [None if sp is None else (sp, int(sd)) for sp, sd in zip(sps, seeds)]
+
+
+def admit(engine, kv, seqs, embeds_list, penalty, per_page=None, lpn=(), prefill_batch=16, reset_each=False):
+    """Put one prompt into each of the sequences `seqs`: reset (the whole cache in one call, or with reset_each only these sequences), then the sampled
+    pages' state (per_page: per_page_sampling's list), then the scored pages' (lpn: alternatives per id, 0 = off), then the prefill in groups of
+    `prefill_batch` -- prompts of several pages share the linear layers' GEMMs, and the prefill makes every page's first pick (its step 0)."""
+    if reset_each:
+        for s in seqs:
+            kv.reset(s)
+    else:
+        kv.reset()
+    for s, e in zip(seqs, per_page or ()):
+        if e is not None:
+            kv.set_sampling(s, e[0].temperature, e[0].top_k, e[0].top_p, e[1])
+    for s, n in zip(seqs, lpn):
+        if n:
+            kv.set_logprobs(s, n)
+    for i0 in range(0, len(seqs), prefill_batch):
+        engine.prefill_batch(kv, seqs[i0:i0 + prefill_batch], embeds_list[i0:i0 + prefill_batch], penalty=penalty)
+
+
+def decode_rows(engine, kv, seqs, max_new_tokens, eos, penalty, check_every=16, budgets=None, look_first=False, on_chunk=None):
+    """The decode behind a prefill of the sequences `seqs` (each holds its first id): all unfinished ones as one batch per step, in chunks of
+    `check_every` steps.  After each chunk a row leaves when it has its budget of ids (budgets: one per sequence, default max_new_tokens for all) or
+    EOS is among them; returns the ids per sequence, in seqs order, as cut_ids cuts them.  Ids are read back (which synchronises the current stream)
+    only at such a look, and only where the answer can matter: with eos None, once per row, at its budget.
+    look_first: also look before the first chunk -- the one-sequence path (_generate), where a prefill whose own pick is EOS issues no decode step.
+    The batch paths do not: a read-back there would hold the host's issue of the first decode step until the whole prefill has run.
+    on_chunk(steps, rows, seconds): called after each chunk's steps are issued, with the host time that took (PagePipeline's counters)."""
+    budget = dict(zip(seqs, budgets if budgets is not None else [max_new_tokens] * len(seqs)))
+    live, done, n = list(seqs), {}, 1
+
+    def look():
+        for i in list(live):
+            if eos is not None or n >= budget[i]:
+                ids = kv.generated(i)
+                if n >= budget[i] or eos in ids:
+                    done[i] = cut_ids(ids, eos, budget[i])
+                    live.remove(i)
+    if look_first or max_new_tokens <= 1:
+        look()
+    while n < max_new_tokens and live:
+        steps = min(check_every, max_new_tokens - n)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            engine.decode(kv, live, penalty=penalty)
+        if on_chunk is not None:
+            on_chunk(steps, len(live), time.perf_counter() - t0)
+        n += steps
+        look()
+    return [done[i] for i in seqs]
+
+
+def read_scores(kv, lpn, outs):
+    """TokenScores of the scored pages (None for the others), cut to the ids returned; on the current stream."""
+    return [TokenScores.read(kv, i, len(ids)) if n else None for i, (n, ids) in enumerate(zip(lpn, outs))]
+
+
+def reply_text(tokenizer, ids, sep):
+    """The response of one sequence's new ids (a list, or the [1, T] tensor a generate_* call returns): decoded, cut at the template's separator."""
+    ids = ids if torch.is_tensor(ids) else torch.tensor([ids])
+    return tokenizer.batch_decode(ids, skip_special_tokens=True)[0].split(sep)[0].strip()
+
+
+def reply_shape(response, history, scores, return_history, return_scores):
+    """response[, history][, scores]: what chat, chat_ocr and dynamic_chat return."""
+    out = (response,) + ((history,) if return_history else ()) + ((scores,) if return_scores else ())
+    return out if len(out) > 1 else response

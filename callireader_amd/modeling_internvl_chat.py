@@ -4,8 +4,9 @@ Same method names, argument meaning, return values and error behaviour as
 /root/reference/InternVL/modeling_internvl_chat.py (extract_feature :299, calli_align :322,
 chat_ocr :649, batch_chat :903, chat :955, generate_origin :1021, generate_ocr :1067), so a
 caller of the reference (inference.py:37-57, evaluate.py) can switch classes.  All tensor
-math runs in libcallireader_hip.so through `Engine`; this file only builds prompts, moves
-ids and pixels, and drives the greedy loop.  There is no PyTorch compute fallback.
+math runs in libcallireader_hip.so through `Engine`; this file only builds prompts and moves
+ids and pixels.  Admission, the decode loop, the EOS / budget cut and the reply text are generation.py's; PagePipeline is pipeline.py's.
+There is no PyTorch compute fallback.
 
 `detect_model` is what the reference passes (inference.py:37-42,98): an ultralytics `YOLO` object (or any callable
 returning raw boxes); with the sorter loaded (`params/orderformer.pth`, as the reference's __init__ :159 does) the
@@ -14,7 +15,6 @@ whole front end of calli_align runs on its detections (ordering.py).  The detect
 """
 import json
 import os
-import sys
 import time
 import weakref
 
@@ -25,6 +25,8 @@ from PIL import Image
 from .config import ModelDims, IMG_CONTEXT_TOKEN_ID, ALIGNED_TOKEN_ID, EOS_TOKEN_ID
 from .conversation import get_conv_template
 from .engine import Engine
+from .generation import admit, check_fits, decode_rows, per_page_sampling, read_scores, reply_shape, reply_text
+from .pipeline import PagePipeline
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
 from .sampling import base_seed, page_seeds, parse as sampling_parse, parse_beams, splitmix64
 from .scores import ResponseScores, TokenScores, generate_output, parse as scores_parse, per_page as scores_per_page
@@ -152,9 +154,14 @@ class InternVLChatModel:
         return self.engine.kv_alloc(n_seqs, max_tokens, dtype=self._kv_cache_dtype)
 
     def kv(self, n_seqs=None):
-        """The model's own KV cache (the pipeline of chat_ocr_stream has two of its own): `n_seqs` sequences when none exists yet (default: max_pages).  The one-page
+        """The model's own KV cache (the pipeline of chat_ocr_stream has two of its own), with at least `n_seqs` sequences: made with `n_seqs` (default: max_pages)
+        when none exists yet, freed and re-made with max(n_seqs, max_pages) when it holds fewer; max_pages follows.  This is the only place that allocates it.  The one-page
         calls ask for ONE sequence -- 1 GB at max_tokens 8192, where a 64-page cache is 69 GB that folder mode's per-image fallback would hold beside the pipeline's."""
-        if self._kv is None:
+        if self._kv is None or self._kv.n_seqs < (n_seqs or 0):
+            if self._kv is not None:
+                self._kv.free()
+                n_seqs = max(n_seqs, self.max_pages)
+            self.max_pages = max(n_seqs or 0, self.max_pages)
             self._kv = self._kv_alloc(n_seqs or self.max_pages, self.max_tokens)
         return self._kv
 
@@ -252,25 +259,14 @@ class InternVLChatModel:
         kv = self.kv(1) if kv is None else kv
         if reset:
             kv.reset(seq)
-        S = kv.length(seq) + input_embeds.shape[0]
-        if S + max_new_tokens > self.max_tokens:
-            raise ValueError(f'prompt of {S} tokens + {max_new_tokens} new exceeds max_tokens={self.max_tokens}')
+        check_fits(kv.length(seq) + input_embeds.shape[0], max_new_tokens, self.max_tokens)
         if sampling is not None:
             kv.set_sampling(seq, sampling.temperature, sampling.top_k, sampling.top_p, page_seeds(1)[0])
         if logprobs:
             kv.set_logprobs(seq, logprobs)
         self.engine.prefill(kv, seq, input_embeds, penalty=repetition_penalty)
-        n = 1
-        while n < max_new_tokens:
-            steps = min(check_every, max_new_tokens - n)
-            if eos_token_id is not None and eos_token_id in kv.generated(seq):
-                break
-            for _ in range(steps):
-                self.engine.decode(kv, [seq], penalty=repetition_penalty)
-            n += steps
-        ids = kv.generated(seq)[:max_new_tokens]
-        if eos_token_id is not None and eos_token_id in ids:
-            ids = ids[:ids.index(eos_token_id) + 1]       # ids past EOS were speculative; the reference stops here
+        # one sequence looks BEFORE its first chunk too: a prefill whose own pick is EOS issues no decode step (the batch paths do not look first)
+        ids = decode_rows(self.engine, kv, [seq], max_new_tokens, eos_token_id, repetition_penalty, check_every, look_first=True)[0]
         out = torch.tensor([ids], dtype=torch.long, device=self.device)
         return (out, TokenScores.read(kv, seq, len(ids))) if logprobs else out
 
@@ -411,12 +407,9 @@ class InternVLChatModel:
         out = self.generate_origin(pixel_values=pixel_values, input_ids=model_inputs['input_ids'],
                                    attention_mask=model_inputs['attention_mask'], **generation_config)
         out, sc = self._with_scores(tokenizer, out)
-        response = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
-        response = response.split(template.sep)[0].strip()
+        response = reply_text(tokenizer, out, template.sep)
         history.append((question, response))
-        if return_scores:
-            return (response, history, sc) if return_history else (response, sc)
-        return (response, history) if return_history else response
+        return reply_shape(response, history, sc, return_history, return_scores)
 
     def chat_ocr(self, tokenizer, detect_model, img_path, questions, generation_config, num_patches_list=None,
                  history=None, return_history=False, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
@@ -436,14 +429,10 @@ class InternVLChatModel:
                     sub_img = Image.fromarray(img[y1:y2, x1:x2])
                     questions = '输出图片中所有文字:'
                     pixel_values = load_image(sub_img).to(torch.bfloat16).to(self.device)
-                elif self.gpu_preprocess:
-                    page = Image.open(img_path).convert('RGB') if isinstance(img_path, str) else img_path.convert('RGB')
-                    jobs, n = plan_page(*page.size)
-                    pixel_values = self.engine.preprocess(torch.from_numpy(np.array(page)), jobs, n)
-                else:
-                    pixel_values = load_image(img_path).to(torch.bfloat16).to(self.device)
             except Exception:
                 raise FileNotFoundError                                         # :670-671
+            if not region_wise:
+                page, pixel_values = self._open_page(img_path)
         out_tokens = None
         if use_p:
             if region_wise:
@@ -453,8 +442,7 @@ class InternVLChatModel:
                 except Exception:
                     return '检测失败'                                            # :676-679
             else:
-                out_tokens, indices = self.calli_align(page if page is not None else img_path, detect_model, drop_zero=drop_zero,
-                                                       use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
+                out_tokens, indices = self.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
         question, history, template, model_inputs, generation_config = self._ocr_prompt(
             tokenizer, questions, history, None if pixel_values is None else len(pixel_values), out_tokens, use_p, num_patches_list, generation_config,
             return_scores, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN)
@@ -463,6 +451,18 @@ class InternVLChatModel:
                                 reference_embeds=out_tokens if use_p else None,
                                 repetition_penalty=repetition_penalty, **generation_config)
         return self._ocr_reply(tokenizer, out, template, question, history, return_history, return_scores)
+
+    def _open_page(self, img_path):
+        """(the decoded page, its tiles' pixel_values) of chat_ocr's image (:664-671), shared with session.PageSession.open: the tiles are cut on the GPU, or
+        through PIL with gpu_preprocess off.  Whatever fails, the reference's FileNotFoundError."""
+        try:
+            page = Image.open(img_path).convert('RGB') if isinstance(img_path, str) else img_path.convert('RGB')
+            if self.gpu_preprocess:
+                jobs, n = plan_page(*page.size)
+                return page, self.engine.preprocess(torch.from_numpy(np.array(page)), jobs, n)
+            return page, load_image(page).to(torch.bfloat16).to(self.device)
+        except Exception:
+            raise FileNotFoundError                                             # :670-671
 
     def _ocr_prompt(self, tokenizer, questions, history, n_tiles, out_tokens, use_p, num_patches_list, generation_config, return_scores,
                     IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]'):
@@ -488,12 +488,9 @@ class InternVLChatModel:
     def _ocr_reply(self, tokenizer, out, template, question, history, return_history, return_scores):
         """chat_ocr after the language model (:752-762): the response text, appended to the history, in the shape the caller asked for."""
         out, sc = self._with_scores(tokenizer, out)
-        response = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
-        response = response.split(template.sep)[0].strip()                      # :752-753
+        response = reply_text(tokenizer, out, template.sep)                     # :752-753
         history.append((question, response))
-        if return_scores:
-            return (response, history, sc) if return_history else (response, sc)
-        return (response, history) if return_history else response
+        return reply_shape(response, history, sc, return_history, return_scores)
 
     def open_page(self, tokenizer, detect_model, img_path, use_p=True, drop_zero=False, hard_vq=False, boxes=None, max_branches=1, verbose=False):
         """A session.PageSession on one page: the visual stage of chat_ocr runs once here, and the turns asked through the session
@@ -541,7 +538,7 @@ class InternVLChatModel:
                 off += num_patches
                 out, sc = self._with_scores(tokenizer, gen(pixel_values=px, input_ids=ids, **generation_config))
                 all_sc.append(sc)
-                responses.append(tokenizer.batch_decode(out, skip_special_tokens=True)[0].split(template.sep)[0].strip())
+                responses.append(reply_text(tokenizer, out, template.sep))
             return (responses, all_sc) if return_scores else responses
         assert isinstance(questions, str)
         if num_patches_list is None:
@@ -564,15 +561,11 @@ class InternVLChatModel:
         out = gen(pixel_values=pixel_values, input_ids=model_inputs['input_ids'], attention_mask=model_inputs['attention_mask'],
                   **generation_config)
         out, sc = self._with_scores(tokenizer, out)
-        response = tokenizer.batch_decode(out, skip_special_tokens=True)[0].split(template.sep)[0].strip()
+        response = reply_text(tokenizer, out, template.sep)
         history.append((questions, response))
-        if return_history:
-            return (response, history, sc) if return_scores else (response, history)
-        if return_scores:
-            return response, sc
-        if verbose:
+        if verbose and not return_history and not return_scores:               # only on the plain-response return
             print(query.replace(IMG_CONTEXT_TOKEN, '').replace(f'{IMG_START_TOKEN}{IMG_END_TOKEN}', '<image>'), response)
-        return response
+        return reply_shape(response, history, sc, return_history, return_scores)
 
     def chat_ocr_pages(self, tokenizer, detect_model, images, question, generation_config, boxes_list=None, use_p=True,
                        drop_zero=False, hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
@@ -621,7 +614,7 @@ class InternVLChatModel:
         sep = meta['template'].sep
         res = [None] * meta['n']
         for i, o in zip(meta['ok'], outs):
-            res[i] = tokenizer.batch_decode(torch.tensor([o]), skip_special_tokens=True)[0].split(sep)[0].strip()
+            res[i] = reply_text(tokenizer, o, sep)
         for i, e in meta['failed'].items():
             res[i] = e
         return res
@@ -787,7 +780,7 @@ class InternVLChatModel:
                         yield sub[k], emb, None, sp, (seeds[sub[k]] if sp is not None else None), lpn
 
         def response(ids):
-            return tokenizer.batch_decode(torch.tensor([ids]), skip_special_tokens=True)[0].split(template.sep)[0].strip()
+            return reply_text(tokenizer, ids, template.sep)
         if not images:
             return
         pipe = ContinuousPipeline(self, slots=slots, max_new_tokens=max_new, eos_token_id=eos, repetition_penalty=repetition_penalty,
@@ -908,10 +901,11 @@ class InternVLChatModel:
         embeds, toff, ioff = [], 0, 0
         for k, i in enumerate(batch.ok):
             S = all_ids[k].numel()
-            if S + max_new > self.max_tokens:
-                err = ValueError(f'prompt of {S} tokens + {max_new} new exceeds max_tokens={self.max_tokens}')       # _generate's check, per page
+            try:
+                check_fits(S, max_new, self.max_tokens)                         # _generate's check, per page
+            except ValueError as err:
                 if errors == 'raise':
-                    raise err
+                    raise
                 meta['failed'][i] = err
             else:
                 embeds.append(self.engine.embed_splice(ids_dev[ioff:ioff + S], feats[toff:toff + batch.n_tiles[k]], refs[k], img_id=self.img_context_token_id,
@@ -949,8 +943,7 @@ class InternVLChatModel:
         outs = self.generate_pages(embeds, max_new, eos, generation_config.get('repetition_penalty', 1.0), sampling=sp,
                                    seeds=page_seeds(len(embeds)) if sp is not None else None, logprobs=lpn)
         outs, tss = outs if lpn else (outs, None)
-        responses = [tokenizer.batch_decode(torch.tensor([o]), skip_special_tokens=True)[0] for o in outs]
-        responses = [r.split(template.sep)[0].strip() for r in responses]
+        responses = [reply_text(tokenizer, o, template.sep) for o in outs]
         return (responses, [ResponseScores.build(tokenizer, o, ts) for o, ts in zip(outs, tss)]) if return_scores else responses
 
     # ---- page-parallel generation (new: the reference decodes one page at a time) ---------------
@@ -976,49 +969,12 @@ class InternVLChatModel:
             if sampling is not None or (logprobs and any(scores_per_page(logprobs, P))):
                 raise NotImplementedError('generate_pages: beam search takes neither sampling nor token scores')
             return self._generate_pages_beams(embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams)
-        per_page = _per_page_sampling(sampling, seeds, P)
+        per_page = per_page_sampling(sampling, seeds, P)
         lpn = scores_per_page(logprobs, P)
-        if self._kv is None or self._kv.n_seqs < P:
-            if self._kv is not None:
-                self._kv.free()
-            self.max_pages = max(P, self.max_pages)
-            self._kv = self._kv_alloc(self.max_pages, self.max_tokens)
-        kv = self._kv
-        kv.reset()
-        _set_sampling(kv, per_page)
-        _set_logprobs(kv, lpn)
-        for i0 in range(0, P, prefill_batch):                       # prompts of several pages share the linear layers' GEMMs
-            idx = list(range(i0, min(P, i0 + prefill_batch)))
-            self.engine.prefill_batch(kv, idx, [embeds_list[i] for i in idx], penalty=repetition_penalty)
-        outs = self._decode_rows(kv, list(range(P)), max_new_tokens, eos_token_id, repetition_penalty, check_every)
-        return (outs, _read_scores(kv, lpn, outs)) if any(lpn) else outs
-
-    def _decode_rows(self, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, check_every=16):
-        """The batched decode behind a prefill of the sequences `seqs` (each holds its first id): all unfinished ones as one batch per step, EOS looked
-        for every check_every steps; the ids per sequence, in seqs order, cut at EOS / max_new_tokens."""
-        live = list(seqs)
-        n = 1
-        done = {}
-        while n < max_new_tokens and live:
-            steps = min(check_every, max_new_tokens - n)
-            for _ in range(steps):
-                self.engine.decode(kv, live, penalty=repetition_penalty)
-            n += steps
-            if eos_token_id is not None:
-                for i in list(live):
-                    ids = kv.generated(i)
-                    if eos_token_id in ids:
-                        done[i] = ids[:ids.index(eos_token_id) + 1]
-                        live.remove(i)
-        outs = []
-        for i in seqs:
-            ids = done.get(i)
-            if ids is None:
-                ids = kv.generated(i)[:max_new_tokens]
-                if eos_token_id is not None and eos_token_id in ids:
-                    ids = ids[:ids.index(eos_token_id) + 1]
-            outs.append(ids)
-        return outs
+        kv, seqs = self.kv(P), list(range(P))
+        admit(self.engine, kv, seqs, embeds_list, repetition_penalty, per_page, lpn, prefill_batch)
+        outs = decode_rows(self.engine, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, check_every)
+        return (outs, read_scores(kv, lpn, outs)) if any(lpn) else outs
 
     def _generate_pages_beams(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams):
         """generate_pages with beam search: page i is the beam group of sequences beam_slots(i, B); the done flags are read every check_every steps,
@@ -1026,15 +982,9 @@ class InternVLChatModel:
         P, Bn = len(embeds_list), beams.num_beams
         if P * Bn > 64:
             raise ValueError(f'{P} pages x {Bn} beams = {P * Bn} decode rows: at most 64 (the batched decode kernels)')
-        if self._kv is None or self._kv.n_seqs < P * Bn:
-            if self._kv is not None:
-                self._kv.free()
-            self.max_pages = max(P * Bn, self.max_pages)
-            self._kv = self._kv_alloc(self.max_pages, self.max_tokens)
-        kv = self._kv
+        kv = self.kv(P * Bn)
         for e in embeds_list:
-            if e.shape[0] + max_new_tokens > self.max_tokens:
-                raise ValueError(f'prompt of {e.shape[0]} tokens + {max_new_tokens} new exceeds max_tokens={self.max_tokens}')
+            check_fits(e.shape[0], max_new_tokens, self.max_tokens)
         kv.reset()
         for i in range(P):
             kv.set_beam(beam_slots(i, Bn)[0], Bn, beams.length_penalty, beams.early_stopping, eos_token_id, max_new_tokens)
@@ -1066,201 +1016,6 @@ class InternVLChatModel:
 def beam_slots(page, num_beams):
     """Cache sequences of page `page` when every page of a batch runs `num_beams` beams: consecutive, the group's first sequence first."""
     return list(range(page * num_beams, (page + 1) * num_beams))
-
-
-class PagePipeline:
-    """Two batches of pages in flight.  The batched decode is HBM-bound (weights + KV cache streamed once per step) and leaves the
-    matrix cores idle; the visual stage and the prefill of the NEXT batch are matrix-bound.  A worker thread decodes batch i-1 on
-    its own HIP stream, through a second context that shares this model's weights (Engine.share_weights_from: own workspace, no
-    copy), while the caller runs batch i's visual stage and prefill as usual.  Measured on MI355X: a 63-tile ViT chunk takes 54 ms
-    instead of 50 beside a decode step that takes 26 ms instead of 11, i.e. 1.33x the work per unit time while both run.  The
-    two streams have to be fed by two host threads: one thread alternating between them got a quarter of that (scripts/overlap_probe.py).
-    Per page the ids are those of generate_pages (same kernels, same order per page).
-
-        pipe = model.page_pipeline(max_new_tokens=..., eos_token_id=...)
-        for batch in batches:
-            embeds = ... visual stage of `batch`, as for generate_pages ...
-            outs_prev = pipe.start(embeds)                 # prefill; returns the PREVIOUS batch's ids (None the first time)
-        outs_last = pipe.finish()
-        pipe.close()
-
-    The two KV caches alternate between batches."""
-
-    def __init__(self, model, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0, check_every=16, prefill_batch=16):
-        import queue
-        import threading
-        from .engine import Engine
-        self.m, self.eng = model, model.engine
-        self.closed = False
-        model._pipes.add(self)                        # the model refuses a kv_cache_dtype change while this is open
-        self.max_new_tokens, self.eos, self.penalty = max_new_tokens, eos_token_id, repetition_penalty
-        self.check_every, self.prefill_batch = int(os.environ.get('CR_PIPE_CHECK_EVERY', check_every)), prefill_batch      # (env: development aid, how often the decode thread looks for EOS)
-        self.dec = Engine(self.eng.dims, device=self.eng.device.index, max_pos=self.eng.max_pos)
-        self.dec.share_weights_from(self.eng)
-        # a stream of another priority level also lands on another hardware queue than the caller's (two streams of one level may share one)
-        self.side = torch.cuda.Stream(device=self.eng.device, priority=int(os.environ.get('CR_PIPE_PRIO', '-1')))
-        self.kvs = [None, None]
-        self.turn = 0
-        self.jobs, self.results = queue.Queue(), queue.Queue()
-        self.in_flight = 0
-        self.host_s, self.host_steps = 0.0, 0         # host time the decode thread spent issuing steps (diagnostic)
-        self.row_steps = 0                            # decode rows summed over those steps (diagnostic)
-        self.worker = threading.Thread(target=self._decode_loop, daemon=True)
-        self.worker.start()
-
-    def _kv(self, slot, P):
-        kv = self.kvs[slot]
-        if kv is None or kv.n_seqs < P:
-            if kv is not None:
-                kv.free()
-            kv = self.kvs[slot] = self.m._kv_alloc(max(P, self.m.max_pages), self.m.max_tokens)
-        return kv
-
-    def _decode_loop(self):
-        torch.cuda.set_device(self.eng.device)
-        while True:
-            job = self.jobs.get()
-            if job is None:
-                return
-            kv, P, ready, budgets, lpn = job
-            try:
-                with torch.cuda.stream(self.side):
-                    self.side.wait_event(ready)                        # the prefill that filled this cache, on the caller's stream
-                    live, done, n = list(range(P)), {}, 1
-                    span = [torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)] if os.environ.get('CR_PIPE_MARKS') else None
-                    if span:
-                        span[0].record(self.side)
-                        t_first = time.perf_counter()
-                    while n < self.max_new_tokens and live:
-                        steps = min(self.check_every, self.max_new_tokens - n)
-                        t0 = time.perf_counter()
-                        for _ in range(steps):
-                            self.dec.decode(kv, live, penalty=self.penalty)
-                        self.host_s += time.perf_counter() - t0
-                        self.host_steps += steps
-                        self.row_steps += steps * len(live)
-                        n += steps
-                        if budgets is not None:
-                            for i in list(live):
-                                if n >= budgets[i]:
-                                    done[i] = kv.generated(i)[:budgets[i]]
-                                    if self.eos is not None and self.eos in done[i]:
-                                        done[i] = done[i][:done[i].index(self.eos) + 1]
-                                    live.remove(i)
-                        if self.eos is not None:
-                            for i in list(live):
-                                ids = kv.generated(i)                  # synchronises the side stream only
-                                if self.eos in ids:
-                                    done[i] = ids[:ids.index(self.eos) + 1]
-                                    live.remove(i)
-                    if span:
-                        t_issued = time.perf_counter()
-                        span[1].record(self.side)
-                        span[1].synchronize()
-                        print(f'[marks] decode of a batch: {span[0].elapsed_time(span[1]):.0f} ms on the GPU, all steps issued after {1e3 * (t_issued - t_first):.0f} ms of host time',
-                              file=sys.stderr, flush=True)
-                    outs = []
-                    for i in range(P):
-                        ids = done.get(i)
-                        if ids is None:
-                            ids = kv.generated(i)[:self.max_new_tokens if budgets is None else budgets[i]]
-                            if self.eos is not None and self.eos in ids:
-                                ids = ids[:ids.index(self.eos) + 1]
-                        outs.append(ids)
-                    if any(lpn):
-                        outs = (outs, _read_scores(kv, lpn, outs))
-                self.results.put(outs)
-            except BaseException as e:                                 # hand the failure to the caller's thread
-                self.results.put(e)
-
-    def _collect(self):
-        if not self.in_flight:
-            return None
-        self.in_flight -= 1
-        out = self.results.get()
-        if isinstance(out, BaseException):
-            raise out
-        return out
-
-    def start(self, embeds_list, budgets=None, sampling=None, seeds=None, logprobs=0):
-        """Prefill a batch on the caller's stream and hand it to the decode thread; returns the previous batch's ids (None if there
-        was none), waiting for them if they are not there yet.  budgets: optional per-page max_new_tokens (<= the pipeline's): a page
-        leaves the batch at the first EOS check at or past its budget and its ids are cut there, as its own generate_pages call would.
-        sampling / seeds / logprobs: as generate_pages takes them; a batch started with a non-zero logprobs is returned as (ids, scores)."""
-        P = len(embeds_list)
-        per_page = _per_page_sampling(sampling, seeds, P)
-        lpn = scores_per_page(logprobs, P)
-        # The OTHER slot may be under the worker's decode right now (the previous batch, not collected yet): it is only ever
-        # CREATED here, on the first batch (28 GB at 64 pages: not inside a later step), never regrown -- a batch larger than it
-        # holds regrows it when that slot's turn comes, i.e. after _collect() has returned the batch that last used it.
-        if self.kvs[self.turn ^ 1] is None:
-            self._kv(self.turn ^ 1, P)
-        kv = self._kv(self.turn, P)                # last used two batches ago, and that batch has been collected
-        self.turn ^= 1
-        kv.reset()
-        _set_sampling(kv, per_page)
-        _set_logprobs(kv, lpn)
-        for i0 in range(0, P, self.prefill_batch):
-            idx = list(range(i0, min(P, i0 + self.prefill_batch)))
-            self.eng.prefill_batch(kv, idx, [embeds_list[i] for i in idx], penalty=self.penalty)
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream())
-        prev = self._collect()
-        self.jobs.put((kv, P, ready, None if budgets is None else [min(int(b), self.max_new_tokens) for b in budgets], lpn))
-        self.in_flight += 1
-        return prev
-
-    def finish(self):
-        return self._collect()
-
-    def close(self):
-        if self.worker is not None:
-            while self.in_flight:
-                self._collect()
-            self.jobs.put(None)
-            self.worker.join()
-            self.worker = None
-        for kv in self.kvs:
-            if kv is not None:
-                kv.free()
-        self.kvs = [None, None]
-        if self.dec is not None:
-            self.dec.close()
-            self.dec = None
-        self.closed = True
-
-
-def _per_page_sampling(sampling, seeds, P):
-    """[(SamplingParams, seed) or None] per page from generate_pages' sampling / seeds arguments."""
-    if sampling is None:
-        return None
-    sps = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * P
-    if len(sps) != P:
-        raise ValueError(f'sampling: {len(sps)} entries for {P} pages')
-    if seeds is None:
-        seeds = page_seeds(P)
-    if len(seeds) != P:
-        raise ValueError(f'seeds: {len(seeds)} entries for {P} pages')
-    return [None if sp is None else (sp, int(sd)) for sp, sd in zip(sps, seeds)]
-
-
-def _set_sampling(kv, per_page):
-    """The sampled pages' state, after the cache's reset and before the prefill (which makes every page's first pick)."""
-    for i, e in enumerate(per_page or ()):
-        if e is not None:
-            kv.set_sampling(i, e[0].temperature, e[0].top_k, e[0].top_p, e[1])
-
-
-def _set_logprobs(kv, lpn):
-    """The scored pages' state, after the cache's reset and before the prefill (whose pick is every page's step 0)."""
-    for i, n in enumerate(lpn):
-        if n:
-            kv.set_logprobs(i, n)
-
-
-def _read_scores(kv, lpn, outs):
-    """TokenScores of the scored pages (None for the others), cut to the ids returned; on the current stream."""
-    return [TokenScores.read(kv, i, len(ids)) if n else None for i, (n, ids) in enumerate(zip(lpn, outs))]
 
 
 def load_boxes_json(path):

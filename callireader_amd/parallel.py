@@ -455,6 +455,7 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     from PIL import Image
     from . import ordering
     from .conversation import get_conv_template
+    from .generation import reply_text
     from .preprocess import plan_page, plan_chars_array, jobs_array
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -561,7 +562,7 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     pseudo_all = finish()
     embeds = [eng.embed_splice(ids[p], feats[p], pseudo_all[off[p]:off[p + 1]], img_id=model.img_context_token_id, ref_id=model.aligned_token_id) for p in mine]
     outs = model.generate_pages(embeds, max_new, eos, repetition_penalty) if embeds else []
-    result = {p: tokenizer.batch_decode(torch.tensor([o]), skip_special_tokens=True)[0].split(template.sep)[0].strip() for p, o in zip(mine, outs)}
+    result = {p: reply_text(tokenizer, o, template.sep) for p, o in zip(mine, outs)}
     if world > 1:
         got = [None] * world
         dist.all_gather_object(got, result, group=group)

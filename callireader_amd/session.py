@@ -26,11 +26,9 @@ same trunk state (greedy decoding; sampled branches have their own seeds: ask_ma
 Not here (NotImplementedError): num_beams > 1 (cr_kv_set_beam needs empty sequences: use chat_ocr(history=...)), e4m3 caches (no bf16 prefix
 to continue from: use kv_cache_dtype='bf16'), region_wise (one turn), and the pipelines / sharded entry points, which own their caches.
 """
-import numpy as np
 import torch
-from PIL import Image
 
-from .preprocess import load_image, plan_page
+from .generation import check_fits, decode_rows, reply_text
 from .sampling import page_seeds, parse_beams
 
 
@@ -80,15 +78,7 @@ class PageSession:
     def open(cls, model, tokenizer, detect_model, img_path, use_p=True, drop_zero=False, hard_vq=False, boxes=None, max_branches=1, verbose=False):
         """What chat_ocr does per call before its prompt (:653-688), once: decode the page, its tiles, extract_feature, calli_align."""
         _refuse_e4m3(model)                                                                   # before any visual work
-        try:
-            page = Image.open(img_path).convert('RGB') if isinstance(img_path, str) else img_path.convert('RGB')
-            if model.gpu_preprocess:
-                jobs, n = plan_page(*page.size)
-                pixel_values = model.engine.preprocess(torch.from_numpy(np.array(page)), jobs, n)
-            else:
-                pixel_values = load_image(page).to(torch.bfloat16).to(model.device)
-        except Exception:
-            raise FileNotFoundError                                                           # :670-671
+        page, pixel_values = model._open_page(img_path)
         out_tokens = None
         if use_p:
             out_tokens, _ = model.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
@@ -140,8 +130,7 @@ class PageSession:
         question, history, template, ids, gc = self._prompt(question, history, generation_config, return_scores)
         p = plan_prefix(self.cached_ids, ids)
         max_new = self.m._gen_args(gc, allow_beams=True)[0]                                   # validated here: a refused turn leaves the trunk as it was
-        if len(ids) + max_new > self.m.max_tokens:                                            # before the trunk changes
-            raise ValueError(f'prompt of {len(ids)} tokens + {max_new} new exceeds max_tokens={self.m.max_tokens}')
+        check_fits(len(ids), max_new, self.m.max_tokens)                                      # before the trunk changes
         self.kv.truncate(0, p)
         self.cached_ids = self.cached_ids[:p]
         embeds = self._embed(ids, p)
@@ -166,8 +155,7 @@ class PageSession:
         gc, template = built[0][4], built[0][2]
         max_new, eos, sp = m._gen_args(gc, allow_beams=True)
         for _, _, _, ids, _ in built:
-            if len(ids) + max_new > m.max_tokens:
-                raise ValueError(f'prompt of {len(ids)} tokens + {max_new} new exceeds max_tokens={m.max_tokens}')
+            check_fits(len(ids), max_new, m.max_tokens)
         if not self.cached_ids:                  # an empty trunk: what the prompts share goes into it first; the pick that prefill appends is dropped
             first = built[0][3]
             shared = min(min(common_prefix(first, b[3]) for b in built), min(len(b[3]) for b in built) - 1)
@@ -191,5 +179,5 @@ class PageSession:
         tails = [self._embed(b[3], p) for b, p in zip(built, prefixes)]
         self.rows_prefilled.append(sum(len(b[3]) - p for b, p in zip(built, prefixes)))
         m.engine.prefill_batch(kv, branches, tails, penalty=repetition_penalty)
-        outs = m._decode_rows(kv, branches, max_new, eos, repetition_penalty)
-        return [self.tokenizer.batch_decode(torch.tensor([o]), skip_special_tokens=True)[0].split(template.sep)[0].strip() for o in outs]
+        outs = decode_rows(m.engine, kv, branches, max_new, eos, repetition_penalty)
+        return [reply_text(self.tokenizer, o, template.sep) for o in outs]
