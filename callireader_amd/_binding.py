@@ -25,6 +25,16 @@ class ModelDesc(C.Structure):
 
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_i32p = C.POINTER(C.c_int32)
+
+
+class Constraints(C.Structure):
+    """cr_constraints: host arrays (None: absent) with their counts"""
+    _fields_ = [('no_repeat_ngram_size', C.c_int32), ('min_new_tokens', C.c_int32), ('eos_id', C.c_int32),
+                ('n_suppress', C.c_int32), ('suppress', _i32p), ('n_begin_suppress', C.c_int32), ('begin_suppress', _i32p),
+                ('n_allowed', C.c_int32), ('allowed', _i32p), ('n_bad_words', C.c_int32), ('bad_word_ids', _i32p),
+                ('bad_word_offsets', _i32p), ('reserved', C.c_int32 * 8)]
+
 
 # name -> (restype, argtypes): exactly the prototypes of include/callireader_hip.h
 SIGNATURES = {
@@ -62,6 +72,7 @@ SIGNATURES = {
     'cr_kv_set_sampling': (i32, [vp, i32, f32, i32, f32, C.c_uint64, vp]),
     'cr_kv_set_logprobs': (i32, [vp, i32, i32, vp]),
     'cr_kv_logprobs': (i32, [vp, i32, vp, vp, vp, i32, vp]),
+    'cr_kv_set_constraints': (i32, [vp, i32, C.POINTER(Constraints), vp]),
     'cr_kv_set_beam': (i32, [vp, i32, i32, f32, i32, i32, i32, vp]),
     'cr_kv_beam_result': (i32, [vp, i32, C.POINTER(i64), i32, C.POINTER(f32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]),
     'cr_kv_beam_reorder': (i32, [vp, i32, i32, C.POINTER(C.c_int32), i32, vp]),
@@ -87,6 +98,7 @@ SIGNATURES = {
     'cr_op_attention_segments': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
     'cr_op_decode_attention_scratch_floats': (i64, [i32, i32]),
     'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'cr_op_constrain': (i32, [C.POINTER(Constraints), vp, i32, i32, vp, vp, i32, vp, vp]),
     'cr_op_logprobs': (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     'cr_op_beam_step': (i32, [vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp]),
     'cr_op_decode_attention': (i32, [i32, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),

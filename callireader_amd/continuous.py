@@ -126,11 +126,12 @@ class ContinuousPipeline:
         self.worker.start()
 
     # ---- caller side ----------------------------------------------------------------------------
-    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None, logprobs=0):
+    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None, logprobs=0, constraints=None):
         """Queue one page's prompt embeddings ([S, hidden] on the device) with its budget of new ids (default, and at most, the pipeline's);
         returns its ticket.  Prefills a group when one is complete.  ValueError for a budget the pipeline cannot take.  sampling (a
         sampling.SamplingParams) with a 64-bit `seed`: the page samples (its sequence's state is set after its reset, before its prefill);
-        None: greedy.  logprobs: 0, or the number of alternatives (1..8) to record per generated id: the page's result is (ids, TokenScores)."""
+        None: greedy.  logprobs: 0, or the number of alternatives (1..8) to record per generated id: the page's result is (ids, TokenScores).
+        constraints (a constraints.Constraints, greedy pages only): installed after the sequence's reset, before its prefill."""
         t0 = time.perf_counter()
         self._raise_worker_error()
         logprobs = check_top_n(logprobs, 'logprobs', allow_zero=True)
@@ -143,7 +144,11 @@ class ContinuousPipeline:
         self.next_ticket += 1
         if sampling is not None and seed is None:
             raise ValueError('a sampled page needs its seed')
-        self.waiting.append((ticket, embeds, budget, sampling, seed, logprobs))
+        if constraints is not None and sampling is not None:
+            raise NotImplementedError('logits constraints on a sampled page are not implemented (greedy decoding only)')
+        if constraints is not None and not constraints.active:
+            constraints = None
+        self.waiting.append((ticket, embeds, budget, sampling, seed, logprobs, constraints))
         self.outstanding += 1
         self._pump(flush=False, block=False)
         self.stats['caller_host_s'] += time.perf_counter() - t0
@@ -171,7 +176,7 @@ class ContinuousPipeline:
                 yield item
 
     def map(self, items, errors='raise'):
-        """items: an iterable of (key, embeds, budget or None[, sampling, seed[, logprobs]]), consumed as pages are admitted (a generator can compute the next pages' embeddings
+        """items: an iterable of (key, embeds, budget or None[, sampling, seed[, logprobs[, constraints]]]), consumed as pages are admitted (a generator can compute the next pages' embeddings
         meanwhile); yields (key, ids) as pages finish.  errors='return': a page whose budget the pipeline refuses yields (key, that ValueError) and
         the others run; 'raise': the ValueError propagates."""
         keys = {}
@@ -237,7 +242,7 @@ class ContinuousPipeline:
             seqs = [self.free.popleft() for _ in range(k)]
             self.scored.update((s, g[5]) for s, g in zip(seqs, group) if g[5])
             admit(self.eng, self.kv, seqs, [g[1] for g in group], self.penalty, per_page=[None if g[3] is None else (g[3], g[4]) for g in group],
-                  lpn=[g[5] for g in group], prefill_batch=k, reset_each=True)
+                  lpn=[g[5] for g in group], prefill_batch=k, reset_each=True, constraints=[g[6] for g in group])
             ready = self.ops.record(self.ops.current())
             for s, (ticket, *_) in zip(seqs, group):
                 self.owner[s] = ticket

@@ -24,6 +24,7 @@ __device__ __forceinline__ void kv_clear_state(const KvState& s, int seq, int n_
     s.stop[1 + 3 * s.n_seqs + seq] = 0;             // no budget
     s.temp[seq] = 0.f;                              // greedy
     if (s.lpn) { s.lpn[seq] = 0; s.lpdone[seq] = 0; }
+    if (s.con_on) s.con_on[seq] = 0;
 }
 
 __global__ __launch_bounds__(64) void kv_truncate_kernel(KvState s, KvSeqs seqs, int n_tokens) {

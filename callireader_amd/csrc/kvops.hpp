@@ -4,17 +4,19 @@
 
 constexpr int KV_FORK_MAX = 64;        // destinations of one fork (the batched decode takes 64 rows)
 
-// The per-sequence device state of a cache that cr_kv_reset clears (llm.hip: cr_kv).  lpn / lpdone are NULL while no sequence has switched scores on.
+// The per-sequence device state of a cache that cr_kv_reset clears (llm.hip: cr_kv).  lpn / lpdone are NULL while no sequence has switched scores on,
+// con_on while none has switched constraints on.
 struct KvState {
     int32_t* len; int32_t* ngen;
     int32_t* stop; int n_seqs;         // the stop block: [1 + n + s] stop count, [1 + 2n + s] EOS id, [1 + 3n + s] budget
     float* temp;                       // sampling temperature (0: greedy)
     int32_t* lpn; int32_t* lpdone;
+    int32_t* con_on;                   // logits constraints (0: off)
 };
 // The sequences a launch writes, by value: no staging buffer, so calls on different streams never share one
 struct KvSeqs { int32_t n; int32_t seq[KV_FORK_MAX]; };
 
-// every listed sequence: length n_tokens, no ids, no criteria and no stop, greedy, scores off
+// every listed sequence: length n_tokens, no ids, no criteria and no stop, greedy, scores off, constraints off
 int launch_kv_truncate(const KvState& s, const KvSeqs& seqs, int n_tokens, hipStream_t st);
 // bf16 cache [layers][n_seqs][8][max_tokens][128] (k, v): positions [0, n_tokens) of `src` go to every listed sequence, every layer, KV head, K and V, and the
 // listed sequences get launch_kv_truncate's state -- one launch.  per_layer = n_seqs * 8 * max_tokens * 128 elements.

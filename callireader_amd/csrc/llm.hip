@@ -17,6 +17,7 @@
 #include "attention.hpp"
 #include "beam.hpp"
 #include "ctx.hpp"
+#include "constrain.hpp"
 #include "decode.hpp"
 #include "kvops.hpp"
 #include "misc.hpp"
@@ -53,6 +54,12 @@ struct cr_kv {
     int32_t *d_lpn = nullptr, *d_lpdone = nullptr, *d_top_id = nullptr;
     float *d_lp = nullptr, *d_top_lp = nullptr;
     std::vector<char> scored;
+    // logits constraints (cr_kv_set_constraints; constrain.hip), allocated by the first call that switches a sequence on: d_con_on int32[n] (0: off), d_con
+    // [n][con_stride] int32 = one block per sequence (constrain.hpp).  `constrained` mirrors d_con_on on the host: a launch whose rows are all off launches
+    // nothing new
+    int32_t *d_con_on = nullptr, *d_con = nullptr;
+    size_t con_stride = 0;
+    std::vector<char> constrained;
     // beam groups (cr_kv_set_beam; beam.hip), allocated by the first call: d_beam BeamState[n] (a group's state at its first sequence), d_bgrp int32[n] = first
     // sequence of the sequence's group (< 0: none), d_bfin [n][gen_cap] ids of the finished slots.  `bgrp` / `bnum` mirror the group and its size on the host:
     // a launch without a group launches nothing new
@@ -890,6 +897,12 @@ static BeamCache beam_cache(const cr_kv* kv) {
     return {kv->k, kv->v, (int64_t)kv->n_seqs * 8 * kv->max_tokens * 128, kv->layers, kv->max_tokens};
 }
 
+static bool any_constrained(const cr_kv* kv, const int32_t* seqs, int n) {
+    if (!kv->d_con) return false;
+    for (int i = 0; i < n; i++) if (kv->constrained[seqs[i]]) return true;
+    return false;
+}
+
 static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
     if (!kv->d_lpn) return false;
     for (int i = 0; i < n; i++) if (kv->scored[seqs[i]]) return true;
@@ -897,10 +910,13 @@ static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
 }
 
 // What follows the LM head in a prefill and in a decode step: the logits out, then the pick (greedy or sampled) appends every row's id and adds len_add
-// to its cached length, then the scores of the rows the pick has just chosen from (h.lg: the penalised rows it left) go into the sequences' slots
+// to its cached length (in front of it, after the raw rows have gone out, the constraint masks of the rows that have any: the pick, the penalty's copy h.lg0
+// and the scores all see the masked row, the caller the raw one), then the scores of the rows the pick has just chosen from (h.lg: the penalised rows it left) go into the sequences' slots
 static int pick_rows(cr_kv* kv, const HeadBufs& h, const int32_t* seqs, const int32_t* d_seqs, float penalty, int len_add, float* out, hipStream_t st, bool prefill) {
     const int n = h.n, V = h.V;
     if (out) CR_HIP(hipMemcpyAsync(out, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
+    if (any_constrained(kv, seqs, n))
+        CR_TRY(launch_constrain(h.lg, V, V, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, ConTables{kv->d_con_on, kv->d_con, (int64_t)kv->con_stride, 1}, st));
     if (h.lg0) CR_HIP(hipMemcpyAsync(h.lg0, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
     const int32_t* bgrp = h.beam ? kv->d_bgrp : nullptr;      // beam rows are skipped by the picks and taken by beam_rows below
     if (beam_row_count(kv, seqs, n) == n) {}                 // nothing but beams: no pick at all
@@ -1069,6 +1085,7 @@ int cr_kv_alloc_ex(cr_ctx* c, int n_seqs, int max_tokens, int format, cr_kv** ou
     CR_HIP(hipMemset(kv->d_samp, 0, (size_t)n_seqs * 24));                           // greedy
     kv->sampled.assign(n_seqs, 0);
     kv->scored.assign(n_seqs, 0);
+    kv->constrained.assign(n_seqs, 0);
     kv->bgrp.assign(n_seqs, -1); kv->bnum.assign(n_seqs, 0);
     kv->len.assign(n_seqs, 0); kv->ngen.assign(n_seqs, 0);
     *out = kv;
@@ -1093,6 +1110,8 @@ int cr_kv_free(cr_kv* kv) {
     if (kv->d_lp) hipFree(kv->d_lp);
     if (kv->d_top_id) hipFree(kv->d_top_id);
     if (kv->d_top_lp) hipFree(kv->d_top_lp);
+    if (kv->d_con_on) hipFree(kv->d_con_on);
+    if (kv->d_con) hipFree(kv->d_con);
     if (kv->d_beam) hipFree(kv->d_beam);
     if (kv->d_bgrp) hipFree(kv->d_bgrp);
     if (kv->d_bfin) hipFree(kv->d_bfin);
@@ -1121,7 +1140,8 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
         CR_HIP(hipMemsetAsync(kv->d_lpn + s0, 0, (size_t)n * 4, st));
         CR_HIP(hipMemsetAsync(kv->d_lpdone + s0, 0, (size_t)n * 4, st));
     }
-    for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; }
+    if (kv->d_con_on) CR_HIP(hipMemsetAsync(kv->d_con_on + s0, 0, (size_t)n * 4, st));   // constraints off
+    for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; kv->constrained[s] = 0; }
     if (kv->d_beam)                                                                     // a beam group goes as a whole with any of its sequences
         for (int s = s0; s < s0 + n; s++) {
             const int f = kv->bgrp[s];
@@ -1135,7 +1155,7 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
     return CR_OK;
 }
 
-static KvState kv_state(cr_kv* kv) { return {kv->d_len, kv->d_ngen, kv->d_stop, kv->n_seqs, kv->d_temp, kv->d_lpn, kv->d_lpdone}; }
+static KvState kv_state(cr_kv* kv) { return {kv->d_len, kv->d_ngen, kv->d_stop, kv->n_seqs, kv->d_temp, kv->d_lpn, kv->d_lpdone, kv->d_con_on}; }
 
 int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream) {
     if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_truncate: bad sequence");
@@ -1146,7 +1166,7 @@ int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream) {
     KvSeqs one{};
     one.n = 1; one.seq[0] = seq;
     CR_TRY(launch_kv_truncate(kv_state(kv), one, n_tokens, (hipStream_t)stream));
-    kv->len[seq] = n_tokens; kv->ngen[seq] = 0; kv->sampled[seq] = 0; kv->scored[seq] = 0;
+    kv->len[seq] = n_tokens; kv->ngen[seq] = 0; kv->sampled[seq] = 0; kv->scored[seq] = 0; kv->constrained[seq] = 0;
     return CR_OK;
 }
 
@@ -1169,7 +1189,7 @@ int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_to
         if (kv->bgrp[d.seq[j]] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_fork: destination %d belongs to the beam group of sequence %d", d.seq[j], kv->bgrp[d.seq[j]]);
     CR_HIP(hipSetDevice(kv->ctx->device));
     CR_TRY(launch_kv_fork(kv_state(kv), kv->k, kv->v, (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD, kv->layers, kv->max_tokens, src, d, n_tokens, (hipStream_t)stream));
-    for (int j = 0; j < n_dst; j++) { const int s = d.seq[j]; kv->len[s] = n_tokens; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; }
+    for (int j = 0; j < n_dst; j++) { const int s = d.seq[j]; kv->len[s] = n_tokens; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; kv->constrained[s] = 0; }
     return CR_OK;
 }
 
@@ -1230,6 +1250,40 @@ int cr_kv_set_logprobs(cr_kv* kv, int seq, int top_n, void* stream) {
     return CR_OK;
 }
 
+int cr_kv_set_constraints(cr_kv* kv, int seq, const cr_constraints* c, void* stream) {
+    if (c) CR_TRY(con_check(c, -1, "cr_kv_set_constraints"));                           // the values first: no cache and no device needed
+    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_constraints: bad sequence");
+    if (c) CR_TRY(con_check(c, kv->ctx->d.vocab, "cr_kv_set_constraints"));
+    if (c && kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_set_constraints: sequence %d belongs to a beam group (no constraints with beams)", seq);
+    if (!kv->d_con && !c) return CR_OK;                                                 // never switched on: nothing to switch off
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int V = kv->ctx->d.vocab;
+    if (!kv->d_con) {
+        const size_t N = kv->n_seqs, stride = con_block_ints(V);
+        if (hipMalloc((void**)&kv->d_con_on, N * 4) != hipSuccess || hipMalloc((void**)&kv->d_con, N * stride * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            if (kv->d_con_on) hipFree(kv->d_con_on);
+            kv->d_con_on = nullptr; kv->d_con = nullptr;
+            return cr_fail(CR_ERR_NOMEM, "cr_kv_set_constraints: %zu bytes of constraint blocks", N * (stride + 1) * 4);
+        }
+        kv->con_stride = stride;
+        CR_HIP(hipMemsetAsync(kv->d_con_on, 0, N * 4, st));
+        CR_HIP(hipStreamSynchronize(st));                                               // once per cache: in place before a call on any other stream
+    }
+    if (!c) {
+        CR_HIP(hipMemsetAsync(kv->d_con_on + seq, 0, 4, st));
+        kv->constrained[seq] = 0;
+        return CR_OK;
+    }
+    std::vector<int32_t> blk;
+    con_pack(c, V, blk);
+    CR_HIP(hipMemcpyAsync(kv->d_con + (size_t)seq * kv->con_stride, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
+    CR_HIP(hipMemsetAsync(kv->d_con_on + seq, 1, 4, st));                               // != 0: on
+    kv->constrained[seq] = 1;
+    return CR_OK;
+}
+
 int cr_kv_logprobs(cr_kv* kv, int seq, float* lp, int32_t* top_ids, float* top_lp, int max, void* stream) {
     if (!kv || !lp || !top_ids || !top_lp || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_logprobs: bad argument");
     if (!kv->d_lpn || !kv->scored[seq]) return cr_fail(CR_ERR_STATE, "cr_kv_logprobs: sequence %d has token scores switched off (cr_kv_set_logprobs)", seq);
@@ -1279,6 +1333,7 @@ int cr_kv_set_beam(cr_kv* kv, int first_seq, int num_beams, float length_penalty
     for (int j = 0; j < num_beams; j++) {
         const int s = first_seq + j;
         if (kv->sampled[s] || kv->scored[s]) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: sequence %d samples or records token scores", s);
+        if (kv->constrained[s]) return cr_fail(CR_ERR_STATE, "cr_kv_set_beam: sequence %d has logits constraints (no constraints with beams: cr_kv_set_constraints(NULL) first)", s);
         if (kv->bgrp[s] >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: sequence %d already belongs to the group of %d (cr_kv_reset first)", s, kv->bgrp[s]);
         if (kv->len[s] != 0 || kv->ngen[s] != 0) return cr_fail(CR_ERR_STATE, "cr_kv_set_beam: sequence %d holds tokens (call after cr_kv_reset, before the prefill)", s);
     }

@@ -326,6 +326,16 @@ class KVCache:
         B.check(B.lib.cr_kv_set_sampling(self._h, seq, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
                 'cr_kv_set_sampling')
 
+    def set_constraints(self, seq, constraints):
+        """cr_kv_set_constraints on the current stream: the sequence's later picks (its prefill's included) choose among the ids `constraints`
+        (a constraints.Constraints) leaves; None switches them off (the default, what reset / truncate / fork restore).  Call after reset(seq) and
+        before the sequence's prefill."""
+        if constraints is None:
+            B.check(B.lib.cr_kv_set_constraints(self._h, int(seq), None, _stream()), 'cr_kv_set_constraints')
+            return
+        c, _keep = c_constraints(constraints)
+        B.check(B.lib.cr_kv_set_constraints(self._h, int(seq), C.byref(c), _stream()), 'cr_kv_set_constraints')
+
     def poll_finished(self, out):
         """cr_kv_poll_finished: enqueue on the current stream an asynchronous copy of the finished queue into `out`, a pinned int32 CPU tensor of
         at least 1 + 2 n_seqs entries ([0] count pushed, [1 + k % n_seqs] the k-th sequence pushed, [1 + n_seqs + s] stop count of s).  Read it
@@ -397,6 +407,25 @@ class KVCache:
             self.free()
         except Exception:
             pass
+
+
+def c_constraints(c):
+    """(cr_constraints of a constraints.Constraints, the ctypes arrays it points to: keep them alive across the call)."""
+    def arr(ids):
+        return (C.c_int32 * len(ids))(*ids) if ids else None
+    sup, beg = arr(c.suppress_tokens), arr(c.begin_suppress_tokens)
+    alw = arr(c.allowed_token_ids) if c.allowed_token_ids is not None else None
+    flat = [t for w in c.bad_words_ids for t in w]
+    offs = [0]
+    for w in c.bad_words_ids:
+        offs.append(offs[-1] + len(w))
+    bw, bo = arr(flat), (arr(offs) if c.bad_words_ids else None)
+    out = B.Constraints(no_repeat_ngram_size=c.no_repeat_ngram_size, min_new_tokens=c.min_new_tokens,
+                        eos_id=-1 if c.eos_token_id is None else c.eos_token_id, n_suppress=len(c.suppress_tokens), suppress=sup,
+                        n_begin_suppress=len(c.begin_suppress_tokens), begin_suppress=beg,
+                        n_allowed=len(c.allowed_token_ids) if c.allowed_token_ids is not None else 0, allowed=alw,
+                        n_bad_words=len(c.bad_words_ids), bad_word_ids=bw, bad_word_offsets=bo)
+    return out, (sup, beg, alw, bw, bo)
 
 
 # ---- single operators (tests / profiling) ----
@@ -611,6 +640,30 @@ def op_sample(eng, logits, temperature, top_k, top_p, seed, step, history=None, 
     B.check(B.lib.cr_op_sample(eng._h, _p(lg), n, V, _p(hist), cap, _p(hl), float(penalty), _p(t), _p(k), _p(p), _p(sd), _p(st), _p(ids), _p(kept),
                                _stream()), 'cr_op_sample')
     return ids, kept
+
+
+def op_constrain(logits, constraints, history=None, hist_len=None, seqs=None):
+    """cr_op_constrain: the constraint kernel on given fp32 rows [n, vocab] (a contiguous device tensor, MODIFIED in place and returned): row r is
+    masked by `constraints` (a constraints.Constraints) against the history of s = seqs[r] (default r): history [n, cap] int64 with hist_len[s] ids.
+    Synchronises the current stream."""
+    assert logits.is_cuda and logits.is_contiguous() and logits.dtype == torch.float32 and logits.dim() == 2
+    n, V = logits.shape
+    dev = logits.device
+    if history is None:
+        hist, cap, hl = None, 0, torch.zeros(n, dtype=torch.int32, device=dev)
+    else:
+        hist = history.to(dev, torch.int64).contiguous()
+        cap = hist.shape[1]
+        hl = (torch.full((n,), cap, dtype=torch.int32) if hist_len is None else torch.as_tensor(hist_len, dtype=torch.int32).reshape(-1)).to(dev).contiguous()
+        assert hist.shape[0] == n and hl.numel() == n
+    sq = None
+    if seqs is not None:
+        sq_host = [int(x) for x in seqs]
+        assert len(sq_host) == n and all(0 <= x < n for x in sq_host)        # the C entry cannot see the device array
+        sq = torch.tensor(sq_host, dtype=torch.int32).to(dev)
+    c, _keep = c_constraints(constraints)
+    B.check(B.lib.cr_op_constrain(C.byref(c), _p(logits), n, V, _p(sq), _p(hist), cap, _p(hl), _stream()), 'cr_op_constrain')
+    return logits
 
 
 BEAM_WORDS = 64          # four-byte words of a beam group's device state (include/callireader_hip.h, cr_op_beam_step)

@@ -372,6 +372,8 @@ def build_parser():
     parser.add_argument('--num_beams', type=int, default=1, help='beam search with this many beams (2..8); 1: the greedy default')
     parser.add_argument('--length_penalty', type=float, default=None, help='with --num_beams > 1 (default 1.0)')
     parser.add_argument('--early_stopping', type=str, default=None, choices=('false', 'true', 'never'), help='with --num_beams > 1 (default false)')
+    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, metavar='N', help='greedy decoding: no n-gram of N ids appears twice in a response (0: off)')
+    parser.add_argument('--min_new_tokens', type=int, default=0, metavar='N', help='greedy decoding: a response has at least N ids before it may end (0: off)')
     parser.add_argument('--reuse_page', action='store_true', help='choice / bilingual / intent: run both turns of a page on one page session (session.PageSession: the visual '
                                                                   'stage once, the second turn prefills only its new rows); greedy or sampled, bf16 cache, no beams')
     parser.add_argument('--allow_no_t2s', action='store_true', help='run without opencc (responses stay unconverted: scores not comparable with the reference\'s)')
@@ -421,8 +423,9 @@ def main(argv=None):
         fp8(True)
     tokenizer = InternLM2Tokenizer.from_pretrained(args.model)
     generation_config = dict(num_beams=1, max_new_tokens=1024, do_sample=False)
-    from .inference import beam_config
+    from .inference import beam_config, constraint_config
     generation_config.update(beam_config(args))
+    generation_config.update(constraint_config(args))
     detect_model = load_detector(args.params)
     common = (args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose)
     if args.type != 'full_page':

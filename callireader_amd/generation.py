@@ -37,10 +37,13 @@ def per_page_sampling(sampling, seeds, P):
     return [None if sp is None else (sp, int(sd)) for sp, sd in zip(sps, seeds)]
 
 
-def admit(engine, kv, seqs, embeds_list, penalty, per_page=None, lpn=(), prefill_batch=16, reset_each=False):
+def admit(engine, kv, seqs, embeds_list, penalty, per_page=None, lpn=(), prefill_batch=16, reset_each=False, constraints=()):
     """Put one prompt into each of the sequences `seqs`: reset (the whole cache in one call, or with reset_each only these sequences), then the sampled
-    pages' state (per_page: per_page_sampling's list), then the scored pages' (lpn: alternatives per id, 0 = off), then the prefill in groups of
+    pages' state (per_page: per_page_sampling's list), then the constrained pages' (constraints: a constraints.Constraints or None per page), then the
+    scored pages' (lpn: alternatives per id, 0 = off), then the prefill in groups of
     `prefill_batch` -- prompts of several pages share the linear layers' GEMMs, and the prefill makes every page's first pick (its step 0)."""
+    if any(c is not None and e is not None for c, e in zip(constraints or (), per_page or ())):
+        raise NotImplementedError('logits constraints on a sampled page are not implemented (greedy decoding only)')
     if reset_each:
         for s in seqs:
             kv.reset(s)
@@ -49,6 +52,9 @@ def admit(engine, kv, seqs, embeds_list, penalty, per_page=None, lpn=(), prefill
     for s, e in zip(seqs, per_page or ()):
         if e is not None:
             kv.set_sampling(s, e[0].temperature, e[0].top_k, e[0].top_p, e[1])
+    for s, c in zip(seqs, constraints or ()):
+        if c is not None:
+            kv.set_constraints(s, c)
     for s, n in zip(seqs, lpn):
         if n:
             kv.set_logprobs(s, n)

@@ -257,6 +257,8 @@ def build_parser():
     parser.add_argument('--num_beams', type=int, default=1, help='beam search with this many beams (2..8; transformers\' deterministic beam search, on the device); 1: the greedy default')
     parser.add_argument('--length_penalty', type=float, default=None, help='with --num_beams > 1: exponent of the hypothesis length a finished score is divided by (default 1.0)')
     parser.add_argument('--early_stopping', type=str, default=None, choices=('false', 'true', 'never'), help="with --num_beams > 1: generation_config.early_stopping (default false)")
+    parser.add_argument('--no_repeat_ngram_size', type=int, default=0, metavar='N', help='greedy decoding: no n-gram of N ids appears twice in a response (transformers\' no_repeat_ngram_size; 0: off)')
+    parser.add_argument('--min_new_tokens', type=int, default=0, metavar='N', help='greedy decoding: a response has at least N ids before it may end (0: off)')
     parser.add_argument('--fp8_kv', action='store_true',
                         help='e4m3 KV cache for the decode (kv_cache_dtype="e4m3": 0.52x the cache bytes; off by default; a throughput option, not parity-preserving)')
     parser.add_argument('--scores', type=int, nargs='?', const=1, default=0, choices=range(0, 9), metavar='N',
@@ -291,6 +293,7 @@ def main(argv=None):
         generation_config['do_sample'] = True
         generation_config.update({k: getattr(args, k) for k in ('temperature', 'top_k', 'top_p') if getattr(args, k) is not None})
     generation_config.update(beam_config(args))
+    generation_config.update(constraint_config(args))
     if args.seed is not None:
         torch.manual_seed(args.seed)
     detect_model = load_detector(args.params)
@@ -306,6 +309,11 @@ def main(argv=None):
                    continuous=args.continuous, scores=args.scores)
     else:
         raise ValueError('The target should be either a image path or a folder that contain images!')
+
+
+def constraint_config(args):
+    """The generation_config entries of --no_repeat_ngram_size / --min_new_tokens (none without them)."""
+    return {k: getattr(args, k) for k in ('no_repeat_ngram_size', 'min_new_tokens') if getattr(args, k, 0)}
 
 
 if __name__ == '__main__':

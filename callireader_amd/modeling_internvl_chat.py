@@ -25,6 +25,7 @@ from PIL import Image
 from .config import ModelDims, IMG_CONTEXT_TOKEN_ID, ALIGNED_TOKEN_ID, EOS_TOKEN_ID
 from .conversation import get_conv_template
 from .engine import Engine
+from .constraints import parse as constraints_parse, per_page as constraints_per_page
 from .generation import admit, check_fits, decode_rows, per_page_sampling, read_scores, reply_shape, reply_text
 from .pipeline import PagePipeline
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
@@ -249,19 +250,23 @@ class InternVLChatModel:
 
     # ---- generation ----------------------------------------------------------------------------
     def _generate(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, sampling=None, check_every=16, logprobs=0, kv=None, seq=0,
-                  reset=True):
+                  reset=True, constraints=None):
         """transformers 4.45.2 GenerationMixin._sample with num_beams=1 for ONE sequence: greedy (sampling None), or do_sample=True with
         `sampling` (a sampling.SamplingParams; the page's seed is page_seeds(1)[0]); returns only the new ids, EOS included (oracle/generate.py
         documents the semantics).  logprobs = n > 0: returns (ids, scores.TokenScores with n alternatives per id, cut like the ids).
         kv / seq: the cache and sequence to run in (default: the model's own, sequence 0).  reset=False (session.PageSession): the sequence keeps the
         tokens it holds -- the caller has rolled it back with KV.truncate, which leaves no ids and no state -- and `input_embeds` are the rows that
-        continue it."""
+        continue it.  constraints (a constraints.Constraints, greedy only): the masks in front of every pick of this call."""
+        if constraints is not None and sampling is not None:
+            raise NotImplementedError('logits constraints with do_sample=True are not implemented (greedy decoding only)')
         kv = self.kv(1) if kv is None else kv
         if reset:
             kv.reset(seq)
         check_fits(kv.length(seq) + input_embeds.shape[0], max_new_tokens, self.max_tokens)
         if sampling is not None:
             kv.set_sampling(seq, sampling.temperature, sampling.top_k, sampling.top_p, page_seeds(1)[0])
+        if constraints is not None and constraints.active:
+            kv.set_constraints(seq, constraints)
         if logprobs:
             kv.set_logprobs(seq, logprobs)
         self.engine.prefill(kv, seq, input_embeds, penalty=repetition_penalty)
@@ -275,7 +280,10 @@ class InternVLChatModel:
         where: _generate's kv / seq / reset (a session's turn; no beams there)."""
         max_new, eos, sp = self._gen_args(generate_kwargs, allow_beams=True)
         beams = parse_beams(generate_kwargs)
-        if beams is not None and where:
+        cons = constraints_parse(generate_kwargs, eos)          # (NotImplementedError with beams or do_sample)
+        if cons is not None:
+            where = dict(where, constraints=cons)
+        if beams is not None and (where.keys() - {'constraints'}):
             raise NotImplementedError(f'num_beams={beams.num_beams} in a page session: cr_kv_set_beam needs empty sequences (use chat_ocr(history=...))')
         if beams is not None:                      # beam search: the page's beams decode as one batch (generate_pages)
             ids, sc = self.generate_pages([input_embeds], max_new, eos, repetition_penalty, num_beams=beams.num_beams, length_penalty=beams.length_penalty,
@@ -577,6 +585,7 @@ class InternVLChatModel:
         exception object in its slot and the other pages run -- what folder mode's per-image try/except needs (inference.py:55-57).
         return_scores (True, or the number of alternatives per token): returns (responses, scores) with one scores.ResponseScores per page (None for a
         page that failed)."""
+        constraints_parse(generation_config, 0)                 # refused before the visual stage (the EOS id does not change what is refused)
         _, lpn = self._score_args(generation_config, return_scores)
         beams = parse_beams(dict(generation_config, return_scores=return_scores))
         embeds, meta = self._ocr_embeds(tokenizer, detect_model, images, question, generation_config, boxes_list, use_p, drop_zero,
@@ -586,7 +595,7 @@ class InternVLChatModel:
                                        early_stopping=beams.early_stopping)[0] if embeds else []
             return self._answer(tokenizer, outs, meta, False)
         outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, sampling=meta['sampling'],
-                                   seeds=self._ok_seeds(meta), logprobs=lpn) if embeds else []
+                                   seeds=self._ok_seeds(meta), logprobs=lpn, constraints=meta['constraints']) if embeds else []
         return self._answer(tokenizer, outs, meta, return_scores)
 
     def _answer(self, tokenizer, outs, meta, return_scores):
@@ -630,6 +639,7 @@ class InternVLChatModel:
         chat_ocr_pages returns it."""
         if parse_beams(generation_config) is not None:
             raise NotImplementedError('chat_ocr_stream: beam search does not go through PagePipeline (use chat_ocr_pages)')
+        constraints_parse(generation_config, 0)                 # refused before the first batch is pulled
         _, lpn = self._score_args(generation_config, return_scores)
         pipe, pending = None, None
         sampled = sampling_parse(generation_config) is not None
@@ -696,7 +706,8 @@ class InternVLChatModel:
                 if pipe is None:
                     pipe = self.page_pipeline(max_new_tokens=meta['max_new'], eos_token_id=meta['eos'], repetition_penalty=repetition_penalty)
                 prev = pipe.start(embeds, sampling=meta['sampling'],
-                                  seeds=[splitmix64(base + page0 + i) for i in meta['ok']] if sampled else None, logprobs=lpn)
+                                  seeds=[splitmix64(base + page0 + i) for i in meta['ok']] if sampled else None, logprobs=lpn,
+                                  constraints=meta['constraints'])
                 if stats is not None:
                     e = torch.cuda.Event(enable_timing=True)
                     e.record(torch.cuda.current_stream())
@@ -756,6 +767,7 @@ class InternVLChatModel:
         template = get_conv_template(self.template)
         gc = dict(generation_config, eos_token_id=tokenizer.convert_tokens_to_ids(template.sep))      # what _ocr_embeds gives every page
         max_new, eos, sp = self._gen_args(gc)
+        cons = constraints_parse(gc, eos)
         seeds = page_seeds(len(images)) if sp is not None else None
         failed = []
 
@@ -777,7 +789,7 @@ class InternVLChatModel:
                 for sub, (embeds, meta) in parts:
                     failed.extend((sub[k], e) for k, e in meta['failed'].items())
                     for k, emb in zip(meta['ok'], embeds):
-                        yield sub[k], emb, None, sp, (seeds[sub[k]] if sp is not None else None), lpn
+                        yield sub[k], emb, None, sp, (seeds[sub[k]] if sp is not None else None), lpn, cons
 
         def response(ids):
             return reply_text(tokenizer, ids, template.sep)
@@ -872,7 +884,8 @@ class InternVLChatModel:
         generation_config = dict(generation_config)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
         max_new, eos, sp = self._gen_args(generation_config, allow_beams=True)      # (the pipelines that call this have refused beams on entry)
-        meta = {'n': len(images), 'ok': [], 'failed': dict(batch.failed), 'max_new': max_new, 'eos': eos, 'template': template, 'sampling': sp}
+        meta = {'n': len(images), 'ok': [], 'failed': dict(batch.failed), 'max_new': max_new, 'eos': eos, 'template': template, 'sampling': sp,
+                'constraints': constraints_parse(generation_config, eos)}
         if not batch.ok:
             return [], meta
         feeder.hand_over(batch)
@@ -941,7 +954,8 @@ class InternVLChatModel:
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
         max_new, eos, sp = self._gen_args(generation_config)
         outs = self.generate_pages(embeds, max_new, eos, generation_config.get('repetition_penalty', 1.0), sampling=sp,
-                                   seeds=page_seeds(len(embeds)) if sp is not None else None, logprobs=lpn)
+                                   seeds=page_seeds(len(embeds)) if sp is not None else None, logprobs=lpn,
+                                   constraints=constraints_parse(generation_config, eos))
         outs, tss = outs if lpn else (outs, None)
         responses = [reply_text(tokenizer, o, template.sep) for o in outs]
         return (responses, [ResponseScores.build(tokenizer, o, ts) for o, ts in zip(outs, tss)]) if return_scores else responses
@@ -952,7 +966,8 @@ class InternVLChatModel:
         return PagePipeline(self, **kw)
 
     def generate_pages(self, embeds_list, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0,
-                       check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0, num_beams=1, length_penalty=1.0, early_stopping=False):
+                       check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0, num_beams=1, length_penalty=1.0, early_stopping=False,
+                       constraints=None):
         """Prefill every page, then decode all unfinished pages as ONE batch per step: the 14.7 GB of LLM weights are
         streamed once per step for all pages.  Per page the ids equal the single-page greedy result.
         sampling: None (every page greedy), one sampling.SamplingParams for every page, or a list with one entry (or None: greedy) per page;
@@ -962,17 +977,23 @@ class InternVLChatModel:
         page with 0.  A page's scores, like its ids, do not depend on the batch it decodes in.
         num_beams > 1 (with length_penalty and early_stopping, validated as sampling.parse_beams does): beam search, every page's B beams as B rows of the one decode
         batch (P * B <= 64).  The return value is then (ids, sequences_scores): per page the best finished hypothesis, EOS included, and its score.  No
-        sampling and no token scores with beams."""
+        sampling and no token scores with beams.
+        constraints: None, one constraints.Constraints for every page, or a list with one entry (or None) per page: the page's picks choose among the
+        ids its constraints leave (csrc/constrain.hip).  Greedy pages only; a page's ids do not depend on the batch it decodes in, and the other pages of
+        the batch keep their ids bit for bit."""
         P = len(embeds_list)
+        cons = constraints_per_page(constraints, P)
         beams = parse_beams(dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping))
         if beams is not None:
             if sampling is not None or (logprobs and any(scores_per_page(logprobs, P))):
                 raise NotImplementedError('generate_pages: beam search takes neither sampling nor token scores')
+            if any(c is not None for c in cons):
+                raise NotImplementedError('generate_pages: logits constraints with beam search are not implemented (greedy decoding only)')
             return self._generate_pages_beams(embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams)
         per_page = per_page_sampling(sampling, seeds, P)
         lpn = scores_per_page(logprobs, P)
         kv, seqs = self.kv(P), list(range(P))
-        admit(self.engine, kv, seqs, embeds_list, repetition_penalty, per_page, lpn, prefill_batch)
+        admit(self.engine, kv, seqs, embeds_list, repetition_penalty, per_page, lpn, prefill_batch, constraints=cons)
         outs = decode_rows(self.engine, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, check_every)
         return (outs, read_scores(kv, lpn, outs)) if any(lpn) else outs
 

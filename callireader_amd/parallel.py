@@ -378,6 +378,9 @@ def sharded_generate(model, page_tiles, char_tiles, input_ids, *, img_id, ref_id
     Returns {page: ids} for every page (gather_results) or for the pages this rank owns.  Per page the ids are the single-process ids."""
     if generate_kw.get('num_beams', 1) not in (1, None):
         raise NotImplementedError('sharded_generate: beam search is not implemented across GPUs (use generate_pages on one)')
+    from .constraints import parse as constraints_parse
+    if constraints_parse(generate_kw, 0) is not None:
+        raise NotImplementedError('sharded_generate: logits constraints are not implemented across GPUs (use generate_pages on one)')
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     n_pages = len(input_ids)
@@ -449,6 +452,9 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
                                   'rank that decodes it); use chat_ocr_pages / chat_ocr_continuous on one GPU')
     if dict(generation_config).get('num_beams', 1) not in (1, None):
         raise NotImplementedError('chat_ocr_pages_sharded: beam search is not implemented across GPUs (use chat_ocr_pages on one)')
+    from .constraints import parse as constraints_parse
+    if constraints_parse(dict(generation_config), 0) is not None:
+        raise NotImplementedError('chat_ocr_pages_sharded: logits constraints are not implemented across GPUs (use chat_ocr_pages / chat_ocr_continuous on one)')
     if dict(generation_config).get('do_sample', False):
         raise NotImplementedError('chat_ocr_pages_sharded: do_sample=True is not implemented across GPUs yet (it needs the per-call seed broadcast '
                                   'to every rank); use chat_ocr_pages / chat_ocr_continuous on one GPU')

@@ -8,6 +8,7 @@ import time
 import torch
 
 from .config import EOS_TOKEN_ID
+from .constraints import per_page as constraints_per_page
 from .generation import admit, decode_rows, per_page_sampling, read_scores
 from .scores import per_page as scores_per_page
 
@@ -101,11 +102,12 @@ class PagePipeline:
             raise out
         return out
 
-    def start(self, embeds_list, budgets=None, sampling=None, seeds=None, logprobs=0):
+    def start(self, embeds_list, budgets=None, sampling=None, seeds=None, logprobs=0, constraints=None):
         """Prefill a batch on the caller's stream and hand it to the decode thread; returns the previous batch's ids (None if there
         was none), waiting for them if they are not there yet.  budgets: optional per-page max_new_tokens (<= the pipeline's): a page
         leaves the batch at the first EOS check at or past its budget and its ids are cut there, as its own generate_pages call would.
-        sampling / seeds / logprobs: as generate_pages takes them; a batch started with a non-zero logprobs is returned as (ids, scores)."""
+        sampling / seeds / logprobs: as generate_pages takes them; a batch started with a non-zero logprobs is returned as (ids, scores).
+        constraints: None, one constraints.Constraints for every page, or a list with one (or None) per page."""
         P = len(embeds_list)
         per_page = per_page_sampling(sampling, seeds, P)
         lpn = scores_per_page(logprobs, P)
@@ -116,7 +118,7 @@ class PagePipeline:
             self._kv(self.turn ^ 1, P)
         kv = self._kv(self.turn, P)                # last used two batches ago, and that batch has been collected
         self.turn ^= 1
-        admit(self.eng, kv, list(range(P)), embeds_list, self.penalty, per_page, lpn, self.prefill_batch)
+        admit(self.eng, kv, list(range(P)), embeds_list, self.penalty, per_page, lpn, self.prefill_batch, constraints=constraints_per_page(constraints, P))
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream())
         prev = self._collect()

@@ -28,6 +28,7 @@ to continue from: use kv_cache_dtype='bf16'), region_wise (one turn), and the pi
 """
 import torch
 
+from .constraints import parse as constraints_parse
 from .generation import check_fits, decode_rows, reply_text
 from .sampling import page_seeds, parse_beams
 
@@ -129,7 +130,8 @@ class PageSession:
         """chat_ocr's arguments after the image, and its return values.  The turn runs on the trunk."""
         question, history, template, ids, gc = self._prompt(question, history, generation_config, return_scores)
         p = plan_prefix(self.cached_ids, ids)
-        max_new = self.m._gen_args(gc, allow_beams=True)[0]                                   # validated here: a refused turn leaves the trunk as it was
+        max_new, eos, _ = self.m._gen_args(gc, allow_beams=True)                              # validated here: a refused turn leaves the trunk as it was
+        constraints_parse(gc, eos)                                                            # (installed by _generate_kw behind the truncate, for this turn only)
         check_fits(len(ids), max_new, self.m.max_tokens)                                      # before the trunk changes
         self.kv.truncate(0, p)
         self.cached_ids = self.cached_ids[:p]
@@ -154,6 +156,7 @@ class PageSession:
         built = [self._prompt(q, None if history is None else list(history), generation_config) for q in questions]
         gc, template = built[0][4], built[0][2]
         max_new, eos, sp = m._gen_args(gc, allow_beams=True)
+        cons = constraints_parse(gc, eos)
         for _, _, _, ids, _ in built:
             check_fits(len(ids), max_new, m.max_tokens)
         if not self.cached_ids:                  # an empty trunk: what the prompts share goes into it first; the pick that prefill appends is dropped
@@ -176,6 +179,9 @@ class PageSession:
         if sp is not None:
             for b, seed in zip(branches, page_seeds(len(branches))):
                 kv.set_sampling(b, sp.temperature, sp.top_k, sp.top_p, seed)
+        if cons is not None:                     # behind the fork / truncate, which leave a branch without any
+            for b in branches:
+                kv.set_constraints(b, cons)
         tails = [self._embed(b[3], p) for b, p in zip(built, prefixes)]
         self.rows_prefilled.append(sum(len(b[3]) - p for b, p in zip(built, prefixes)))
         m.engine.prefill_batch(kv, branches, tails, penalty=repetition_penalty)

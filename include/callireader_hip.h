@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_truncate, cr_kv_fork; cr_kv_set_beam, cr_kv_beam_result, cr_kv_beam_reorder, cr_op_beam_step, cr_kv_reset also dissolves beam groups; cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_set_constraints, cr_op_constrain, cr_kv_reset / cr_kv_truncate / cr_kv_fork also switch constraints off; cr_kv_truncate, cr_kv_fork; cr_kv_set_beam, cr_kv_beam_result, cr_kv_beam_reorder, cr_op_beam_step, cr_kv_reset also dissolves beam groups; cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -152,7 +152,7 @@ int cr_kv_length(const cr_kv* kv, int seq);           /* tokens currently cached
  * device-wide synchronisation: ordered after earlier work on that stream and before what the caller enqueues next. */
 int cr_kv_reset(cr_kv* kv, int seq, void* stream);
 /* Roll `seq` back to its first n_tokens cached positions: it keeps positions [0, n_tokens) and forgets everything else that cr_kv_reset forgets -- its
- * generated ids, its stop criteria and stop count, its sampling state (greedy again; a later sampled pick's `step` counts from 0) and its token scores (off).
+ * generated ids, its stop criteria and stop count, its sampling state (greedy again; a later sampled pick's `step` counts from 0), its token scores (off) and its logits constraints (off).
  * cr_kv_length and the host-side id count follow.  State only: no cache row is touched, rows at positions >= n_tokens are dead and later appends overwrite
  * them.  n_tokens == 0 is cr_kv_reset of the sequence.  What it is for: the next turn of a conversation whose prompt begins with what the cache holds -- cut
  * the speculative rows behind EOS, continue with cr_llm_prefill of the new rows; the repetition penalty of the new turn then sees that turn's ids only, as
@@ -160,7 +160,7 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream);
  * beam group.  Enqueued on `stream`, no device-wide synchronisation.  Added within ABI v13. */
 int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream);
 /* Give the n_dst sequences dsts_host[] (host array) the prefix of `src`: each becomes a sequence that holds cached positions [0, n_tokens) of src -- every
- * layer, KV head, K and V -- and is otherwise as after cr_kv_truncate(dst, n_tokens): no ids, no criteria, greedy, scores off.  One launch of the copy kernel
+ * layer, KV head, K and V -- and is otherwise as after cr_kv_truncate(dst, n_tokens): no ids, no criteria, greedy, scores off, no constraints.  One launch of the copy kernel
  * of csrc/kvops.hip, which reads the source once however many destinations there are ((1 + n_dst) * layers * 4096 * n_tokens bytes of traffic); rows of a
  * destination at positions >= n_tokens are not written; src is unchanged.  A row's bits do not depend on its sequence, so a destination continued by a
  * prefill computes what src continued by that prefill computes.  CR_ERR_ARG for n_tokens outside 1..cr_kv_length(src), n_dst outside 1..min(n_seqs - 1, 64),
@@ -221,6 +221,40 @@ int cr_kv_set_logprobs(cr_kv* kv, int seq, int top_n, void* stream);
  * [max][8] int32, top_lp [max][8] fp32.  Returns the count (cr_kv_generated's), or < 0: CR_ERR_STATE for a sequence whose scores are off.
  * Synchronises `stream`.  Added within ABI v13. */
 int cr_kv_logprobs(cr_kv* kv, int seq, float* lp, int32_t* top_ids, float* top_lp, int max, void* stream);
+/* Logits constraints of a greedy sequence (csrc/constrain.hip): what transformers' NoRepeatNGram / NoBadWords / SuppressTokens /
+ * SuppressTokensAtBegin / MinNewTokensLength processors do, as masks.  All arrays are HOST arrays, read before the call returns. */
+typedef struct cr_constraints {
+    int32_t no_repeat_ngram_size;          /* N >= 0; 0: off */
+    int32_t min_new_tokens;                /* m >= 0: eos_id is banned while fewer than m ids have been generated (max of min_new_tokens / min_length) */
+    int32_t eos_id;                        /* the call's EOS id, < 0: none (min_new_tokens then bans nothing) */
+    int32_t n_suppress;                    /* suppress_tokens: banned at every step */
+    const int32_t* suppress;
+    int32_t n_begin_suppress;              /* begin_suppress_tokens: banned at the sequence's first pick only */
+    const int32_t* begin_suppress;
+    int32_t n_allowed;                     /* whitelist: with allowed != NULL every id NOT listed is banned at every step (n_allowed >= 1) */
+    const int32_t* allowed;
+    int32_t n_bad_words;                   /* bad_words_ids: word w is bad_word_ids[bad_word_offsets[w] .. bad_word_offsets[w + 1]), offsets[0] = 0 */
+    const int32_t* bad_word_ids;
+    const int32_t* bad_word_offsets;       /* n_bad_words + 1 entries */
+    int32_t reserved[8];                   /* 0 */
+} cr_constraints;
+/* Constraints of `seq`: before every later pick of the sequence (the prefill's included) one workgroup sets the banned ids of its fp32 score row to -inf, in
+ * front of the repetition penalty and the pick (masks commute with the penalty: -inf stays -inf for any penalty > 0, so the result is transformers' whatever
+ * order its processor list has).  With g[0 .. ng) = the ids the sequence has generated (the prompt is not seen: the reference generates from inputs_embeds),
+ *   - suppress, one-id bad words and the complement of `allowed`: always;   begin_suppress: while ng == 0;   eos_id: while ng < min_new_tokens;
+ *   - no_repeat_ngram_size N: g[i + N - 1] for every i in [0, ng - N] with g[i .. i + N - 2] == g[ng - N + 1 .. ng - 1] (N = 1: every generated id), over the
+ *     whole history;
+ *   - a bad word of L >= 2 ids: its last id when ng >= L and the last L - 1 generated ids equal its first L - 1 (ng >= L, not L - 1: transformers'
+ *     SequenceBiasLogitsProcessor ignores a word longer than the ids generated so far, and its result is the one kept);
+ *   - a row in which every id would be banned keeps id 0 at its raw value: the pick is id 0, torch.argmax's answer on an all -inf row.
+ * The logits a prefill / decode call returns stay the raw rows; token scores (cr_kv_set_logprobs) see the masked, penalised row.  c == NULL switches the
+ * sequence off, as cr_kv_reset, cr_kv_truncate and cr_kv_fork do for the sequences they reset.  A launch in which no row is constrained launches nothing.
+ * Limits of the bad words of two or more ids: 256 words, 16 ids per word, 4096 ids in all; vocab <= 491520.  Checked BEFORE the cache and any device call:
+ * CR_ERR_ARG for N < 0, m < 0, a negative count, a missing array, an id < 0, an empty whitelist or bad word, offsets that do not ascend from 0, or a limit
+ * passed; then CR_ERR_ARG for a bad cache / sequence or an id >= vocab; CR_ERR_STATE for a member of a beam group (and cr_kv_set_beam refuses a constrained
+ * sequence with CR_ERR_STATE).  Call after cr_kv_reset and BEFORE the prefill.  The blocks (about 41 KB per sequence at vocab 92553) are allocated by the first
+ * call that switches a sequence of the cache on, which also synchronises `stream`.  Enqueued on `stream`.  Added within ABI v13. */
+int cr_kv_set_constraints(cr_kv* kv, int seq, const cr_constraints* c, void* stream);
 /* Beam search (csrc/beam.hip): the `num_beams` (2..8) consecutive sequences first_seq .. first_seq + num_beams - 1 become one beam group that runs the
  * deterministic beam search of transformers 5.x GenerationMixin._beam_search (do_sample=False, one returned sequence, no group / diverse / constrained beams)
  * as `generate(inputs_embeds=...)` drives it, entirely on the device.  With g = ids generated before a step, B = num_beams, K = 2 B, every step
@@ -387,6 +421,12 @@ int cr_op_decode_swizzle(int which, const void* W, int64_t ldw, int N, int K, vo
 int cr_op_sample(cr_ctx* ctx, const float* logits, int n, int vocab, const int64_t* history, int hist_cap, const int32_t* hist_len, float penalty,
                  const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed, const int32_t* step, int64_t* out_ids,
                  int32_t* out_kept, void* stream);
+/* The constraint kernel of cr_kv_set_constraints alone (test / tuning entry; the prefill and decode launch the same kernel): logits [n][vocab] fp32, MODIFIED
+ * in place (banned ids become -inf, every other value is untouched); row r reads the history of s = seqs[r] (seqs: DEVICE int32 [n], NULL: s = r): history
+ * [.][hist_cap] int64 with hist_len[s] ids (DEVICE arrays; counts above hist_cap are read as hist_cap; history may be NULL when hist_cap == 0).  `c` (host, not
+ * NULL) constrains every row and is checked as cr_kv_set_constraints checks it.  Synchronises `stream`.  Added within ABI v13. */
+int cr_op_constrain(const cr_constraints* c, float* logits, int n, int vocab, const int32_t* seqs, const int64_t* history, int hist_cap, const int32_t* hist_len,
+                    void* stream);
 /* The score kernels of cr_kv_set_logprobs alone (test entry; the prefill and decode launch the same kernels): logits [n][vocab] fp32 = the rows z
  * (not modified), ids [n] int64 = the id scored in each row; lp [n], top_ids [n][8], top_lp [n][8] as above with top_n alternatives (1..8, CR_ERR_ARG
  * otherwise; vocab >= 8, n <= 65535).  All pointers are DEVICE arrays.  Synchronises `stream`.  Added within ABI v13. */
