@@ -1,6 +1,6 @@
 // Logits constraints of a greedy sequence, as masks in front of the pick: transformers' NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor,
 // SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor and MinNewTokensLengthLogitsProcessor (and a whitelist, the complement of a
-// SuppressTokens list).  One workgroup of 1024 threads per logits row (as pick_kernel), launched by pick_rows (llm.hip) between the copy of the raw row to the
+// SuppressTokens list).  One workgroup of 1024 threads per logits row (as pick_kernel), launched by pick_rows (pick.hip) between the copy of the raw row to the
 // caller and the pick.
 //
 // Order: every constraint writes -inf, and the repetition penalty maps -inf to -inf for any penalty > 0 (-inf * p = -inf), so masking before the penalty
@@ -156,9 +156,9 @@ void con_pack(const cr_constraints* c, int vocab, std::vector<int32_t>& blk) {
     blk.resize(con_block_ints(vocab) - CON_MAX_WORD_IDS + ids);
 }
 
-int launch_constrain(float* logits, int64_t ld, int vocab, int rows, const int32_t* seqs, const int64_t* gen, const int32_t* ngen, int gen_cap,
-                     const ConTables& t, hipStream_t st) {
-    hipLaunchKernelGGL(constrain_kernel, dim3(rows), dim3(1024), (size_t)((vocab + 31) / 32) * 4, st, logits, ld, vocab, seqs, gen, ngen, gen_cap, t);
+int launch_constrain(const ConstrainLaunch& p, hipStream_t st) {
+    hipLaunchKernelGGL(constrain_kernel, dim3(p.rows), dim3(1024), (size_t)((p.vocab + 31) / 32) * 4, st, p.logits, p.ld, p.vocab, p.h.seqs, (const int64_t*)p.h.gen,
+                       (const int32_t*)p.h.ngen, p.h.gen_cap, p.t);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
@@ -181,7 +181,8 @@ extern "C" int cr_op_constrain(const cr_constraints* c, float* logits, int n, in
     hipError_t e = hipMemcpyAsync(d, blk.data(), (blk.size() - 1) * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_on, &blk.back(), 4, hipMemcpyHostToDevice, st);
     int r = CR_OK;
-    if (e == hipSuccess) r = launch_constrain(logits, vocab, vocab, n, seqs, history, hist_len, hist_cap, ConTables{d_on, d, 0, 0}, st);
+    const ConstrainLaunch p{logits, vocab, vocab, n, {seqs, const_cast<int64_t*>(history), const_cast<int32_t*>(hist_len), hist_cap}, {d_on, d, 0, 0}};
+    if (e == hipSuccess) r = launch_constrain(p, st);
     const hipError_t e2 = hipStreamSynchronize(st);
     hipFree(d);
     if (e != hipSuccess || e2 != hipSuccess) return cr_fail(CR_ERR_HIP, "cr_op_constrain: %s", hipGetErrorString(e != hipSuccess ? e : e2));

@@ -25,7 +25,7 @@ int con_check(const cr_constraints* c, int vocab, const char* who);
 // the block of a checked cr_constraints, cut behind the last word id in use (what has to be uploaded)
 void con_pack(const cr_constraints* c, int vocab, std::vector<int32_t>& blk);
 
-// rows of logits [rows][ld] in place: the banned ids of every constrained row become -inf; seq = seqs[row] (seqs NULL: seq = row) indexes the history
-// (gen [.][gen_cap], ngen, clamped to gen_cap) and the tables
-int launch_constrain(float* logits, int64_t ld, int vocab, int rows, const int32_t* seqs, const int64_t* gen, const int32_t* ngen, int gen_cap,
-                     const ConTables& t, hipStream_t st);
+// rows of logits [rows][ld] in place: the banned ids of every constrained row become -inf; seq = h.seqs[row] (NULL: seq = row) indexes the history
+// (ngen clamped to gen_cap) and the tables
+struct ConstrainLaunch { float* logits; int64_t ld; int vocab; int rows; Hist h; ConTables t; };
+int launch_constrain(const ConstrainLaunch& p, hipStream_t st);

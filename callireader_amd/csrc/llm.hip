@@ -7,6 +7,9 @@
 //            -> flash attention (causal GQA in prefill; 4 heads of a KV group as the "rows" in decode)
 //            -> GEMM wo (+x in place) -> RMSNorm -> GEMM w1|w3 with SwiGLU epilogue -> GEMM w2 (+x in place).
 // Decode (<= 64 rows): wqkv / wo / w2 leave fp32 K-slices that RoPE-split and a fused residual-add + RMSNorm sum up.
+//
+// This file holds the model: the kernels, the two layer loops, the weight preparation and the entry points cr_llm_prefill_batch / cr_llm_decode.  The cache
+// object (struct cr_kv, every cr_kv_* entry point) is kv.hpp / kv.hip; what follows the LM head (the picks, scores, constraints, the beam step) is pick.hip.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,64 +18,12 @@
 #include <vector>
 
 #include "attention.hpp"
-#include "beam.hpp"
-#include "ctx.hpp"
-#include "constrain.hpp"
 #include "decode.hpp"
-#include "kvops.hpp"
+#include "kv.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
-#include "logprobs.hpp"
-#include "pick.hpp"
-
-struct cr_kv {
-    cr_ctx* ctx;
-    int n_seqs, max_tokens, gen_cap, layers;
-    int fmt;             // CR_KV_BF16 | CR_KV_E4M3 (cr_kv_alloc_ex), fixed for the cache's lifetime
-    bf16* k;             // [layers][n_seqs][8][max_tokens][128]  (bf16 caches only)
-    bf16* v;
-    // e4m3 caches: one row = the 128 values of (layer, seq, KV head, position) as OCP e4m3fn bytes + one fp32 scale (max|x| / 448, 1 for a zero row)
-    unsigned char* k8;   // [layers][n_seqs][8][max_tokens][128]
-    unsigned char* v8;
-    float* ks;           // [layers][n_seqs][8][max_tokens]: a wave's 64 keys read 256 contiguous bytes of scales
-    float* vs;
-    int32_t* d_len;      // [n_seqs] tokens cached
-    int32_t* d_ngen;     // [n_seqs] ids generated
-    int64_t* d_gen;      // [n_seqs][gen_cap]; gen_cap = max_tokens: every generated id costs a cached token, so the cache fills first
-    // stop tracking (cr_kv_set_stop / cr_kv_poll_finished), one block of 1 + 4 n_seqs int32:
-    //   [0] finished count (monotonic), [1, 1 + n) ring of finished sequence indices (entry k at 1 + k % n),
-    //   [1 + n, 1 + 2n) stop count per sequence (0 = not stopped), [1 + 2n, 1 + 3n) EOS id (< 0: none), [1 + 3n, 1 + 4n) budget (<= 0: none)
-    int32_t* d_stop;
-    // sampling state (cr_kv_set_sampling), one block: temperature float[n] (<= 0: greedy), top_k int32[n], top_p float[n], seed uint64[n];
-    // `sampled` mirrors "temperature > 0" on the host: a launch whose rows are all greedy keeps pick_kernel
-    char* d_samp;
-    float* d_temp; int32_t* d_topk; float* d_topp; uint64_t* d_seed;
-    std::vector<char> sampled;
-    // token scores (cr_kv_set_logprobs; logprobs.hip), allocated by the first call that switches a sequence on: d_lpn int32[n] = alternatives per sequence
-    // (0: off), d_lpdone int32[n] = slots written, d_lp [n][gen_cap] fp32, d_top_id [n][gen_cap][8] int32, d_top_lp [n][gen_cap][8] fp32, indexed like
-    // d_gen.  `scored` mirrors d_lpn on the host: a launch whose rows are all off launches nothing new
-    int32_t *d_lpn = nullptr, *d_lpdone = nullptr, *d_top_id = nullptr;
-    float *d_lp = nullptr, *d_top_lp = nullptr;
-    std::vector<char> scored;
-    // logits constraints (cr_kv_set_constraints; constrain.hip), allocated by the first call that switches a sequence on: d_con_on int32[n] (0: off), d_con
-    // [n][con_stride] int32 = one block per sequence (constrain.hpp).  `constrained` mirrors d_con_on on the host: a launch whose rows are all off launches
-    // nothing new
-    int32_t *d_con_on = nullptr, *d_con = nullptr;
-    size_t con_stride = 0;
-    std::vector<char> constrained;
-    // beam groups (cr_kv_set_beam; beam.hip), allocated by the first call: d_beam BeamState[n] (a group's state at its first sequence), d_bgrp int32[n] = first
-    // sequence of the sequence's group (< 0: none), d_bfin [n][gen_cap] ids of the finished slots.  `bgrp` / `bnum` mirror the group and its size on the host:
-    // a launch without a group launches nothing new
-    BeamState* d_beam = nullptr;
-    int32_t* d_bgrp = nullptr;
-    int64_t* d_bfin = nullptr;
-    std::vector<int> bgrp, bnum;
-    std::vector<int> len, ngen;
-};
 
 namespace {
-
-constexpr int D = 4096, HD = 128, NH = 32, NKV = 8, QKV = 6144;
 
 // x[i] = tok_embeddings[id_i]; id_i = force[i] or the last generated id of seq_i
 __global__ __launch_bounds__(256) void embed_rows_kernel(const bf16* __restrict__ table, const int64_t* __restrict__ force,
@@ -235,65 +186,6 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
     *(bf16x8*)(dst + c * 8) = y;
 }
 
-// RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) + argmax (first max wins) + append the id (+ its stop check).
-// One workgroup of 1024 per row.  The three steps are pick.hpp's, shared with the sampling pick (sample.hip).
-__global__ __launch_bounds__(1024) void pick_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty,
-                                                    int seq0, const int32_t* __restrict__ seqs, int64_t* __restrict__ gen,
-                                                    int32_t* __restrict__ ngen, int32_t* __restrict__ lens, int gen_cap, int len_add,
-                                                    int32_t* __restrict__ stop, int n_seqs, const float* __restrict__ orig,
-                                                    const int32_t* __restrict__ bgrp) {
-    __shared__ float bv[1024];
-    __shared__ int bi[1024];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const int seq = seqs ? seqs[row] : seq0;
-    if (bgrp && bgrp[seq] >= 0) return;                       // a beam row: beam.hip picks for it
-    float* lg = logits + (int64_t)row * ld;
-    const int ng = ngen[seq];
-    int64_t* g = gen + (int64_t)seq * gen_cap;
-    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid, orig ? orig + (int64_t)row * ld : nullptr);
-    argmax_row(lg, vocab, tid, bv, bi);
-    if (tid == 0) {
-        if (ng < gen_cap) {
-            g[ng] = bi[0]; ngen[seq] = ng + 1;
-            stop_check(stop, n_seqs, seq, bi[0], ng + 1);
-        }
-        lens[seq] += len_add;
-    }
-}
-
-// cr_kv_set_stop: install the criteria of `seq` and apply them to the ids it has generated already (a call after the prefill sees its first id).
-// A sequence that has stopped keeps its first stop (pushed once); only the criteria are replaced.  One workgroup.
-__global__ __launch_bounds__(256) void set_stop_kernel(int32_t* __restrict__ stop, int n_seqs, int seq, int eos, int budget,
-                                                       const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen, int gen_cap) {
-    __shared__ int first;
-    if (threadIdx.x == 0) first = 0x7fffffff;
-    __syncthreads();
-    const int ng = ngen[seq];
-    if (eos >= 0)
-        for (int i = threadIdx.x; i < ng; i += 256)
-            if (gen[(int64_t)seq * gen_cap + i] == eos) atomicMin(&first, i + 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        stop[1 + 2 * n_seqs + seq] = eos;
-        stop[1 + 3 * n_seqs + seq] = budget;
-        if (stop[1 + n_seqs + seq] == 0) {
-            int at = first <= ng ? first : 0;
-            if (budget > 0 && ng >= budget && (at == 0 || at > budget)) at = budget;
-            if (at) {
-                stop[1 + n_seqs + seq] = at;
-                const int k = atomicAdd(stop, 1);
-                stop[1 + k % n_seqs] = seq;
-            }
-        }
-    }
-}
-
-// cr_kv_set_sampling: one sequence's sampling state
-__global__ __launch_bounds__(64) void set_sampling_kernel(float* __restrict__ temp, int32_t* __restrict__ topk, float* __restrict__ topp,
-                                                          uint64_t* __restrict__ seed, int seq, float t, int k, float p, uint64_t sd) {
-    if (threadIdx.x == 0) { temp[seq] = t; topk[seq] = k; topp[seq] = p; seed[seq] = sd; }
-}
-
 // prefill: the cached length of every page's sequence = its first position + its rows (d_seg: 4 per page, see cr_llm_prefill_batch).
 // Only the prefilled sequences are written: another context may be decoding other sequences of the same cache meanwhile.
 __global__ __launch_bounds__(256) void set_len_kernel(const int32_t* __restrict__ seg, int n, int32_t* __restrict__ lens) {
@@ -451,25 +343,6 @@ template <class Bufs> int ws_carve(cr_ctx* c, const char* who, Bufs& b) {
     return ar.ok() ? CR_OK : cr_fail(CR_ERR_STATE, "%s: the carve passed the %zu bytes of workspace (%zu measured)", who, c->ws_bytes, measure.bytes());
 }
 
-// The LM head's n rows of a prefill / decode call, carved after the layer buffers
-struct HeadBufs {
-    int n, V;
-    bool scored, deep;      // a row of the launch has token scores on / a history of more than 4096 ids under a penalty
-    bool beam;              // a row of the launch belongs to a beam group: beam.hip's candidate scratch
-    bf16* hl;               // the normalised rows
-    float* lg;              // their logits [n][V]
-    void* score;            // scored: logprobs.hip's scratch
-    float* lg0;             // deep: the rows before the penalty, for the pick
-    char* cand;             // beam: the rows' candidates
-    void carve(Arena& ar) {
-        hl = ar.take<bf16>((size_t)n * D);
-        lg = ar.take<float>((size_t)n * V);
-        score = scored ? ar.take<char>(logprobs_scratch_bytes(n, V)) : nullptr;
-        lg0 = deep ? ar.take<float>((size_t)n * V) : nullptr;
-        cand = beam ? ar.take<char>(beam_scratch_bytes(n)) : nullptr;
-    }
-};
-
 struct Segment { int seq, row0, S, pos0; };     // a page's rows inside a batched prefill
 
 // The index arrays of a batched prefill (M rows, n pages): one block of ints, laid out the same on the host and on the device
@@ -500,9 +373,9 @@ struct PrefillBufs {
     PrefillRows rows;
     HeadBufs head;
 
-    PrefillBufs(cr_ctx* c, const cr_kv* kv, int M, int n_pages, int max_S, bool scored, bool deep, bool beam)
+    PrefillBufs(cr_ctx* c, const cr_kv* kv, int M, int n_pages, int max_S, const RowFeatures& f)
         : M(M), n_pages(n_pages), max_S(max_S), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), any8(c->fp8_mfma && M >= 256),
-          last_rows(c->prefill_last_rows && !any8 && !c->probe_dst), head{n_pages, c->d.vocab, scored, deep, beam} {}
+          last_rows(c->prefill_last_rows && !any8 && !c->probe_dst), head{n_pages, c->d.vocab, f} {}
 
     void carve(Arena& ar) {
         x = ar.take<bf16>((size_t)M * D);
@@ -604,11 +477,11 @@ struct DecodeBufs {
     float *part, *pbuf;      // the attention splits' partials; the K-slices of one GEMM ([slices][M][N] fp32, the largest of the three)
     HeadBufs head;
 
-    DecodeBufs(cr_ctx* c, const cr_kv* kv, int M, int nsplit, bool scored, bool deep, bool beam)
+    DecodeBufs(cr_ctx* c, const cr_kv* kv, int M, int nsplit, const RowFeatures& f)
         : M(M), nsplit(nsplit), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), s_qkv(gemm_partial_splits(QKV, D)),
           s_o(gemm_partial_splits(D, D)), s_2(gemm_partial_splits(D, ff)), sliced(M <= 64 && s_qkv > 0 && s_o > 0 && s_2 > 0 && !c->no_sliced_decode),
           fused(sliced && c->fused_decode && !c->fp8_decode && !kv8 && decode_fused_supported(M, ff) && s_qkv == DEC_SLICES_WQKV && s_o == DEC_SLICES_WO &&
-                s_2 == DEC_SLICES_W2), head{M, c->d.vocab, scored, deep, beam} {}
+                s_2 == DEC_SLICES_W2), head{M, c->d.vocab, f} {}
 
     void carve(Arena& ar) {
         x = ar.take<bf16>((size_t)M * D);
@@ -863,76 +736,6 @@ int llm_finalize(cr_ctx* c, hipStream_t st) {
     return CR_OK;
 }
 
-static bool any_sampled(const cr_kv* kv, const int32_t* seqs, int n) {
-    for (int i = 0; i < n; i++) if (kv->sampled[seqs[i]]) return true;
-    return false;
-}
-
-// a row whose history is longer than the 4096 ids apply_penalty gathers in registers: the pick then needs an untouched copy of the rows (pick.hpp)
-static bool long_history(const cr_kv* kv, const int32_t* seqs, int n, float penalty) {
-    if (penalty == 1.0f) return false;
-    for (int i = 0; i < n; i++) if (kv->ngen[seqs[i]] > 4096) return true;
-    return false;
-}
-
-// rows of the launch that belong to a beam group
-static int beam_row_count(const cr_kv* kv, const int32_t* seqs, int n) {
-    if (!kv->d_beam) return 0;
-    int k = 0;
-    for (int i = 0; i < n; i++) if (kv->bgrp[seqs[i]] >= 0) k++;
-    return k;
-}
-
-// The beam step of the launch's groups, after the picks of its other rows: candidates and select on the logits rows (first_only: a prefill, which holds a
-// group's first sequence only), and in a decode step the re-order behind them (the prefill's follows its set_len_kernel)
-static BeamLaunch beam_launch(cr_kv* kv, const HeadBufs& h, const int32_t* d_seqs, float penalty, int len_add, int first_only) {
-    BeamLaunch p{};
-    p.logits = h.lg; p.ld = h.V; p.vocab = h.V; p.penalty = penalty; p.rows = h.n; p.seqs = d_seqs; p.grp = kv->d_bgrp; p.state = kv->d_beam;
-    p.gen = kv->d_gen; p.ngen = kv->d_ngen; p.gen_cap = kv->gen_cap; p.lens = kv->d_len; p.len_add = len_add; p.orig = h.lg0;
-    p.cand_v = (float*)h.cand; p.cand_i = (int32_t*)(h.cand + (size_t)h.n * 2 * BEAM_MAX * 4); p.fin_ids = kv->d_bfin; p.stop = kv->d_stop; p.n_seqs = kv->n_seqs;
-    p.first_only = first_only;
-    return p;
-}
-static BeamCache beam_cache(const cr_kv* kv) {
-    return {kv->k, kv->v, (int64_t)kv->n_seqs * 8 * kv->max_tokens * 128, kv->layers, kv->max_tokens};
-}
-
-static bool any_constrained(const cr_kv* kv, const int32_t* seqs, int n) {
-    if (!kv->d_con) return false;
-    for (int i = 0; i < n; i++) if (kv->constrained[seqs[i]]) return true;
-    return false;
-}
-
-static bool any_scored(const cr_kv* kv, const int32_t* seqs, int n) {
-    if (!kv->d_lpn) return false;
-    for (int i = 0; i < n; i++) if (kv->scored[seqs[i]]) return true;
-    return false;
-}
-
-// What follows the LM head in a prefill and in a decode step: the logits out, then the pick (greedy or sampled) appends every row's id and adds len_add
-// to its cached length (in front of it, after the raw rows have gone out, the constraint masks of the rows that have any: the pick, the penalty's copy h.lg0
-// and the scores all see the masked row, the caller the raw one), then the scores of the rows the pick has just chosen from (h.lg: the penalised rows it left) go into the sequences' slots
-static int pick_rows(cr_kv* kv, const HeadBufs& h, const int32_t* seqs, const int32_t* d_seqs, float penalty, int len_add, float* out, hipStream_t st, bool prefill) {
-    const int n = h.n, V = h.V;
-    if (out) CR_HIP(hipMemcpyAsync(out, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-    if (any_constrained(kv, seqs, n))
-        CR_TRY(launch_constrain(h.lg, V, V, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, ConTables{kv->d_con_on, kv->d_con, (int64_t)kv->con_stride, 1}, st));
-    if (h.lg0) CR_HIP(hipMemcpyAsync(h.lg0, h.lg, (size_t)n * V * 4, hipMemcpyDeviceToDevice, st));
-    const int32_t* bgrp = h.beam ? kv->d_bgrp : nullptr;      // beam rows are skipped by the picks and taken by beam_rows below
-    if (beam_row_count(kv, seqs, n) == n) {}                 // nothing but beams: no pick at all
-    else if (any_sampled(kv, seqs, n))
-        CR_TRY(launch_sample(h.lg, V, V, penalty, n, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed,
-                             nullptr, 1, kv->d_len, len_add, kv->d_stop, kv->n_seqs, nullptr, nullptr, st, h.lg0, bgrp));
-    else
-        hipLaunchKernelGGL(pick_kernel, dim3(n), dim3(1024), 0, st, h.lg, (int64_t)V, V, penalty, 0, d_seqs, kv->d_gen, kv->d_ngen,
-                           kv->d_len, kv->gen_cap, len_add, kv->d_stop, kv->n_seqs, h.lg0, bgrp);
-    if (h.scored)
-        CR_TRY(launch_logprobs(h.lg, V, V, n, d_seqs, kv->d_lpn, 0, kv->d_gen, kv->d_ngen, kv->gen_cap, kv->d_lpdone, h.score, kv->d_lp, kv->d_top_id,
-                               kv->d_top_lp, st));
-    if (h.beam) CR_TRY(launch_beam_step(beam_launch(kv, h, d_seqs, penalty, len_add, prefill ? 1 : 0), st));
-    return CR_OK;
-}
-
 extern "C" {
 
 int cr_op_quantize_fp8(const void* w, int64_t ldw, int N, int K, void* q, float* scale, void* stream) {
@@ -1051,387 +854,6 @@ int cr_embed_splice(cr_ctx* c, const int64_t* ids, int S, const void* vit, int n
     return CR_OK;
 }
 
-int cr_kv_alloc(cr_ctx* c, int n_seqs, int max_tokens, cr_kv** out) { return cr_kv_alloc_ex(c, n_seqs, max_tokens, CR_KV_BF16, out); }
-
-int cr_kv_alloc_ex(cr_ctx* c, int n_seqs, int max_tokens, int format, cr_kv** out) {
-    if (format != CR_KV_BF16 && format != CR_KV_E4M3)
-        return cr_fail(CR_ERR_ARG, "cr_kv_alloc_ex: unknown cache format %d (CR_KV_BF16 = 0, CR_KV_E4M3 = 1)", format);
-    if (!c || !out || n_seqs <= 0 || max_tokens <= 0) return cr_fail(CR_ERR_ARG, "cr_kv_alloc: bad argument (null context or output, or a size <= 0)");
-    if (max_tokens > c->d.max_pos) return cr_fail(CR_ERR_ARG, "cr_kv_alloc: max_tokens %d exceeds the RoPE table (%d rows)", max_tokens, c->d.max_pos);
-    CR_HIP(hipSetDevice(c->device));
-    cr_kv* kv = new cr_kv();
-    kv->ctx = c; kv->n_seqs = n_seqs; kv->max_tokens = max_tokens; kv->gen_cap = max_tokens; kv->layers = c->d.llm_layers; kv->fmt = format;
-    const size_t rows = (size_t)kv->layers * n_seqs * NKV * max_tokens;
-    const size_t bytes = rows * HD * (format == CR_KV_E4M3 ? 1 : 2);
-    const bool data_ok = format == CR_KV_E4M3
-        ? hipMalloc((void**)&kv->k8, bytes) == hipSuccess && hipMalloc((void**)&kv->v8, bytes) == hipSuccess &&
-          hipMalloc((void**)&kv->ks, rows * 4) == hipSuccess && hipMalloc((void**)&kv->vs, rows * 4) == hipSuccess
-        : hipMalloc((void**)&kv->k, bytes) == hipSuccess && hipMalloc((void**)&kv->v, bytes) == hipSuccess;
-    if (!data_ok ||
-        hipMalloc((void**)&kv->d_len, n_seqs * 4) != hipSuccess || hipMalloc((void**)&kv->d_ngen, n_seqs * 4) != hipSuccess ||
-        hipMalloc((void**)&kv->d_stop, ((size_t)4 * n_seqs + 1) * 4) != hipSuccess ||
-        hipMalloc((void**)&kv->d_samp, (size_t)n_seqs * 24) != hipSuccess ||
-        hipMalloc((void**)&kv->d_gen, (size_t)n_seqs * kv->gen_cap * 8) != hipSuccess) {
-        cr_kv_free(kv);
-        return cr_fail(CR_ERR_NOMEM, "cr_kv_alloc: %zu bytes per K/V", bytes);
-    }
-    CR_HIP(hipMemset(kv->d_len, 0, n_seqs * 4));
-    CR_HIP(hipMemset(kv->d_ngen, 0, n_seqs * 4));
-    CR_HIP(hipMemset(kv->d_stop, 0, ((size_t)2 * n_seqs + 1) * 4));
-    CR_HIP(hipMemset(kv->d_stop + 1 + 2 * n_seqs, 0xff, (size_t)n_seqs * 4));       // no EOS id
-    CR_HIP(hipMemset(kv->d_stop + 1 + 3 * n_seqs, 0, (size_t)n_seqs * 4));          // no budget
-    kv->d_seed = (uint64_t*)kv->d_samp; kv->d_temp = (float*)(kv->d_seed + n_seqs); kv->d_topk = (int32_t*)(kv->d_temp + n_seqs);
-    kv->d_topp = (float*)(kv->d_topk + n_seqs);
-    CR_HIP(hipMemset(kv->d_samp, 0, (size_t)n_seqs * 24));                           // greedy
-    kv->sampled.assign(n_seqs, 0);
-    kv->scored.assign(n_seqs, 0);
-    kv->constrained.assign(n_seqs, 0);
-    kv->bgrp.assign(n_seqs, -1); kv->bnum.assign(n_seqs, 0);
-    kv->len.assign(n_seqs, 0); kv->ngen.assign(n_seqs, 0);
-    *out = kv;
-    return CR_OK;
-}
-
-int cr_kv_free(cr_kv* kv) {
-    if (!kv) return CR_OK;
-    hipDeviceSynchronize();
-    if (kv->k) hipFree(kv->k);
-    if (kv->v) hipFree(kv->v);
-    if (kv->k8) hipFree(kv->k8);
-    if (kv->v8) hipFree(kv->v8);
-    if (kv->ks) hipFree(kv->ks);
-    if (kv->vs) hipFree(kv->vs);
-    if (kv->d_len) hipFree(kv->d_len);
-    if (kv->d_ngen) hipFree(kv->d_ngen);
-    if (kv->d_stop) hipFree(kv->d_stop);
-    if (kv->d_samp) hipFree(kv->d_samp);
-    if (kv->d_gen) hipFree(kv->d_gen);
-    if (kv->d_lpn) hipFree(kv->d_lpn);
-    if (kv->d_lp) hipFree(kv->d_lp);
-    if (kv->d_top_id) hipFree(kv->d_top_id);
-    if (kv->d_top_lp) hipFree(kv->d_top_lp);
-    if (kv->d_con_on) hipFree(kv->d_con_on);
-    if (kv->d_con) hipFree(kv->d_con);
-    if (kv->d_beam) hipFree(kv->d_beam);
-    if (kv->d_bgrp) hipFree(kv->d_bgrp);
-    if (kv->d_bfin) hipFree(kv->d_bfin);
-    delete kv;
-    return CR_OK;
-}
-
-int cr_kv_length(const cr_kv* kv, int seq) { return (kv && seq >= 0 && seq < kv->n_seqs) ? kv->len[seq] : -1; }
-
-int cr_kv_format(const cr_kv* kv) { return kv ? kv->fmt : cr_fail(CR_ERR_ARG, "cr_kv_format: null cache"); }
-
-int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
-    if (!kv || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_reset: bad sequence");
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int s0 = seq < 0 ? 0 : seq, n = seq < 0 ? kv->n_seqs : 1;
-    CR_HIP(hipMemsetAsync(kv->d_len + s0, 0, (size_t)n * 4, st));
-    CR_HIP(hipMemsetAsync(kv->d_ngen + s0, 0, (size_t)n * 4, st));
-    const int N = kv->n_seqs;
-    CR_HIP(hipMemsetAsync(kv->d_stop + 1 + N + s0, 0, (size_t)n * 4, st));              // not stopped
-    CR_HIP(hipMemsetAsync(kv->d_stop + 1 + 2 * N + s0, 0xff, (size_t)n * 4, st));       // no EOS id
-    CR_HIP(hipMemsetAsync(kv->d_stop + 1 + 3 * N + s0, 0, (size_t)n * 4, st));          // no budget
-    if (seq < 0) CR_HIP(hipMemsetAsync(kv->d_stop, 0, 4, st));                          // every sequence: the finished ring starts over
-    CR_HIP(hipMemsetAsync(kv->d_temp + s0, 0, (size_t)n * 4, st));                      // greedy
-    if (kv->d_lpn) {                                                                    // scores off
-        CR_HIP(hipMemsetAsync(kv->d_lpn + s0, 0, (size_t)n * 4, st));
-        CR_HIP(hipMemsetAsync(kv->d_lpdone + s0, 0, (size_t)n * 4, st));
-    }
-    if (kv->d_con_on) CR_HIP(hipMemsetAsync(kv->d_con_on + s0, 0, (size_t)n * 4, st));   // constraints off
-    for (int s = s0; s < s0 + n; s++) { kv->len[s] = 0; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; kv->constrained[s] = 0; }
-    if (kv->d_beam)                                                                     // a beam group goes as a whole with any of its sequences
-        for (int s = s0; s < s0 + n; s++) {
-            const int f = kv->bgrp[s];
-            if (f < 0) continue;
-            const int B = kv->bnum[f];
-            CR_HIP(hipMemsetAsync(kv->d_bgrp + f, 0xff, (size_t)B * 4, st));
-            CR_HIP(hipMemsetAsync(kv->d_stop + 1 + N + f, 0, 4, st));                   // the group's stop record sits at its first sequence
-            for (int j = 0; j < B; j++) kv->bgrp[f + j] = -1;
-            kv->bnum[f] = 0;
-        }
-    return CR_OK;
-}
-
-static KvState kv_state(cr_kv* kv) { return {kv->d_len, kv->d_ngen, kv->d_stop, kv->n_seqs, kv->d_temp, kv->d_lpn, kv->d_lpdone, kv->d_con_on}; }
-
-int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream) {
-    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_truncate: bad sequence");
-    if (n_tokens < 0 || n_tokens > kv->len[seq]) return cr_fail(CR_ERR_ARG, "cr_kv_truncate: n_tokens %d outside 0..%d, the tokens sequence %d holds", n_tokens, kv->len[seq], seq);
-    if (kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_truncate: sequence %d belongs to the beam group of sequence %d (cr_kv_reset dissolves the group)", seq, kv->bgrp[seq]);
-    if (n_tokens == 0) return cr_kv_reset(kv, seq, stream);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    KvSeqs one{};
-    one.n = 1; one.seq[0] = seq;
-    CR_TRY(launch_kv_truncate(kv_state(kv), one, n_tokens, (hipStream_t)stream));
-    kv->len[seq] = n_tokens; kv->ngen[seq] = 0; kv->sampled[seq] = 0; kv->scored[seq] = 0; kv->constrained[seq] = 0;
-    return CR_OK;
-}
-
-int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream) {
-    if (!kv || !dsts_host || src < 0 || src >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_fork: bad argument (null cache or destinations, or a source out of range)");
-    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_fork: the fork copies bf16 rows only (an e4m3 cache keeps no bf16 prefix for a continued prefill to read)");
-    if (n_dst < 1 || n_dst > kv->n_seqs - 1 || n_dst > KV_FORK_MAX)
-        return cr_fail(CR_ERR_ARG, "cr_kv_fork: %d destinations (want 1..%d)", n_dst, kv->n_seqs - 1 < KV_FORK_MAX ? kv->n_seqs - 1 : KV_FORK_MAX);
-    if (n_tokens < 1 || n_tokens > kv->len[src]) return cr_fail(CR_ERR_ARG, "cr_kv_fork: n_tokens %d outside 1..%d, the tokens sequence %d holds", n_tokens, kv->len[src], src);
-    KvSeqs d{};
-    d.n = n_dst;
-    for (int j = 0; j < n_dst; j++) {
-        const int s = dsts_host[j];
-        if (s < 0 || s >= kv->n_seqs || s == src) return cr_fail(CR_ERR_ARG, "cr_kv_fork: destination %d (want 0..%d, not the source %d)", s, kv->n_seqs - 1, src);
-        for (int i = 0; i < j; i++) if (dsts_host[i] == s) return cr_fail(CR_ERR_ARG, "cr_kv_fork: destination %d listed twice", s);
-        d.seq[j] = s;
-    }
-    if (kv->bgrp[src] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_fork: the source %d belongs to the beam group of sequence %d", src, kv->bgrp[src]);
-    for (int j = 0; j < n_dst; j++)
-        if (kv->bgrp[d.seq[j]] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_fork: destination %d belongs to the beam group of sequence %d", d.seq[j], kv->bgrp[d.seq[j]]);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    CR_TRY(launch_kv_fork(kv_state(kv), kv->k, kv->v, (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD, kv->layers, kv->max_tokens, src, d, n_tokens, (hipStream_t)stream));
-    for (int j = 0; j < n_dst; j++) { const int s = d.seq[j]; kv->len[s] = n_tokens; kv->ngen[s] = 0; kv->sampled[s] = 0; kv->scored[s] = 0; kv->constrained[s] = 0; }
-    return CR_OK;
-}
-
-int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream) {
-    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: bad sequence");
-    if (max_new > kv->max_tokens - kv->len[seq])
-        return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: budget %d exceeds what the cache leaves after %d tokens (%d)", max_new, kv->len[seq], kv->max_tokens);
-    if (eos_id >= kv->ctx->d.vocab) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: EOS id %d outside the vocabulary", eos_id);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipLaunchKernelGGL(set_stop_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kv->d_stop, kv->n_seqs, seq, eos_id < 0 ? -1 : eos_id,
-                       max_new > 0 ? max_new : 0, kv->d_gen, kv->d_ngen, kv->gen_cap);
-    CR_HIP(hipGetLastError());
-    return CR_OK;
-}
-
-int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float top_p, uint64_t seed, void* stream) {
-    if (!(temperature >= 0.f && temperature <= 3.402823466e38f) || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f))
-        return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: temperature %g, top_k %d, top_p %g (want a finite temperature >= 0, top_k >= 0, 0 <= top_p <= 1)",
-                       temperature, top_k, top_p);
-    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: bad sequence");
-    if (temperature > 0.f && kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: sequence %d belongs to a beam group (no beam sampling)", seq);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed, seq,
-                       temperature, top_k, top_p, seed);
-    CR_HIP(hipGetLastError());
-    kv->sampled[seq] = temperature > 0.f;
-    return CR_OK;
-}
-
-int cr_kv_set_logprobs(cr_kv* kv, int seq, int top_n, void* stream) {
-    if (top_n < 0 || top_n > LOGPROBS_MAX_TOP) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: top_n %d (want 0 = off, or 1..%d)", top_n, LOGPROBS_MAX_TOP);
-    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: bad sequence");
-    if (top_n > 0 && kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_logprobs: sequence %d belongs to a beam group (no token scores with beams)", seq);
-    if (top_n > 0 && kv->ngen[seq] != 0)
-        return cr_fail(CR_ERR_STATE, "cr_kv_set_logprobs: sequence %d has generated %d ids already (switch scores on after cr_kv_reset and before the prefill)",
-                       seq, kv->ngen[seq]);
-    if (!kv->d_lpn && top_n == 0) return CR_OK;                                         // never switched on: nothing to switch off
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    if (!kv->d_lpn) {
-        const size_t N = kv->n_seqs, slots = N * kv->gen_cap;
-        if (hipMalloc((void**)&kv->d_lpn, N * 8) != hipSuccess || hipMalloc((void**)&kv->d_lp, slots * 4) != hipSuccess ||
-            hipMalloc((void**)&kv->d_top_id, slots * LOGPROBS_MAX_TOP * 4) != hipSuccess ||
-            hipMalloc((void**)&kv->d_top_lp, slots * LOGPROBS_MAX_TOP * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            if (kv->d_lpn) hipFree(kv->d_lpn);
-            if (kv->d_lp) hipFree(kv->d_lp);
-            if (kv->d_top_id) hipFree(kv->d_top_id);
-            if (kv->d_top_lp) hipFree(kv->d_top_lp);
-            kv->d_lpn = nullptr; kv->d_lp = nullptr; kv->d_top_id = nullptr; kv->d_top_lp = nullptr;
-            return cr_fail(CR_ERR_NOMEM, "cr_kv_set_logprobs: %zu bytes of token scores", slots * (4 + 8 * LOGPROBS_MAX_TOP));
-        }
-        kv->d_lpdone = kv->d_lpn + N;
-        CR_HIP(hipMemsetAsync(kv->d_lpn, 0, N * 8, (hipStream_t)stream));
-        CR_HIP(hipStreamSynchronize((hipStream_t)stream));                              // once per cache: in place before a call on any other stream
-    }
-    CR_TRY(launch_set_logprobs(kv->d_lpn, kv->d_lpdone, seq, top_n, (hipStream_t)stream));
-    kv->scored[seq] = top_n > 0;
-    return CR_OK;
-}
-
-int cr_kv_set_constraints(cr_kv* kv, int seq, const cr_constraints* c, void* stream) {
-    if (c) CR_TRY(con_check(c, -1, "cr_kv_set_constraints"));                           // the values first: no cache and no device needed
-    if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_constraints: bad sequence");
-    if (c) CR_TRY(con_check(c, kv->ctx->d.vocab, "cr_kv_set_constraints"));
-    if (c && kv->bgrp[seq] >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_set_constraints: sequence %d belongs to a beam group (no constraints with beams)", seq);
-    if (!kv->d_con && !c) return CR_OK;                                                 // never switched on: nothing to switch off
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int V = kv->ctx->d.vocab;
-    if (!kv->d_con) {
-        const size_t N = kv->n_seqs, stride = con_block_ints(V);
-        if (hipMalloc((void**)&kv->d_con_on, N * 4) != hipSuccess || hipMalloc((void**)&kv->d_con, N * stride * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            if (kv->d_con_on) hipFree(kv->d_con_on);
-            kv->d_con_on = nullptr; kv->d_con = nullptr;
-            return cr_fail(CR_ERR_NOMEM, "cr_kv_set_constraints: %zu bytes of constraint blocks", N * (stride + 1) * 4);
-        }
-        kv->con_stride = stride;
-        CR_HIP(hipMemsetAsync(kv->d_con_on, 0, N * 4, st));
-        CR_HIP(hipStreamSynchronize(st));                                               // once per cache: in place before a call on any other stream
-    }
-    if (!c) {
-        CR_HIP(hipMemsetAsync(kv->d_con_on + seq, 0, 4, st));
-        kv->constrained[seq] = 0;
-        return CR_OK;
-    }
-    std::vector<int32_t> blk;
-    con_pack(c, V, blk);
-    CR_HIP(hipMemcpyAsync(kv->d_con + (size_t)seq * kv->con_stride, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
-    CR_HIP(hipMemsetAsync(kv->d_con_on + seq, 1, 4, st));                               // != 0: on
-    kv->constrained[seq] = 1;
-    return CR_OK;
-}
-
-int cr_kv_logprobs(cr_kv* kv, int seq, float* lp, int32_t* top_ids, float* top_lp, int max, void* stream) {
-    if (!kv || !lp || !top_ids || !top_lp || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_logprobs: bad argument");
-    if (!kv->d_lpn || !kv->scored[seq]) return cr_fail(CR_ERR_STATE, "cr_kv_logprobs: sequence %d has token scores switched off (cr_kv_set_logprobs)", seq);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int n = kv->ngen[seq] < max ? kv->ngen[seq] : max;
-    const size_t at = (size_t)seq * kv->gen_cap;
-    if (n > 0) {
-        CR_HIP(hipMemcpyAsync(lp, kv->d_lp + at, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        CR_HIP(hipMemcpyAsync(top_ids, kv->d_top_id + at * LOGPROBS_MAX_TOP, (size_t)n * LOGPROBS_MAX_TOP * 4, hipMemcpyDeviceToHost, st));
-        CR_HIP(hipMemcpyAsync(top_lp, kv->d_top_lp + at * LOGPROBS_MAX_TOP, (size_t)n * LOGPROBS_MAX_TOP * 4, hipMemcpyDeviceToHost, st));
-    }
-    CR_HIP(hipStreamSynchronize(st));
-    return n;
-}
-
-// The beam blocks of a cache, allocated by the first call that needs them (that call also synchronises `st`: in place before a call on any other stream)
-static int beam_alloc(cr_kv* kv, hipStream_t st) {
-    if (!kv->d_beam) {
-        const size_t N = kv->n_seqs;
-        if (hipMalloc((void**)&kv->d_beam, N * sizeof(BeamState)) != hipSuccess || hipMalloc((void**)&kv->d_bgrp, N * 4) != hipSuccess ||
-            hipMalloc((void**)&kv->d_bfin, N * kv->gen_cap * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            if (kv->d_beam) hipFree(kv->d_beam);
-            if (kv->d_bgrp) hipFree(kv->d_bgrp);
-            if (kv->d_bfin) hipFree(kv->d_bfin);
-            kv->d_beam = nullptr; kv->d_bgrp = nullptr; kv->d_bfin = nullptr;
-            return cr_fail(CR_ERR_NOMEM, "beam search: %zu bytes of beam state", N * (sizeof(BeamState) + 4 + (size_t)kv->gen_cap * 8));
-        }
-        CR_HIP(hipMemsetAsync(kv->d_beam, 0, N * sizeof(BeamState), st));
-        CR_HIP(hipMemsetAsync(kv->d_bgrp, 0xff, N * 4, st));
-        CR_HIP(hipStreamSynchronize(st));                                               // once per cache: in place before a call on any other stream
-    }
-    return CR_OK;
-}
-
-int cr_kv_set_beam(cr_kv* kv, int first_seq, int num_beams, float length_penalty, int early_stopping, int eos_id, int max_new, void* stream) {
-    if (num_beams < 2 || num_beams > BEAM_MAX) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: num_beams %d (want 2..%d)", num_beams, BEAM_MAX);
-    if (early_stopping < 0 || early_stopping > 2 || !(length_penalty >= -3.402823466e38f && length_penalty <= 3.402823466e38f))
-        return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: early_stopping %d (0 False, 1 True, 2 'never') / length_penalty %g (finite)", early_stopping, length_penalty);
-    if (!kv || first_seq < 0 || first_seq + num_beams > kv->n_seqs)
-        return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: a group of %d from sequence %d runs past the cache's sequences", num_beams, first_seq);
-    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: beam search needs a bf16 cache (the re-order does not move e4m3 rows and scales)");
-    if (eos_id >= kv->ctx->d.vocab) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: EOS id %d outside the vocabulary", eos_id);
-    if (kv->ctx->d.vocab < 2 * BEAM_MAX) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: vocabulary of %d ids", kv->ctx->d.vocab);
-    if (max_new < 1 || max_new > kv->max_tokens) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: max_new %d (want 1..max_tokens = %d)", max_new, kv->max_tokens);
-    for (int j = 0; j < num_beams; j++) {
-        const int s = first_seq + j;
-        if (kv->sampled[s] || kv->scored[s]) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: sequence %d samples or records token scores", s);
-        if (kv->constrained[s]) return cr_fail(CR_ERR_STATE, "cr_kv_set_beam: sequence %d has logits constraints (no constraints with beams: cr_kv_set_constraints(NULL) first)", s);
-        if (kv->bgrp[s] >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_beam: sequence %d already belongs to the group of %d (cr_kv_reset first)", s, kv->bgrp[s]);
-        if (kv->len[s] != 0 || kv->ngen[s] != 0) return cr_fail(CR_ERR_STATE, "cr_kv_set_beam: sequence %d holds tokens (call after cr_kv_reset, before the prefill)", s);
-    }
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    CR_TRY(beam_alloc(kv, st));
-    CR_TRY(launch_set_beam(kv->d_beam, kv->d_bgrp, first_seq, num_beams, length_penalty, early_stopping, eos_id < 0 ? -1 : eos_id, max_new, st));
-    for (int j = 0; j < num_beams; j++) kv->bgrp[first_seq + j] = first_seq;
-    kv->bnum[first_seq] = num_beams;
-    return CR_OK;
-}
-
-int cr_kv_beam_result(cr_kv* kv, int first_seq, int64_t* out_host, int max, float* score, int32_t* length, int32_t* done, void* stream) {
-    if (!kv || !out_host || !score || !length || !done || first_seq < 0 || first_seq >= kv->n_seqs || max < 0) return cr_fail(CR_ERR_ARG, "cr_kv_beam_result: bad argument");
-    if (!kv->d_beam || kv->bgrp[first_seq] != first_seq) return cr_fail(CR_ERR_STATE, "cr_kv_beam_result: sequence %d is not the first of a beam group", first_seq);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    BeamState s;
-    CR_HIP(hipMemcpyAsync(&s, kv->d_beam + first_seq, sizeof(s), hipMemcpyDeviceToHost, st));
-    CR_HIP(hipStreamSynchronize(st));
-    *done = s.done;
-    *score = s.n_fin > 0 ? s.fin_score[0] : -1.0e9f;
-    *length = s.n_fin > 0 ? s.fin_len[0] : 0;
-    const int n = *length < max ? *length : max;
-    if (n > 0) {
-        CR_HIP(hipMemcpyAsync(out_host, kv->d_bfin + (size_t)(first_seq + s.fin_phys[0]) * kv->gen_cap, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        CR_HIP(hipStreamSynchronize(st));
-    }
-    return n;
-}
-
-int cr_kv_beam_reorder(cr_kv* kv, int first_seq, int num_beams, const int32_t* src_host, int from, void* stream) {
-    if (num_beams < 2 || num_beams > BEAM_MAX) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: num_beams %d (want 2..%d)", num_beams, BEAM_MAX);
-    if (!kv || !src_host || first_seq < 0 || first_seq + num_beams > kv->n_seqs || from < 0) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: bad argument");
-    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: the re-order moves bf16 rows only");
-    BeamState tmp{};
-    tmp.B = num_beams; tmp.prompt = from;
-    for (int j = 0; j < BEAM_MAX; j++) {
-        tmp.next_src[j] = j < num_beams ? src_host[j] : j;
-        if (tmp.next_src[j] < 0 || (j < num_beams && tmp.next_src[j] >= num_beams)) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: source %d of beam %d", tmp.next_src[j], j);
-    }
-    for (int j = 0; j < num_beams; j++) {
-        if (kv->bgrp[first_seq + j] >= 0)
-            return cr_fail(CR_ERR_STATE, "cr_kv_beam_reorder: sequence %d belongs to a live beam group (the entry is for plain sequences: it would overwrite the group's state)", first_seq + j);
-        if (kv->len[first_seq + j] != kv->len[first_seq] || kv->ngen[first_seq + j] != kv->ngen[first_seq])
-            return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: sequences %d and %d hold different counts of tokens or ids", first_seq, first_seq + j);
-    }
-    if (from > kv->len[first_seq]) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: from %d past the %d cached tokens", from, kv->len[first_seq]);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    CR_TRY(beam_alloc(kv, st));
-    // the slot of a sequence that is in no group is free: cr_kv_set_beam initialises it whole (pageable source: staged before the call returns)
-    CR_HIP(hipMemcpyAsync(kv->d_beam + first_seq, &tmp, sizeof(tmp), hipMemcpyHostToDevice, st));
-    BeamLaunch p{};
-    p.rows = 1; p.seqs = nullptr; p.grp = kv->d_bgrp; p.state = kv->d_beam; p.gen = kv->d_gen; p.ngen = kv->d_ngen; p.gen_cap = kv->gen_cap; p.lens = kv->d_len;
-    const int row = first_seq;                 // seqs NULL: a row is its sequence
-    return launch_beam_reorder(p, beam_cache(kv), &row, 1, kv->len[first_seq] - from, 0, st);
-}
-
-int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream) {
-    if (!kv || !host_out) return cr_fail(CR_ERR_ARG, "cr_kv_poll_finished: bad argument");
-    const int need = 1 + 2 * kv->n_seqs;
-    if (max < need) return cr_fail(CR_ERR_ARG, "cr_kv_poll_finished: %d int32 of room, %d needed", max, need);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    CR_HIP(hipMemcpyAsync(host_out, kv->d_stop, (size_t)need * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    return CR_OK;
-}
-
-int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, void* stream) {
-    if (!kv || !out || layer < 0 || layer >= kv->layers || seq < 0 || seq >= kv->n_seqs || pos < 0 || pos >= kv->max_tokens || (which != 0 && which != 1))
-        return cr_fail(CR_ERR_ARG, "cr_kv_read: bad argument");
-    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_read: the cache holds e4m3 rows, not bf16 (format %d): read them with cr_kv_read_e4m3", kv->fmt);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    const bf16* base = (which ? kv->v : kv->k) + (((int64_t)layer * kv->n_seqs + seq) * NKV * kv->max_tokens + pos) * HD;
-    CR_HIP(hipMemcpy2DAsync(out, HD * 2, base, (size_t)kv->max_tokens * HD * 2, HD * 2, NKV, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return CR_OK;
-}
-
-int cr_kv_read_e4m3(cr_kv* kv, int layer, int seq, int pos, int which, uint8_t* q_out, float* s_out, void* stream) {
-    if (!kv || !q_out || !s_out || layer < 0 || layer >= kv->layers || seq < 0 || seq >= kv->n_seqs || pos < 0 || pos >= kv->max_tokens ||
-        (which != 0 && which != 1))
-        return cr_fail(CR_ERR_ARG, "cr_kv_read_e4m3: bad argument");
-    if (kv->fmt != CR_KV_E4M3) return cr_fail(CR_ERR_ARG, "cr_kv_read_e4m3: the cache holds bf16 rows (format %d): read them with cr_kv_read", kv->fmt);
-    CR_HIP(hipSetDevice(kv->ctx->device));
-    const int64_t row = ((int64_t)layer * kv->n_seqs + seq) * NKV * kv->max_tokens + pos;
-    CR_HIP(hipMemcpy2DAsync(q_out, HD, (which ? kv->v8 : kv->k8) + row * HD, (size_t)kv->max_tokens * HD, HD, NKV, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    CR_HIP(hipMemcpy2DAsync(s_out, 4, (which ? kv->vs : kv->ks) + row, (size_t)kv->max_tokens * 4, 4, NKV, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return CR_OK;
-}
-
-int cr_kv_generated(cr_kv* kv, int seq, int64_t* out_host, int max, void* stream) {
-    if (!kv || !out_host || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_generated: bad argument");
-    const int n = kv->ngen[seq] < max ? kv->ngen[seq] : max;
-    if (n > 0) CR_HIP(hipMemcpyAsync(out_host, kv->d_gen + (size_t)seq * kv->gen_cap, (size_t)n * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    CR_HIP(hipStreamSynchronize((hipStream_t)stream));
-    return n;
-}
-
 int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, float penalty,
                          float* last_logits, void* stream) {
     if (!c || !kv || !seqs || !lens || !embeds || n <= 0 || n > kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_prefill_batch: bad argument");
@@ -1443,25 +865,26 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         const int s = seqs[i];
         if (s < 0 || s >= kv->n_seqs || lens[i] <= 0) return cr_fail(CR_ERR_ARG, "cr_llm_prefill_batch: bad sequence %d / length %d", s, lens[i]);
         for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_prefill_batch: sequence %d listed twice", s);
-        if (kv->len[s] + lens[i] > kv->max_tokens)
-            return cr_fail(CR_ERR_ARG, "cr_llm_prefill: %d + %d tokens exceed the cache (%d)", kv->len[s], lens[i], kv->max_tokens);
-        if (kv->fmt == CR_KV_E4M3 && kv->len[s] != 0)
+        if (kv->seq[s].len + lens[i] > kv->max_tokens)
+            return cr_fail(CR_ERR_ARG, "cr_llm_prefill: %d + %d tokens exceed the cache (%d)", kv->seq[s].len, lens[i], kv->max_tokens);
+        if (kv->fmt == CR_KV_E4M3 && kv->seq[s].len != 0)
             return cr_fail(CR_ERR_ARG, "cr_llm_prefill: sequence %d of an e4m3 cache already holds %d tokens (the prefill attends in bf16 and an e4m3 cache "
-                           "keeps no bf16 copy of a prefix: cr_kv_reset it first)", s, kv->len[s]);
-        if (kv->bgrp[s] >= 0 && (kv->bgrp[s] != s || kv->len[s] != 0 || kv->ngen[s] != 0))
+                           "keeps no bf16 copy of a prefix: cr_kv_reset it first)", s, kv->seq[s].len);
+        if (kv->seq[s].bgrp >= 0 && (kv->seq[s].bgrp != s || kv->seq[s].len != 0 || kv->seq[s].ngen != 0))
             return cr_fail(CR_ERR_ARG, "cr_llm_prefill: sequence %d belongs to the beam group of sequence %d: prefill the group's FIRST sequence, once, after "
-                           "cr_kv_reset and cr_kv_set_beam", s, kv->bgrp[s]);
-        segs.push_back({s, M, lens[i], kv->len[s]});
+                           "cr_kv_reset and cr_kv_set_beam", s, kv->seq[s].bgrp);
+        segs.push_back({s, M, lens[i], kv->seq[s].len});
         M += lens[i];
     }
-    const bool beams = beam_row_count(kv, seqs, n) > 0;
+    const RowFeatures feat = kv_scan_rows(kv, seqs, n, penalty);
+    const bool beams = feat.beam_rows > 0;
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const int V = c->d.vocab;
     const bool kv8 = kv->fmt == CR_KV_E4M3;
     int max_S = 0;
     for (const Segment& sg : segs) max_S = sg.S > max_S ? sg.S : max_S;
-    PrefillBufs b(c, kv, M, n, max_S, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty), beams);
+    PrefillBufs b(c, kv, M, n, max_S, feat);
     CR_TRY(ws_carve(c, "cr_llm_prefill_batch", b));
     {
         std::vector<int32_t> h(prefill_rows_ints(M, n, kv8));
@@ -1493,19 +916,20 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     for (int i = 0; i < n; i++)
         CR_TRY(rms(b.x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, b.head.hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
     CR_TRY(linear(c, EPI_F32, b.head.hl, head, LIN_LOADED, b.head.lg, n, st));
-    CR_TRY(pick_rows(kv, b.head, seqs, c->d_seqs, penalty, 0, last_logits, st, true));
+    CR_TRY(pick_rows(kv, b.head, c->d_seqs, penalty, 0, last_logits, st, true));
     hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, b.rows.seg, n, kv->d_len);
     if (beams) {    // the fan-out: the prompt's cache rows, the first id and the length go from a group's first sequence to its others
         std::vector<int> firsts;
-        for (int i = 0; i < n; i++) if (kv->bgrp[seqs[i]] == seqs[i]) firsts.push_back(i);
+        for (int i = 0; i < n; i++) if (kv->seq[seqs[i]].bgrp == seqs[i]) firsts.push_back(i);
         CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, c->d_seqs, penalty, 0, 1), beam_cache(kv), firsts.data(), (int)firsts.size(), max_S, 1, st));
     }
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
-        kv->len[sg.seq] += sg.S;
-        if (kv->ngen[sg.seq] < kv->gen_cap) kv->ngen[sg.seq] += 1;
-        if (kv->bgrp[sg.seq] == sg.seq)
-            for (int j = 1; j < kv->bnum[sg.seq]; j++) { kv->len[sg.seq + j] = kv->len[sg.seq]; kv->ngen[sg.seq + j] = kv->ngen[sg.seq]; }
+        Seq& q = kv->seq[sg.seq];
+        q.len += sg.S;
+        if (q.ngen < kv->gen_cap) q.ngen += 1;
+        if (q.bgrp == sg.seq)
+            for (int j = 1; j < q.bnum; j++) { kv->seq[sg.seq + j].len = q.len; kv->seq[sg.seq + j].ngen = q.ngen; }
     }
     return CR_OK;
 }
@@ -1530,21 +954,21 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     for (int i = 0; i < n; i++) {
         const int s = seqs[i];
         if (s < 0 || s >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_decode: sequence %d out of range", s);
-        if (kv->len[s] + 1 > kv->max_tokens) return cr_fail(CR_ERR_ARG, "cr_llm_decode: sequence %d cache full", s);
-        if (!force_tokens && kv->ngen[s] == 0) return cr_fail(CR_ERR_STATE, "cr_llm_decode: sequence %d has no generated id to feed", s);
+        if (kv->seq[s].len + 1 > kv->max_tokens) return cr_fail(CR_ERR_ARG, "cr_llm_decode: sequence %d cache full", s);
+        if (!force_tokens && kv->seq[s].ngen == 0) return cr_fail(CR_ERR_STATE, "cr_llm_decode: sequence %d has no generated id to feed", s);
         for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_decode: sequence %d listed twice", s);
     }
     int beam_span = 0;                                        // > 0: the launch holds beam groups; the most cache positions their re-order moves
     std::vector<int> beam_firsts;                             // the rows of the groups' first sequences
     for (int i = 0; i < n && kv->d_beam; i++) {
-        const int f = kv->bgrp[seqs[i]];
+        const int f = kv->seq[seqs[i]].bgrp;
         if (f < 0) continue;
-        const int B = kv->bnum[f];
+        const int B = kv->seq[f].bnum;
         if (seqs[i] != f || i + B > n) return cr_fail(CR_ERR_ARG, "cr_llm_decode: a beam group decodes whole: its %d sequences from %d on, consecutive in seqs[]", B, f);
         for (int j = 1; j < B; j++)
             if (seqs[i + j] != f + j) return cr_fail(CR_ERR_ARG, "cr_llm_decode: a beam group decodes whole: its %d sequences from %d on, consecutive in seqs[]", B, f);
         if (force_tokens) return cr_fail(CR_ERR_ARG, "cr_llm_decode: force_tokens with a beam group (sequence %d)", f);
-        beam_span = std::max(beam_span, kv->ngen[f] + 1);
+        beam_span = std::max(beam_span, kv->seq[f].ngen + 1);
         beam_firsts.push_back(i);
         i += B - 1;
     }
@@ -1555,9 +979,9 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     hipStream_t st = (hipStream_t)stream;
     const int V = c->d.vocab;
     int max_len = 0;
-    for (int i = 0; i < n; i++) max_len = kv->len[seqs[i]] > max_len ? kv->len[seqs[i]] : max_len;
+    for (int i = 0; i < n; i++) max_len = kv->seq[seqs[i]].len > max_len ? kv->seq[seqs[i]].len : max_len;
     const int nsplit = ((max_len + 1 + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
-    DecodeBufs b(c, kv, n, nsplit, any_scored(kv, seqs, n), long_history(kv, seqs, n, penalty), beam_span > 0);
+    DecodeBufs b(c, kv, n, nsplit, kv_scan_rows(kv, seqs, n, penalty));
     CR_TRY(ws_carve(c, "cr_llm_decode", b));
     CR_TRY(stage_seqs(c, seqs, n, st, false));
     const int32_t* d_seqs = c->d_seqs;
@@ -1575,13 +999,14 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         CR_TRY(rms(b.x, b.head.hl, nw, n, c->d.rms_eps, st));
         CR_TRY(linear(c, EPI_F32, b.head.hl, head, c->fp8_decode && n <= 64 && head.e4m3() ? LIN_E4M3 : LIN_DECODE, b.head.lg, n, st));
     }
-    CR_TRY(pick_rows(kv, b.head, seqs, d_seqs, penalty, 1, logits, st, false));
+    CR_TRY(pick_rows(kv, b.head, d_seqs, penalty, 1, logits, st, false));
     if (beam_span > 0)
         CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, d_seqs, penalty, 1, 0), beam_cache(kv), beam_firsts.data(), (int)beam_firsts.size(), beam_span, 1, st));
     CR_HIP(hipGetLastError());
     for (int i = 0; i < n; i++) {
-        kv->len[seqs[i]] += 1;
-        if (kv->ngen[seqs[i]] < kv->gen_cap) kv->ngen[seqs[i]] += 1;
+        Seq& q = kv->seq[seqs[i]];
+        q.len += 1;
+        if (q.ngen < kv->gen_cap) q.ngen += 1;
     }
     return CR_OK;
 }

@@ -186,17 +186,17 @@ size_t logprobs_scratch_bytes(int rows, int vocab) {
     return 256 + rc * 8 + rc * 4 + rc * TOPN * 8;
 }
 
-int launch_logprobs(const float* logits, int64_t ld, int vocab, int rows, const int32_t* seqs, const int32_t* lpn, int top_n, const int64_t* gen,
-                    const int32_t* ngen, int gen_cap, int32_t* done, void* scratch, float* out_lp, int32_t* out_id, float* out_tlp, hipStream_t st) {
-    const int chunks = logprobs_chunks(vocab);
-    const size_t rc = (size_t)rows * chunks;
-    double* ps = (double*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+int launch_logprobs(const LogprobsLaunch& p, hipStream_t st) {
+    const int chunks = logprobs_chunks(p.vocab);
+    const size_t rc = (size_t)p.rows * chunks;
+    double* ps = (double*)(((uintptr_t)p.scratch + 255) & ~(uintptr_t)255);
     float* pm = (float*)(ps + rc);
     float* pv = pm + rc;
     int32_t* pi = (int32_t*)(pv + rc * TOPN);
-    hipLaunchKernelGGL(logprobs_chunk_kernel, dim3(chunks, rows), dim3(THREADS), 0, st, logits, ld, vocab, chunks, seqs, lpn, pm, ps, pv, pi);
-    hipLaunchKernelGGL(logprobs_merge_kernel, dim3(rows), dim3(64), 0, st, logits, ld, vocab, chunks, seqs, lpn, top_n, gen, ngen, gen_cap, done,
-                       (const float*)pm, (const double*)ps, (const float*)pv, (const int32_t*)pi, out_lp, out_id, out_tlp);
+    hipLaunchKernelGGL(logprobs_chunk_kernel, dim3(chunks, p.rows), dim3(THREADS), 0, st, p.logits, p.ld, p.vocab, chunks, p.h.seqs, p.lpn, pm, ps, pv, pi);
+    hipLaunchKernelGGL(logprobs_merge_kernel, dim3(p.rows), dim3(64), 0, st, p.logits, p.ld, p.vocab, chunks, p.h.seqs, p.lpn, p.top_n, (const int64_t*)p.h.gen,
+                       (const int32_t*)p.h.ngen, p.h.gen_cap, p.done, (const float*)pm, (const double*)ps, (const float*)pv, (const int32_t*)pi, p.out_lp, p.out_id,
+                       p.out_tlp);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
@@ -215,7 +215,8 @@ extern "C" int cr_op_logprobs(const float* logits, int n, int vocab, const int64
     hipStream_t st = (hipStream_t)stream;
     void* scratch = nullptr;
     if (hipMalloc(&scratch, logprobs_scratch_bytes(n, vocab)) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "cr_op_logprobs: scratch");
-    const int rc = launch_logprobs(logits, vocab, vocab, n, nullptr, nullptr, top_n, ids, nullptr, 0, nullptr, scratch, lp, top_ids, top_lp, st);
+    const LogprobsLaunch p{logits, vocab, vocab, n, {nullptr, const_cast<int64_t*>(ids), nullptr, 0}, nullptr, top_n, nullptr, scratch, lp, top_ids, top_lp};
+    const int rc = launch_logprobs(p, st);
     hipStreamSynchronize(st);
     hipFree(scratch);
     return rc;

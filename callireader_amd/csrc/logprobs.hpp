@@ -6,9 +6,14 @@ constexpr int LOGPROBS_MAX_TOP = 8;
 
 // bytes of device scratch launch_logprobs needs for `rows` rows (the chunk partials)
 size_t logprobs_scratch_bytes(int rows, int vocab);
-// Scores of `rows` rows of logits [rows][ld] that a pick has just chosen from.  seqs given (device, one cache slot per row): rows whose lpn[seq] is 0 are
+// Scores of `rows` rows of logits [rows][ld] that a pick has just chosen from.  h.seqs given (device, one cache slot per row): rows whose lpn[seq] is 0 are
 // skipped; the others write slot t = ngen[seq] - 1 of out_lp [n_seqs][gen_cap] / out_id, out_tlp [n_seqs][gen_cap][8] with lpn[seq] alternatives, for the
-// id gen[seq][t], and advance done[seq].  seqs NULL: every row is scored with top_n alternatives for the id gen[row] into out_*[row].
-int launch_logprobs(const float* logits, int64_t ld, int vocab, int rows, const int32_t* seqs, const int32_t* lpn, int top_n, const int64_t* gen,
-                    const int32_t* ngen, int gen_cap, int32_t* done, void* scratch, float* out_lp, int32_t* out_id, float* out_tlp, hipStream_t st);
+// id gen[seq][t], and advance done[seq].  h.seqs NULL: every row is scored with top_n alternatives for the id gen[row] into out_*[row].
+struct LogprobsLaunch {
+    const float* logits; int64_t ld; int vocab; int rows;
+    Hist h;
+    const int32_t* lpn; int top_n; int32_t* done;
+    void* scratch; float* out_lp; int32_t* out_id; float* out_tlp;
+};
+int launch_logprobs(const LogprobsLaunch& p, hipStream_t st);
 int launch_set_logprobs(int32_t* lpn, int32_t* done, int seq, int top_n, hipStream_t st);

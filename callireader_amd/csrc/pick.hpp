@@ -1,4 +1,4 @@
-// Token choice shared by the greedy pick (llm.hip pick_kernel) and the sampling pick (sample.hip): the repetition penalty, the
+// Token choice shared by the greedy pick (pick.hip pick_kernel) and the sampling pick (sample.hip): the repetition penalty, the
 // first-max-wins argmax and the stop check run the same device code in both kernels, so a greedy row gets the same bits from either.
 #pragma once
 #include "common.hpp"
@@ -63,12 +63,48 @@ __device__ __forceinline__ void argmax_row(const float* __restrict__ lg, int voc
     }
 }
 
-// Sampling pick (sample.hip) over `rows` rows of logits (modified in place: penalty).  Per row, seq = seqs[row] (seqs NULL: seq = row) indexes the
-// history (gen [.][gen_cap], ngen) and the sampling state (temp / topk / topp / seed); a row whose temperature is not > 0 is greedy (pick_kernel's
-// result).  step NULL: step = ngen[seq]; else step[row].  append != 0: the id is appended to the sequence's history with pick_kernel's stop check and
-// lens update (lens[seq] += len_add).  out_ids / out_kept (may be NULL): the id and the size of the kept set of each row (0 for a greedy row).
+// Sampling pick (sample.hip) over `rows` rows of logits (modified in place: penalty).  Per row, seq = h.seqs[row] (NULL: seq = row) indexes the history and
+// the sampling state (temp / topk / topp / seed); a row whose temperature is not > 0 is greedy (pick_kernel's result).  step NULL: step = ngen[seq]; else
+// step[row].  append != 0: the id is appended to the sequence's history with pick_kernel's stop check and lens update (lens[seq] += len_add).  out_ids /
+// out_kept (may be NULL): the id and the size of the kept set of each row (0 for a greedy row).
 // orig (may be NULL): a copy of the rows made before the launch, for histories of more than 4096 ids (apply_penalty).
 // bgrp (may be NULL): [n_seqs] beam group of every sequence; a row whose sequence has one (>= 0) is left untouched (beam.hip picks for it).
-int launch_sample(float* logits, int64_t ld, int vocab, float penalty, int rows, const int32_t* seqs, int64_t* gen, int32_t* ngen, int gen_cap,
-                  const float* temp, const int32_t* topk, const float* topp, const uint64_t* seed, const int32_t* step, int append, int32_t* lens,
-                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig = nullptr, const int32_t* bgrp = nullptr);
+struct SampleLaunch {
+    float* logits; int64_t ld; int vocab; float penalty; int rows;
+    Hist h;
+    const float* temp; const int32_t* topk; const float* topp; const uint64_t* seed; const int32_t* step;
+    int append; int32_t* lens; int len_add; int32_t* stop; int n_seqs;
+    int64_t* out_ids; int32_t* out_kept;
+    const float* orig; const int32_t* bgrp;
+};
+int launch_sample(const SampleLaunch& p, hipStream_t st);
+
+// ---- what follows the LM head in a prefill / decode call (pick.hip; host) ----
+struct cr_kv; struct Arena; struct BeamLaunch; struct BeamCache;
+
+// which features the rows of a call use (kv.hip: kv_scan_rows): a call without a row that uses a feature launches nothing for it
+struct RowFeatures {
+    bool sampled, scored, constrained;      // a row samples / has token scores on / has logits constraints
+    bool deep; int beam_rows;               // a row has more than 4096 ids under a penalty: the pick needs an untouched copy of the rows / rows in a beam group
+};
+
+// The LM head's n rows of a prefill / decode call, carved after the layer buffers
+struct HeadBufs {
+    int n, V;
+    RowFeatures f;
+    bf16* hl;               // the normalised rows
+    float* lg;              // their logits [n][V]
+    void* score;            // f.scored: logprobs.hip's scratch
+    float* lg0;             // f.deep: the rows before the penalty, for the pick
+    char* cand;             // f.beam_rows: beam.hip's candidate scratch
+    void carve(Arena& ar);
+};
+
+// The logits h.lg out to the caller (`out`, may be NULL), then the constraint masks of the rows that have any (the pick, the penalty's copy h.lg0 and the scores
+// all see the masked row, the caller the raw one), then the pick (greedy or sampled; none if every row is a beam row) appends every row's id and adds len_add to
+// its cached length, then the scores of the rows the pick has just chosen from (h.lg: the penalised rows it left) go into the sequences' slots, then the beam step
+int pick_rows(cr_kv* kv, const HeadBufs& h, const int32_t* d_seqs, float penalty, int len_add, float* out, hipStream_t st, bool prefill);
+// The beam step of the launch's groups, after the picks of its other rows: candidates and select on the logits rows (first_only: a prefill, which holds a
+// group's first sequence only), and in a decode step the re-order behind them (the prefill's follows its set_len_kernel)
+BeamLaunch beam_launch(cr_kv* kv, const HeadBufs& h, const int32_t* d_seqs, float penalty, int len_add, int first_only);
+BeamCache beam_cache(const cr_kv* kv);

@@ -321,11 +321,9 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
 
 }  // namespace
 
-int launch_sample(float* logits, int64_t ld, int vocab, float penalty, int rows, const int32_t* seqs, int64_t* gen, int32_t* ngen, int gen_cap,
-                  const float* temp, const int32_t* topk, const float* topp, const uint64_t* seed, const int32_t* step, int append, int32_t* lens,
-                  int len_add, int32_t* stop, int n_seqs, int64_t* out_ids, int32_t* out_kept, hipStream_t st, const float* orig, const int32_t* bgrp) {
-    hipLaunchKernelGGL(sample_kernel, dim3(rows), dim3(1024), 0, st, logits, ld, vocab, penalty, seqs, gen, ngen, gen_cap, temp, topk, topp, seed,
-                       step, append, lens, len_add, stop, n_seqs, out_ids, out_kept, orig, bgrp);
+int launch_sample(const SampleLaunch& p, hipStream_t st) {
+    hipLaunchKernelGGL(sample_kernel, dim3(p.rows), dim3(1024), 0, st, p.logits, p.ld, p.vocab, p.penalty, p.h.seqs, p.h.gen, p.h.ngen, p.h.gen_cap, p.temp, p.topk,
+                       p.topp, p.seed, p.step, p.append, p.lens, p.len_add, p.stop, p.n_seqs, p.out_ids, p.out_kept, p.orig, p.bgrp);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
@@ -341,6 +339,9 @@ extern "C" int cr_op_sample(cr_ctx* c, const float* logits, int n, int vocab, co
     CR_TRY(ws_ensure(c, (size_t)n * vocab * 4));
     float* lg = (float*)c->ws;
     CR_HIP(hipMemcpyAsync(lg, logits, (size_t)n * vocab * 4, hipMemcpyDeviceToDevice, st));
-    return launch_sample(lg, vocab, vocab, penalty, n, nullptr, const_cast<int64_t*>(history), const_cast<int32_t*>(hist_len), hist_cap,
-                         temperature, top_k, top_p, seed, step, 0, nullptr, 0, nullptr, 0, out_ids, out_kept, st);
+    SampleLaunch p{};
+    p.logits = lg; p.ld = vocab; p.vocab = vocab; p.penalty = penalty; p.rows = n;
+    p.h = {nullptr, const_cast<int64_t*>(history), const_cast<int32_t*>(hist_len), hist_cap};
+    p.temp = temperature; p.topk = top_k; p.topp = top_p; p.seed = seed; p.step = step; p.out_ids = out_ids; p.out_kept = out_kept;
+    return launch_sample(p, st);
 }

@@ -1,4 +1,4 @@
-"""cr_kv_truncate / cr_kv_fork (csrc/kvops.hip) on a real MI355X: a 2-layer LLM at full width, the fixture style of test_gpu_llm.py.
+"""cr_kv_reset / cr_kv_truncate / cr_kv_fork (csrc/kv.hip) on a real MI355X: a 2-layer LLM at full width, the fixture style of test_gpu_llm.py.
 
 Truncate is state only, fork copies exactly a prefix, and a sequence that was rolled back or forked computes the bits of one that never ran ahead --
 the properties callireader_amd/session.py builds a page's second turn and its branches on.  The composed path is held against the CPU oracle under
@@ -211,4 +211,97 @@ def test_truncate_fork_prefill_against_the_oracle(setup):
     assert kv.length(1) == a + b + 6 and kv.length(0) == a
     if diverged:
         print(f'greedy picks differed from the oracle at measured near-ties, steps {diverged}')
+    kv.free()
+
+
+CLEAR_SEQS = (0, 63, 64, 65)       # 66 sequences: past the 64 threads of the truncate kernel's workgroup and the 64 entries of its sequence list
+CLEAR_KEEP = 5                     # positions truncate / fork keep of the 8-row prompt
+SAMPLING = dict(temperature=100.0, seed=20240229)
+
+
+@pytest.fixture(scope='module')
+def fresh(setup):
+    """What a sequence that never had a feature switched on computes for the 8-row prompt at penalty 1.5, with n = 0 and n = CLEAR_KEEP of its positions
+    cached already (the cached prefix is the prompt's own: prefill, then truncate): {n: (raw logits, greedy id, the id SAMPLING picks instead)}."""
+    eng = setup['eng']
+    P = prompt(8, 77).cuda()
+    out = {}
+    for n in (0, CLEAR_KEEP):
+        kv = eng.kv_alloc(2, 64)
+        for s in (0, 1):
+            if n:
+                eng.prefill(kv, s, P)
+                kv.truncate(s, n)
+            if s:
+                kv.set_sampling(s, **SAMPLING)
+            lg = eng.prefill(kv, s, P[:, n:], penalty=1.5, want_logits=True).clone()
+            if s == 0:
+                logits = lg
+        out[n] = (logits, kv.generated(0)[0], kv.generated(1)[0])
+        kv.free()
+    return P, out
+
+
+@pytest.mark.parametrize('way', ['reset_seq', 'reset_all', 'truncate', 'fork'])
+def test_every_way_of_clearing_forgets_everything(setup, fresh, way):
+    """Sequences 0, 63, 64 and 65 of a 66-sequence cache carry every per-sequence feature that coexists (a stop budget that has fired, sampling, token
+    scores, a constraint that bans the id a fresh sequence picks), sequences 10 and 11 are a prefilled beam group.  After reset(seq), reset(),
+    truncate(seq, n > 0) or fork(src, [seq], n) a sequence computes the bits of one that never had a feature on."""
+    from callireader_amd._binding import CalliReaderError
+    from callireader_amd.constraints import Constraints
+    eng = setup['eng']
+    P, ref = fresh
+    n = CLEAR_KEEP if way in ('truncate', 'fork') else 0
+    logits, greedy_id, sampled_id = ref[n]
+    for k in ref:
+        assert ref[k][2] != ref[k][1], (k, ref[k][1:])              # SAMPLING picks another id than greedy: sampling left on would show
+    N = 66
+    kv = eng.kv_alloc(N, 64)
+    for s in CLEAR_SEQS:
+        kv.set_stop(s, max_new=1)
+        kv.set_sampling(s, **SAMPLING)
+        kv.set_logprobs(s, 3)
+        kv.set_constraints(s, Constraints(suppress_tokens=(greedy_id,)))
+        eng.prefill(kv, s, P, penalty=1.5)
+        eng.decode(kv, [s], penalty=1.5)
+    kv.set_beam(10, 2, eos_id=None, max_new=8)
+    eng.prefill(kv, 10, P)
+    eng.prefill(kv, 20, P)                                           # the fork's source: a plain sequence
+    got = poll(kv)
+    for s in CLEAR_SEQS:
+        assert got[1 + N + s] == 1 and len(kv.generated(s)) == 2 and greedy_id not in kv.generated(s)[:1]
+        assert len(kv.logprobs(s)[0]) == 2
+    assert got[0] >= len(CLEAR_SEQS)
+    with pytest.raises(CalliReaderError, match=STATE):
+        kv.truncate(10, 3)
+    if way == 'reset_all':
+        kv.reset()
+        assert poll(kv)[0] == 0                                      # the finished ring starts over
+    for s in CLEAR_SEQS:
+        if way == 'reset_seq':
+            kv.reset(s)
+        elif way == 'truncate':
+            kv.truncate(s, n)
+        elif way == 'fork':
+            kv.fork(20, [s], n)
+    got = poll(kv)
+    for s in CLEAR_SEQS:
+        assert kv.length(s) == n and kv.generated(s) == []
+        assert got[1 + N + s] == 0, s                                # no stop
+        with pytest.raises(CalliReaderError, match=STATE):
+            kv.logprobs(s)
+        lg = eng.prefill(kv, s, P[:, n:], penalty=1.5, want_logits=True)
+        assert torch.equal(lg, logits), (s, float((lg - logits).abs().max()))
+        assert kv.generated(s) == [greedy_id], (s, kv.generated(s), greedy_id, sampled_id)
+    assert all(v == 0 for v in poll(kv)[1 + N:]), 'a budget outlived the clear'
+    if way in ('reset_seq', 'reset_all'):
+        if way == 'reset_seq':
+            kv.reset(11)                                             # one member: the group goes as a whole
+        kv.truncate(10, 3 if way == 'reset_seq' else 0)              # the other member: no STATE error any more
+        assert kv.length(10) == (3 if way == 'reset_seq' else 0)
+        kv.reset(10)
+        assert poll(kv)[1 + N + 10] == 0
+        kv.set_beam(10, 2, eos_id=None, max_new=8)                   # accepted again
+        eng.prefill(kv, 10, P)
+        assert kv.length(11) == 8
     kv.free()
