@@ -80,6 +80,7 @@ SIGNATURES = {
     'cr_llm_prefill_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), f32, vp, vp]),
     'cr_llm_hidden_probe': (i32, [vp, vp, i32, i32]),
     'cr_llm_decode': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, f32, vp, vp]),
+    'cr_llm_decode_draft': (i32, [vp, vp, C.POINTER(C.c_int32), i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, f32, C.POINTER(C.c_int32), vp]),
     'cr_share_weights': (i32, [vp, vp]),
     'cr_enable_fp8_decode': (i32, [vp, i32, vp]),
     'cr_enable_fp8_mfma': (i32, [vp, i32, vp]),

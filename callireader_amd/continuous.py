@@ -126,12 +126,15 @@ class ContinuousPipeline:
         self.worker.start()
 
     # ---- caller side ----------------------------------------------------------------------------
-    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None, logprobs=0, constraints=None):
+    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None, logprobs=0, constraints=None, draft_ids=None):
         """Queue one page's prompt embeddings ([S, hidden] on the device) with its budget of new ids (default, and at most, the pipeline's);
         returns its ticket.  Prefills a group when one is complete.  ValueError for a budget the pipeline cannot take.  sampling (a
         sampling.SamplingParams) with a 64-bit `seed`: the page samples (its sequence's state is set after its reset, before its prefill);
         None: greedy.  logprobs: 0, or the number of alternatives (1..8) to record per generated id: the page's result is (ids, TokenScores).
         constraints (a constraints.Constraints, greedy pages only): installed after the sequence's reset, before its prefill."""
+        if draft_ids is not None:
+            from .draft import refuse
+            refuse('ContinuousPipeline (its rows stop on the device, its worker never waits for a step)')
         t0 = time.perf_counter()
         self._raise_worker_error()
         logprobs = check_top_n(logprobs, 'logprobs', allow_zero=True)

@@ -73,8 +73,9 @@ template <int D> __device__ __forceinline__ int vswz(int r) { return D == 64 ? (
 // 10 waves per CU: 0.62 ms) and of 8 waves (256 queries; one workgroup per CU: 0.56 ms) against 0.50-0.51 for these 4.  The lean tile is 138 vector instructions + 16 MFMAs +
 // 24 LDS reads per wave; per SIMD the three waves' vector (~1 340 cycles) and matrix (1 536) work would fit 2 880 cycles even
 // with no overlap at all, the measured round is ~5 400: the SIMD idles while all three waves sit at their workgroups' barriers.
-template <int D, bool CAUSAL, bool SPLIT = false, bool DIV = false>
+template <int D, bool CAUSAL, bool SPLIT = false, bool DIV = false, bool OFF = false>      // OFF (split form only): AttnParams::sk_off, a per-batch addition to the key count
 __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) {
+    static_assert(!OFF || SPLIT, "key-count offsets belong to the decode launch");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWB = D * 2;
     constexpr int TILE = 64 * ROWB;
@@ -109,6 +110,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
     const int kvh = head / p.kv_group;
     int slot = p.seq_map ? p.seq_map[batch] : batch;
     int Sk = p.sk_arr ? p.sk_arr[slot] + p.sk_add : p.Sk;
+    if (OFF) Sk += p.sk_off[batch];
     int Sq = p.Sq, q_pos0 = p.q_pos0;
     int64_t q_base = (int64_t)batch * p.q_bs, o_base = (int64_t)batch * p.o_bs;
     if (CAUSAL && p.seg) {                                    // several pages' prompts in one launch (wave-uniform)
@@ -412,12 +414,12 @@ __global__ __launch_bounds__(D) void attn_combine_kernel(const AttnParams p) {
     p.O[(int64_t)batch * p.o_bs + (int64_t)q * p.o_rs + (int64_t)head * p.o_hs + d] = f2bf(acc / L);
 }
 
-template <int D, bool DIV>
+template <int D, bool DIV, bool OFF = false>
 int launch_split_d(const AttnParams& p, hipStream_t stream) {
     constexpr int LDS = 2 * 2 * 64 * D * 2;
     static std::atomic<uint64_t> attr_done{0};
-    if (!cr_dyn_lds_once(attr_done, (const void*)flash_attn_kernel<D, false, true, DIV>, LDS)) return CR_ERR_HIP;
-    hipLaunchKernelGGL((flash_attn_kernel<D, false, true, DIV>), dim3(p.nsplit, p.H, p.B), dim3(256), LDS, stream, p);
+    if (!cr_dyn_lds_once(attr_done, (const void*)flash_attn_kernel<D, false, true, DIV, OFF>, LDS)) return CR_ERR_HIP;
+    hipLaunchKernelGGL((flash_attn_kernel<D, false, true, DIV, OFF>), dim3(p.nsplit, p.H, p.B), dim3(256), LDS, stream, p);
     hipLaunchKernelGGL((attn_combine_kernel<D>), dim3(p.Sq, p.H, p.B), dim3(D), 0, stream, p);
     return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
 }
@@ -442,6 +444,10 @@ int launch_flash_attn_split(const AttnParams& p, int head_dim, hipStream_t strea
         if (launch_decode_attn(p, stream) != CR_OK) return CR_ERR_HIP;
         hipLaunchKernelGGL((attn_combine_kernel<128>), dim3(p.Sq, p.H, p.B), dim3(128), 0, stream, p);
         return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
+    }
+    if (p.sk_off) {                                           // a draft window's rows (llm.hip): the LLM's shape only
+        if (head_dim != 128 || !p.sk_arr) return CR_ERR_ARG;
+        return dv ? launch_split_d<128, true, true>(p, stream) : launch_split_d<128, false, true>(p, stream);
     }
     if (head_dim == 64) return dv ? launch_split_d<64, true>(p, stream) : launch_split_d<64, false>(p, stream);
     if (head_dim == 128) return dv ? launch_split_d<128, true>(p, stream) : launch_split_d<128, false>(p, stream);

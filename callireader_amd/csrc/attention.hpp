@@ -41,6 +41,10 @@ struct AttnParams {
     const float* k_scale;
     const float* v_scale;
     int64_t s_bs, s_hs;
+    // decode with several consecutive positions of one sequence as rows (cr_llm_decode_draft), may be NULL: batch b holds sk_arr[slot] + sk_add + sk_off[b] keys.
+    // The streaming bf16 kernel and the matrix-core split kernel take it (instances of their own: a launch without it runs the code it always ran); the folded
+    // form and the e4m3 kernel do not (decode_attn_fold_supported / decode_attn8_supported are false)
+    const int32_t* sk_off;
 };
 
 bool decode_attn_fold_supported(const AttnParams& p, int head_dim);

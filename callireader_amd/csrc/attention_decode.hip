@@ -52,8 +52,12 @@ constexpr int FOLD_MAX_SPLITS = 8;       // K-slices of the wqkv partial-sum GEM
 // slot are one DPP row); the six bf16 rows meet in 1.5 KiB of LDS behind one barrier.  q is read from there; the workgroup whose split holds the new position also
 // stores the K / V row to the cache and puts it into the registers of the lanes that would have loaded it (every lane at or past the new position: the cache row
 // itself is not written yet when they load it).  The same fp32 sums, the same roundings: a row's bits do not depend on which form its batch takes.
-template <bool DIV, bool FOLD = false>
+// OFF: batch b holds p.sk_off[b] keys more than its slot's length says (cr_llm_decode_draft: the rows of one sequence's draft window sit at consecutive
+// positions).  An instance of its own, so a launch without offsets runs the code it always ran; never with FOLD (a row would read cache rows that other workgroups
+// of the same launch are still writing).
+template <bool DIV, bool FOLD = false, bool OFF = false>
 __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const AttnParams p) {
+    static_assert(!(FOLD && OFF), "the folded form takes one new token per sequence");
     __shared__ __attribute__((aligned(16))) float s_o[16][NQ][HD];      // the workgroup's 16 partials: un-normalised O ...
     __shared__ float s_ml[16][NQ][2];                                   // ... maximum and row sum
     __shared__ __attribute__((aligned(16))) bf16x8 s_qkv[FOLD ? 6 : 1][16];   // FOLD: the rotated q heads, the new K row, the new V row
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const AttnParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.x, head = blockIdx.y, batch = blockIdx.z;
     const int slot = p.seq_map ? p.seq_map[batch] : batch;
-    const int Sk = p.sk_arr ? p.sk_arr[slot] + p.sk_add : p.Sk;
+    const int Sk = (p.sk_arr ? p.sk_arr[slot] + p.sk_add : p.Sk) + (OFF ? p.sk_off[batch] : 0);
     const int64_t prow = (((int64_t)batch * p.H + head) * p.nsplit + split) * NQ;
     if (split * 256 >= Sk) {                                  // a shorter row's empty split: (-inf, 0, 0), as the matrix-core kernel leaves it
         for (int idx = tid; idx < NQ * HD; idx += 256) p.part_o[prow * HD + idx] = 0.f;
@@ -412,7 +416,7 @@ bool decode_attn8_available() { return !decode_attn_off(); }
 
 // the e4m3 kernel's shape: the streaming kernel's, with 128-byte keys (16-byte aligned rows and planes) and fp32 scales
 bool decode_attn8_supported(const AttnParams& p, int head_dim) {
-    return decode_attn8_available() && !p.force_matrix_core && p.K8 && p.V8 && p.k_scale && p.v_scale && !p.qkv_part && p.kv_group == 1 && head_dim == HD &&
+    return decode_attn8_available() && !p.force_matrix_core && p.K8 && p.V8 && p.k_scale && p.v_scale && !p.qkv_part && !p.sk_off && p.kv_group == 1 && head_dim == HD &&
            p.Sq == NQ && ATTN_SPLIT_TILES == 4 && p.q_prescale == 1.0f && p.part_ml && p.part_o && p.nsplit > 0 &&
            (p.q_rs & 7) == 0 && (p.q_hs & 7) == 0 && (p.q_bs & 7) == 0 && (p.k_rs & 15) == 0 && (p.v_rs & 15) == 0 && (p.k_hs & 15) == 0 && (p.v_hs & 15) == 0 &&
            (p.k_bs & 15) == 0 && (p.v_bs & 15) == 0 && (p.sk_arr || p.Sk > 0) && p.k_rs > 0 && p.v_rs > 0 && p.k_rs < 65536 && p.v_rs < 65536 &&
@@ -433,7 +437,7 @@ bool decode_attn_supported(const AttnParams& p, int head_dim) {
 
 // the folded form on top: partial sums of the [H groups][4 q | k | v][128] row, at most FOLD_MAX_SPLITS slices, one new token per row at position sk_arr[slot]
 bool decode_attn_fold_supported(const AttnParams& p, int head_dim) {
-    return decode_attn_supported(p, head_dim) && p.qkv_part && p.rope_cos && p.rope_sin && p.qkv_splits >= 1 && p.qkv_splits <= FOLD_MAX_SPLITS &&
+    return decode_attn_supported(p, head_dim) && !p.sk_off && p.qkv_part && p.rope_cos && p.rope_sin && p.qkv_splits >= 1 && p.qkv_splits <= FOLD_MAX_SPLITS &&
            p.sk_arr && p.sk_add == 1 && p.k_rs == HD && p.v_rs == HD && (p.qkv_ld & 3) == 0 && p.qkv_ld >= (int64_t)p.H * 6 * HD &&
            (((uintptr_t)p.qkv_part | (uintptr_t)p.rope_cos | (uintptr_t)p.rope_sin) & 15) == 0;
 }
@@ -448,6 +452,9 @@ int launch_decode_attn(const AttnParams& p, hipStream_t stream) {
         if (!decode_attn_fold_supported(p, HD)) return CR_ERR_ARG;
         if (p.s_div != 1.0f) hipLaunchKernelGGL((decode_attn_kernel<true, true>), grid, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((decode_attn_kernel<false, true>), grid, dim3(256), 0, stream, p);
+    } else if (p.sk_off) {
+        if (p.s_div != 1.0f) hipLaunchKernelGGL((decode_attn_kernel<true, false, true>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((decode_attn_kernel<false, false, true>), grid, dim3(256), 0, stream, p);
     } else if (p.s_div != 1.0f) hipLaunchKernelGGL((decode_attn_kernel<true, false>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((decode_attn_kernel<false, false>), grid, dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;

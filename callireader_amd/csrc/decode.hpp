@@ -25,6 +25,7 @@ struct DecodeGemmParams {
     bf16 *q_out, *kc, *vc;
     const int32_t *seqs, *lens;
     int max_tokens;
+    const int32_t* pos_off;              // DEC_WQKV, may be NULL: row m's RoPE position and cache row are lens[seq] + pos_off[m] (cr_llm_decode_draft: several rows of one sequence)
     int flags;                           // tuning knobs (cr_op_decode_gemm / CR_DEC_FLAGS): bit 0 forces, bit 1 forbids the one-wave-per-row RMSNorm prologue of w1|w3 / the LM head
 };
 

@@ -35,7 +35,7 @@ namespace {
 constexpr int D4 = 4096, HD = 128, NKV = 8;
 constexpr int LIN_FLOATS = 16 * 17;
 
-enum { DEPI_ROPE = 100 };
+enum { DEPI_ROPE = 100, DEPI_ROPE_OFF = 101 };      // _OFF: row m sits p.pos_off[m] positions past its sequence's cached length (a draft window, llm.hip)
 
 // PRO: X = RMSNorm(xres) built in LDS and read from there; otherwise X comes as fragment-shaped loads from L2, one batch ahead.
 // TG: tile groups per workgroup -- TG * KW waves, group tg = wave / KW works on tile base + tg, all groups share the normalised rows in LDS
@@ -54,6 +54,7 @@ enum { DEPI_ROPE = 100 };
 template <int EPI, int KW, int VS, int KPR, bool PRO, int TG = 1, bool ALIAS = false, bool SW = false, bool PROW = false>
 __global__ __launch_bounds__(TG * KW * 64, (PRO && !PROW) ? 4 : 2) void gemm_decode_kernel(const DecodeGemmParams p) {      // PRO forms: 128 registers, 16 waves per CU
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr bool ROPE = EPI == DEPI_ROPE || EPI == DEPI_ROPE_OFF;
     constexpr int T = VS * KPR;            // 32-deep k-steps per wave and tile
     constexpr int UB = 8;                  // k-steps per register batch; two batches of weight loads are in flight (batches of 16 in the 256-register forms: +-0, round 5)
     static_assert(T % UB == 0 && T / UB >= 2, "whole batches, at least two");
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(TG * KW * 64, (PRO && !PROW) ? 4 : 2) void gemm_dec
     red += tg * KW * VS * LIN_FLOATS;
 
     auto wrow = [&](int tile, int r) -> int {
-        if (EPI == DEPI_ROPE) {            // head slot gs = tile / 8: rows 8j..8j+7 of its first half and the 8 rows 64 further on
+        if (ROPE) {                        // head slot gs = tile / 8: rows 8j..8j+7 of its first half and the 8 rows 64 further on
             const int gs = tile >> 3, j8 = tile & 7;
             return gs * HD + (r < 8 ? 8 * j8 + r : 64 + 8 * j8 + (r - 8));
         }
@@ -111,9 +112,10 @@ __global__ __launch_bounds__(TG * KW * 64, (PRO && !PROW) ? 4 : 2) void gemm_dec
     float xpre = 0.f, cs = 0.f, sn = 0.f;
     int seq = 0, pos = 0;
     if (EPI == EPI_RES && elive0) xpre = bf2f(p.xio[(int64_t)em * D4 + etile0 * 16 + en]);
-    if (EPI == DEPI_ROPE && elive0) {
+    if (ROPE && elive0) {
         const int j8 = etile0 & 7, c = en < 8 ? 8 * j8 + en : 64 + 8 * j8 + (en - 8);
         seq = p.seqs[em]; pos = p.lens[seq];
+        if (EPI == DEPI_ROPE_OFF) pos += p.pos_off[em];
         cs = bf2f(p.cosT[(int64_t)pos * HD + c]); sn = bf2f(p.sinT[(int64_t)pos * HD + c]);
     }
 
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(TG * KW * 64, (PRO && !PROW) ? 4 : 2) void gemm_dec
             } else if (EPI == EPI_F32) {
                 const int gn = etile * 16 + en;
                 if (gn < p.N) ((float*)p.C)[(int64_t)em * p.ldc + gn] = rbf(lt[en * 17 + em] + 0.f);
-            } else if (EPI == DEPI_ROPE) {
+            } else if (ROPE) {
                 // rope_split_kernel: the bf16 linear output, rotated (slots 0..4 of a group: 4 q heads and k), split into q rows and the cache
                 const int gs = etile >> 3, j8 = etile & 7, grp = gs / 6, slot = gs - grp * 6;
                 const int c = en < 8 ? 8 * j8 + en : 64 + 8 * j8 + (en - 8);
@@ -366,6 +368,7 @@ static int launch_decode_gemm_(int which, const DecodeGemmParams& p, hipStream_t
         case DEC_WQKV:
             if (p.N != 6144 || p.K != 4096 || !p.xres || !p.gamma || !p.cosT || !p.sinT || !p.q_out || !p.kc || !p.vc || !p.seqs || !p.lens) return CR_ERR_ARG;
             // (one wave per row here too -- which costs the second workgroup per CU its registers -- measured 15.1-17.2 us against 11.2-15.5 at 1-8 rows: not kept)
+            if (p.pos_off) return launch_one<DEPI_ROPE_OFF, 8, DEC_SLICES_WQKV, 8, true, 1, true>(p, 0, st);      // a draft window's rows: the same sums, another position
             return launch_one<DEPI_ROPE, 8, DEC_SLICES_WQKV, 8, true, 1, true>(p, 0, st);              // one tile per workgroup: sums alias the normalised rows
         case DEC_WO:
             if (p.N != 4096 || p.K != 4096 || !p.X || !p.xio) return CR_ERR_ARG;

@@ -19,6 +19,7 @@
 
 #include "attention.hpp"
 #include "decode.hpp"
+#include "draft.hpp"
 #include "kv.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
@@ -26,13 +27,16 @@
 namespace {
 
 // x[i] = tok_embeddings[id_i]; id_i = force[i] or the last generated id of seq_i
+// OFF (a draft window's rows, cr_llm_decode_draft): row i is fed the id row_off[i] slots behind that one -- the drafted ids that draft.hip staged there
+template <bool OFF = false>
 __global__ __launch_bounds__(256) void embed_rows_kernel(const bf16* __restrict__ table, const int64_t* __restrict__ force,
                                                          const int32_t* __restrict__ seqs, const int64_t* __restrict__ gen,
-                                                         const int32_t* __restrict__ ngen, int gen_cap, bf16* __restrict__ x) {
+                                                         const int32_t* __restrict__ ngen, int gen_cap, bf16* __restrict__ x,
+                                                         const int32_t* __restrict__ row_off = nullptr) {
     const int i = blockIdx.x;
     int64_t id;
     if (force) id = force[i];
-    else { const int s = seqs[i]; id = gen[(int64_t)s * gen_cap + ngen[s] - 1]; }
+    else { const int s = seqs[i]; id = gen[(int64_t)s * gen_cap + ngen[s] - 1 + (OFF ? row_off[i] : 0)]; }
     const bf16x8* src = (const bf16x8*)(table + id * D);
     bf16x8* dst = (bf16x8*)(x + (int64_t)i * D);
     dst[threadIdx.x] = src[threadIdx.x];
@@ -116,7 +120,8 @@ __device__ __forceinline__ float row_max16(float v) {
 // Q8 (e4m3 cache): the K / V rows go to the cache as e4m3 bytes + one fp32 scale each (common.hpp's e4m3 row rule, as quant_fp8_rows_kernel; a slot's 16 chunks
 // are one DPP row, so the row maximum is four rotate-max steps), and -- when kc / vc are given (prefill) -- as bf16 into the prefill's staging
 // [pages][8][stage_T][128] at (row_page[row], pos), which the prefill attention reads instead of the cache.
-template <bool Q8 = false>
+// OFF (a draft window's rows, cr_llm_decode_draft): the row sits row_off[row] positions past lens[seq]; an instance of its own.
+template <bool Q8 = false, bool OFF = false>
 __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ cosT,
                                                          const bf16* __restrict__ sinT, bf16* __restrict__ q_out,
                                                          bf16* __restrict__ kc, bf16* __restrict__ vc, int pos0, int seq0,
@@ -125,14 +130,15 @@ __global__ __launch_bounds__(128) void rope_split_kernel(const bf16* __restrict_
                                                          const float* __restrict__ part, int splits,
                                                          unsigned char* __restrict__ k8 = nullptr, unsigned char* __restrict__ v8 = nullptr,
                                                          float* __restrict__ ks = nullptr, float* __restrict__ vs = nullptr,
-                                                         const int32_t* __restrict__ row_page = nullptr, int stage_T = 0) {
+                                                         const int32_t* __restrict__ row_page = nullptr, int stage_T = 0,
+                                                         const int32_t* __restrict__ row_off = nullptr) {
     // part != nullptr (decode): the wqkv output arrives as `splits` fp32 K-slices [s][rows][QKV]; their sum in slice
     // order, rounded once, is the bf16 linear output the reference rotates
     const int row = blockIdx.x, grp = blockIdx.y;
     const int slot = threadIdx.x >> 4, c = threadIdx.x & 15;
     if (slot >= 6) return;
     const int seq = seqs ? seqs[row] : seq0;
-    const int pos = row_pos ? row_pos[row] : (lens ? lens[seq] : pos0 + row);
+    const int pos = (row_pos ? row_pos[row] : (lens ? lens[seq] : pos0 + row)) + (OFF ? row_off[row] : 0);
     const int64_t col0 = (int64_t)(grp * 6 + slot) * HD;
     auto chunk = [&](int cc) -> bf16x8 {
         if (!part) return *(const bf16x8*)(qkv + (int64_t)row * QKV + col0 + cc * 8);
@@ -428,7 +434,7 @@ int prefill_layers(cr_ctx* c, cr_kv* kv, const PrefillBufs& b, hipStream_t st) {
         CR_TRY(m8 ? linear_f8(c, EPI_STORE, b.h, b.hs, w.qkv, b.qkv, M, st) : linear(c, EPI_STORE, b.h, w.qkv, LIN_PREFILL, b.qkv, M, st));
         // (bf16 cache: lk's e4m3 pointers are null, and the kernel takes no staging)
         hipLaunchKernelGGL(b.kv8 ? rope_split_kernel<true> : rope_split_kernel<false>, dim3(M, NKV), dim3(128), 0, st, b.qkv, cosT, sinT, b.q, lk.k, lk.v, 0, 0,
-                           r.row_seq, nullptr, r.row_pos, kv->max_tokens, nullptr, 0, lk.k8, lk.v8, lk.ks, lk.vs, b.kv8 ? r.row_page : nullptr, b.kv8 ? b.max_S : 0);
+                           r.row_seq, nullptr, r.row_pos, kv->max_tokens, nullptr, 0, lk.k8, lk.v8, lk.ks, lk.vs, b.kv8 ? r.row_page : nullptr, b.kv8 ? b.max_S : 0, nullptr);
         // FINAL layer: only each page's last row is ever read again (the LM head, :1081-1082 + _sample; the reference computes every row).  K / V of
         // every row still go to the cache, so the norm, wqkv and RoPE + split run on all rows; attention, wo, the second norm, w1|w3 and w2 run on the n last rows
         // only -- 88 % of that layer's linear work.  Bit-exact: the tiled kernels give a row the same sum whatever it is batched with (LIN_PREFILL pins rows <= 64;
@@ -476,6 +482,9 @@ struct DecodeBufs {
     bf16 *x, *h, *qkv, *q, *ao, *act;
     float *part, *pbuf;      // the attention splits' partials; the K-slices of one GEMM ([slices][M][N] fp32, the largest of the three)
     HeadBufs head;
+    // cr_llm_decode_draft: rows of one sequence's draft window.  off (NULL in a plain step, and in a draft step without a window): row i sits off[i] positions past
+    // its sequence's cached length -- RoPE, the cache row and the key count follow it, and the RoPE-folded attention form is not taken.  Set by DraftBufs' carve.
+    const int32_t* off = nullptr;
 
     DecodeBufs(cr_ctx* c, const cr_kv* kv, int M, int nsplit, const RowFeatures& f)
         : M(M), nsplit(nsplit), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), s_qkv(gemm_partial_splits(QKV, D)),
@@ -503,7 +512,7 @@ AttnParams decode_attn_params(const cr_kv* kv, const LayerKV& lk, const DecodeBu
     }
     ap.q_bs = D; ap.q_rs = HD; ap.q_hs = 4 * HD; ap.o_bs = D; ap.o_rs = HD; ap.o_hs = 4 * HD;
     ap.B = b.M; ap.H = NKV; ap.Sq = NH / NKV; ap.Sk = 0; ap.kv_group = 1; ap.q_pos0 = 0;
-    ap.seq_map = d_seqs; ap.sk_arr = kv->d_len; ap.sk_add = 1;
+    ap.seq_map = d_seqs; ap.sk_arr = kv->d_len; ap.sk_add = 1; ap.sk_off = b.off;
     ap.nsplit = b.nsplit; ap.part_ml = b.part; ap.part_o = b.part + (size_t)b.M * NKV * b.nsplit * (NH / NKV) * 2;
     return ap;
 }
@@ -526,6 +535,7 @@ int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_se
         DecodeGemmParams dp = fused_gemm_params(c, w.qkv, M);
         dp.xres = b.x; dp.gamma = w.an;
         dp.cosT = cosT; dp.sinT = sinT; dp.q_out = b.q; dp.kc = lk.k; dp.vc = lk.v; dp.seqs = d_seqs; dp.lens = kv->d_len; dp.max_tokens = kv->max_tokens;
+        dp.pos_off = b.off;
         CR_TRY(launch_decode_gemm(DEC_WQKV, dp, st));
         if (launch_flash_attn_split(decode_attn_params(kv, lk, b, d_seqs), HD, st) != CR_OK) return cr_fail(CR_ERR_HIP, "decode attention launch failed");
         dp = fused_gemm_params(c, w.o, M);
@@ -562,12 +572,17 @@ int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_se
         // (not on an e4m3 cache: rope_split_kernel<true> quantises the new rows, decode_attn8_kernel reads them back from the cache)
         AttnParams fp = ap;
         fp.qkv_part = b.pbuf; fp.qkv_splits = b.s_qkv; fp.qkv_ld = QKV; fp.rope_cos = cosT; fp.rope_sin = sinT;
+        // (never with a draft window's rows: a row would read cache rows that other workgroups of the same launch are still writing; decode_attn_fold_supported
+        // refuses AttnParams::sk_off, and the separate launch below gives the same bits)
         const bool rope_folded = b.sliced && c->fold_rope && !b.kv8 && decode_attn_fold_supported(fp, HD);
         if (rope_folded) ap = fp;
         // (b.pbuf: wqkv's K-slices when sliced, else null and the kernel reads b.qkv; of lk either the bf16 or the e4m3 pointers are null)
+        else if (b.off)      // (bf16 caches only: cr_llm_decode_draft refuses an e4m3 one)
+            hipLaunchKernelGGL((rope_split_kernel<false, true>), dim3(M, NKV), dim3(128), 0, st, b.qkv, cosT, sinT, b.q, lk.k, lk.v, 0, 0, d_seqs, kv->d_len, nullptr,
+                               kv->max_tokens, (const float*)b.pbuf, b.s_qkv, nullptr, nullptr, nullptr, nullptr, nullptr, 0, b.off);
         else
             hipLaunchKernelGGL(b.kv8 ? rope_split_kernel<true> : rope_split_kernel<false>, dim3(M, NKV), dim3(128), 0, st, b.qkv, cosT, sinT, b.q, lk.k, lk.v, 0, 0,
-                               d_seqs, kv->d_len, nullptr, kv->max_tokens, (const float*)b.pbuf, b.s_qkv, lk.k8, lk.v8, lk.ks, lk.vs, nullptr, 0);
+                               d_seqs, kv->d_len, nullptr, kv->max_tokens, (const float*)b.pbuf, b.s_qkv, lk.k8, lk.v8, lk.ks, lk.vs, nullptr, 0, nullptr);
         if (launch_flash_attn_split(ap, HD, st) != CR_OK) return cr_fail(CR_ERR_HIP, "decode attention launch failed");
         if (b.sliced) {
             CR_TRY(linear(c, EPI_PARTIAL, b.ao, w.o, dec, b.pbuf, M, st));
@@ -590,6 +605,35 @@ int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_se
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
+
+// The final RMSNorm and the LM head over the rows of a decode step: b.head.lg
+int decode_head(cr_ctx* c, const DecodeBufs& b, hipStream_t st) {
+    const int n = b.M, V = c->d.vocab;
+    const bf16* nw = W(c, "language_model.model.norm.weight");
+    const LinW head = lin_weight(c, "language_model.output.weight", V, D);
+    if (!nw || !head.w) return CR_ERR_STATE;
+    if (c->fused_decode && !c->fp8_decode && !c->no_sliced_decode && decode_fused_supported(n, b.ff)) {
+        DecodeGemmParams dh = fused_gemm_params(c, head, n);      // final RMSNorm folded into the LM head (gemm_decode.hip)
+        dh.xres = b.x; dh.gamma = nw; dh.C = b.head.lg; dh.ldc = V;
+        return launch_decode_gemm(DEC_HEAD, dh, st);
+    }
+    CR_TRY(rms(b.x, b.head.hl, nw, n, c->d.rms_eps, st));
+    return linear(c, EPI_F32, b.head.hl, head, c->fp8_decode && n <= 64 && head.e4m3() ? LIN_E4M3 : LIN_DECODE, b.head.lg, n, st);
+}
+
+// A draft-verified step: the decode step's buffers for its M rows and draft.hpp's index block for its n sequences
+struct DraftBufs {
+    DecodeBufs dec;
+    int n;
+    bool windows;
+    int64_t* index;
+    DraftBufs(cr_ctx* c, const cr_kv* kv, int M, int n, int nsplit, const RowFeatures& f) : dec(c, kv, M, nsplit, f), n(n), windows(M > n), index(nullptr) {}
+    void carve(Arena& ar) {
+        dec.carve(ar);
+        index = ar.take<int64_t>(draft_index_words(n, dec.M));
+        dec.off = windows && index ? draft_index(index, n, dec.M).off : nullptr;
+    }
+};
 
 }  // namespace
 
@@ -977,7 +1021,6 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
                        "split kernel, which reads bf16 caches");
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    const int V = c->d.vocab;
     int max_len = 0;
     for (int i = 0; i < n; i++) max_len = kv->seq[seqs[i]].len > max_len ? kv->seq[seqs[i]].len : max_len;
     const int nsplit = ((max_len + 1 + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
@@ -986,19 +1029,10 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     CR_TRY(stage_seqs(c, seqs, n, st, false));
     const int32_t* d_seqs = c->d_seqs;
     const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
-    const bf16* nw = W(c, "language_model.model.norm.weight");
-    const LinW head = lin_weight(c, "language_model.output.weight", V, D);
-    if (!table || !nw || !head.w) return CR_ERR_STATE;
-    hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(256), 0, st, table, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.x);
+    if (!table) return CR_ERR_STATE;
+    hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(n), dim3(256), 0, st, table, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.x, nullptr);
     CR_TRY(decode_layers(c, kv, b, d_seqs, st));
-    if (c->fused_decode && !c->fp8_decode && !c->no_sliced_decode && decode_fused_supported(n, b.ff)) {
-        DecodeGemmParams dh = fused_gemm_params(c, head, n);      // final RMSNorm folded into the LM head (gemm_decode.hip)
-        dh.xres = b.x; dh.gamma = nw; dh.C = b.head.lg; dh.ldc = V;
-        CR_TRY(launch_decode_gemm(DEC_HEAD, dh, st));
-    } else {
-        CR_TRY(rms(b.x, b.head.hl, nw, n, c->d.rms_eps, st));
-        CR_TRY(linear(c, EPI_F32, b.head.hl, head, c->fp8_decode && n <= 64 && head.e4m3() ? LIN_E4M3 : LIN_DECODE, b.head.lg, n, st));
-    }
+    CR_TRY(decode_head(c, b, st));
     CR_TRY(pick_rows(kv, b.head, d_seqs, penalty, 1, logits, st, false));
     if (beam_span > 0)
         CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, d_seqs, penalty, 1, 0), beam_cache(kv), beam_firsts.data(), (int)beam_firsts.size(), beam_span, 1, st));
@@ -1007,6 +1041,93 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
         Seq& q = kv->seq[seqs[i]];
         q.len += 1;
         if (q.ngen < kv->gen_cap) q.ngen += 1;
+    }
+    return CR_OK;
+}
+
+int cr_llm_decode_draft(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_t* draft_host, const int32_t* draft_lens_host, int draft_stride,
+                        float penalty, int32_t* appended_host, void* stream) {
+    if (!c || !kv || !seqs || !draft_lens_host || !appended_host || n <= 0 || n > kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: bad argument");
+    if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: call cr_finalize first");
+    CR_TRY(ctx_share_ok(c, "cr_llm_decode_draft"));
+    const int V = c->d.vocab;
+    int M = 0, max_keys = 0;
+    bool deep = false;
+    for (int i = 0; i < n; i++) {
+        const int s = seqs[i], k = draft_lens_host[i];
+        if (s < 0 || s >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: sequence %d out of range", s);
+        for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: sequence %d listed twice", s);
+        if (k < 0 || k > DRAFT_MAX) return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: %d drafted ids for sequence %d (want 0..%d)", k, s, DRAFT_MAX);
+        if (k > 0 && (!draft_host || draft_stride < k)) return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: %d drafted ids for sequence %d, but no draft array of that stride", k, s);
+        const Seq& q = kv->seq[s];
+        if (q.len + k + 1 > kv->max_tokens || q.ngen + k + 1 > kv->gen_cap)
+            return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: sequence %d holds %d tokens, %d more exceed the cache (%d)", s, q.len, k + 1, kv->max_tokens);
+        for (int j = 0; j < k; j++) {
+            const int64_t id = draft_host[(size_t)i * draft_stride + j];
+            if (id < 0 || id >= V) return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: drafted id %lld of sequence %d outside the vocabulary (%d)", (long long)id, s, V);
+        }
+        M += k + 1;
+        max_keys = std::max(max_keys, q.len + k + 1);
+        deep |= penalty != 1.0f && q.ngen + k > 4096;
+    }
+    if (M > DRAFT_MAX_ROWS)
+        return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: %d rows in all (sequences + drafted ids; at most %d: the decode forms whose bits do not depend on the batch)", M,
+                       DRAFT_MAX_ROWS);
+    if (kv->fmt != CR_KV_BF16)
+        return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: an e4m3 cache (left out: the window's rows are written by the bf16 RoPE + split forms only)");
+    for (int i = 0; i < n; i++) {
+        const Seq& q = kv->seq[seqs[i]];
+        if (q.ngen == 0) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d has no generated id to feed", seqs[i]);
+        // left out, each for its own reason: a sampled pick is a draw, not a comparison; scores and constraints are per appended id and would have to be redone for
+        // the accepted prefix; a beam group's step re-orders the cache
+        if (q.sampled) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d samples (greedy rows only)", seqs[i]);
+        if (q.scored) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d records token scores (not with drafts)", seqs[i]);
+        if (q.constrained) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d has logits constraints (not with drafts)", seqs[i]);
+        if (q.bgrp >= 0) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d belongs to the beam group of sequence %d (not with drafts)", seqs[i], q.bgrp);
+    }
+    CR_HIP(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int nsplit = ((max_keys + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
+    RowFeatures feat{};
+    feat.deep = deep;                       // histories of more than 4096 ids under a penalty: the pick reads an untouched copy of the rows, as pick_rows does
+    DraftBufs b(c, kv, M, n, nsplit, feat);
+    CR_TRY(ws_carve(c, "cr_llm_decode_draft", b));
+    // the rows: sequence i's window is rows row0[i] .. row0[i] + k_i, all naming its cache slot
+    std::vector<int32_t> row_seq(M);
+    std::vector<int64_t> hix(draft_index_host_words(n, M), 0);
+    const DraftIndex hx = draft_index(hix.data(), n, M);
+    for (int i = 0, r = 0; i < n; i++) {
+        const int k = draft_lens_host[i];
+        hx.row0[i] = r; hx.klen[i] = k;
+        for (int j = 0; j < k; j++) hx.ids[i * DRAFT_MAX + j] = draft_host[(size_t)i * draft_stride + j];
+        for (int j = 0; j <= k; j++, r++) { row_seq[r] = seqs[i]; hx.off[r] = j; }
+    }
+    CR_HIP(hipMemcpyAsync(b.index, hix.data(), hix.size() * 8, hipMemcpyHostToDevice, st));      // pageable source: staged before return
+    CR_TRY(stage_seqs(c, row_seq.data(), M, st, false));
+    const int32_t* d_seqs = c->d_seqs;
+    const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
+    if (!table) return CR_ERR_STATE;
+    DraftLaunch dl{};
+    dl.logits = b.dec.head.lg; dl.ld = V; dl.vocab = V; dl.penalty = penalty; dl.rows = M; dl.n = n; dl.seqs = d_seqs; dl.ix = draft_index(b.index, n, M);
+    dl.windows = b.windows; dl.gen = kv->d_gen; dl.ngen = kv->d_ngen; dl.lens = kv->d_len; dl.gen_cap = kv->gen_cap; dl.stop = kv->d_stop; dl.n_seqs = kv->n_seqs;
+    dl.orig = b.dec.head.lg0;
+    CR_TRY(launch_draft_stage(dl, st));
+    if (b.dec.off)
+        hipLaunchKernelGGL(embed_rows_kernel<true>, dim3(M), dim3(256), 0, st, table, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, b.dec.off);
+    else
+        hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(M), dim3(256), 0, st, table, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, nullptr);
+    CR_TRY(decode_layers(c, kv, b.dec, d_seqs, st));
+    CR_TRY(decode_head(c, b.dec, st));
+    if (dl.orig) CR_HIP(hipMemcpyAsync(b.dec.head.lg0, b.dec.head.lg, (size_t)M * V * 4, hipMemcpyDeviceToDevice, st));
+    CR_TRY(launch_draft_pick_accept(dl, st));
+    CR_HIP(hipGetLastError());
+    // the price of a variable step: the host's mirror of the lengths needs the counts, and the next window depends on them anyway
+    CR_HIP(hipMemcpyAsync(appended_host, dl.ix.app, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    CR_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) {
+        Seq& q = kv->seq[seqs[i]];
+        q.len += appended_host[i];
+        q.ngen += appended_host[i];
     }
     return CR_OK;
 }

@@ -259,6 +259,21 @@ class Engine:
         B.check(B.lib.cr_llm_decode(self._h, kv._h, seq_arr, n, _p(ft), float(penalty), _p(logits), _stream()), 'cr_llm_decode')
         return logits
 
+    def decode_draft(self, kv, seqs, drafts, penalty=1.0):
+        """cr_llm_decode_draft on the current stream: one greedy step that checks `drafts[i]` (0..7 guessed next ids) for sequence seqs[i] in the same
+        weight pass.  Returns the count of ids appended per sequence (1 .. len(drafts[i]) + 1); the ids are those of plain decode steps whatever the
+        drafts hold.  Synchronises the stream."""
+        n = len(seqs)
+        lens = [len(d) for d in drafts]
+        stride = max(max(lens), 1)
+        flat = (C.c_int64 * (n * stride))()
+        for i, d in enumerate(drafts):
+            flat[i * stride:i * stride + len(d)] = [int(t) for t in d]
+        app = (C.c_int32 * n)()
+        B.check(B.lib.cr_llm_decode_draft(self._h, kv._h, (C.c_int32 * n)(*seqs), n, flat, (C.c_int32 * n)(*lens), stride, float(penalty), app,
+                                          _stream()), 'cr_llm_decode_draft')
+        return list(app)
+
 
 KV_DTYPES = {'bf16': B.CR_KV_BF16, 'e4m3': B.CR_KV_E4M3}
 

@@ -61,18 +61,23 @@ def boxes_for(image_path, boxes_arg=None, required=True):
 
 
 def single_rec(model, tokenizer, detect_model, generation_config, image_path, prompt, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
-               boxes=None, quiet=False, scores=0):
+               boxes=None, quiet=False, scores=0, draft=None):
     """scores = n > 0 (--scores): the page's token scores are taken with n alternatives; prints one more line (`confidence <c> min <p> at token <k>
-    (<piece>)`) and returns (response, scores.ResponseScores)."""
+    (<piece>)`) and returns (response, scores.ResponseScores).
+    draft = 'align' (--draft): the page's CalliAlign indices draft its answer (chat_ocr(draft='align')); the same response, one more line (`draft: <s> decode
+    steps for <n> ids, <a> of <d> drafted ids accepted`)."""
     bx = None
     if use_p and (boxes is not None or detect_model is None):
         bx = boxes_for(image_path, boxes)
     out = model.chat_ocr(tokenizer, detect_model, image_path, prompt, generation_config, use_p=use_p, hard_vq=hard_vq,
                          drop_zero=drop_zero, repetition_penalty=repetition_penalty, return_history=True,
-                         verbose=verbose, boxes=bx, **(dict(return_scores=scores) if scores else {}))
+                         verbose=verbose, boxes=bx, **(dict(return_scores=scores) if scores else {}), **(dict(draft=draft) if draft else {}))
     response = out[0]
     if not quiet:
         print(f'User: {prompt}\nAssistant: {response}')
+        if draft:
+            st = model.draft_stats
+            print(f"draft: {st['steps']} decode steps for {st['steps'] + st['accepted'] + 1} ids, {st['accepted']} of {st['drafted']} drafted ids accepted")
         if scores:
             print(out[2].summary_line())
     return (response, out[2]) if scores else response
@@ -82,7 +87,7 @@ DEFAULT_BATCH_PAGES = 64       # pages per decode batch in folder mode: the most
 
 
 def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, prompt, save_name, use_p, hard_vq, drop_zero, repetition_penalty,
-               verbose, batch_pages=DEFAULT_BATCH_PAGES, continuous=False, scores=0):
+               verbose, batch_pages=DEFAULT_BATCH_PAGES, continuous=False, scores=0, draft=None):
     """inference.py:47-62: every image of the folder -> results JSON [{imagePath, prompt, response}], an image that fails -> "ERROR!" for that entry only.
     The reference calls chat_ocr image after image; here the images go through `chat_ocr_stream` in batches of `batch_pages` (two batches in flight, files
     decoded ahead on threads): each response is the one the image's own chat_ocr call gives, pages/s is what changes (batch_pages <= 1: the serial loop).
@@ -92,7 +97,10 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
     the same responses, JSON and console lines.
     scores = n > 0 (--scores): a second file, the results JSON's name with `.scores.json` in place of its `json` ending, holds per image
     {imagePath, scores: ResponseScores.to_json() with n alternatives per token, or null for an image whose entry is "ERROR!"}; the results JSON itself is
-    byte-identical to a run without it."""
+    byte-identical to a run without it.
+    draft = 'align' (--draft): image after image through chat_ocr(draft='align') -- the serial loop, whatever batch_pages says (the pipelines take no draft)."""
+    if draft:
+        batch_pages = 1
     paths = get_image_paths(folder_path)
     responses, page_scores = {}, {}
     skw = dict(return_scores=scores) if scores else {}
@@ -107,7 +115,7 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
     def one(pic_path):
         try:
             return single_rec(model, tokenizer, detect_model, generation_config, pic_path, prompt, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
-                              quiet=True, scores=scores)
+                              quiet=True, scores=scores, draft=draft)
         except Exception as e:                               # inference.py:55-57
             return e
 
@@ -264,6 +272,9 @@ def build_parser():
     parser.add_argument('--scores', type=int, nargs='?', const=1, default=0, choices=range(0, 9), metavar='N',
                         help='per-token log-probabilities with the N (default 1, at most 8) most likely alternatives: single image prints one more line '
                              '(confidence, the least certain token); folder mode writes <save_name minus json>.scores.json next to the results JSON, which does not change')
+    parser.add_argument('--draft', action='store_true',
+                        help="draft-verified decoding: the page's CalliAlign indices (vocabulary ids of its character boxes, in reading order) draft the answer and several "
+                             'ids are checked per decode step; the same response in fewer steps where the draft is right (greedy only; needs --use_p; folder mode runs image after image)')
     return parser
 
 
@@ -300,13 +311,13 @@ def main(argv=None):
     if is_image(args.tgt):
         print('Single image recognition mode.')
         single_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, args.use_p, args.hard_vq, args.drop_zero,
-                   args.repetition_penalty, args.verbose, args.boxes, scores=args.scores)
+                   args.repetition_penalty, args.verbose, args.boxes, scores=args.scores, draft='align' if args.draft else None)
     elif os.path.isdir(args.tgt):
         print('Multiple images recognition mode')
         os.makedirs('results', exist_ok=True)
         folder_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, os.path.join('results', args.save_name),
                    args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose, batch_pages=args.batch_pages,
-                   continuous=args.continuous, scores=args.scores)
+                   continuous=args.continuous, scores=args.scores, draft='align' if args.draft else None)
     else:
         raise ValueError('The target should be either a image path or a folder that contain images!')
 

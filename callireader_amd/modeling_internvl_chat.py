@@ -26,7 +26,8 @@ from .config import ModelDims, IMG_CONTEXT_TOKEN_ID, ALIGNED_TOKEN_ID, EOS_TOKEN
 from .conversation import get_conv_template
 from .engine import Engine
 from .constraints import parse as constraints_parse, per_page as constraints_per_page
-from .generation import admit, check_fits, decode_rows, per_page_sampling, read_scores, reply_shape, reply_text
+from . import draft as drafting
+from .generation import admit, check_fits, decode_rows, decode_rows_drafted, per_page_sampling, read_scores, reply_shape, reply_text
 from .pipeline import PagePipeline
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
 from .sampling import base_seed, page_seeds, parse as sampling_parse, parse_beams, splitmix64
@@ -56,6 +57,7 @@ class InternVLChatModel:
         self.max_tokens = max_tokens
         self.max_pages = max_pages
         self.sorter = None                 # ordering.OrderFormer once load_orderformer() has run (modeling_internvl_chat.py:159)
+        self.draft_stats = {}            # steps / drafted / accepted of the last call that decoded with a draft (generation.decode_rows_drafted)
         self.gpu_preprocess = True       # tiles are cut/resized/normalised on the GPU (bit-identical to the PIL path)
         self._kv = None
         self._ready = False
@@ -250,16 +252,27 @@ class InternVLChatModel:
 
     # ---- generation ----------------------------------------------------------------------------
     def _generate(self, input_embeds, max_new_tokens, eos_token_id, repetition_penalty, sampling=None, check_every=16, logprobs=0, kv=None, seq=0,
-                  reset=True, constraints=None):
+                  reset=True, constraints=None, draft_ids=None):
         """transformers 4.45.2 GenerationMixin._sample with num_beams=1 for ONE sequence: greedy (sampling None), or do_sample=True with
         `sampling` (a sampling.SamplingParams; the page's seed is page_seeds(1)[0]); returns only the new ids, EOS included (oracle/generate.py
         documents the semantics).  logprobs = n > 0: returns (ids, scores.TokenScores with n alternatives per id, cut like the ids).
         kv / seq: the cache and sequence to run in (default: the model's own, sequence 0).  reset=False (session.PageSession): the sequence keeps the
         tokens it holds -- the caller has rolled it back with KV.truncate, which leaves no ids and no state -- and `input_embeds` are the rows that
-        continue it.  constraints (a constraints.Constraints, greedy only): the masks in front of every pick of this call."""
+        continue it.  constraints (a constraints.Constraints, greedy only): the masks in front of every pick of this call.
+        draft_ids (a list of ids, greedy only): a guess at the ids to come, checked several per decode step (generation.decode_rows_drafted); the ids
+        returned are the same with any draft, self.draft_stats says how many steps they took."""
         if constraints is not None and sampling is not None:
             raise NotImplementedError('logits constraints with do_sample=True are not implemented (greedy decoding only)')
         kv = self.kv(1) if kv is None else kv
+        if draft_ids is not None:
+            if sampling is not None:
+                drafting.refuse('do_sample=True')
+            if logprobs:
+                drafting.refuse('token scores (output_scores / return_scores)')
+            if constraints is not None and constraints.active:
+                drafting.refuse('logits constraints')
+            if kv.format != 'bf16':
+                drafting.refuse("an e4m3 KV cache (kv_cache_dtype='e4m3')")
         if reset:
             kv.reset(seq)
         check_fits(kv.length(seq) + input_embeds.shape[0], max_new_tokens, self.max_tokens)
@@ -271,15 +284,25 @@ class InternVLChatModel:
             kv.set_logprobs(seq, logprobs)
         self.engine.prefill(kv, seq, input_embeds, penalty=repetition_penalty)
         # one sequence looks BEFORE its first chunk too: a prefill whose own pick is EOS issues no decode step (the batch paths do not look first)
-        ids = decode_rows(self.engine, kv, [seq], max_new_tokens, eos_token_id, repetition_penalty, check_every, look_first=True)[0]
+        if draft_ids is not None:
+            self.draft_stats = {}
+            ids = decode_rows_drafted(self.engine, kv, [seq], max_new_tokens, eos_token_id, repetition_penalty, [draft_ids], stats=self.draft_stats)[0]
+        else:
+            ids = decode_rows(self.engine, kv, [seq], max_new_tokens, eos_token_id, repetition_penalty, check_every, look_first=True)[0]
         out = torch.tensor([ids], dtype=torch.long, device=self.device)
         return (out, TokenScores.read(kv, seq, len(ids))) if logprobs else out
 
     def _generate_kw(self, input_embeds, repetition_penalty, generate_kwargs, **where):
         """_generate driven by transformers' keyword arguments: the new ids, or under return_dict_in_generate=True a scores.GenerateOutput.
-        where: _generate's kv / seq / reset (a session's turn; no beams there)."""
+        where: _generate's kv / seq / reset (a session's turn; no beams there).  draft_ids among the keywords: _generate's draft."""
+        generate_kwargs = dict(generate_kwargs)
+        draft_ids = generate_kwargs.pop('draft_ids', None)
         max_new, eos, sp = self._gen_args(generate_kwargs, allow_beams=True)
         beams = parse_beams(generate_kwargs)
+        if draft_ids is not None:
+            if beams is not None:
+                drafting.refuse(f'num_beams={beams.num_beams}')
+            draft_ids = [int(t) for t in draft_ids]
         cons = constraints_parse(generate_kwargs, eos)          # (NotImplementedError with beams or do_sample)
         if cons is not None:
             where = dict(where, constraints=cons)
@@ -294,6 +317,8 @@ class InternVLChatModel:
             out = generate_output(seq)
             out.sequences_scores = torch.tensor([sc[0]], dtype=torch.float32)
             return out
+        if draft_ids is not None:
+            where = dict(where, draft_ids=draft_ids)
         n = scores_parse(generate_kwargs)
         if not generate_kwargs.get('return_dict_in_generate', False):
             return self._generate(input_embeds, max_new, eos, repetition_penalty, sp, **where)
@@ -333,7 +358,8 @@ class InternVLChatModel:
     def generate_ocr(self, pixel_values=None, input_ids=None, attention_mask=None, visual_features=None,
                      generation_config=None, reference_embeds=None, output_hidden_states=None, return_dict=None,
                      repetition_penalty=1.5, **generate_kwargs):
-        """:1067-1122"""
+        """:1067-1122.  draft_ids=[...] among the keywords (not the reference's): a guess at the answer's ids, checked several per decode step; the
+        ids returned do not depend on it (draft.py).  Greedy, num_beams=1, no scores, no constraints, a bf16 cache."""
         assert self.img_context_token_id is not None                        # :1081
         if input_ids.shape[0] != 1:
             raise NotImplementedError('generate_ocr handles one page per call, as chat_ocr does')
@@ -423,9 +449,16 @@ class InternVLChatModel:
                  history=None, return_history=False, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
                  IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', verbose=False, image_counts=None,
                  batch=False, use_p=True, drop_zero=False, hard_vq=False, repetition_penalty=1.5, region_wise=False,
-                 boxes=None, return_scores=False):
+                 boxes=None, return_scores=False, draft=None):
         """:649-762.  return_scores (True, or the number of alternatives per token): a scores.ResponseScores is returned after the response
-        (after `history` when that is returned); a detection failure still returns its message alone."""
+        (after `history` when that is returned); a detection failure still returns its message alone.
+        draft (None: off): 'align' drafts the answer with this call's CalliAlign indices -- the rows of the LLM's own embedding table that the VQ step
+        snapped the character boxes to (draft.from_indices; needs use_p) -- or a list of ids does; the response is the same, in fewer decode steps where
+        the draft is right."""
+        if draft is not None and return_scores:
+            drafting.refuse('return_scores')
+        if isinstance(draft, str) and (draft != 'align' or not use_p):
+            raise ValueError(f"chat_ocr: draft={draft!r} (want None, 'align' with use_p=True, or a list of ids)")
         pixel_values = None
         sub_img = None
         page = None                       # the decoded page, handed on to calli_align (the reference opens the file a second time there, :558: 14.5 ms of JPEG decode on the example page)
@@ -454,6 +487,8 @@ class InternVLChatModel:
         question, history, template, model_inputs, generation_config = self._ocr_prompt(
             tokenizer, questions, history, None if pixel_values is None else len(pixel_values), out_tokens, use_p, num_patches_list, generation_config,
             return_scores, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN)
+        if draft is not None:
+            generation_config['draft_ids'] = drafting.from_indices(indices) if isinstance(draft, str) else list(draft)
         out = self.generate_ocr(pixel_values=pixel_values, input_ids=model_inputs['input_ids'],
                                 attention_mask=model_inputs['attention_mask'],
                                 reference_embeds=out_tokens if use_p else None,
@@ -630,7 +665,7 @@ class InternVLChatModel:
 
     def chat_ocr_stream(self, tokenizer, detect_model, image_batches, question, generation_config, boxes_batches=None, use_p=True,
                         drop_zero=False, hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
-                        IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise', stats=None, return_scores=False):
+                        IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise', stats=None, return_scores=False, draft=None):
         """chat_ocr_pages over a sequence of page batches with two batches in flight (PagePipeline): a generator that yields one
         list of responses per batch, in order; batch i decodes on a second stream while batch i+1 is detected, tiled, encoded and
         prefilled, and the image files of batch i+2 are being decoded on the feeder's threads (pageio.PageFeeder).  Every page gets the
@@ -639,6 +674,8 @@ class InternVLChatModel:
         chat_ocr_pages returns it."""
         if parse_beams(generation_config) is not None:
             raise NotImplementedError('chat_ocr_stream: beam search does not go through PagePipeline (use chat_ocr_pages)')
+        if draft is not None:
+            drafting.refuse('PagePipeline (chat_ocr_stream: its decode thread issues steps without waiting for them)')
         constraints_parse(generation_config, 0)                 # refused before the first batch is pulled
         _, lpn = self._score_args(generation_config, return_scores)
         pipe, pending = None, None
@@ -739,7 +776,7 @@ class InternVLChatModel:
     def chat_ocr_continuous(self, tokenizer, detect_model, images, question, generation_config, boxes_list=None, use_p=True, drop_zero=False,
                             hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
                             ALIGNED_TOKEN='[UNUSED_TOKEN_140]', slots=64, admit_group=16, visual_group=16, errors='raise', stats=None,
-                            return_scores=False):
+                            return_scores=False, draft=None):
         """chat_ocr_pages over any number of pages with continuous batching (continuous.ContinuousPipeline): a generator that yields
         (index into `images`, response) as pages finish -- a page that stops early frees its decode row for the next page at once, instead of
         waiting for the longest page of a batch.  The visual stage runs `visual_group` pages at a time ahead of admission (the next group's files
@@ -750,6 +787,8 @@ class InternVLChatModel:
         (index, response, scores.ResponseScores), the scores None for a page that failed."""
         if parse_beams(generation_config) is not None:
             raise NotImplementedError('chat_ocr_continuous: beam search does not go through ContinuousPipeline (use chat_ocr_pages)')
+        if draft is not None:
+            drafting.refuse('ContinuousPipeline (chat_ocr_continuous: its rows stop on the device, its worker never waits for a step)')
         from .continuous import ContinuousPipeline
         _, lpn = self._score_args(generation_config, return_scores)
         images = list(images)
@@ -967,7 +1006,7 @@ class InternVLChatModel:
 
     def generate_pages(self, embeds_list, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0,
                        check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0, num_beams=1, length_penalty=1.0, early_stopping=False,
-                       constraints=None):
+                       constraints=None, drafts=None):
         """Prefill every page, then decode all unfinished pages as ONE batch per step: the 14.7 GB of LLM weights are
         streamed once per step for all pages.  Per page the ids equal the single-page greedy result.
         sampling: None (every page greedy), one sampling.SamplingParams for every page, or a list with one entry (or None: greedy) per page;
@@ -980,10 +1019,26 @@ class InternVLChatModel:
         sampling and no token scores with beams.
         constraints: None, one constraints.Constraints for every page, or a list with one entry (or None) per page: the page's picks choose among the
         ids its constraints leave (csrc/constrain.hip).  Greedy pages only; a page's ids do not depend on the batch it decodes in, and the other pages of
-        the batch keep their ids bit for bit."""
+        the batch keep their ids bit for bit.
+        drafts: None, or a list with one entry per page -- a list of ids that guesses the page's answer, or None -- checked several per decode step
+        (generation.decode_rows_drafted); every page's ids are what they are without drafts.  Greedy pages on a bf16 cache, without scores, constraints
+        or beams."""
         P = len(embeds_list)
         cons = constraints_per_page(constraints, P)
         beams = parse_beams(dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping))
+        if drafts is not None:
+            if len(drafts) != P:
+                raise ValueError(f'drafts: {len(drafts)} entries for {P} pages')
+            if beams is not None:
+                drafting.refuse(f'num_beams={beams.num_beams}')
+            if sampling is not None:
+                drafting.refuse('do_sample=True (sampling=)')
+            if logprobs and any(scores_per_page(logprobs, P)):
+                drafting.refuse('token scores (logprobs=)')
+            if any(c is not None for c in cons):
+                drafting.refuse('logits constraints')
+            if self.kv_cache_dtype != 'bf16':
+                drafting.refuse("an e4m3 KV cache (kv_cache_dtype='e4m3')")
         if beams is not None:
             if sampling is not None or (logprobs and any(scores_per_page(logprobs, P))):
                 raise NotImplementedError('generate_pages: beam search takes neither sampling nor token scores')
@@ -994,6 +1049,9 @@ class InternVLChatModel:
         lpn = scores_per_page(logprobs, P)
         kv, seqs = self.kv(P), list(range(P))
         admit(self.engine, kv, seqs, embeds_list, repetition_penalty, per_page, lpn, prefill_batch, constraints=cons)
+        if drafts is not None:
+            self.draft_stats = {}
+            return decode_rows_drafted(self.engine, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, drafts, stats=self.draft_stats)
         outs = decode_rows(self.engine, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, check_every)
         return (outs, read_scores(kv, lpn, outs)) if any(lpn) else outs
 

@@ -378,6 +378,9 @@ def sharded_generate(model, page_tiles, char_tiles, input_ids, *, img_id, ref_id
     Returns {page: ids} for every page (gather_results) or for the pages this rank owns.  Per page the ids are the single-process ids."""
     if generate_kw.get('num_beams', 1) not in (1, None):
         raise NotImplementedError('sharded_generate: beam search is not implemented across GPUs (use generate_pages on one)')
+    if generate_kw.get('drafts') is not None or generate_kw.get('draft_ids') is not None:
+        from .draft import refuse
+        refuse('sharded_generate (a page and its draft may live on different ranks)')
     from .constraints import parse as constraints_parse
     if constraints_parse(generate_kw, 0) is not None:
         raise NotImplementedError('sharded_generate: logits constraints are not implemented across GPUs (use generate_pages on one)')
@@ -439,7 +442,7 @@ def plan_even(n_pages, world, page_tiles, char_tiles, prompt_tokens, new_tokens,
 
 def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, generation_config, boxes_list=None, hard_vq=False, repetition_penalty=1.5,
                            plan=None, cost=None, group=None, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>', IMG_CONTEXT_TOKEN='<IMG_CONTEXT>',
-                           ALIGNED_TOKEN='[UNUSED_TOKEN_140]', return_scores=False):
+                           ALIGNED_TOKEN='[UNUSED_TOKEN_140]', return_scores=False, draft=None):
     """`model.chat_ocr_pages` over the ranks of `group`: every rank calls it with the same pages (paths or PIL images) and gets every page's response -- the one
     its own single-GPU `chat_ocr(..., use_p=True, drop_zero=False)` call gives (modeling_internvl_chat.py:649-763 per page; the reference has no multi-GPU form).
 
@@ -447,6 +450,9 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     `sharded_generate`: each rank crops and encodes ITS contiguous shard of the flat character-box list (GPU resize / pad / normalise, ViT -> mlp1 -> resampler ->
     VQ -> de-norm), one all-gather of the pseudo-token rows, and the owners of a page (plan_balanced over the pages' real sizes, or `plan`) encode its own
     tiles, splice, prefill and decode.  drop_zero is not offered here: it makes a page's prompt length depend on the VQ result of tiles another rank encodes."""
+    if draft is not None:
+        from .draft import refuse
+        refuse('chat_ocr_pages_sharded (a page and its CalliAlign indices may live on different ranks)')
     if return_scores or dict(generation_config).get('return_dict_in_generate', False):
         raise NotImplementedError('chat_ocr_pages_sharded: token scores (return_scores=True) are not implemented across GPUs (a page\'s scores stay on the '
                                   'rank that decodes it); use chat_ocr_pages / chat_ocr_continuous on one GPU')

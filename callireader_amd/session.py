@@ -29,7 +29,8 @@ to continue from: use kv_cache_dtype='bf16'), region_wise (one turn), and the pi
 import torch
 
 from .constraints import parse as constraints_parse
-from .generation import check_fits, decode_rows, reply_text
+from . import draft as drafting
+from .generation import check_fits, decode_rows, decode_rows_drafted, reply_text
 from .sampling import page_seeds, parse_beams
 
 
@@ -64,7 +65,7 @@ def _refuse_e4m3(model):
 class PageSession:
     """See the module docstring.  Made by InternVLChatModel.open_page; a context manager (close() frees the cache)."""
 
-    def __init__(self, model, tokenizer, vit_embeds, ref_embeds, n_tiles, use_p=True, max_branches=1):
+    def __init__(self, model, tokenizer, vit_embeds, ref_embeds, n_tiles, use_p=True, max_branches=1, indices=None):
         _refuse_e4m3(model)
         if max_branches < 1:
             raise ValueError(f'max_branches has to be >= 1, got {max_branches}')
@@ -74,6 +75,8 @@ class PageSession:
         self.kv = model.engine.kv_alloc(1 + max_branches, model.max_tokens, dtype='bf16')
         self.cached_ids = []                     # the id at every cached position of the trunk
         self.rows_prefilled = []                 # rows of every prefill the session made (turns and ask_many), in order
+        self.align_ids = drafting.from_indices(indices)      # draft='align': the page's CalliAlign indices as vocabulary ids, in reading order
+        self.answer_ids = []                     # draft='previous': the ids of the last answer a turn on the trunk generated
 
     @classmethod
     def open(cls, model, tokenizer, detect_model, img_path, use_p=True, drop_zero=False, hard_vq=False, boxes=None, max_branches=1, verbose=False):
@@ -81,9 +84,11 @@ class PageSession:
         _refuse_e4m3(model)                                                                   # before any visual work
         page, pixel_values = model._open_page(img_path)
         out_tokens = None
+        indices = None
         if use_p:
-            out_tokens, _ = model.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
-        return cls(model, tokenizer, model.extract_feature(pixel_values), out_tokens, pixel_values.shape[0], use_p=use_p, max_branches=max_branches)
+            out_tokens, indices = model.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
+        return cls(model, tokenizer, model.extract_feature(pixel_values), out_tokens, pixel_values.shape[0], use_p=use_p, max_branches=max_branches,
+                   indices=indices)
 
     # ---- lifetime ----
     def close(self):
@@ -124,14 +129,34 @@ class PageSession:
         """cached position S + i holds generated id i (the decode step that fed it cached it); the last id generated is cached nowhere yet"""
         self.cached_ids = list(ids) + self.kv.generated(0)[:self.kv.length(0) - len(ids)]
 
+    def _draft_ids(self, draft):
+        """draft=None | 'align' (the page's CalliAlign indices) | 'previous' (the session's last answer) | a list of ids -> the ids, or None"""
+        if draft is None:
+            return None
+        if isinstance(draft, str):
+            if draft not in ('align', 'previous'):
+                raise ValueError(f"draft={draft!r} (want None, 'align', 'previous' or a list of ids)")
+            return list(self.align_ids if draft == 'align' else self.answer_ids)
+        return [int(t) for t in draft]
+
     # ---- turns ----
     @torch.no_grad()
-    def chat_ocr(self, question, generation_config, history=None, return_history=False, repetition_penalty=1.5, return_scores=False):
-        """chat_ocr's arguments after the image, and its return values.  The turn runs on the trunk."""
+    def chat_ocr(self, question, generation_config, history=None, return_history=False, repetition_penalty=1.5, return_scores=False, draft=None):
+        """chat_ocr's arguments after the image, and its return values.  The turn runs on the trunk.
+        draft: None, 'align', 'previous' or a list of ids (_draft_ids): a guess at the answer, checked several ids per decode step; the answer is the same."""
+        draft_ids = self._draft_ids(draft)
+        if draft_ids is not None and return_scores:
+            drafting.refuse('return_scores')
         question, history, template, ids, gc = self._prompt(question, history, generation_config, return_scores)
+        if draft_ids is not None:
+            if gc.get('do_sample'):
+                drafting.refuse('do_sample=True')                                             # here, before the trunk changes (_generate checks again)
+            gc['draft_ids'] = draft_ids
         p = plan_prefix(self.cached_ids, ids)
-        max_new, eos, _ = self.m._gen_args(gc, allow_beams=True)                              # validated here: a refused turn leaves the trunk as it was
-        constraints_parse(gc, eos)                                                            # (installed by _generate_kw behind the truncate, for this turn only)
+        max_new, eos, _ = self.m._gen_args({k: v for k, v in gc.items() if k != 'draft_ids'}, allow_beams=True)      # validated here: a refused turn leaves the trunk as it was
+        cons = constraints_parse({k: v for k, v in gc.items() if k != 'draft_ids'}, eos)    # (installed by _generate_kw behind the truncate, for this turn only)
+        if draft_ids is not None and cons is not None:
+            drafting.refuse('logits constraints')
         check_fits(len(ids), max_new, self.m.max_tokens)                                      # before the trunk changes
         self.kv.truncate(0, p)
         self.cached_ids = self.cached_ids[:p]
@@ -139,16 +164,19 @@ class PageSession:
         self.rows_prefilled.append(len(ids) - p)
         out = self.m._generate_kw(embeds, repetition_penalty, gc, kv=self.kv, seq=0, reset=False)
         self._after_turn(ids)
+        self.answer_ids = (out.sequences if hasattr(out, 'sequences') else out)[0].tolist()
         return self.m._ocr_reply(self.tokenizer, out, template, question, history, return_history, return_scores)
 
     @torch.no_grad()
-    def ask_many(self, questions, generation_config, history=None, repetition_penalty=1.5):
+    def ask_many(self, questions, generation_config, history=None, repetition_penalty=1.5, draft=None):
         """Several questions about the page as ONE decode batch: every question's prompt is built as chat_ocr builds it (the same `history` for all),
         its branch is forked off the trunk at the prefix the two share, the tails are prefilled together and the branches decode together.  Returns
         the responses in order.  The trunk is not changed -- except that an EMPTY trunk first takes the part all the prompts share.
         Greedy: a branch gives the ids its question gives when asked alone from the same trunk state.  do_sample=True: branch j draws with
         page_seeds(n)[j] (chat_ocr_pages' rule), not with the page_seeds(1)[0] of a lone session.chat_ocr -- reproducible under torch.manual_seed, but
-        not the lone call's draws.  No return_scores here."""
+        not the lone call's draws.  No return_scores here.
+        draft: as chat_ocr's, one draft for every branch (greedy, no constraints)."""
+        draft_ids = self._draft_ids(draft)
         questions = list(questions)
         if not 1 <= len(questions) <= self.max_branches:
             raise ValueError(f'ask_many: {len(questions)} questions for a session opened with max_branches={self.max_branches}')
@@ -157,6 +185,10 @@ class PageSession:
         gc, template = built[0][4], built[0][2]
         max_new, eos, sp = m._gen_args(gc, allow_beams=True)
         cons = constraints_parse(gc, eos)
+        if draft_ids is not None and sp is not None:
+            drafting.refuse('do_sample=True')
+        if draft_ids is not None and cons is not None:
+            drafting.refuse('logits constraints')
         for _, _, _, ids, _ in built:
             check_fits(len(ids), max_new, m.max_tokens)
         if not self.cached_ids:                  # an empty trunk: what the prompts share goes into it first; the pick that prefill appends is dropped
@@ -185,5 +217,9 @@ class PageSession:
         tails = [self._embed(b[3], p) for b, p in zip(built, prefixes)]
         self.rows_prefilled.append(sum(len(b[3]) - p for b, p in zip(built, prefixes)))
         m.engine.prefill_batch(kv, branches, tails, penalty=repetition_penalty)
-        outs = decode_rows(m.engine, kv, branches, max_new, eos, repetition_penalty)
+        if draft_ids is not None:
+            m.draft_stats = {}
+            outs = decode_rows_drafted(m.engine, kv, branches, max_new, eos, repetition_penalty, [draft_ids] * len(branches), stats=m.draft_stats)
+        else:
+            outs = decode_rows(m.engine, kv, branches, max_new, eos, repetition_penalty)
         return [reply_text(self.tokenizer, o, template.sep) for o in outs]

@@ -326,6 +326,26 @@ int cr_llm_hidden_probe(cr_ctx* ctx, void* dst, int row0, int rows);
  * prepare_inputs_for_generation (InternVL/modeling_internlm2.py:1112-1149). */
 int cr_llm_decode(cr_ctx* ctx, cr_kv* kv, const int32_t* seqs, int n, const int64_t* force_tokens, float penalty,
                   float* logits, void* stream);
+/* One DRAFT-VERIFIED greedy step for sequences seqs[0..n) (host array): sequence i brings k = draft_lens_host[i] (0..7) drafted ids
+ * d[0..k) = draft_host[i * draft_stride ..] (host arrays; draft_host may be NULL when every k is 0), a guess at the ids it is about to generate, and takes
+ * k + 1 rows of the ONE decode launch: row r is fed the sequence's last generated id (r = 0) or d[r - 1], sits at position cr_kv_length + r (RoPE, cache
+ * row) and attends over the cr_kv_length + r + 1 keys up to itself.  Row r's pick p_r is cr_llm_decode's -- the repetition penalty over the generated ids
+ * followed by d[0..r), argmax with first-max-wins -- so with a the longest prefix for which p_j == d[j], the ids p_0 .. p_a are exactly what a + 1 calls
+ * of cr_llm_decode would have appended, and they are appended, in order, each with the stop check of cr_kv_set_stop at its own count: the first id that
+ * stops the sequence is appended and nothing behind it.  The sequence then holds cr_kv_length + (ids appended) tokens; cache rows past that are dead, as
+ * after cr_kv_truncate.  EXACT, not approximate: whatever the draft holds, the ids, the stops and the live cache rows are those of plain steps (the decode
+ * GEMMs give a row the same bits at 1..64 rows, the attention of a row depends on its own key count only); a wrong draft costs rows, never an id.  With
+ * every draft_lens_host[i] == 0 the call computes what cr_llm_decode(seqs, n, NULL, penalty, NULL) computes, bit for bit.
+ * The call SYNCHRONISES `stream`, as cr_kv_generated does, and writes the count of ids appended per sequence (1..k + 1) to appended_host[n]; cr_kv_length
+ * and the host-side id counts follow it.  That is the price of a variable step: the caller's next window depends on the counts anyway.
+ * Checked before anything is enqueued, nothing changes on refusal: CR_ERR_ARG for a sequence out of range or listed twice, k outside 0..7, more than 64
+ * rows in all (the step stays inside the decode forms whose bits do not depend on the batch), cr_kv_length + k + 1 > max_tokens, a drafted id outside the
+ * vocabulary, or an e4m3 cache (left out: a window's rows are written by the bf16 RoPE + split forms only); CR_ERR_STATE for a sequence without a generated
+ * id, one that samples (a sampled pick is a draw, not a comparison), records token scores or has logits constraints (both are per appended id), or belongs
+ * to a beam group (its step re-orders the cache).  A history of more than 4096 ids under a penalty is handled as cr_llm_decode handles it (the pick reads
+ * an untouched copy of the rows).  Added within ABI v13. */
+int cr_llm_decode_draft(cr_ctx* ctx, cr_kv* kv, const int32_t* seqs, int n, const int64_t* draft_host, const int32_t* draft_lens_host,
+                        int draft_stride, float penalty, int32_t* appended_host, void* stream);
 
 /* fp8 weight path (BASELINE.json configs[4]; the reference itself has no fp8 -- an option, OFF by default, the headline stays
  * bf16).  enable != 0: every linear weight of the language model the batched decode streams (wqkv, wo, w1|w3, w2 of each
