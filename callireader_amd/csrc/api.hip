@@ -1,5 +1,5 @@
 // C ABI of libcallireader_hip.so: lifetime, weights, single-operator entry points.
-// Stage orchestration lives in vision.hip / calli.hip / llm.hip.
+// Stage orchestration lives in vision.hip / calli.hip / llm.hip; the weight map and what is derived from it in weights.hip.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -13,6 +13,7 @@
 #include "decode.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
+#include "weights.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -49,6 +50,37 @@ int ws_ensure(cr_ctx* c, size_t bytes) {
     size_t want = bytes + (bytes >> 3);
     if (hipMalloc((void**)&c->ws, want) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "workspace of %zu bytes", want);
     c->ws_bytes = want;
+    return CR_OK;
+}
+
+// The seqs[] of a prefill / decode call in the context's device staging (per context, not per cache: two contexts that share weights may work
+// on different sequences of one cache at once).  `always` = false skips the host-to-device copy of an unchanged list.  The copy goes through one of
+// a few pinned host buffers (a pageable copy makes the host wait for the stream, which would stall a decode thread whose rows change every few
+// steps); a buffer is reused once the copy that last read it has run.
+int ctx_stage_seqs(cr_ctx* c, const int32_t* seqs, int n, hipStream_t st, bool always) {
+    if (n > c->d_seqs_cap) {
+        CR_HIP(hipDeviceSynchronize());                 // the old staging may still be read by enqueued work
+        if (c->d_seqs) CR_HIP(hipFree(c->d_seqs));
+        c->d_seqs = nullptr; c->d_seqs_cap = 0; c->seqs_on_device.clear();
+        const int cap = n > 256 ? n : 256;
+        if (hipMalloc((void**)&c->d_seqs, (size_t)cap * 4) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "sequence staging of %d entries", cap);
+        c->d_seqs_cap = cap;
+    }
+    if (always || (int)c->seqs_on_device.size() != n || memcmp(c->seqs_on_device.data(), seqs, (size_t)n * 4) != 0) {
+        cr_ctx::SeqStage& h = c->seq_stage[c->seq_stage_next++ % cr_ctx::SEQ_STAGES];
+        if (h.copied) CR_HIP(hipEventSynchronize(h.copied));
+        else CR_HIP(hipEventCreateWithFlags(&h.copied, hipEventDisableTiming));
+        if (h.cap < n) {
+            if (h.host) CR_HIP(hipHostFree(h.host));
+            h.host = nullptr; h.cap = 0;
+            CR_HIP(hipHostMalloc((void**)&h.host, (size_t)c->d_seqs_cap * 4, hipHostMallocDefault));
+            h.cap = c->d_seqs_cap;
+        }
+        memcpy(h.host, seqs, (size_t)n * 4);
+        CR_HIP(hipMemcpyAsync(c->d_seqs, h.host, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        CR_HIP(hipEventRecord(h.copied, st));
+        c->seqs_on_device.assign(seqs, seqs + n);
+    }
     return CR_OK;
 }
 
@@ -110,6 +142,15 @@ int ctx_gemm(cr_ctx* c, int epi, const GemmParams& p, hipStream_t st) {
     }
     if (r != CR_OK) return cr_fail(r, "gemm(epi=%d M=%d N=%d K=%d) rejected or failed to launch", epi, p.M, p.N, p.K);
     return CR_OK;
+}
+
+int ctx_gemm_f8(cr_ctx* c, int epi, const void* a8, const float* ascale, const void* w8, const float* wscale, void* C, int64_t ldc,
+                const bf16* bias, int M, int N, int K, hipStream_t st, const bf16* res, int64_t ldr) {
+    GemmParams p{};
+    p.res = res; p.ldr = ldr;
+    p.A = (const bf16*)a8; p.lda = K; p.W = (const bf16*)w8; p.ldw = K; p.C = C; p.ldc = ldc; p.bias = bias; p.M = M; p.N = N; p.K = K;
+    p.w8 = 1; p.wscale = wscale; p.a8 = 1; p.ascale = ascale;
+    return ctx_gemm(c, epi, p, st);
 }
 
 static size_t dtype_size(int dt) { return dt == CR_BF16 ? 2 : dt == CR_F32 ? 4 : dt == CR_I64 ? 8 : dt == CR_I32 ? 4 : 0; }   // CR_U8 is internal: not loadable
@@ -179,6 +220,7 @@ int cr_share_weights(cr_ctx* dst, const cr_ctx* src) {
     if (!src->finalized) return cr_fail(CR_ERR_STATE, "cr_share_weights: finalize the source first");
     if (ctx_share_ok(src, "cr_share_weights (source)") != CR_OK) return CR_ERR_STATE;      // a stale borrower hands on nothing
     dst->w = src->w;                    // device pointers only: nothing is copied
+    dst->llm.reset();                   // (the one write to the map outside weights.hip)
     dst->borrowed = true;
     dst->d = src->d;
     dst->finalized = true;
@@ -196,41 +238,17 @@ int cr_load_weight(cr_ctx* c, const char* name, const void* src, int dtype, cons
     if (c->borrowed) return cr_fail(CR_ERR_STATE, "cr_load_weight(%s): this context borrows its weights (cr_share_weights); load into the owner", name);
     const size_t es = dtype_size(dtype);
     if (!es) return cr_fail(CR_ERR_ARG, "cr_load_weight(%s): unknown dtype %d", name, dtype);
-    DevTensor t;
-    t.dtype = dtype;
-    t.shape.assign(shape, shape + ndim);
-    if (t.numel() <= 0) return cr_fail(CR_ERR_ARG, "cr_load_weight(%s): empty tensor", name);
-    t.bytes = (size_t)t.numel() * es;
-    auto it = c->w.find(name);
-    if (it != c->w.end()) {
-        if (it->second.bytes != t.bytes) { hipFree(it->second.ptr); c->w.erase(it); it = c->w.end(); }
-        else t.ptr = it->second.ptr;
-    }
-    if (!t.ptr && hipMalloc(&t.ptr, (t.bytes + 255) & ~(size_t)255) != hipSuccess)
-        return cr_fail(CR_ERR_NOMEM, "cr_load_weight(%s): %zu bytes", name, t.bytes);
-    CR_HIP(hipMemcpyAsync(t.ptr, src, t.bytes, src_is_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    int64_t numel = 1;
+    for (int i = 0; i < ndim; i++) numel *= shape[i];
+    if (numel <= 0) return cr_fail(CR_ERR_ARG, "cr_load_weight(%s): empty tensor", name);
+    const size_t bytes = (size_t)numel * es;
+    DevTensor* t = w_put(c, name, dtype, std::vector<int64_t>(shape, shape + ndim), bytes);      // a reload of the same size lands in the old allocation
+    if (!t) return cr_fail(CR_ERR_NOMEM, "cr_load_weight(%s): %zu bytes", name, bytes);
+    CR_HIP(hipMemcpyAsync(t->ptr, src, bytes, src_is_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (src_is_host) CR_HIP(hipStreamSynchronize((hipStream_t)stream));   // caller may free host memory right away
-    c->w[name] = t;
-    // copies cr_finalize / cr_enable_fp8_* derived from the tensor this one replaces (decode layout, e4m3 bytes + scales, fc1's bound) would go on
-    // serving the OLD values to the kernels that read them (round-4 advice): they go now, cr_finalize rebuilds the decode layout, and the fp8
-    // options switch off until cr_enable_fp8_* is called again (it rebuilds what is missing)
-    bool had_fp8 = false;
-    for (const char* pre : {"declayout.", "fp8.", "fp8s.", "fp8b.", "fp8dl."}) {
-        auto d = c->w.find(std::string(pre) + name);
-        if (d == c->w.end()) continue;
-        if (pre[0] == 'f') had_fp8 = true;
-        hipFree(d->second.ptr);
-        c->w.erase(d);
-    }
-    {   // fc1's bound {max row norm of W1, max |b1|} also depends on the bias
-        const std::string nm(name);
-        const size_t at = nm.rfind("mlp.fc1.bias");
-        if (at != std::string::npos && at + 12 == nm.size()) {
-            auto d = c->w.find("fp8b." + nm.substr(0, at) + "mlp.fc1.weight");
-            if (d != c->w.end()) { hipFree(d->second.ptr); c->w.erase(d); had_fp8 = true; }
-        }
-    }
-    if (had_fp8) { c->fp8_decode = false; c->fp8_mfma = 0; }
+    // copies cr_finalize / cr_enable_fp8_* derived from the tensor this one replaces would go on serving the OLD values to the kernels that read them: they go
+    // now (and the fp8 options with them, weights.hpp), cr_finalize rebuilds the decode layout, cr_enable_fp8_* what is missing of the rest
+    w_drop_copies(c, name);
     cr_bump_gen(c);
     if (strncmp(name, "orderformer.", 12) != 0) c->finalized = false;      // the sorter (f4) has no derived tensors to refresh
     return CR_OK;

@@ -1,7 +1,7 @@
 // CalliAlign stage: PerceiverResampler, cosine VQ, de-normalisation.
 //   reference: models/perceiver_resampler.py:8-100,130-141; models/similarity.py:9-27;
 //              InternVL/modeling_internvl_chat.py:602-640
-#include "ctx.hpp"
+#include "weights.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
 
@@ -287,18 +287,11 @@ int calli_finalize(cr_ctx* c, hipStream_t st) {
     const DevTensor* tb = WT(c, "normed_emb.weight");
     if (!tb) return CR_ERR_STATE;
     if (tb->shape.size() != 2 || tb->shape[1] != D) return cr_fail(CR_ERR_ARG, "normed_emb.weight must be [vocab,4096]");
-    DevTensor t;
-    t.dtype = CR_BF16; t.shape = tb->shape; t.bytes = tb->bytes;
-    auto it = c->w.find("derived.vq_table");
-    if (it != c->w.end() && it->second.bytes == t.bytes) t.ptr = it->second.ptr;
-    else {
-        if (it != c->w.end() && it->second.ptr) CR_HIP(hipFree(it->second.ptr));      // a table of another size: release it
-        CR_HIP(hipMalloc(&t.ptr, t.bytes));
-    }
+    DevTensor* t = w_put(c, "derived.vq_table", CR_BF16, tb->shape, tb->bytes);
+    if (!t) return cr_fail(CR_ERR_NOMEM, "derived.vq_table");
     // F.normalize(embedding_weight, p=2, dim=1) is input-independent: do it once (similarity.py:18 does it per call)
-    hipLaunchKernelGGL(l2norm_rows_kernel, dim3((unsigned)tb->shape[0]), dim3(256), 0, st, (const bf16*)tb->ptr, (bf16*)t.ptr, tb->shape[0]);
+    hipLaunchKernelGGL(l2norm_rows_kernel, dim3((unsigned)tb->shape[0]), dim3(256), 0, st, (const bf16*)tb->ptr, (bf16*)t->ptr, tb->shape[0]);
     CR_HIP(hipGetLastError());
-    c->w["derived.vq_table"] = t;
     return CR_OK;
 }
 

@@ -1,5 +1,6 @@
 // Context of libcallireader_hip.so: weights (library-owned device copies), derived
 // tensors, a grow-only device workspace.  Host-side C++ only; no torch types.
+// The weight map is read everywhere and written in weights.hip only (weights.hpp: w_put, w_drop_*).
 #pragma once
 #include <atomic>
 #include <deque>
@@ -19,6 +20,8 @@ struct DevTensor {
     int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
 };
 
+struct LlmWeights;                      // weights.hpp
+
 struct cr_ctx {
     int device = 0;
     cr_model_desc d{};
@@ -35,7 +38,8 @@ struct cr_ctx {
     bool no_sliced_decode = false;      // CR_NO_SLICED_DECODE=1: decode through the one-tile weight-streaming GEMMs (A/B aid)
     bool perceiver_v1 = false;          // CR_PERCEIVER_ATTN_V1=1 at cr_create: round 1's perceiver attention kernel (the bit-for-bit yardstick of the current one)
     bool fold_rope = true;              // 9..64-row decode: RoPE + split + the new token's cache row inside the attention kernel (attention_decode.hip FOLD; bit-identical); CR_DECODE_FOLD_ROPE=0 at cr_create: rope_split_kernel as its own launch
-    std::unordered_map<std::string, DevTensor> w;
+    std::unordered_map<std::string, DevTensor> w;      // loaded tensors, "derived.*" tensors and the prefixed copies of weights.hpp's CopyKind
+    std::shared_ptr<LlmWeights> llm;    // the language model's weights resolved from `w` (weights.hpp llm_weights); reset by whatever writes `w`
     // workspace
     char* ws = nullptr;
     size_t ws_bytes = 0;
@@ -46,7 +50,7 @@ struct cr_ctx {
     std::shared_ptr<std::atomic<uint64_t>> owner_cell;      // borrowed: the owning context's cell, and its value when the map was copied: a reload /
     uint64_t owner_gen = 0;             //     re-finalize / fp8 toggle / destroy of the owner frees or replaces tensors this copy still points at -> the
                                         //     stage entry points refuse to run (ctx_share_ok)
-    // the seqs[] of the last prefill / decode call (llm.hip stage_seqs); per context, so that two contexts sharing weights can work on one KV cache
+    // the seqs[] of the last prefill / decode call (ctx_stage_seqs); per context, so that two contexts sharing weights can work on one KV cache
     int32_t* d_seqs = nullptr;
     int d_seqs_cap = 0;
     std::vector<int32_t> seqs_on_device;   // what d_seqs holds
@@ -68,17 +72,15 @@ struct cr_ctx {
 
 inline void cr_bump_gen(cr_ctx* c) { c->weight_gen++; c->gen_cell->store(c->weight_gen, std::memory_order_release); }
 
-// e4m3 copy + per-row fp32 scale of weight `name` as "fp8.<name>" / "fp8s.<name>" (llm.hip); a no-op when already built for this shape
-int build_fp8_copy(cr_ctx* c, const std::string& name, int k_multiple, hipStream_t st);
-// C = epi((A8 . W8^T) * ascale[m] * wscale[n] + bias): both operands e4m3 (gemm256's F8 instance)
-int ctx_gemm_f8(cr_ctx* c, int epi, const void* a8, const float* ascale, const DevTensor* w8, const DevTensor* ws, void* C, int64_t ldc,
-                const bf16* bias, int M, int N, int K, hipStream_t st, const bf16* res = nullptr, int64_t ldr = 0);
 
 // CR_OK, or CR_ERR_STATE when this context borrows weights whose owner has changed them since cr_share_weights
 int ctx_share_ok(const cr_ctx* c, const char* who);
 
 // GEMM launch used by every stage: validates, launches, and (when profiling) brackets the launch with events.
 int ctx_gemm(cr_ctx* c, int epi, const GemmParams& p, hipStream_t st);
+// C = epi((A8 . W8^T) * ascale[m] * wscale[n] + bias): both operands e4m3 (gemm256's F8 instance), the weight's e4m3 copy and its row scales
+int ctx_gemm_f8(cr_ctx* c, int epi, const void* a8, const float* ascale, const void* w8, const float* wscale, void* C, int64_t ldc,
+                const bf16* bias, int M, int N, int K, hipStream_t st, const bf16* res = nullptr, int64_t ldr = 0);
 
 void cr_set_error(const char* fmt, ...);
 int cr_fail(int code, const char* fmt, ...);
@@ -97,9 +99,11 @@ int cr_fail(int code, const char* fmt, ...);
 const bf16* W(cr_ctx* c, const std::string& name);
 const DevTensor* WT(cr_ctx* c, const std::string& name);
 int ws_ensure(cr_ctx* c, size_t bytes);
+// the seqs[] of a prefill / decode call into c->d_seqs (api.hip)
+int ctx_stage_seqs(cr_ctx* c, const int32_t* seqs, int n, hipStream_t st, bool always);
 
 // simple bump allocator over the workspace.  Without a base it only measures: the takes return null and bytes() is what they need.  With a capacity,
-// a take that would pass it returns null and clears ok(); the caller checks ok() before it launches anything (llm.hip's ws_carve).  A caller that
+// a take that would pass it returns null and clears ok(); the caller checks ok() before it launches anything (ws_carve below).  A caller that
 // passes no capacity (the other stages, which size the workspace by their own formulas) gets no check.
 struct Arena {
     char* base; size_t cap; size_t off = 0; bool fits = true;
@@ -113,3 +117,14 @@ struct Arena {
     size_t bytes() const { return off; }
     bool ok() const { return fits; }
 };
+
+// Runs the call's carve twice: on an Arena without a base to measure what the call needs, then -- the workspace grown to that -- on the workspace itself.
+// The bytes reserved and the pointers handed out come from the same takes.
+template <class Bufs> int ws_carve(cr_ctx* c, const char* who, Bufs& b) {
+    Arena measure;
+    b.carve(measure);
+    CR_TRY(ws_ensure(c, measure.bytes()));
+    Arena ar(c->ws, c->ws_bytes);
+    b.carve(ar);
+    return ar.ok() ? CR_OK : cr_fail(CR_ERR_STATE, "%s: the carve passed the %zu bytes of workspace (%zu measured)", who, c->ws_bytes, measure.bytes());
+}

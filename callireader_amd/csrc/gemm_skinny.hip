@@ -15,7 +15,7 @@
 //   * partial tiles of the waves are summed through LDS in a fixed order (bitwise reproducible, and a row's
 //     result does not depend on how many other rows are in the batch);
 //   * epilogues: store / +residual / SwiGLU (rows [8 gate | 8 up] of one tile -> 8 outputs) / fp32 logits.
-//   * W8: the weights are e4m3 bytes with one fp32 scale per row (llm.hip: cr_enable_fp8_decode) -- half the HBM bytes of the
+//   * W8: the weights are e4m3 bytes with one fp32 scale per row (weights.hip: cr_enable_fp8_decode) -- half the HBM bytes of the
 //     kernel's bound.  A lane loads 16 B = 16 consecutive k of its row per 64-deep step and turns them into two bf16
 //     fragments with v_cvt_scalef32_pk_bf16_fp8 (exact: e4m3 is a subset of bf16); the X fragments take the same k
 //     (16*(lane>>4) + 0..7 and + 8..15), the MFMA, the accumulation and the epilogue stay as they are, and the row scale

@@ -8,12 +8,9 @@
 //            -> GEMM wo (+x in place) -> RMSNorm -> GEMM w1|w3 with SwiGLU epilogue -> GEMM w2 (+x in place).
 // Decode (<= 64 rows): wqkv / wo / w2 leave fp32 K-slices that RoPE-split and a fused residual-add + RMSNorm sum up.
 //
-// This file holds the model: the kernels, the two layer loops, the weight preparation and the entry points cr_llm_prefill_batch / cr_llm_decode.  The cache
-// object (struct cr_kv, every cr_kv_* entry point) is kv.hpp / kv.hip; what follows the LM head (the picks, scores, constraints, the beam step) is pick.hip.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
+// This file holds the model: the kernels, the two layer loops and the entry points cr_llm_prefill_batch / cr_llm_decode / cr_llm_decode_draft.  The weights come
+// resolved (weights.hpp: LlmWeights; weight preparation and every tensor name are in weights.hip).  The cache object (struct cr_kv, every cr_kv_* entry point) is
+// kv.hpp / kv.hip; what follows the LM head (the picks, scores, constraints, the beam step) is pick.hip.
 #include <algorithm>
 #include <vector>
 
@@ -21,8 +18,8 @@
 #include "decode.hpp"
 #include "draft.hpp"
 #include "kv.hpp"
-#include "misc.hpp"
 #include "norm.hpp"
+#include "weights.hpp"
 
 namespace {
 
@@ -198,91 +195,11 @@ __global__ __launch_bounds__(256) void set_len_kernel(const int32_t* __restrict_
     for (int i = threadIdx.x; i < n; i += 256) lens[seg[4 * i + 3]] = seg[4 * i + 2] + seg[4 * i + 1];
 }
 
-// w13 rows: [16q + e] = w1[8q + e], [16q + 8 + e] = w3[8q + e]   (pairs gate/up for the SwiGLU epilogue)
-__global__ __launch_bounds__(256) void interleave8_kernel(const bf16* __restrict__ w1, const bf16* __restrict__ w3,
-                                                          bf16* __restrict__ out, int ff) {
-    const int r = blockIdx.x;                 // output row, 0 .. 2*ff
-    const int q = r >> 4, e = r & 15;
-    const bf16* src = (e < 8 ? w1 : w3) + (int64_t)(q * 8 + (e & 7)) * D;
-    const bf16x8* sp = (const bf16x8*)src;
-    bf16x8* dp = (bf16x8*)(out + (int64_t)r * D);
-    dp[threadIdx.x] = sp[threadIdx.x];
-    dp[threadIdx.x + 256] = sp[threadIdx.x + 256];
-}
-
-// One weight row -> e4m3 bytes + its scale (common.hpp's e4m3 row rule): q = round-to-nearest-even (w / scale).  One workgroup per row, K % 8 == 0.
-__global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* __restrict__ w, int64_t ldw, int K, unsigned char* __restrict__ q,
-                                                              float* __restrict__ scale) {
-    __shared__ float red[4];
-    const int64_t r = blockIdx.x;
-    const int tid = threadIdx.x;
-    const bf16* wr = w + r * ldw;
-    float mx = 0.f;
-    for (int k = tid * 8; k < K; k += 256 * 8) {
-        const bf16x8 v = *(const bf16x8*)(wr + k);
-#pragma unroll
-        for (int e = 0; e < 8; e++) mx = fmaxf(mx, fabsf(bf2f(v[e])));
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float sc = e4m3_row_scale(mx);
-    const float inv = 1.0f / sc;
-    if (tid == 0) scale[r] = sc;
-    for (int k = tid * 8; k < K; k += 256 * 8) *(uint2*)(q + r * (int64_t)K + k) = pack8_e4m3(*(const bf16x8*)(wr + k), inv);
-}
-
-// out[0] = max over rows of ||w_row||_2, out[1] = max |b| (positive floats order like their bit patterns: atomicMax on the bits)
-__global__ __launch_bounds__(256) void row_norm_max_kernel(const bf16* __restrict__ w, int K, const bf16* __restrict__ b, float* __restrict__ out) {
-    __shared__ float red[4];
-    const int tid = threadIdx.x;
-    const bf16* wr = w + (int64_t)blockIdx.x * K;
-    float ss = 0.f;
-    for (int k = tid; k < K; k += 256) { const float v = bf2f(wr[k]); ss += v * v; }
-    ss = wave_sum(ss);
-    if ((tid & 63) == 0) red[tid >> 6] = ss;
-    __syncthreads();
-    if (tid == 0) {
-        atomicMax((unsigned*)out, __float_as_uint(sqrtf(red[0] + red[1] + red[2] + red[3])));
-        if (b) atomicMax((unsigned*)out + 1, __float_as_uint(fabsf(bf2f(b[blockIdx.x]))));
-    }
-}
-
 int rms(const bf16* in, bf16* out, const bf16* w, int64_t rows, float eps, hipStream_t st, float* row_scale = nullptr) {
     NormParams np{};
     np.in = in; np.ld_in = D; np.out = out; np.ld_out = D; np.gamma = w; np.rows = rows; np.eps = eps;
     if (row_scale) { np.out8 = (unsigned char*)out; np.out8_scale = row_scale; }     // e4m3 rows in the first half of `out`
     return launch_rmsnorm(np, D, st);
-}
-
-const DevTensor* opt(cr_ctx* c, const std::string& name) {
-    auto it = c->w.find(name);
-    return it == c->w.end() ? nullptr : &it->second;
-}
-
-// One linear layer's weight [N][K] in the forms the GEMM kernels take; all but `w` may be null
-struct LinW {
-    const bf16* w;                // bf16 as loaded (nn.Linear's layout; w1|w3: the interleaved derived tensor)
-    int N, K;
-    const DevTensor* dl;          // its decode-layout copy (llm_finalize)
-    int dl_kind;                  // GemmParams::wsw of that copy: 1 plain tiles, 2 wqkv's RoPE tile order (only the K-sliced kernel reads it)
-    const DevTensor *q8, *s8;     // e4m3 copy + one fp32 scale per row (cr_enable_fp8_mfma / cr_enable_fp8_decode)
-    const DevTensor* dl8;         // the e4m3 copy in its decode layout (cr_enable_fp8_decode)
-    bool e4m3() const { return q8 && s8; }
-};
-struct LayerW { const bf16 *an, *fn; LinW qkv, o, w13, w2; };
-
-LinW lin_weight(cr_ctx* c, const std::string& nm, int N, int K, int dl_kind = 1) {
-    return {W(c, nm), N, K, opt(c, "declayout." + nm), dl_kind, opt(c, "fp8." + nm), opt(c, "fp8s." + nm), opt(c, "fp8dl." + nm)};
-}
-
-int layer_weights(cr_ctx* c, int l, int ff, LayerW& w) {
-    const std::string p = "language_model.model.layers." + std::to_string(l) + ".";
-    w.an = W(c, p + "attention_norm.weight"); w.fn = W(c, p + "ffn_norm.weight");
-    w.qkv = lin_weight(c, p + "attention.wqkv.weight", QKV, D, 2); w.o = lin_weight(c, p + "attention.wo.weight", D, D);
-    w.w13 = lin_weight(c, "derived.w13." + std::to_string(l), 2 * ff, D); w.w2 = lin_weight(c, p + "feed_forward.w2.weight", D, ff);
-    return (w.an && w.fn && w.qkv.w && w.o.w && w.w13.w && w.w2.w) ? CR_OK : CR_ERR_STATE;
 }
 
 enum LinForm {
@@ -300,9 +217,9 @@ int linear(cr_ctx* c, int epi, const bf16* A, const LinW& w, LinForm form, void*
     if (epi == EPI_RES) { p.res = (const bf16*)C; p.ldr = p.ldc; }
     if (form == LIN_E4M3) {
         if (!w.e4m3()) return cr_fail(CR_ERR_STATE, "linear: no e4m3 copy of this weight (cr_enable_fp8_decode)");
-        p.W = (const bf16*)w.q8->ptr; p.w8 = 1; p.wscale = (const float*)w.s8->ptr;
-        if (w.dl8 && M <= 64) { p.W = (const bf16*)w.dl8->ptr; p.wsw = 1; }
-    } else if (form == LIN_DECODE && w.dl && M <= 64) { p.W = (const bf16*)w.dl->ptr; p.wsw = w.dl_kind; }
+        p.W = (const bf16*)w.q8; p.w8 = 1; p.wscale = w.s8;
+        if (w.dl8 && M <= 64) { p.W = (const bf16*)w.dl8; p.wsw = 1; }
+    } else if (form == LIN_DECODE && w.dl && M <= 64) { p.W = w.dl; p.wsw = w.dl_kind; }
     else if (form == LIN_PREFILL && M <= 64) p.kernel = 128;
     return ctx_gemm(c, epi, p, st);
 }
@@ -338,17 +255,6 @@ AttnParams prefill_attn_params(const LayerKV& lk, int T, bf16* q, bf16* ao, int 
     return segment_attn_params(lk.k, lk.v, T, q, ao, NH, NH / NKV, n_segs, seg, Sq, attn_params(lk, T, q, ao).s_div);      // (attention.hpp; cr_op_attention_segments fills its launch there too)
 }
 
-// Runs the call's carve twice: on an Arena without a base to measure what the call needs, then -- the workspace grown to that -- on the workspace itself.
-// The bytes reserved and the pointers handed out come from the same takes.
-template <class Bufs> int ws_carve(cr_ctx* c, const char* who, Bufs& b) {
-    Arena measure;
-    b.carve(measure);
-    CR_TRY(ws_ensure(c, measure.bytes()));
-    Arena ar(c->ws, c->ws_bytes);
-    b.carve(ar);
-    return ar.ok() ? CR_OK : cr_fail(CR_ERR_STATE, "%s: the carve passed the %zu bytes of workspace (%zu measured)", who, c->ws_bytes, measure.bytes());
-}
-
 struct Segment { int seq, row0, S, pos0; };     // a page's rows inside a batched prefill
 
 // The index arrays of a batched prefill (M rows, n pages): one block of ints, laid out the same on the host and on the device
@@ -379,8 +285,8 @@ struct PrefillBufs {
     PrefillRows rows;
     HeadBufs head;
 
-    PrefillBufs(cr_ctx* c, const cr_kv* kv, int M, int n_pages, int max_S, const RowFeatures& f)
-        : M(M), n_pages(n_pages), max_S(max_S), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), any8(c->fp8_mfma && M >= 256),
+    PrefillBufs(cr_ctx* c, int ff, const cr_kv* kv, int M, int n_pages, int max_S, const RowFeatures& f)
+        : M(M), n_pages(n_pages), max_S(max_S), ff(ff), kv8(kv->fmt == CR_KV_E4M3), any8(c->fp8_mfma && M >= 256),
           last_rows(c->prefill_last_rows && !any8 && !c->probe_dst), head{n_pages, c->d.vocab, f} {}
 
     void carve(Arena& ar) {
@@ -402,12 +308,11 @@ struct PrefillBufs {
 };
 
 // The decoder stack over the prompt rows b.x of a batched prefill.
-int prefill_layers(cr_ctx* c, cr_kv* kv, const PrefillBufs& b, hipStream_t st) {
+int prefill_layers(cr_ctx* c, const LlmWeights& lw, cr_kv* kv, const PrefillBufs& b, hipStream_t st) {
     const PrefillRows& r = b.rows;
-    const int M = b.M, ff = b.ff, n_pages = b.n_pages, layers = c->d.llm_layers;
+    const int M = b.M, n_pages = b.n_pages, layers = c->d.llm_layers;
     const float eps = c->d.rms_eps;
-    const bf16 *cosT = W(c, "rope.cos"), *sinT = W(c, "rope.sin");      // [max_pos][128] each
-    if (!cosT || !sinT) return CR_ERR_STATE;
+    const bf16 *cosT = lw.cosT, *sinT = lw.sinT;
     // cr_llm_hidden_probe (parity tooling): rows [row0, row0 + rows) of the residual stream before layer 0 and after every layer
     auto probe = [&](int slot) -> int {
         if (!c->probe_dst || c->probe_row0 + c->probe_rows > M) return CR_OK;
@@ -417,18 +322,17 @@ int prefill_layers(cr_ctx* c, cr_kv* kv, const PrefillBufs& b, hipStream_t st) {
     };
     CR_TRY(probe(0));
     for (int l = 0; l < layers; l++) {
-        LayerW w;
-        CR_TRY(layer_weights(c, l, ff, w));
+        const LayerW& w = lw.layer[l];
         LayerKV lk = layer_kv(kv, l);
         if (b.kv8) { lk.k = b.stage_k; lk.v = b.stage_v; }
         const int T = b.kv8 ? b.max_S : kv->max_tokens;      // rows per (slot, head) of what the attention reads
         const bool m8 = b.any8 && w.qkv.e4m3() && w.w13.e4m3();
         const bool m8all = m8 && c->fp8_mfma >= 2 && w.o.e4m3() && w.w2.e4m3();      // level 2: wo and w2 as well (their inputs take a quantiser pass)
         // x += in . W^T for wo and w2.  Level 2: their inputs are activations no norm produced, so one quantiser pass each (row maximum, then the e4m3 row)
-        auto add_linear = [&](const bf16* in, const LinW& lw) -> int {
-            if (!m8all) return linear(c, EPI_RES, in, lw, LIN_PREFILL, b.x, M, st);
-            hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, in, (int64_t)lw.K, lw.K, b.a8, b.hs);
-            return linear_f8(c, EPI_RES, b.a8, b.hs, lw, b.x, M, st);
+        auto add_linear = [&](const bf16* in, const LinW& lin) -> int {
+            if (!m8all) return linear(c, EPI_RES, in, lin, LIN_PREFILL, b.x, M, st);
+            launch_quant_fp8_rows(in, lin.K, M, lin.K, b.a8, b.hs, st);
+            return linear_f8(c, EPI_RES, b.a8, b.hs, lin, b.x, M, st);
         };
         CR_TRY(rms(b.x, b.h, w.an, M, eps, st, m8 ? b.hs : nullptr));
         CR_TRY(m8 ? linear_f8(c, EPI_STORE, b.h, b.hs, w.qkv, b.qkv, M, st) : linear(c, EPI_STORE, b.h, w.qkv, LIN_PREFILL, b.qkv, M, st));
@@ -486,8 +390,8 @@ struct DecodeBufs {
     // its sequence's cached length -- RoPE, the cache row and the key count follow it, and the RoPE-folded attention form is not taken.  Set by DraftBufs' carve.
     const int32_t* off = nullptr;
 
-    DecodeBufs(cr_ctx* c, const cr_kv* kv, int M, int nsplit, const RowFeatures& f)
-        : M(M), nsplit(nsplit), ff((int)WT(c, "derived.w13.0")->shape[0] / 2), kv8(kv->fmt == CR_KV_E4M3), s_qkv(gemm_partial_splits(QKV, D)),
+    DecodeBufs(cr_ctx* c, int ff, const cr_kv* kv, int M, int nsplit, const RowFeatures& f)
+        : M(M), nsplit(nsplit), ff(ff), kv8(kv->fmt == CR_KV_E4M3), s_qkv(gemm_partial_splits(QKV, D)),
           s_o(gemm_partial_splits(D, D)), s_2(gemm_partial_splits(D, ff)), sliced(M <= 64 && s_qkv > 0 && s_o > 0 && s_2 > 0 && !c->no_sliced_decode),
           fused(sliced && c->fused_decode && !c->fp8_decode && !kv8 && decode_fused_supported(M, ff) && s_qkv == DEC_SLICES_WQKV && s_o == DEC_SLICES_WO &&
                 s_2 == DEC_SLICES_W2), head{M, c->d.vocab, f} {}
@@ -521,16 +425,15 @@ AttnParams decode_attn_params(const cr_kv* kv, const LayerKV& lk, const DecodeBu
 DecodeGemmParams fused_gemm_params(cr_ctx* c, const LinW& w, int M) {
     DecodeGemmParams dp{};
     dp.M = M; dp.eps = c->d.rms_eps; dp.W = w.w; dp.ldw = w.K; dp.N = w.N; dp.K = w.K;
-    if (w.dl) { dp.W = (const bf16*)w.dl->ptr; dp.swizzled = 1; }
+    if (w.dl) { dp.W = w.dl; dp.swizzled = 1; }
     return dp;
 }
 
 // The decoder stack over the rows b.x of a decode step (row i = the next token of sequence d_seqs[i]).
-int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_seqs, hipStream_t st) {
+int decode_layers(cr_ctx* c, const LlmWeights& lw, cr_kv* kv, const DecodeBufs& b, const int32_t* d_seqs, hipStream_t st) {
     const int M = b.M, layers = c->d.llm_layers;
     const float eps = c->d.rms_eps;
-    const bf16 *cosT = W(c, "rope.cos"), *sinT = W(c, "rope.sin");      // [max_pos][128] each
-    if (!cosT || !sinT) return CR_ERR_STATE;
+    const bf16 *cosT = lw.cosT, *sinT = lw.sinT;
     auto fused_layer = [&](const LayerW& w, const LayerKV& lk) -> int {
         DecodeGemmParams dp = fused_gemm_params(c, w.qkv, M);
         dp.xres = b.x; dp.gamma = w.an;
@@ -549,8 +452,7 @@ int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_se
         return launch_decode_gemm(DEC_W2, dp, st);
     };
     for (int l = 0; l < layers; l++) {
-        LayerW w;
-        CR_TRY(layer_weights(c, l, b.ff, w));
+        const LayerW& w = lw.layer[l];
         const LayerKV lk = layer_kv(kv, l);
         if (b.fused) {
             CR_TRY(fused_layer(w, lk));
@@ -595,9 +497,7 @@ int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_se
         if (b.sliced) {
             CR_TRY(linear(c, EPI_PARTIAL, b.act, w.w2, dec, b.pbuf, M, st));
             // the last layer's sum only lands in x: the caller norms what it needs
-            const bf16* next_norm = l + 1 < layers ? W(c, "language_model.model.layers." + std::to_string(l + 1) + ".attention_norm.weight") : nullptr;
-            if (l + 1 < layers && !next_norm) return CR_ERR_STATE;
-            CR_TRY(launch_add_rmsnorm(b.x, b.pbuf, b.s_2, M, next_norm, b.h, eps, st));
+            CR_TRY(launch_add_rmsnorm(b.x, b.pbuf, b.s_2, M, l + 1 < layers ? lw.layer[l + 1].an : nullptr, b.h, eps, st));
         } else {
             CR_TRY(linear(c, EPI_RES, b.act, w.w2, plain, b.x, M, st));
         }
@@ -607,17 +507,15 @@ int decode_layers(cr_ctx* c, cr_kv* kv, const DecodeBufs& b, const int32_t* d_se
 }
 
 // The final RMSNorm and the LM head over the rows of a decode step: b.head.lg
-int decode_head(cr_ctx* c, const DecodeBufs& b, hipStream_t st) {
+int decode_head(cr_ctx* c, const LlmWeights& lw, const DecodeBufs& b, hipStream_t st) {
     const int n = b.M, V = c->d.vocab;
-    const bf16* nw = W(c, "language_model.model.norm.weight");
-    const LinW head = lin_weight(c, "language_model.output.weight", V, D);
-    if (!nw || !head.w) return CR_ERR_STATE;
+    const LinW& head = lw.head;
     if (c->fused_decode && !c->fp8_decode && !c->no_sliced_decode && decode_fused_supported(n, b.ff)) {
         DecodeGemmParams dh = fused_gemm_params(c, head, n);      // final RMSNorm folded into the LM head (gemm_decode.hip)
-        dh.xres = b.x; dh.gamma = nw; dh.C = b.head.lg; dh.ldc = V;
+        dh.xres = b.x; dh.gamma = lw.norm; dh.C = b.head.lg; dh.ldc = V;
         return launch_decode_gemm(DEC_HEAD, dh, st);
     }
-    CR_TRY(rms(b.x, b.head.hl, nw, n, c->d.rms_eps, st));
+    CR_TRY(rms(b.x, b.head.hl, lw.norm, n, c->d.rms_eps, st));
     return linear(c, EPI_F32, b.head.hl, head, c->fp8_decode && n <= 64 && head.e4m3() ? LIN_E4M3 : LIN_DECODE, b.head.lg, n, st);
 }
 
@@ -627,7 +525,7 @@ struct DraftBufs {
     int n;
     bool windows;
     int64_t* index;
-    DraftBufs(cr_ctx* c, const cr_kv* kv, int M, int n, int nsplit, const RowFeatures& f) : dec(c, kv, M, nsplit, f), n(n), windows(M > n), index(nullptr) {}
+    DraftBufs(cr_ctx* c, int ff, const cr_kv* kv, int M, int n, int nsplit, const RowFeatures& f) : dec(c, ff, kv, M, nsplit, f), n(n), windows(M > n), index(nullptr) {}
     void carve(Arena& ar) {
         dec.carve(ar);
         index = ar.take<int64_t>(draft_index_words(n, dec.M));
@@ -637,249 +535,14 @@ struct DraftBufs {
 
 }  // namespace
 
-// The seqs[] of a prefill / decode call in the context's device staging (per context, not per cache: two contexts that share weights may work
-// on different sequences of one cache at once).  `always` = false skips the host-to-device copy of an unchanged list.  The copy goes through one of
-// a few pinned host buffers (a pageable copy makes the host wait for the stream, which would stall a decode thread whose rows change every few
-// steps); a buffer is reused once the copy that last read it has run.
-static int stage_seqs(cr_ctx* c, const int32_t* seqs, int n, hipStream_t st, bool always) {
-    if (n > c->d_seqs_cap) {
-        CR_HIP(hipDeviceSynchronize());                 // the old staging may still be read by enqueued work
-        if (c->d_seqs) CR_HIP(hipFree(c->d_seqs));
-        c->d_seqs = nullptr; c->d_seqs_cap = 0; c->seqs_on_device.clear();
-        const int cap = n > 256 ? n : 256;
-        if (hipMalloc((void**)&c->d_seqs, (size_t)cap * 4) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "sequence staging of %d entries", cap);
-        c->d_seqs_cap = cap;
-    }
-    if (always || (int)c->seqs_on_device.size() != n || memcmp(c->seqs_on_device.data(), seqs, (size_t)n * 4) != 0) {
-        cr_ctx::SeqStage& h = c->seq_stage[c->seq_stage_next++ % cr_ctx::SEQ_STAGES];
-        if (h.copied) CR_HIP(hipEventSynchronize(h.copied));
-        else CR_HIP(hipEventCreateWithFlags(&h.copied, hipEventDisableTiming));
-        if (h.cap < n) {
-            if (h.host) CR_HIP(hipHostFree(h.host));
-            h.host = nullptr; h.cap = 0;
-            CR_HIP(hipHostMalloc((void**)&h.host, (size_t)c->d_seqs_cap * 4, hipHostMallocDefault));
-            h.cap = c->d_seqs_cap;
-        }
-        memcpy(h.host, seqs, (size_t)n * 4);
-        CR_HIP(hipMemcpyAsync(c->d_seqs, h.host, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        CR_HIP(hipEventRecord(h.copied, st));
-        c->seqs_on_device.assign(seqs, seqs + n);
-    }
-    return CR_OK;
-}
-
-int build_fp8_copy(cr_ctx* c, const std::string& nm, int k_multiple, hipStream_t st) {
-    const DevTensor* src = WT(c, nm);
-    if (!src) return CR_ERR_STATE;
-    const int64_t N = src->shape[0], K = src->shape[1];
-    if ((K % k_multiple) != 0) return cr_fail(CR_ERR_ARG, "fp8 copy: %s has K = %lld, not a multiple of %d", nm.c_str(), (long long)K, k_multiple);
-    auto have = c->w.find("fp8." + nm);
-    if (have != c->w.end() && have->second.shape == src->shape && c->w.count("fp8s." + nm)) return CR_OK;     // built already for these weights
-    DevTensor q, s;
-    q.dtype = CR_U8; q.shape = src->shape; q.bytes = (size_t)N * K;
-    s.dtype = CR_F32; s.shape = {N}; s.bytes = (size_t)N * 4;
-    if (hipMalloc(&q.ptr, q.bytes) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "fp8 copy: %s", nm.c_str());
-    if (hipMalloc(&s.ptr, s.bytes) != hipSuccess) { hipFree(q.ptr); return cr_fail(CR_ERR_NOMEM, "fp8 copy: %s", nm.c_str()); }
-    hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)N), dim3(256), 0, st, (const bf16*)src->ptr, K, (int)K, (unsigned char*)q.ptr, (float*)s.ptr);
-    for (const char* pre : {"fp8.", "fp8s."}) {
-        auto old = c->w.find(pre + nm);
-        if (old != c->w.end()) { hipFree(old->second.ptr); c->w.erase(old); }
-    }
-    c->w["fp8." + nm] = q;
-    c->w["fp8s." + nm] = s;
-    return CR_OK;
-}
-
-int ctx_gemm_f8(cr_ctx* c, int epi, const void* a8, const float* ascale, const DevTensor* w8, const DevTensor* ws, void* C, int64_t ldc,
-                const bf16* bias, int M, int N, int K, hipStream_t st, const bf16* res, int64_t ldr) {
-    GemmParams p{};
-    p.res = res; p.ldr = ldr;
-    p.A = (const bf16*)a8; p.lda = K; p.W = (const bf16*)w8->ptr; p.ldw = K; p.C = C; p.ldc = ldc; p.bias = bias; p.M = M; p.N = N; p.K = K;
-    p.w8 = 1; p.wscale = (const float*)ws->ptr; p.a8 = 1; p.ascale = ascale;
-    return ctx_gemm(c, epi, p, st);
-}
-
-int llm_finalize(cr_ctx* c, hipStream_t st) {
-    for (int l = 0; l < c->d.llm_layers; l++) {
-        const std::string p = "language_model.model.layers." + std::to_string(l) + ".feed_forward.";
-        auto i1 = c->w.find(p + "w1.weight"), i3 = c->w.find(p + "w3.weight");
-        const std::string dn = "derived.w13." + std::to_string(l);
-        if (i1 == c->w.end() || i3 == c->w.end()) {
-            // one of the pair reloaded without the other: the interleaved tensor cannot be rebuilt (the other original was released)
-            if (i1 != c->w.end() || i3 != c->w.end()) return cr_fail(CR_ERR_STATE, "layer %d: reload feed_forward.w1 and w3 together", l);
-            if (c->w.count(dn)) continue;          // already derived, originals released
-            return cr_fail(CR_ERR_STATE, "layer %d: w1/w3 missing", l);
-        }
-        const int ff = (int)i1->second.shape[0];
-        if (i1->second.shape[1] != D || i3->second.shape != i1->second.shape || (ff % 8))
-            return cr_fail(CR_ERR_ARG, "layer %d: w1/w3 must be [ff,4096] with ff %% 8 == 0", l);
-        DevTensor t;
-        t.dtype = CR_BF16; t.shape = {2 * ff, D}; t.bytes = (size_t)2 * ff * D * 2;
-        auto old = c->w.find(dn);
-        if (old != c->w.end()) { hipFree(old->second.ptr); c->w.erase(old); }
-        // the e4m3 copies derived from the interleaved tensor carry ITS name, not w1's / w3's: cr_load_weight's invalidation (by the reloaded tensor's own name)
-        // cannot see them (round-5 advice).  They go with the tensor they were made from, and the fp8 options switch off until cr_enable_fp8_* rebuilds them.
-        for (const char* pre : {"fp8.", "fp8s.", "fp8b.", "fp8dl."}) {
-            auto d8 = c->w.find(std::string(pre) + dn);
-            if (d8 == c->w.end()) continue;
-            hipFree(d8->second.ptr);
-            c->w.erase(d8);
-            c->fp8_decode = false; c->fp8_mfma = 0;
-        }
-        CR_HIP(hipMalloc(&t.ptr, t.bytes));
-        hipLaunchKernelGGL(interleave8_kernel, dim3(2 * ff), dim3(256), 0, st, (const bf16*)i1->second.ptr,
-                           (const bf16*)i3->second.ptr, (bf16*)t.ptr, ff);
-        CR_HIP(hipStreamSynchronize(st));
-        hipFree(i1->second.ptr); hipFree(i3->second.ptr);      // the interleaved copy replaces them
-        c->w.erase(i1); c->w.erase(c->w.find(p + "w3.weight"));
-        c->w[dn] = t;
-    }
-    // Decode-layout copies of the five weight streams of a small-batch decode step (gemm_decode.hip: one contiguous KiB per load instruction instead of
-    // 16 rows x 64 bytes; wqkv 16.7 -> 11.1 us, w1|w3 43.1 -> 37.5, w2 26.0 -> 20.5, LM head 130 -> 116 at one row, the same bits): +15.9 GB on
-    // InternLM2.5-7B, taken from the 288 GB only if the shapes are the ones the kernels are built for.  CR_DECODE_LAYOUT=0: none (A/B aid); a failed allocation
-    // leaves the decode path on the nn.Linear layout.
-    {
-        for (auto it = c->w.begin(); it != c->w.end();) {         // copies of an earlier cr_finalize: the weights may have been reloaded
-            if (it->first.rfind("declayout.", 0) == 0) { hipFree(it->second.ptr); it = c->w.erase(it); } else ++it;
-        }
-        const char* e = getenv("CR_DECODE_LAYOUT");
-        const DevTensor* w13_0 = WT(c, "derived.w13.0");
-        const bool want = !(e && atoi(e) == 0) && w13_0 && decode_fused_supported(1, (int)w13_0->shape[0] / 2);
-        auto derive = [&](int which, const std::string& nm, int64_t N, int64_t K) -> bool {
-            const DevTensor* src = WT(c, nm);
-            if (!src || src->shape.size() != 2 || src->shape[0] != N || src->shape[1] != K) return false;
-            DevTensor t;
-            t.dtype = CR_BF16; t.shape = {(N + 15) / 16 * 16, K}; t.bytes = decode_swizzled_bytes((int)N, (int)K);
-            if (hipMalloc(&t.ptr, t.bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-            if (decode_swizzle_weight(which, (const bf16*)src->ptr, K, (int)N, (int)K, (bf16*)t.ptr, st) != CR_OK) { hipFree(t.ptr); return false; }
-            c->w["declayout." + nm] = t;
-            return true;
-        };
-        bool ok = want;
-        for (int l = 0; ok && l < c->d.llm_layers; l++) {
-            const std::string p = "language_model.model.layers." + std::to_string(l) + ".";
-            const int64_t ff = w13_0->shape[0] / 2;
-            ok = derive(DEC_WQKV, p + "attention.wqkv.weight", QKV, D) && derive(DEC_WO, p + "attention.wo.weight", D, D) &&
-                 derive(DEC_W13, "derived.w13." + std::to_string(l), 2 * ff, D) && derive(DEC_W2, p + "feed_forward.w2.weight", D, ff);
-        }
-        if (ok) {
-            const DevTensor* ow = WT(c, "language_model.output.weight");
-            if (ow && ow->shape.size() == 2 && ow->shape[1] == D) ok = derive(DEC_HEAD, "language_model.output.weight", ow->shape[0], D);
-        }
-        CR_HIP(hipStreamSynchronize(st));
-        if (want && !ok) {
-            // all or nothing (round-4 advice): a partial set would leave the device nearly full and the decode path on two layouts
-            size_t freed = 0;
-            for (auto it = c->w.begin(); it != c->w.end();) {
-                if (it->first.rfind("declayout.", 0) == 0) { freed += it->second.bytes; hipFree(it->second.ptr); it = c->w.erase(it); } else ++it;
-            }
-            fprintf(stderr, "[callireader_hip] no room (or not the shapes) for the decode-layout copies of the LLM weights: %zu MB released, decode streams the nn.Linear layout\n",
-                    freed >> 20);
-        }
-    }
-    return CR_OK;
-}
-
 extern "C" {
-
-int cr_op_quantize_fp8(const void* w, int64_t ldw, int N, int K, void* q, float* scale, void* stream) {
-    if (!w || !q || !scale || N <= 0 || K <= 0 || (K & 7) || (ldw & 7)) return cr_fail(CR_ERR_ARG, "cr_op_quantize_fp8: bad argument");
-    hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, (const bf16*)w, ldw, K, (unsigned char*)q, scale);
-    CR_HIP(hipGetLastError());
-    return CR_OK;
-}
-
-int cr_enable_fp8_mfma(cr_ctx* c, int enable, void* stream) {
-    if (!c) return cr_fail(CR_ERR_ARG, "cr_enable_fp8_mfma: null context");
-    if (!enable) { if (c->fp8_mfma) cr_bump_gen(c); c->fp8_mfma = 0; return CR_OK; }      // borrowers of these weights watch weight_gen (ctx_share_ok)
-    if (c->borrowed) return cr_fail(CR_ERR_STATE, "cr_enable_fp8_mfma: enable it on the context that owns the weights, then share again");
-    if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_enable_fp8_mfma: call cr_finalize first");
-    CR_HIP(hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<std::string> names;
-    // the linears whose input is a norm's output: that kernel emits the e4m3 row and its scale for free
-    for (int l = 0; l < c->d.vit_layers; l++) {
-        const std::string p = "vision_model.encoder.layers." + std::to_string(l) + ".";
-        if (!c->w.count(p + "attn.qkv.weight")) continue;
-        names.push_back(p + "attn.qkv.weight"); names.push_back(p + "mlp.fc1.weight"); names.push_back(p + "mlp.fc2.weight");
-        // fc1's output goes to fc2 as e4m3 straight from fc1's epilogue (EPI_GELU_Q8); its row scale is a bound LayerNorm 2 derives:
-        // "fp8b.<fc1>" = {max row norm of W1, max |b1|}
-        const DevTensor *w1 = WT(c, p + "mlp.fc1.weight"), *b1 = WT(c, p + "mlp.fc1.bias");
-        if (!w1 || !b1) return CR_ERR_STATE;
-        if (!c->w.count("fp8b." + p + "mlp.fc1.weight")) {
-            DevTensor t;
-            t.dtype = CR_F32; t.shape = {2}; t.bytes = 8;
-            if (hipMalloc(&t.ptr, 8) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "cr_enable_fp8_mfma: bound of layer %d", l);
-            CR_HIP(hipMemsetAsync(t.ptr, 0, 8, st));
-            hipLaunchKernelGGL(row_norm_max_kernel, dim3((unsigned)w1->shape[0]), dim3(256), 0, st, (const bf16*)w1->ptr, (int)w1->shape[1], (const bf16*)b1->ptr, (float*)t.ptr);
-            c->w["fp8b." + p + "mlp.fc1.weight"] = t;
-        }
-    }
-    if (c->w.count("mlp1.1.weight")) names.push_back("mlp1.1.weight");
-    for (int l = 0; l < c->d.llm_layers; l++) {
-        const std::string p = "language_model.model.layers." + std::to_string(l) + ".";
-        if (c->w.count(p + "attention.wqkv.weight")) {
-            names.push_back(p + "attention.wqkv.weight"); names.push_back("derived.w13." + std::to_string(l));
-            names.push_back(p + "attention.wo.weight"); names.push_back(p + "feed_forward.w2.weight");     // their inputs take a quantiser pass
-        }
-    }
-    for (const std::string& nm : names) CR_TRY(build_fp8_copy(c, nm, 256, st));
-    CR_HIP(hipGetLastError());
-    CR_HIP(hipStreamSynchronize(st));
-    c->fp8_mfma = enable >= 2 ? 2 : 1;
-    cr_bump_gen(c);
-    return CR_OK;
-}
-
-int cr_enable_fp8_decode(cr_ctx* c, int enable, void* stream) {
-    if (!c) return cr_fail(CR_ERR_ARG, "cr_enable_fp8_decode: null context");
-    if (!enable) { if (c->fp8_decode) cr_bump_gen(c); c->fp8_decode = false; return CR_OK; }
-    if (c->borrowed) return cr_fail(CR_ERR_STATE, "cr_enable_fp8_decode: enable it on the context that owns the weights, then share again");
-    if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_enable_fp8_decode: call cr_finalize first");
-    CR_HIP(hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<std::string> names;
-    for (int l = 0; l < c->d.llm_layers; l++) {
-        const std::string p = "language_model.model.layers." + std::to_string(l) + ".";
-        names.push_back(p + "attention.wqkv.weight"); names.push_back(p + "attention.wo.weight");
-        names.push_back("derived.w13." + std::to_string(l)); names.push_back(p + "feed_forward.w2.weight");
-    }
-    names.push_back("language_model.output.weight");
-    for (const std::string& nm : names) CR_TRY(build_fp8_copy(c, nm, 512, st));
-    // ... and each of them once more in the decode layout (gemm_decode.hip: decode_swizzle8_kernel; + 7.7 GB on InternLM2.5-7B): without it the e4m3-weight
-    // decode LOST to the bf16 decode on ITS decode layout (round 4: 9.76 against 9.23 ms per 64-row step).  All or nothing; CR_DECODE_LAYOUT=0: none.
-    {
-        const char* e = getenv("CR_DECODE_LAYOUT");
-        bool ok = !(e && atoi(e) == 0);
-        for (size_t i = 0; ok && i < names.size(); i++) {
-            const std::string& nm = names[i];
-            if (c->w.count("fp8dl." + nm)) continue;
-            const DevTensor* q8 = WT(c, "fp8." + nm);
-            if (!q8 || q8->shape.size() != 2) { ok = false; break; }
-            DevTensor t;
-            t.dtype = CR_U8; t.shape = {(q8->shape[0] + 15) / 16 * 16, q8->shape[1]}; t.bytes = decode_swizzled8_bytes((int)q8->shape[0], (int)q8->shape[1]);
-            if (hipMalloc(&t.ptr, t.bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; break; }
-            if (decode_swizzle_weight8((const unsigned char*)q8->ptr, q8->shape[1], (int)q8->shape[0], (int)q8->shape[1], (unsigned char*)t.ptr, st) != CR_OK) { hipFree(t.ptr); ok = false; break; }
-            c->w["fp8dl." + nm] = t;
-        }
-        if (!ok)
-            for (auto it = c->w.begin(); it != c->w.end();) {
-                if (it->first.rfind("fp8dl.", 0) == 0) { hipFree(it->second.ptr); it = c->w.erase(it); } else ++it;
-            }
-    }
-    CR_HIP(hipGetLastError());
-    CR_HIP(hipStreamSynchronize(st));
-    c->fp8_decode = true;
-    cr_bump_gen(c);
-    return CR_OK;
-}
 
 int cr_embed_splice(cr_ctx* c, const int64_t* ids, int S, const void* vit, int n_vit, int64_t img_id, const void* ref,
                     int n_ref, int64_t ref_id, void* out, void* stream) {
     if (!c || !ids || !out || S <= 0) return cr_fail(CR_ERR_ARG, "cr_embed_splice: bad argument");
     if ((size_t)S * 4 + 64 > c->scratch_bytes) return cr_fail(CR_ERR_ARG, "cr_embed_splice: S too large");
     CR_HIP(hipSetDevice(c->device));
-    const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
+    const bf16* table = llm_embed_table(c);
     if (!table) return CR_ERR_STATE;
     hipStream_t st = (hipStream_t)stream;
     int32_t* counts = (int32_t*)c->scratch;
@@ -903,6 +566,8 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     if (!c || !kv || !seqs || !lens || !embeds || n <= 0 || n > kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_prefill_batch: bad argument");
     if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_llm_prefill_batch: call cr_finalize first");
     CR_TRY(ctx_share_ok(c, "cr_llm_prefill_batch"));
+    const LlmWeights* lw;
+    CR_TRY(llm_weights(c, &lw));
     std::vector<Segment> segs;
     int M = 0;
     for (int i = 0; i < n; i++) {
@@ -924,11 +589,10 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     const bool beams = feat.beam_rows > 0;
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    const int V = c->d.vocab;
     const bool kv8 = kv->fmt == CR_KV_E4M3;
     int max_S = 0;
     for (const Segment& sg : segs) max_S = sg.S > max_S ? sg.S : max_S;
-    PrefillBufs b(c, kv, M, n, max_S, feat);
+    PrefillBufs b(c, lw->ff, kv, M, n, max_S, feat);
     CR_TRY(ws_carve(c, "cr_llm_prefill_batch", b));
     {
         std::vector<int32_t> h(prefill_rows_ints(M, n, kv8));
@@ -950,16 +614,13 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         }
         CR_HIP(hipMemcpyAsync(b.rows.row_seq, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
     }
-    CR_TRY(stage_seqs(c, seqs, n, st, true));
+    CR_TRY(ctx_stage_seqs(c, seqs, n, st, true));
     CR_HIP(hipMemcpyAsync(b.x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
-    CR_TRY(prefill_layers(c, kv, b, st));
-    const bf16* nw = W(c, "language_model.model.norm.weight");
-    const LinW head = lin_weight(c, "language_model.output.weight", V, D);
-    if (!nw || !head.w) return CR_ERR_STATE;
+    CR_TRY(prefill_layers(c, *lw, kv, b, st));
     // only each page's last row feeds the LM head (the reference computes all S rows and reads the last, :1081 + _sample)
     for (int i = 0; i < n; i++)
-        CR_TRY(rms(b.x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, b.head.hl + (size_t)i * D, nw, 1, c->d.rms_eps, st));
-    CR_TRY(linear(c, EPI_F32, b.head.hl, head, LIN_LOADED, b.head.lg, n, st));
+        CR_TRY(rms(b.x + (size_t)(segs[i].row0 + segs[i].S - 1) * D, b.head.hl + (size_t)i * D, lw->norm, 1, c->d.rms_eps, st));
+    CR_TRY(linear(c, EPI_F32, b.head.hl, lw->head, LIN_LOADED, b.head.lg, n, st));
     CR_TRY(pick_rows(kv, b.head, c->d_seqs, penalty, 0, last_logits, st, true));
     hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, b.rows.seg, n, kv->d_len);
     if (beams) {    // the fan-out: the prompt's cache rows, the first id and the length go from a group's first sequence to its others
@@ -995,6 +656,8 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     if (!c || !kv || !seqs || n <= 0 || n > kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_decode: bad argument");
     if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_llm_decode: call cr_finalize first");
     CR_TRY(ctx_share_ok(c, "cr_llm_decode"));
+    const LlmWeights* lw;
+    CR_TRY(llm_weights(c, &lw));
     for (int i = 0; i < n; i++) {
         const int s = seqs[i];
         if (s < 0 || s >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_decode: sequence %d out of range", s);
@@ -1024,15 +687,13 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     int max_len = 0;
     for (int i = 0; i < n; i++) max_len = kv->seq[seqs[i]].len > max_len ? kv->seq[seqs[i]].len : max_len;
     const int nsplit = ((max_len + 1 + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
-    DecodeBufs b(c, kv, n, nsplit, kv_scan_rows(kv, seqs, n, penalty));
+    DecodeBufs b(c, lw->ff, kv, n, nsplit, kv_scan_rows(kv, seqs, n, penalty));
     CR_TRY(ws_carve(c, "cr_llm_decode", b));
-    CR_TRY(stage_seqs(c, seqs, n, st, false));
+    CR_TRY(ctx_stage_seqs(c, seqs, n, st, false));
     const int32_t* d_seqs = c->d_seqs;
-    const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
-    if (!table) return CR_ERR_STATE;
-    hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(n), dim3(256), 0, st, table, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.x, nullptr);
-    CR_TRY(decode_layers(c, kv, b, d_seqs, st));
-    CR_TRY(decode_head(c, b, st));
+    hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(n), dim3(256), 0, st, lw->embed, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.x, nullptr);
+    CR_TRY(decode_layers(c, *lw, kv, b, d_seqs, st));
+    CR_TRY(decode_head(c, *lw, b, st));
     CR_TRY(pick_rows(kv, b.head, d_seqs, penalty, 1, logits, st, false));
     if (beam_span > 0)
         CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, d_seqs, penalty, 1, 0), beam_cache(kv), beam_firsts.data(), (int)beam_firsts.size(), beam_span, 1, st));
@@ -1050,6 +711,8 @@ int cr_llm_decode_draft(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const 
     if (!c || !kv || !seqs || !draft_lens_host || !appended_host || n <= 0 || n > kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_llm_decode_draft: bad argument");
     if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: call cr_finalize first");
     CR_TRY(ctx_share_ok(c, "cr_llm_decode_draft"));
+    const LlmWeights* lw;
+    CR_TRY(llm_weights(c, &lw));
     const int V = c->d.vocab;
     int M = 0, max_keys = 0;
     bool deep = false;
@@ -1090,7 +753,7 @@ int cr_llm_decode_draft(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const 
     const int nsplit = ((max_keys + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
     RowFeatures feat{};
     feat.deep = deep;                       // histories of more than 4096 ids under a penalty: the pick reads an untouched copy of the rows, as pick_rows does
-    DraftBufs b(c, kv, M, n, nsplit, feat);
+    DraftBufs b(c, lw->ff, kv, M, n, nsplit, feat);
     CR_TRY(ws_carve(c, "cr_llm_decode_draft", b));
     // the rows: sequence i's window is rows row0[i] .. row0[i] + k_i, all naming its cache slot
     std::vector<int32_t> row_seq(M);
@@ -1103,21 +766,19 @@ int cr_llm_decode_draft(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const 
         for (int j = 0; j <= k; j++, r++) { row_seq[r] = seqs[i]; hx.off[r] = j; }
     }
     CR_HIP(hipMemcpyAsync(b.index, hix.data(), hix.size() * 8, hipMemcpyHostToDevice, st));      // pageable source: staged before return
-    CR_TRY(stage_seqs(c, row_seq.data(), M, st, false));
+    CR_TRY(ctx_stage_seqs(c, row_seq.data(), M, st, false));
     const int32_t* d_seqs = c->d_seqs;
-    const bf16* table = W(c, "language_model.model.tok_embeddings.weight");
-    if (!table) return CR_ERR_STATE;
     DraftLaunch dl{};
     dl.logits = b.dec.head.lg; dl.ld = V; dl.vocab = V; dl.penalty = penalty; dl.rows = M; dl.n = n; dl.seqs = d_seqs; dl.ix = draft_index(b.index, n, M);
     dl.windows = b.windows; dl.gen = kv->d_gen; dl.ngen = kv->d_ngen; dl.lens = kv->d_len; dl.gen_cap = kv->gen_cap; dl.stop = kv->d_stop; dl.n_seqs = kv->n_seqs;
     dl.orig = b.dec.head.lg0;
     CR_TRY(launch_draft_stage(dl, st));
     if (b.dec.off)
-        hipLaunchKernelGGL(embed_rows_kernel<true>, dim3(M), dim3(256), 0, st, table, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, b.dec.off);
+        hipLaunchKernelGGL(embed_rows_kernel<true>, dim3(M), dim3(256), 0, st, lw->embed, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, b.dec.off);
     else
-        hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(M), dim3(256), 0, st, table, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, nullptr);
-    CR_TRY(decode_layers(c, kv, b.dec, d_seqs, st));
-    CR_TRY(decode_head(c, b.dec, st));
+        hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(M), dim3(256), 0, st, lw->embed, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, nullptr);
+    CR_TRY(decode_layers(c, *lw, kv, b.dec, d_seqs, st));
+    CR_TRY(decode_head(c, *lw, b.dec, st));
     if (dl.orig) CR_HIP(hipMemcpyAsync(b.dec.head.lg0, b.dec.head.lg, (size_t)M * V * 4, hipMemcpyDeviceToDevice, st));
     CR_TRY(launch_draft_pick_accept(dl, st));
     CR_HIP(hipGetLastError());

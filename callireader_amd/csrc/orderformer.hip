@@ -8,7 +8,7 @@
 // output, the residual sums and the LayerNorm outputs are bf16; softmax and LayerNorm statistics are fp32.
 #include <string>
 
-#include "ctx.hpp"
+#include "weights.hpp"
 
 namespace {
 
@@ -118,13 +118,11 @@ extern "C" int cr_orderformer(cr_ctx* c, const void* boxes, int B, int L, float*
     const DevTensor* ew = WT(c, P + "embedding.weight");
     if (!ew || ew->numel() != (int64_t)OD * 4) return cr_fail(CR_ERR_STATE, "cr_orderformer: load the orderformer.* weights first (embedding.weight [256,4])");
     // the embedding weight padded to the GEMM's K granule, derived once
-    if (!WT(c, "derived.orderformer.emb")) {
-        DevTensor t;
-        t.dtype = CR_BF16; t.shape = {OD, OKPAD}; t.bytes = (size_t)OD * OKPAD * 2;
-        CR_HIP(hipMalloc(&t.ptr, t.bytes));
-        CR_HIP(hipMemsetAsync(t.ptr, 0, t.bytes, st));
-        CR_HIP(hipMemcpy2DAsync(t.ptr, OKPAD * 2, ew->ptr, 4 * 2, 4 * 2, OD, hipMemcpyDeviceToDevice, st));
-        c->w["derived.orderformer.emb"] = t;
+    if (!w_find(c, "derived.orderformer.emb")) {
+        DevTensor* t = w_put(c, "derived.orderformer.emb", CR_BF16, {OD, OKPAD}, (size_t)OD * OKPAD * 2);
+        if (!t) return cr_fail(CR_ERR_NOMEM, "derived.orderformer.emb");
+        CR_HIP(hipMemsetAsync(t->ptr, 0, t->bytes, st));
+        CR_HIP(hipMemcpy2DAsync(t->ptr, OKPAD * 2, ew->ptr, 4 * 2, 4 * 2, OD, hipMemcpyDeviceToDevice, st));
     }
     const int rows = B * L;
     CR_TRY(ws_ensure(c, (size_t)rows * (OKPAD + 3 * OD + 3 * OD + OFF) * 2 + 8192));

@@ -11,6 +11,7 @@
 #include "ctx.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
+#include "weights.hpp"
 
 static constexpr int VIT_CHUNK = 255;  // 255*1025 rows = 1021 row-tiles of 256: x4 column tiles = 15.95 rounds of 256 CUs; per-launch fixed costs (cold
                                        // start, tail) spread over 4x the work of round 1's 63-tile chunks: 1.3 % on 510 tiles; operands stay < 4 GiB
@@ -30,20 +31,11 @@ int vit_finalize(cr_ctx* c, hipStream_t st) {
     const DevTensor* pw = WT(c, "vision_model.embeddings.patch_embedding.weight");
     if (!pw) return CR_ERR_STATE;
     if (pw->numel() != (int64_t)C1 * 588) return cr_fail(CR_ERR_ARG, "patch_embedding.weight must be [1024,3,14,14]");
-    DevTensor t;
-    t.dtype = CR_BF16; t.shape = {C1, KPAD}; t.bytes = (size_t)C1 * KPAD * 2;
-    auto it = c->w.find("derived.patch_w");
-    if (it != c->w.end()) t.ptr = it->second.ptr;
-    else CR_HIP(hipMalloc(&t.ptr, t.bytes));
-    CR_HIP(hipMemsetAsync(t.ptr, 0, t.bytes, st));
-    CR_HIP(hipMemcpy2DAsync(t.ptr, KPAD * 2, pw->ptr, 588 * 2, 588 * 2, C1, hipMemcpyDeviceToDevice, st));
-    c->w["derived.patch_w"] = t;
+    DevTensor* t = w_put(c, "derived.patch_w", CR_BF16, {C1, KPAD}, (size_t)C1 * KPAD * 2);
+    if (!t) return cr_fail(CR_ERR_NOMEM, "derived.patch_w");
+    CR_HIP(hipMemsetAsync(t->ptr, 0, t->bytes, st));
+    CR_HIP(hipMemcpy2DAsync(t->ptr, KPAD * 2, pw->ptr, 588 * 2, 588 * 2, C1, hipMemcpyDeviceToDevice, st));
     return CR_OK;
-}
-
-static const DevTensor* WTopt(cr_ctx* c, const std::string& name) {
-    auto it = c->w.find(name);
-    return it == c->w.end() ? nullptr : &it->second;
 }
 
 static int gemm(cr_ctx* c, int epi, const bf16* A, int64_t lda, const bf16* Wt, int64_t ldw, void* C, int64_t ldc, const bf16* bias,
@@ -89,10 +81,10 @@ static int vit_chunk(cr_ctx* c, const bf16* px, int T, bf16* x, hipStream_t st) 
             return CR_ERR_STATE;
 
         // cr_enable_fp8_mfma: the two LayerNorms emit e4m3 rows + scales (into h) and QKV / fc1 multiply e4m3 x e4m3
-        const DevTensor *q_qkv = WTopt(c, "fp8." + p + "attn.qkv.weight"), *s_qkv = WTopt(c, "fp8s." + p + "attn.qkv.weight");
-        const DevTensor *q_f1 = WTopt(c, "fp8." + p + "mlp.fc1.weight"), *s_f1 = WTopt(c, "fp8s." + p + "mlp.fc1.weight");
-        const DevTensor *q_f2 = WTopt(c, "fp8." + p + "mlp.fc2.weight"), *s_f2 = WTopt(c, "fp8s." + p + "mlp.fc2.weight");
-        const DevTensor* bnd = WTopt(c, "fp8b." + p + "mlp.fc1.weight");
+        const DevTensor *q_qkv = w_copy(c, COPY_FP8, p + "attn.qkv.weight"), *s_qkv = w_copy(c, COPY_FP8_SCALE, p + "attn.qkv.weight");
+        const DevTensor *q_f1 = w_copy(c, COPY_FP8, p + "mlp.fc1.weight"), *s_f1 = w_copy(c, COPY_FP8_SCALE, p + "mlp.fc1.weight");
+        const DevTensor *q_f2 = w_copy(c, COPY_FP8, p + "mlp.fc2.weight"), *s_f2 = w_copy(c, COPY_FP8_SCALE, p + "mlp.fc2.weight");
+        const DevTensor* bnd = w_copy(c, COPY_FP8_BOUND, p + "mlp.fc1.weight");
         const bool m8 = c->fp8_mfma && q_qkv && s_qkv && q_f1 && s_f1;
         const bool m8all = m8 && c->fp8_mfma >= 2 && q_f2 && s_f2 && bnd;      // level 2: fc1 hands fc2 e4m3 rows straight from its epilogue
 
@@ -101,7 +93,7 @@ static int vit_chunk(cr_ctx* c, const bf16* px, int T, bf16* x, hipStream_t st) 
         np.gamma = n1w; np.beta = n1b;
         if (m8) { np.out8 = (unsigned char*)h; np.out8_scale = hs; }
         CR_TRY(launch_layernorm(np, C1, 0, st));
-        if (m8) CR_TRY(ctx_gemm_f8(c, EPI_STORE, h, hs, q_qkv, s_qkv, qkv, C3, qkvb, M, C3, C1, st));
+        if (m8) CR_TRY(ctx_gemm_f8(c, EPI_STORE, h, hs, q_qkv->ptr, (const float*)s_qkv->ptr, qkv, C3, qkvb, M, C3, C1, st));
         else CR_TRY(gemm(c, EPI_STORE, h, C1, qkvw, C1, qkv, C3, qkvb, nullptr, nullptr, 0, M, C3, C1, 0, st));
 
         AttnParams ap{};
@@ -119,7 +111,7 @@ static int vit_chunk(cr_ctx* c, const bf16* px, int T, bf16* x, hipStream_t st) 
         CR_TRY(launch_layernorm(np, C1, 0, st));
         if (m8 && !m8all) {
             // level 1: fc1 (its input is LayerNorm 2's e4m3 row) multiplies e4m3 x e4m3 and writes bf16; fc2 stays bf16
-            CR_TRY(ctx_gemm_f8(c, EPI_GELU, h, hs, q_f1, s_f1, f, FF, f1b, M, FF, C1, st));
+            CR_TRY(ctx_gemm_f8(c, EPI_GELU, h, hs, q_f1->ptr, (const float*)s_f1->ptr, f, FF, f1b, M, FF, C1, st));
             CR_TRY(gemm(c, EPI_LS_RES, f, FF, f2w, FF, x, C1, f2b, ls2, x, C1, M, C1, FF, 0, st));
         } else if (m8all) {
             // fc1 in e4m3, its GELU output written as e4m3 rows (scale = the bound LayerNorm 2 derived), fc2 in e4m3 on those rows
@@ -155,14 +147,14 @@ static int project_chunk(cr_ctx* c, const bf16* vit_out, int T, bf16* out, hipSt
     const bf16 *w1 = W(c, "mlp1.1.weight"), *b1 = W(c, "mlp1.1.bias");
     const bf16 *w3 = W(c, "mlp1.3.weight"), *b3 = W(c, "mlp1.3.bias");
     if (!lw || !lb || !w1 || !b1 || !w3 || !b3) return CR_ERR_STATE;
-    const DevTensor *q_w1 = WTopt(c, "fp8.mlp1.1.weight"), *s_w1 = WTopt(c, "fp8s.mlp1.1.weight");
+    const DevTensor *q_w1 = w_copy(c, COPY_FP8, "mlp1.1.weight"), *s_w1 = w_copy(c, COPY_FP8_SCALE, "mlp1.1.weight");
     const bool m8 = c->fp8_mfma && q_w1 && s_w1;
     float* as = ar.take<float>((size_t)M);
     NormParams np{};
     np.in = vit_out; np.out = a; np.ld_out = 4096; np.rows = M; np.eps = 1e-5f; np.gamma = lw; np.beta = lb;
     if (m8) { np.out8 = (unsigned char*)a; np.out8_scale = as; }
     CR_TRY(launch_layernorm(np, 4096, 1, st));     // drop CLS + pixel_shuffle folded into the load
-    if (m8) CR_TRY(ctx_gemm_f8(c, EPI_GELU, a, as, q_w1, s_w1, b, 4096, b1, M, 4096, 4096, st));
+    if (m8) CR_TRY(ctx_gemm_f8(c, EPI_GELU, a, as, q_w1->ptr, (const float*)s_w1->ptr, b, 4096, b1, M, 4096, 4096, st));
     else CR_TRY(gemm(c, EPI_GELU, a, 4096, w1, 4096, b, 4096, b1, nullptr, nullptr, 0, M, 4096, 4096, 0, st));
     CR_TRY(gemm(c, EPI_STORE, b, 4096, w3, 4096, out, 4096, b3, nullptr, nullptr, 0, M, 4096, 4096, 0, st));
     return CR_OK;

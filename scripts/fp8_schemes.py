@@ -53,7 +53,7 @@ def q_int8(x):
 
 
 def fq_row(x, q, qmax):
-    """one fp32 scale per row: max|x| / qmax (1 for an all-zero row) -- llm.hip: quant_fp8_rows_kernel, norm.hip's e4m3 rows"""
+    """one fp32 scale per row: max|x| / qmax (1 for an all-zero row) -- weights.hip: quant_fp8_rows_kernel, norm.hip's e4m3 rows"""
     mx = x.abs().amax(-1, keepdim=True)
     sc = torch.where(mx > 0, mx / qmax, torch.ones_like(mx))
     return q(x / sc) * sc

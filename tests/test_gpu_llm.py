@@ -245,6 +245,71 @@ def test_reloading_w1_and_w3_with_the_fp8_options_on_rebuilds_their_e4m3_copies(
     a.close(); b.close()
 
 
+def test_reloading_a_weight_by_its_own_name_with_the_fp8_options_on_drops_its_e4m3_copies(setup):
+    """The companion of the w1|w3 test above, for copies named after the reloaded tensor itself: with fp8 prefill (level 2) + fp8 decode on, one wo and the LM
+    head are reloaded.  Their e4m3 copies (bytes, scales, decode layout) go with the load, so the options are OFF after cr_finalize -- the logits are a fresh bf16
+    context's, bit for bit -- and re-enabled they are a fresh context's with both options on."""
+    from callireader_amd.engine import Engine
+    dims, sd = setup['dims'], dict(setup['sd'])
+
+    def run(e):
+        emb = prompt(300, 79).cuda()                                  # >= 256 rows: the prefill takes the e4m3 matrix-core linears
+        kv = e.kv_alloc(1, 512)
+        first = e.prefill(kv, 0, emb, want_logits=True).clone()
+        steps = [e.decode(kv, [0], want_logits=True).clone() for _ in range(3)]
+        torch.cuda.synchronize()
+        kv.free()
+        return [first] + steps
+    a = Engine(dims, max_pos=2048)
+    a.load_state_dict(sd); a.load_rope(); a.finalize()
+    a.enable_fp8_mfma(True, level=2); a.enable_fp8_decode(True)
+    before = run(a)
+    g = torch.Generator().manual_seed(11)
+    changed = {}
+    for k in ('language_model.model.layers.0.attention.wo.weight', 'language_model.output.weight'):
+        changed[k] = (sd[k].float() + 0.02 * torch.randn(sd[k].shape, generator=g)).to(torch.bfloat16)
+        a.load_weight(k, changed[k])
+    a.finalize()
+    bf16_after = run(a)                                               # the options went off with the copies they read
+    a.enable_fp8_mfma(True, level=2); a.enable_fp8_decode(True)
+    after = run(a)
+    sd.update(changed)
+    b = Engine(dims, max_pos=2048)
+    b.load_state_dict(sd); b.load_rope(); b.finalize()
+    plain = run(b)
+    b.enable_fp8_mfma(True, level=2); b.enable_fp8_decode(True)
+    fresh = run(b)
+    for x, y in zip(bf16_after, plain):
+        assert torch.equal(x, y)
+    for x, y in zip(after, fresh):
+        assert torch.equal(x, y)
+    for x, y in zip(after, before):
+        assert not torch.equal(x, y)
+    a.close(); b.close()
+
+
+def test_a_context_without_a_language_model_refuses_the_llm_stage(setup):
+    """A finalized context that holds only the RoPE tables has no language model to run: prefill and decode return an error (CR_ERR_STATE, the message names the
+    first missing tensor) instead of reading weights that are not there, and the process goes on -- a loaded engine still decodes afterwards."""
+    from callireader_amd.engine import Engine
+    from callireader_amd._binding import CalliReaderError
+    e = Engine(setup['dims'], max_pos=2048)
+    e.load_rope(); e.finalize()
+    kv = e.kv_alloc(1, 64)
+    with pytest.raises(CalliReaderError):
+        e.prefill(kv, 0, prompt(4, 80).cuda())
+    with pytest.raises(CalliReaderError):
+        e.decode(kv, [0], force_tokens=torch.tensor([5]))
+    kv.free(); e.close()
+    eng = setup['eng']
+    kv = eng.kv_alloc(1, 64)
+    eng.prefill(kv, 0, prompt(4, 80).cuda())
+    lg = eng.decode(kv, [0], want_logits=True)
+    torch.cuda.synchronize()
+    assert torch.isfinite(lg).all() and len(kv.generated(0)) == 2
+    kv.free()
+
+
 @pytest.mark.parametrize('rows', [1, 2, 3, 4, 5, 7, 8, 9])
 def test_fused_small_batch_decode_gives_the_separate_kernels_bits(setup, rows):
     """Batches of <= 8 rows decode through gemm_decode.hip (RMSNorm prologues, RoPE + cache-write epilogue, residual-add epilogues: six
