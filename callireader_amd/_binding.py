@@ -78,6 +78,7 @@ SIGNATURES = {
     'cr_kv_beam_reorder': (i32, [vp, i32, i32, C.POINTER(C.c_int32), i32, vp]),
     'cr_llm_prefill': (i32, [vp, vp, i32, vp, i32, f32, vp, vp]),
     'cr_llm_prefill_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), f32, vp, vp]),
+    'cr_llm_score_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), C.POINTER(i64), f32, i32, vp, vp, vp, vp, vp]),
     'cr_llm_hidden_probe': (i32, [vp, vp, i32, i32]),
     'cr_llm_decode': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, f32, vp, vp]),
     'cr_llm_decode_draft': (i32, [vp, vp, C.POINTER(C.c_int32), i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, f32, C.POINTER(C.c_int32), vp]),
@@ -101,6 +102,7 @@ SIGNATURES = {
     'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'cr_op_constrain': (i32, [C.POINTER(Constraints), vp, i32, i32, vp, vp, i32, vp, vp]),
     'cr_op_logprobs': (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
+    'cr_op_score_rows': (i32, [vp, i32, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), f32, i32, vp, vp, vp, vp]),
     'cr_op_beam_step': (i32, [vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp]),
     'cr_op_decode_attention': (i32, [i32, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
     'cr_op_decode_attention_e4m3': (i32, [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),

@@ -8,9 +8,11 @@
 //            -> GEMM wo (+x in place) -> RMSNorm -> GEMM w1|w3 with SwiGLU epilogue -> GEMM w2 (+x in place).
 // Decode (<= 64 rows): wqkv / wo / w2 leave fp32 K-slices that RoPE-split and a fused residual-add + RMSNorm sum up.
 //
-// This file holds the model: the kernels, the two layer loops and the entry points cr_llm_prefill_batch / cr_llm_decode / cr_llm_decode_draft.  The weights come
+// This file holds the model: the kernels, the two layer loops and the entry points cr_llm_prefill_batch / cr_llm_score_batch / cr_llm_decode / cr_llm_decode_draft.  The weights come
 // resolved (weights.hpp: LlmWeights; weight preparation and every tensor name are in weights.hip).  The cache object (struct cr_kv, every cr_kv_* entry point) is
 // kv.hpp / kv.hip; what follows the LM head (the picks, scores, constraints, the beam step) is pick.hip.
+#include <float.h>
+
 #include <algorithm>
 #include <vector>
 
@@ -18,7 +20,9 @@
 #include "decode.hpp"
 #include "draft.hpp"
 #include "kv.hpp"
+#include "logprobs.hpp"
 #include "norm.hpp"
+#include "score.hpp"
 #include "weights.hpp"
 
 namespace {
@@ -369,6 +373,60 @@ int prefill_layers(cr_ctx* c, const LlmWeights& lw, cr_kv* kv, const PrefillBufs
     return CR_OK;
 }
 
+// The index arrays of a batched prefill, built on the host and copied into b.rows
+int stage_prefill_rows(const PrefillBufs& b, const std::vector<Segment>& segs, hipStream_t st) {
+    const int M = b.M, n = b.n_pages;
+    const bool kv8 = b.kv8;
+    std::vector<int32_t> h(prefill_rows_ints(M, n, kv8));
+    const PrefillRows hr = prefill_rows(h.data(), M, n);
+    for (int i = 0; i < n; i++) {
+        const Segment& sg = segs[i];
+        int32_t *e = hr.seg + 4 * i, *f = hr.seg_last + 4 * i;
+        e[0] = sg.row0; e[1] = sg.S; e[2] = sg.pos0; e[3] = sg.seq;
+        // the attention kernel's query blocks are 128 rows of a segment, its waves 32: rows [32 k, 32 k + 32) of a page meet in one wave
+        const int w0 = (sg.S - 1) / 32 * 32;
+        f[0] = sg.row0 + w0; f[1] = sg.S - w0; f[2] = sg.pos0 + w0; f[3] = sg.seq;
+        hr.last[i] = sg.row0 + sg.S - 1;
+        for (int r = 0; r < sg.S; r++) { hr.row_seq[sg.row0 + r] = sg.seq; hr.row_pos[sg.row0 + r] = sg.pos0 + r; }
+        if (kv8) {
+            for (int k = 0; k < 3; k++) { hr.seg8[4 * i + k] = e[k]; hr.seg_last8[4 * i + k] = f[k]; }
+            hr.seg8[4 * i + 3] = hr.seg_last8[4 * i + 3] = i;
+            for (int r = 0; r < sg.S; r++) hr.row_page[sg.row0 + r] = i;
+        }
+    }
+    CR_HIP(hipMemcpyAsync(b.rows.row_seq, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
+    return CR_OK;
+}
+
+// What cr_llm_score_batch takes from the workspace: a batched prefill whose final layer runs on every row, then the R scored rows' head in tiles
+struct ScoreBufs {
+    PrefillBufs pre;
+    int R, tile, V;
+    bool pen;           // penalty != 1: one first-occurrence table per sequence of the call (score.hpp)
+    bf16 *xs, *hl;      // the scored rows of the residual stream, gathered; one tile of them normalised
+    float* lg;          // one tile of logits [tile][V]
+    void* scratch;      // the score kernels' partials for one tile
+    int32_t* gather;    // per scored row: its row in the prefill
+    int64_t* index;     // score.hpp's index block
+    int32_t* first;
+
+    ScoreBufs(cr_ctx* c, int ff, const cr_kv* kv, int M, int n_pages, int max_S, int R, bool pen)
+        : pre(c, ff, kv, M, n_pages, max_S, RowFeatures{}), R(R), tile(std::min(R, SCORE_HEAD_ROWS)), V(c->d.vocab), pen(pen) {
+        pre.last_rows = false;      // any row may be scored
+        pre.head.n = 0;             // no pick: the head below is the call's own
+    }
+
+    void carve(Arena& ar) {
+        pre.carve(ar);
+        xs = ar.take<bf16>((size_t)R * D); hl = ar.take<bf16>((size_t)tile * D);
+        lg = ar.take<float>((size_t)tile * V);
+        scratch = ar.take<char>(logprobs_scratch_bytes(tile, V));
+        gather = ar.take<int32_t>((size_t)R);
+        index = ar.take<int64_t>(score_index_words(R));
+        first = pen ? ar.take<int32_t>((size_t)pre.n_pages * V) : nullptr;
+    }
+};
+
 // What a decode step (M rows, one per sequence; the longest sequence's keys in nsplit attention splits) takes from the workspace
 struct DecodeBufs {
     int M, nsplit, ff;
@@ -589,31 +647,11 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     const bool beams = feat.beam_rows > 0;
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    const bool kv8 = kv->fmt == CR_KV_E4M3;
     int max_S = 0;
     for (const Segment& sg : segs) max_S = sg.S > max_S ? sg.S : max_S;
     PrefillBufs b(c, lw->ff, kv, M, n, max_S, feat);
     CR_TRY(ws_carve(c, "cr_llm_prefill_batch", b));
-    {
-        std::vector<int32_t> h(prefill_rows_ints(M, n, kv8));
-        const PrefillRows hr = prefill_rows(h.data(), M, n);
-        for (int i = 0; i < n; i++) {
-            const Segment& sg = segs[i];
-            int32_t *e = hr.seg + 4 * i, *f = hr.seg_last + 4 * i;
-            e[0] = sg.row0; e[1] = sg.S; e[2] = sg.pos0; e[3] = sg.seq;
-            // the attention kernel's query blocks are 128 rows of a segment, its waves 32: rows [32 k, 32 k + 32) of a page meet in one wave
-            const int w0 = (sg.S - 1) / 32 * 32;
-            f[0] = sg.row0 + w0; f[1] = sg.S - w0; f[2] = sg.pos0 + w0; f[3] = sg.seq;
-            hr.last[i] = sg.row0 + sg.S - 1;
-            for (int r = 0; r < sg.S; r++) { hr.row_seq[sg.row0 + r] = sg.seq; hr.row_pos[sg.row0 + r] = sg.pos0 + r; }
-            if (kv8) {
-                for (int k = 0; k < 3; k++) { hr.seg8[4 * i + k] = e[k]; hr.seg_last8[4 * i + k] = f[k]; }
-                hr.seg8[4 * i + 3] = hr.seg_last8[4 * i + 3] = i;
-                for (int r = 0; r < sg.S; r++) hr.row_page[sg.row0 + r] = i;
-            }
-        }
-        CR_HIP(hipMemcpyAsync(b.rows.row_seq, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));   // pageable source: staged before return
-    }
+    CR_TRY(stage_prefill_rows(b, segs, st));
     CR_TRY(ctx_stage_seqs(c, seqs, n, st, true));
     CR_HIP(hipMemcpyAsync(b.x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
     CR_TRY(prefill_layers(c, *lw, kv, b, st));
@@ -649,6 +687,82 @@ int cr_llm_prefill(cr_ctx* c, cr_kv* kv, int seq, const void* embeds, int S, flo
     if (!kv || S <= 0) return cr_fail(CR_ERR_ARG, "cr_llm_prefill: bad argument");
     const int32_t s = seq, l = S;
     return cr_llm_prefill_batch(c, kv, &s, 1, embeds, &l, penalty, last_logits, stream);
+}
+
+int cr_llm_score_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host, float penalty,
+                       int top_n, float* lp, int32_t* top_ids, float* top_lp, float* logits, void* stream) {
+    if (top_n < 0 || top_n > LOGPROBS_MAX_TOP) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: top_n %d (want 0..%d)", top_n, LOGPROBS_MAX_TOP);
+    if (!c || !kv || !seqs || !lens || !embeds || !targets_host || !lp || (top_n > 0 && (!top_ids || !top_lp)) || n <= 0 || n > kv->n_seqs)
+        return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: bad argument");
+    if (!(penalty > 0.f) || penalty > FLT_MAX) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: penalty %g (want a finite value > 0)", penalty);
+    if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_llm_score_batch: call cr_finalize first");
+    CR_TRY(ctx_share_ok(c, "cr_llm_score_batch"));
+    const LlmWeights* lw;
+    CR_TRY(llm_weights(c, &lw));
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: an e4m3 cache (left out: a continued prefill needs the bf16 prefix)");
+    const int V = c->d.vocab;
+    std::vector<Segment> segs;
+    int M = 0, max_S = 0;
+    for (int i = 0; i < n; i++) {
+        const int s = seqs[i];
+        if (s < 0 || s >= kv->n_seqs || lens[i] <= 0) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: bad sequence %d / length %d", s, lens[i]);
+        for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: sequence %d listed twice", s);
+        if (kv->seq[s].len + lens[i] > kv->max_tokens)
+            return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: %d + %d tokens exceed the cache (%d)", kv->seq[s].len, lens[i], kv->max_tokens);
+        if (kv->seq[s].bgrp >= 0) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: sequence %d belongs to the beam group of sequence %d", s, kv->seq[s].bgrp);
+        segs.push_back({s, M, lens[i], kv->seq[s].len});
+        M += lens[i];
+        max_S = std::max(max_S, lens[i]);
+    }
+    // the scored rows, in row order: slot r of lp / top_* / logits; history = the call's sequence ordinal, ordinal = the row's place among that sequence's scored rows
+    std::vector<int32_t> gather;
+    std::vector<int64_t> tgt;
+    std::vector<int32_t> hist, ord;
+    for (int i = 0; i < n; i++) {
+        int j = 0;
+        for (int r = 0; r < segs[i].S; r++) {
+            const int64_t y = targets_host[segs[i].row0 + r];
+            if (y < 0) continue;
+            if (y >= V) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: target %lld of sequence %d outside the vocabulary (%d)", (long long)y, segs[i].seq, V);
+            gather.push_back(segs[i].row0 + r); tgt.push_back(y); hist.push_back(i); ord.push_back(j++);
+        }
+    }
+    const int R = (int)gather.size();
+    if (R == 0) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: no scored row (every target < 0)");
+    for (int i = 0; i < n; i++)
+        if (kv->seq[seqs[i]].ngen != 0)
+            return cr_fail(CR_ERR_STATE, "cr_llm_score_batch: sequence %d holds %d generated ids (the penalty history is the call's own: cr_kv_truncate / cr_kv_fork / "
+                           "cr_kv_reset give a sequence without ids)", seqs[i], kv->seq[seqs[i]].ngen);
+    CR_HIP(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool pen = penalty != 1.0f;
+    ScoreBufs b(c, lw->ff, kv, M, n, max_S, R, pen);
+    CR_TRY(ws_carve(c, "cr_llm_score_batch", b));
+    CR_TRY(stage_prefill_rows(b.pre, segs, st));
+    {
+        std::vector<int64_t> h(score_index_words(R));
+        const ScoreIndex hx = score_index(h.data(), R);
+        for (int r = 0; r < R; r++) { hx.tgt[r] = tgt[r]; hx.hist[r] = hist[r]; hx.ord[r] = ord[r]; }
+        CR_HIP(hipMemcpyAsync(b.index, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));      // pageable sources: staged before return
+        CR_HIP(hipMemcpyAsync(b.gather, gather.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
+    }
+    const ScoreIndex ix = score_index(b.index, R);
+    CR_HIP(hipMemcpyAsync(b.pre.x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
+    CR_TRY(prefill_layers(c, *lw, kv, b.pre, st));
+    hipLaunchKernelGGL(move_rows_kernel<true>, dim3(R), dim3(256), 0, st, b.pre.x, b.gather, b.xs);
+    if (pen) CR_TRY(launch_score_table(ix, R, n, V, b.first, st));
+    // the head in tiles: LIN_PREFILL keeps a row's logits independent of the tile's size and of the row's place in it
+    for (int r0 = 0; r0 < R; r0 += b.tile) {
+        const int rows = std::min(b.tile, R - r0);
+        CR_TRY(rms(b.xs + (size_t)r0 * D, b.hl, lw->norm, rows, c->d.rms_eps, st));
+        CR_TRY(linear(c, EPI_F32, b.hl, lw->head, LIN_PREFILL, b.lg, rows, st));
+        if (logits) CR_HIP(hipMemcpyAsync(logits + (size_t)r0 * V, b.lg, (size_t)rows * V * 4, hipMemcpyDeviceToDevice, st));
+        CR_TRY(launch_score_rows(ScoreLaunch{b.lg, V, V, rows, r0, ix, b.first, penalty, top_n, b.scratch, lp, top_ids, top_lp}, st));
+    }
+    hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, b.pre.rows.seg, n, kv->d_len);
+    CR_HIP(hipGetLastError());
+    for (const Segment& sg : segs) kv->seq[sg.seq].len += sg.S;      // no pick: no id is appended
+    return CR_OK;
 }
 
 int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_t* force_tokens, float penalty, float* logits,

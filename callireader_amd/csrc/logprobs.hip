@@ -21,102 +21,26 @@
 // Precision: exp is the accurate expf (<= 1 ulp), the terms are accumulated in double from the first add on, the merge and the logarithm run in double,
 // and the results are rounded to fp32 once.  What remains: that rounding (half an ulp of a value below 128: 3.8e-6), the fp32 rounding of z - m
 // (weighted by the term's share of the sum: below 5e-7 for |z| <= 32) and expf's ulp (1.2e-7 relative): under 5e-6 absolute in all.
-#include <float.h>
-
 #include "ctx.hpp"
-#include "logprobs.hpp"
+#include "logprobs_dev.hpp"
 
 namespace {
 
-constexpr int CHUNK = 4096, THREADS = 256, PER = CHUNK / THREADS, TOPN = LOGPROBS_MAX_TOP;
-static_assert(PER == 16 && TOPN == 8, "logprobs.hip: 16 scores per lane, 8 alternatives");
+using namespace lpdev;
 
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-
-// (value, id) order of the alternatives: larger value first, the lower id on an exact tie.  NaN compares false either way.
-__device__ __forceinline__ bool before(float v, int i, float v2, int i2) { return v > v2 || (v == v2 && i < i2); }
-
-__device__ __forceinline__ void wave_best(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(v, o, 64);
-        const int i2 = __shfl_xor(i, o, 64);
-        if (before(v2, i2, v, i)) { v = v2; i = i2; }
-    }
-}
-
-// Partials of one (row, chunk): pm = chunk maximum, ps = sum of exp(z - pm) over the chunk's entries above -inf (0 for a chunk of -inf), pv / pi = its top-8 in order
-// (missing entries: -inf with id INT_MAX, which sort last).  seqs NULL: every row is scored (cr_op_logprobs); else rows whose sequence has scores off exit.
+// Partials of one (row, chunk), logprobs_dev.hpp reduce_chunk.  seqs NULL: every row is scored (cr_op_logprobs); else rows whose sequence has scores off exit.
 __global__ __launch_bounds__(THREADS) void logprobs_chunk_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int chunks,
                                                                  const int32_t* __restrict__ seqs, const int32_t* __restrict__ lpn,
                                                                  float* __restrict__ pm, double* __restrict__ ps, float* __restrict__ pv,
                                                                  int32_t* __restrict__ pi) {
-    __shared__ float sm[4];
-    __shared__ double ss[4];
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    const int chunk = blockIdx.x, row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int chunk = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
     if (seqs && lpn[seqs[row]] <= 0) return;
-    const float* lg = logits + (int64_t)row * ld;
-    const int base = chunk * CHUNK;
     float z[PER];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int i0 = base + (k * THREADS + tid) * 4;
-        if (i0 + 3 < vocab) {
-            const f32x4u q = *(const f32x4u*)(lg + i0);
-            z[4 * k] = q.x; z[4 * k + 1] = q.y; z[4 * k + 2] = q.z; z[4 * k + 3] = q.w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) z[4 * k + e] = i0 + e < vocab ? lg[i0 + e] : -INFINITY;
-        }
-    }
-    // chunk maximum (a NaN score is skipped here and poisons the sum below)
-    float m = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < PER; j++) m = z[j] > m ? z[j] : m;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float m2 = __shfl_xor(m, o, 64); m = m2 > m ? m2 : m; }
-    if (lane == 0) sm[w] = m;
-    __syncthreads();
-    m = sm[0];
-#pragma unroll
-    for (int k = 1; k < 4; k++) m = sm[k] > m ? sm[k] : m;
-    // sum of exp(z - m): lane order, then the xor tree, then the four waves in order
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < PER; j++)
-        if (z[j] != -INFINITY) s += (double)expf(z[j] - m);    // (ids past the row's end were loaded as -inf)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) ss[w] = s;
-    // the chunk's top-8: round r finds the best (value, id) that comes strictly after round r - 1's winner
-    float pvv = INFINITY; int pii = -1;
-    const int64_t po = ((int64_t)row * chunks + chunk) * TOPN;
-    for (int r = 0; r < TOPN; r++) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            const int i = base + ((j >> 2) * THREADS + tid) * 4 + (j & 3);
-            if (i < vocab && before(pvv, pii, z[j], i) && before(z[j], i, bv, bi)) { bv = z[j]; bi = i; }
-        }
-        wave_best(bv, bi);
-        __syncthreads();                                      // round r - 1's readers are done with sv / si
-        if (lane == 0) { sv[w] = bv; si[w] = bi; }
-        __syncthreads();
-        bv = sv[0]; bi = si[0];
-#pragma unroll
-        for (int k = 1; k < 4; k++) if (before(sv[k], si[k], bv, bi)) { bv = sv[k]; bi = si[k]; }
-        if (tid == 0) { pv[po + r] = bv; pi[po + r] = bi; }
-        pvv = bv; pii = bi;
-    }
-    if (tid == 0) {
-        pm[(int64_t)row * chunks + chunk] = m;
-        ps[(int64_t)row * chunks + chunk] = ss[0] + ss[1] + ss[2] + ss[3];
-    }
+    load_chunk<false>(logits + (int64_t)row * ld, vocab, chunk * CHUNK, tid, z);
+    reduce_chunk(z, vocab, chunk * CHUNK, (int64_t)row * chunks + chunk, tid, pm, ps, pv, pi);
 }
 
-// One wave per row: lse from the chunk pairs in chunk order, the row's top-n from the chunks' candidates, the picked id's score.
+// One wave per row: lse from the chunk pairs in chunk order, the row's top-n from the chunks' candidates, the picked id's score (logprobs_dev.hpp merge_row).
 // Cache rows (seqs given): the slot is t = ngen[seq] - 1, the id gen[seq][t]; a sequence whose history is full appended nothing, so nothing is scored
 // (done[seq] counts the slots written).  Op rows (seqs NULL): slot `row`, id ids[row], n = top_n.
 __global__ __launch_bounds__(64) void logprobs_merge_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int chunks,
@@ -140,37 +64,8 @@ __global__ __launch_bounds__(64) void logprobs_merge_kernel(const float* __restr
     } else {
         id = gen[row];
     }
-    const float* m_ = pm + (int64_t)row * chunks;
-    const double* s_ = ps + (int64_t)row * chunks;
-    float M = -INFINITY;
-    for (int c = 0; c < chunks; c++) M = m_[c] > M ? m_[c] : M;
-    double S = 0.0;
-    for (int c = 0; c < chunks; c++)
-        if (s_[c] != 0.0) S += s_[c] * exp((double)m_[c] - (double)M);                        // (a chunk of -inf holds (-inf, 0): skipped)
-    const double lse = (double)M + log(S);
-    // candidates: chunks * 8, lane l holds l, l + 64, ...
-    const int ncand = chunks * TOPN;
-    const float* cv = pv + (int64_t)row * ncand;
-    const int32_t* ci = pi + (int64_t)row * ncand;
-    float pvv = INFINITY; int pii = -1;
-    for (int r = 0; r < n; r++) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int j = lane; j < ncand; j += 64) {
-            const float v = cv[j]; const int i = ci[j];
-            if (before(pvv, pii, v, i) && before(v, i, bv, bi)) { bv = v; bi = i; }
-        }
-        wave_best(bv, bi);
-        if (lane == 0) {
-            out_id[slot * TOPN + r] = bi == 0x7fffffff ? -1 : bi;
-            out_tlp[slot * TOPN + r] = (float)((double)bv - lse);
-        }
-        pvv = bv; pii = bi;
-    }
-    if (lane == 0) {
-        for (int r = n; r < TOPN; r++) { out_id[slot * TOPN + r] = -1; out_tlp[slot * TOPN + r] = -INFINITY; }
-        const float zi = (id >= 0 && id < vocab) ? logits[(int64_t)row * ld + id] : NAN;
-        out_lp[slot] = (float)((double)zi - lse);
-    }
+    const float zi = (id >= 0 && id < vocab) ? logits[(int64_t)row * ld + id] : NAN;
+    merge_row(row, chunks, n, slot, zi, lane, pm, ps, pv, pi, out_lp, out_id, out_tlp);
 }
 
 __global__ __launch_bounds__(64) void set_logprobs_kernel(int32_t* __restrict__ lpn, int32_t* __restrict__ done, int seq, int top_n) {

@@ -4,6 +4,8 @@
 
 constexpr int LOGPROBS_MAX_TOP = 8;
 
+// chunks of 4096 scores a row of `vocab` is split into
+int logprobs_chunks(int vocab);
 // bytes of device scratch launch_logprobs needs for `rows` rows (the chunk partials)
 size_t logprobs_scratch_bytes(int rows, int vocab);
 // Scores of `rows` rows of logits [rows][ld] that a pick has just chosen from.  h.seqs given (device, one cache slot per row): rows whose lpn[seq] is 0 are

@@ -240,6 +240,43 @@ class Engine:
                                            float(penalty), _p(logits), _stream()), 'cr_llm_prefill_batch')
         return logits
 
+    def score_batch(self, kv, seqs, embeds_list, targets_list, penalty=1.0, top_n=0, want_logits=False):
+        """cr_llm_score_batch on the current stream: a continued prefill of embeds_list[i] into sequence seqs[i] that makes no pick and scores the rows
+        whose target is >= 0 -- targets_list[i][r] is the id that FOLLOWS row r (< 0: not scored); the repetition penalty of a row runs over the targets of
+        the sequence's scored rows before it.  Returns one scores.TokenScores per sequence (top_ids / top_logprobs [T, top_n]), or with want_logits
+        (scores, logits): logits [R, vocab] float32 on the device, the raw rows of all R scored rows in row order.  Synchronises the stream."""
+        from .scores import TokenScores
+        n = len(seqs)
+        top_n = int(top_n)
+        if not 0 <= top_n <= 8:
+            raise ValueError(f'top_n has to be 0..8, got {top_n}')
+        if len(embeds_list) != n or len(targets_list) != n:
+            raise ValueError(f'score_batch: {n} sequences, {len(embeds_list)} embeddings, {len(targets_list)} target lists')
+        es = [e.reshape(-1, self.dims.llm_hidden) for e in embeds_list]
+        lens = [e.shape[0] for e in es]
+        tg = [[int(t) for t in tl] for tl in targets_list]
+        for i in range(n):
+            if len(tg[i]) != lens[i]:
+                raise ValueError(f'score_batch: sequence {seqs[i]} has {lens[i]} rows but {len(tg[i])} targets')
+        flat = [t for tl in tg for t in tl]
+        counts = [sum(1 for t in tl if t >= 0) for tl in tg]
+        R = sum(counts)
+        cat = es[0].contiguous() if n == 1 else torch.cat(es, dim=0)
+        lp = torch.empty(max(R, 1), device=self.device, dtype=torch.float32)
+        ti = torch.empty(max(R, 1), 8, device=self.device, dtype=torch.int32) if top_n else None
+        tl = torch.empty(max(R, 1), 8, device=self.device, dtype=torch.float32) if top_n else None
+        logits = torch.empty(max(R, 1), self.dims.vocab, device=self.device, dtype=torch.float32) if want_logits else None
+        B.check(B.lib.cr_llm_score_batch(self._h, kv._h, (C.c_int32 * n)(*seqs), n, _p(cat), (C.c_int32 * n)(*lens), (C.c_int64 * len(flat))(*flat),
+                                         float(penalty), top_n, _p(lp), _p(ti), _p(tl), _p(logits), _stream()), 'cr_llm_score_batch')
+        lp_h = lp.cpu().numpy()
+        ti_h = ti.cpu().numpy()[:, :top_n] if top_n else np.empty((R, 0), dtype=np.int32)
+        tl_h = tl.cpu().numpy()[:, :top_n] if top_n else np.empty((R, 0), dtype=np.float32)
+        out, r = [], 0
+        for k in counts:
+            out.append(TokenScores(lp_h[r:r + k].copy(), ti_h[r:r + k].copy(), tl_h[r:r + k].copy()))
+            r += k
+        return (out, logits) if want_logits else out
+
     def hidden_probe(self, rows=None, row0=0):
         """cr_llm_hidden_probe: `rows` > 0 arms it and returns the [llm_layers + 1, rows, 4096] bf16 tensor the next prefill fills
         (residual stream before layer 0 and after each layer); rows=None disarms."""
@@ -694,6 +731,27 @@ def op_beam_step(logits, history, hist_len, group, state, fin_ids, penalty=1.0):
     assert history.shape[0] == n and fin_ids.shape == history.shape and state.shape == (n, BEAM_WORDS) and hist_len.numel() == n and group.numel() == n
     B.check(B.lib.cr_op_beam_step(_p(logits), n, V, _p(history), history.shape[1], _p(hist_len), float(penalty), _p(group), _p(state), _p(fin_ids), _stream()),
             'cr_op_beam_step')
+
+
+def op_score_rows(logits, targets, row_seq, hist_index, penalty=1.0, top_n=1):
+    """cr_op_score_rows: the score kernels of cr_llm_score_batch on given raw fp32 rows [n, vocab] (device, not modified).  targets[r] = the id scored in row
+    r, row_seq[r] = which history the row belongs to, hist_index[r] = its ordinal in it (host lists): row r is penalised at the targets of the rows of the same
+    history with a smaller ordinal.  Returns (lp [n] float32, top_ids [n, top_n] int32, top_lp [n, top_n] float32) on the device."""
+    top_n = int(top_n)
+    if not 0 <= top_n <= 8:
+        raise ValueError(f'top_n has to be 0..8, got {top_n}')
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+    n, V = logits.shape
+    tg, rs, hi = [int(t) for t in targets], [int(t) for t in row_seq], [int(t) for t in hist_index]
+    assert len(tg) == n and len(rs) == n and len(hi) == n
+    lp = torch.empty(n, dtype=torch.float32, device=logits.device)
+    ti = torch.empty(n, 8, dtype=torch.int32, device=logits.device) if top_n else None
+    tl = torch.empty(n, 8, dtype=torch.float32, device=logits.device) if top_n else None
+    B.check(B.lib.cr_op_score_rows(_p(logits), n, V, (C.c_int64 * n)(*tg), (C.c_int32 * n)(*rs), (C.c_int32 * n)(*hi), float(penalty), top_n, _p(lp), _p(ti),
+                                   _p(tl), _stream()), 'cr_op_score_rows')
+    if not top_n:
+        return lp, None, None
+    return lp, ti[:, :top_n].contiguous(), tl[:, :top_n].contiguous()
 
 
 def op_logprobs(logits, ids, top_n=1):

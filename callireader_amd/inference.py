@@ -83,6 +83,33 @@ def single_rec(model, tokenizer, detect_model, generation_config, image_path, pr
     return (response, out[2]) if scores else response
 
 
+def answer_scores_name(save_name):
+    """The file of --score_answer: `.answer_scores.json` in place of the results name's `json` ending."""
+    if not save_name.endswith('json'):
+        save_name += '_result.json'
+    return save_name[:-len('json')].rstrip('.') + '.answer_scores.json'
+
+
+def score_rec(model, tokenizer, detect_model, generation_config, image_path, prompt, answer, save_name, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
+              boxes=None, scores=0):
+    """--score_answer TEXT on a single image: what the model thinks of TEXT as its reply to `prompt` (model.score_ocr).  Prints `Scored: TEXT`, the
+    scores' summary line and `total logprob <t> over <k> tokens`, writes {imagePath, prompt, answer, scores: ResponseScores.to_json(total=True)} to
+    `save_name`, and returns the ResponseScores."""
+    bx = None
+    if use_p and (boxes is not None or detect_model is None):
+        bx = boxes_for(image_path, boxes)
+    gc = {k: v for k, v in generation_config.items() if k not in ('max_new_tokens',) and not (k == 'num_beams' and v == 1) and not (k == 'do_sample' and not v)}
+    sc = model.score_ocr(tokenizer, detect_model, image_path, prompt, answer, gc, repetition_penalty=repetition_penalty, top_logprobs=scores or 1, use_p=use_p,
+                         hard_vq=hard_vq, drop_zero=drop_zero, boxes=bx, verbose=verbose)
+    print(f'Scored: {answer}')
+    print(sc.summary_line())
+    print(f'total logprob {sc.total_logprob:.4f} over {len(sc.kept)} tokens')
+    os.makedirs(os.path.dirname(save_name) or '.', exist_ok=True)
+    with open(save_name, 'w', encoding='utf-8') as f:
+        json.dump({'imagePath': image_path, 'prompt': prompt, 'answer': answer, 'scores': sc.to_json(total=True)}, f, ensure_ascii=False, indent=4)
+    return sc
+
+
 DEFAULT_BATCH_PAGES = 64       # pages per decode batch in folder mode: the most rows the batched decode kernels take, and the batch the headline is measured on
 
 
@@ -275,6 +302,9 @@ def build_parser():
     parser.add_argument('--draft', action='store_true',
                         help="draft-verified decoding: the page's CalliAlign indices (vocabulary ids of its character boxes, in reading order) draft the answer and several "
                              'ids are checked per decode step; the same response in fewer steps where the draft is right (greedy only; needs --use_p; folder mode runs image after image)')
+    parser.add_argument('--score_answer', type=str, default=None, metavar='TEXT',
+                        help='single image: besides the recognition, score TEXT as the reply to --prompt (per-token log-probabilities of a text you bring: a ground '
+                             'truth, a candidate); prints its confidence line and total log-probability and writes results/<save_name minus json>.answer_scores.json')
     return parser
 
 
@@ -312,7 +342,13 @@ def main(argv=None):
         print('Single image recognition mode.')
         single_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, args.use_p, args.hard_vq, args.drop_zero,
                    args.repetition_penalty, args.verbose, args.boxes, scores=args.scores, draft='align' if args.draft else None)
+        if args.score_answer is not None:
+            score_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, args.score_answer,
+                      answer_scores_name(os.path.join('results', args.save_name)), args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose,
+                      args.boxes, scores=args.scores)
     elif os.path.isdir(args.tgt):
+        if args.score_answer is not None:
+            raise ValueError('--score_answer works on a single image')
         print('Multiple images recognition mode')
         os.makedirs('results', exist_ok=True)
         folder_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, os.path.join('results', args.save_name),

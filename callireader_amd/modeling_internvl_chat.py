@@ -27,6 +27,7 @@ from .conversation import get_conv_template
 from .engine import Engine
 from .constraints import parse as constraints_parse, per_page as constraints_per_page
 from . import draft as drafting
+from . import scoring
 from .generation import admit, check_fits, decode_rows, decode_rows_drafted, per_page_sampling, read_scores, reply_shape, reply_text
 from .pipeline import PagePipeline
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
@@ -1054,6 +1055,51 @@ class InternVLChatModel:
             return decode_rows_drafted(self.engine, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, drafts, stats=self.draft_stats)
         outs = decode_rows(self.engine, kv, seqs, max_new_tokens, eos_token_id, repetition_penalty, check_every)
         return (outs, read_scores(kv, lpn, outs)) if any(lpn) else outs
+
+    @torch.no_grad()
+    def score_pages(self, embeds_list, answer_ids_list, repetition_penalty=1.0, logprobs=0, eos_token_id=EOS_TOKEN_ID, score_eos=True):
+        """The batched twin of generate_pages for texts the caller brings: page i's prompt rows embeds_list[i] are followed by the embeddings of
+        answer_ids_list[i], and ONE prefill-shaped pass (cr_llm_score_batch) scores every answer id -- and eos_token_id behind it unless score_eos is False
+        or there is none -- by the definition of `logprobs=` in generate_pages: the log-softmax of the LM-head row after the repetition penalty over the
+        answer ids before it.  Returns (ids, scores): per page the scored ids and a scores.TokenScores with `logprobs` (0..8) alternatives per id.
+        A bf16 cache; nothing is generated."""
+        P = len(embeds_list)
+        if len(answer_ids_list) != P:
+            raise ValueError(f'score_pages: {len(answer_ids_list)} answers for {P} pages')
+        penalty, top_n = scoring.check_penalty(repetition_penalty), scoring.top_n_of(logprobs)
+        if self.kv_cache_dtype != 'bf16':
+            raise NotImplementedError("scoring continues a prefill in bf16: an e4m3 KV cache (kv_cache_dtype='e4m3') is not scored")
+        es = [e.reshape(-1, e.shape[-1]) for e in embeds_list]
+        plans = [scoring.plan(e.shape[0], a, eos_token_id, score_eos, self.dims.vocab) for e, a in zip(es, answer_ids_list)]
+        for e, pl in zip(es, plans):
+            scoring.check_fits(e.shape[0] + len(pl.feed), 0, self.max_tokens)
+        kv, seqs = self.kv(P), list(range(P))
+        for s in seqs:
+            kv.reset(s)
+        rows = [torch.cat([e, self.engine.embed_splice(torch.tensor(pl.feed, dtype=torch.long))], dim=0) if pl.feed else e for e, pl in zip(es, plans)]
+        ts = self.engine.score_batch(kv, seqs, rows, [pl.targets for pl in plans], penalty=penalty, top_n=top_n)
+        return [pl.ids for pl in plans], ts
+
+    @torch.no_grad()
+    def score_ocr(self, tokenizer, detect_model, img_path, question, answer, generation_config=None, repetition_penalty=1.5, top_logprobs=1, history=None,
+                  use_p=True, drop_zero=False, hard_vq=False, boxes=None, score_eos=True, draft=None, verbose=False):
+        """What the model thinks of `answer` (a string, or a list of ids) as the reply chat_ocr would give to `question` about the page: the visual stage and
+        the prompt are chat_ocr's, the answer's ids and the end-of-turn id behind them (score_eos) are scored in one pass.  Returns a scores.ResponseScores
+        as chat_ocr(return_scores=top_logprobs) does for a reply it generated -- for the ids chat_ocr generates the numbers agree to within the bf16 noise
+        of two kernel paths -- with total_logprob for ranking candidates.  generation_config may carry nothing that steers a generation (do_sample,
+        num_beams > 1, constraints) and there is no draft: ValueError."""
+        gc = scoring.refuse_generation(generation_config, draft, 'score_ocr')
+        top_n, penalty = scoring.top_n_of(top_logprobs), scoring.check_penalty(repetition_penalty)
+        page, pixel_values = self._open_page(img_path)
+        out_tokens = None
+        if use_p:
+            out_tokens, _ = self.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
+        _, _, _, model_inputs, gc = self._ocr_prompt(tokenizer, question, history, len(pixel_values), out_tokens, use_p, None, gc, False)
+        ids = model_inputs['input_ids'].reshape(-1)
+        prompt = self.engine.embed_splice(ids, self.extract_feature(pixel_values), out_tokens if use_p else None,
+                                          img_id=self.img_context_token_id, ref_id=self.aligned_token_id)
+        toks, ts = self.score_pages([prompt], [scoring.answer_to_ids(tokenizer, answer)], penalty, top_n, eos_token_id=gc['eos_token_id'], score_eos=score_eos)
+        return scoring.response_scores(tokenizer, toks[0], ts[0])
 
     def _generate_pages_beams(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams):
         """generate_pages with beam search: page i is the beam group of sequences beam_slots(i, B); the done flags are read every check_every steps,

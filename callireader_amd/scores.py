@@ -121,6 +121,7 @@ class ResponseScores:
     min_logprob: float
     min_index: int
     confidence: float
+    total_logprob: float = float('nan')     # sum over the kept tokens: log P(text) up to the special ids (scoring.py ranks candidates by it)
 
     @classmethod
     def build(cls, tokenizer, ids, ts):
@@ -138,15 +139,17 @@ class ResponseScores:
             lps = [tokens[t].logprob for t in kept]
             mean = float(sum(lps) / len(lps))
             k = min(range(len(lps)), key=lambda j: lps[j])
-            return cls(tokens, kept, mean, float(lps[k]), kept[k], math.exp(mean))
+            return cls(tokens, kept, mean, float(lps[k]), kept[k], math.exp(mean), float(sum(lps)))
         return cls(tokens, kept, float('nan'), float('nan'), -1, float('nan'))
 
     def pieces(self):
         """The pieces of the kept tokens, in order: tokenizer.convert_tokens_to_string of them is the response before stripping."""
         return [self.tokens[t].piece for t in self.kept]
 
-    def to_json(self):
-        """Plain lists and floats (inference.py --scores writes this per image)."""
+    def to_json(self, total=False):
+        """Plain lists and floats (inference.py --scores writes this per image).  total: also `total_logprob` (inference.py --score_answer)."""
+        if total:
+            return dict(self.to_json(), total_logprob=self.total_logprob)
         return {'tokens': [tk.piece for tk in self.tokens], 'ids': [tk.id for tk in self.tokens],
                 'logprobs': [tk.logprob for tk in self.tokens],
                 'alternatives': [[{'id': a, 'token': p, 'logprob': l} for a, p, l in tk.top] for tk in self.tokens],

@@ -30,6 +30,7 @@ import torch
 
 from .constraints import parse as constraints_parse
 from . import draft as drafting
+from . import scoring
 from .generation import check_fits, decode_rows, decode_rows_drafted, reply_text
 from .sampling import page_seeds, parse_beams
 
@@ -223,3 +224,33 @@ class PageSession:
         else:
             outs = decode_rows(m.engine, kv, branches, max_new, eos, repetition_penalty)
         return [reply_text(self.tokenizer, o, template.sep) for o in outs]
+
+    @torch.no_grad()
+    def score(self, question, answers, repetition_penalty=1.5, history=None, top_logprobs=1, score_eos=True, generation_config=None, draft=None):
+        """What the model thinks of each of `answers` (strings or id lists; at most max_branches) as the reply to `question` on this page: the prompt is
+        chat_ocr's, every candidate gets a branch forked off the trunk at the prefix the prompt shares with it (cr_kv_fork), and ONE cr_llm_score_batch
+        scores all candidates -- the prompt's tail, the answer's ids and the end-of-turn id (score_eos).  Returns one scores.ResponseScores per candidate,
+        as chat_ocr(return_scores=top_logprobs) reports a reply it generated, with total_logprob for ranking.  The trunk is not changed."""
+        gc = scoring.refuse_generation(generation_config, draft, 'PageSession.score')
+        top_n, penalty = scoring.top_n_of(top_logprobs), scoring.check_penalty(repetition_penalty)
+        answers = list(answers)
+        if not 1 <= len(answers) <= self.max_branches:
+            raise ValueError(f'score: {len(answers)} answers for a session opened with max_branches={self.max_branches}')
+        m, kv = self.m, self.kv
+        _, _, _, ids, gc = self._prompt(question, None if history is None else list(history), gc)
+        plans = [scoring.plan(len(ids), scoring.answer_to_ids(self.tokenizer, a), gc['eos_token_id'], score_eos, getattr(getattr(m, 'dims', None), 'vocab', None))
+                 for a in answers]
+        for pl in plans:
+            scoring.check_fits(len(ids) + len(pl.feed), 0, m.max_tokens)
+        p = plan_prefix(self.cached_ids, ids)
+        branches = list(range(1, 1 + len(plans)))
+        if p > 0:
+            kv.fork(0, branches, p)
+        else:
+            for b in branches:
+                kv.truncate(b, 0)
+        tail = self._embed(ids, p)
+        rows = [torch.cat([tail, m.engine.embed_splice(torch.tensor(pl.feed, dtype=torch.long))], dim=0) if pl.feed else tail for pl in plans]
+        self.rows_prefilled.append(sum(r.shape[0] for r in rows))
+        ts = m.engine.score_batch(kv, branches, rows, [pl.targets[p:] for pl in plans], penalty=penalty, top_n=top_n)
+        return [scoring.response_scores(self.tokenizer, pl.ids, t) for pl, t in zip(plans, ts)]

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_kv_set_constraints, cr_op_constrain, cr_kv_reset / cr_kv_truncate / cr_kv_fork also switch constraints off; cr_kv_truncate, cr_kv_fork; cr_kv_set_beam, cr_kv_beam_result, cr_kv_beam_reorder, cr_op_beam_step, cr_kv_reset also dissolves beam groups; cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
+#define CR_ABI_VERSION 13  /* 13 (additions that change no existing entry point keep the number: a caller built against the earlier v13 header runs unchanged, and a binding that names a missing symbol fails at load): cr_llm_score_batch, cr_op_score_rows; cr_kv_set_constraints, cr_op_constrain, cr_kv_reset / cr_kv_truncate / cr_kv_fork also switch constraints off; cr_kv_truncate, cr_kv_fork; cr_kv_set_beam, cr_kv_beam_result, cr_kv_beam_reorder, cr_op_beam_step, cr_kv_reset also dissolves beam groups; cr_kv_set_logprobs, cr_kv_logprobs, cr_op_logprobs, cr_kv_reset also switches token scores off; cr_kv_alloc_ex (CR_KV_E4M3 caches), cr_kv_format, cr_kv_read_e4m3, cr_op_decode_attention_e4m3, cr_kv_read refuses e4m3 caches; 12: cr_kv_set_sampling, cr_op_sample, cr_kv_reset clears the sampling state; 11: cr_kv_set_stop, cr_kv_poll_finished, cr_kv_reset clears the stop state, seqs staging per context; 10: cr_op_decode_attention(+_scratch_floats); 9: cr_build_flags, cr_diag_register; 8: cr_op_decode_swizzle, cr_op_decode_gemm flags bit 8, cr_op_gemm bits 18-19; 7: cr_op_decode_gemm; 6: cr_build_id, cr_llm_hidden_probe; 5: cr_share_weights, cr_op_gemm_q8, cr_op_norm_fp8 takes the next linear's bound; 4: cr_enable_fp8_mfma, cr_op_norm_fp8, cr_op_gemm bit 17; 2: cr_orderformer; cr_op_gemm kernel pin and EPI_PARTIAL (epi 7); 3: cr_profile_stats, cr_kv_read, cr_kv_reset takes a stream, cr_enable_fp8_decode, cr_op_quantize_fp8, epi 8 */
 
 enum { CR_OK = 0, CR_ERR_ARG = -1, CR_ERR_HIP = -2, CR_ERR_STATE = -3, CR_ERR_NOMEM = -4 };
 enum { CR_BF16 = 0, CR_F32 = 1, CR_I64 = 2, CR_I32 = 3, CR_U8 = 4 /* library-internal: e4m3 weight copies */ };
@@ -314,6 +314,29 @@ int cr_llm_prefill(cr_ctx* ctx, cr_kv* kv, int seq, const void* embeds, int S, f
  * last_logits [n,vocab] fp32 (may be NULL). */
 int cr_llm_prefill_batch(cr_ctx* ctx, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens,
                          float penalty, float* last_logits, void* stream);
+/* Teacher-forced scores: what the model thinks of a text the CALLER brings (a ground truth, a candidate, a correction).  A continued prefill exactly as
+ * cr_llm_prefill_batch defines it -- the rows are appended at each sequence's current length, RoPE and the causal mask count from that length, cr_kv_length
+ * grows by lens[i], every row's K / V reach the cache -- that makes NO pick: no id is appended, and no stop, sampling, constraint or score state of the
+ * sequences is read or changed.  Instead every row r with targets_host[r] = y >= 0 (host array over the concatenated rows, < 0: the row is not scored) is
+ * scored by cr_kv_set_logprobs' definition, on the distribution over the id that FOLLOWS row r: with h = the targets of the scored rows of the same sequence
+ * that precede r in this call,
+ *     z        = the raw fp32 LM-head row of r after the repetition penalty over h (v < 0 ? v * penalty : v / penalty; an id repeated in h is penalised
+ *                once: every duplicate sees the original score)
+ *     logprob  = z[y] - lse(z);   top_ids / top_lp = the top_n largest entries of z (descending, an exact tie towards the lower id) as id and z - lse
+ * -- what a greedy generation that happened to produce the text would have recorded for it.  The usual call holds the rows prompt ++ embed(y[0 .. T-1)) with
+ * targets [-1] * (P - 1) ++ y[0 .. T); put the EOS id into y to score the stop as well.  To score over a cache that already holds the WHOLE prompt (L rows),
+ * roll it back by one row and feed that row again: cr_kv_truncate(seq, L - 1), then the rows prompt[L - 1] ++ embed(y[0 .. T-1)) with targets y[0 .. T).
+ * Outputs (device), one slot per SCORED row in row order: lp [R] fp32, top_ids [R][8] int32 and top_lp [R][8] fp32 (entries top_n..8 hold -1 and -inf; both
+ * may be NULL when top_n == 0), logits [R][vocab] fp32 = the raw rows (may be NULL).  The final decoder layer runs on every row; the LM head runs on the scored
+ * rows in tiles of 256 with the tiled kernels, so a row's logits do not depend on what it is batched with (they need not equal cr_llm_prefill's last_logits bit
+ * for bit: that head may take the weight-streaming kernel); the score kernels (csrc/score.hip) keep csrc/logprobs.hip's summation order, so a row's scores are
+ * bit-equal to cr_op_logprobs on the penalised row, within 5e-6 absolute of the float64 log-softmax for |z| <= 32.
+ * Checked before anything is enqueued, nothing changes on refusal: CR_ERR_ARG for a sequence out of range or listed twice, lens[i] <= 0, rows that exceed the
+ * cache, a call without any scored row, a target >= vocab, top_n outside 0..8, a penalty that is not finite and > 0, an e4m3 cache, or a member of a beam
+ * group; CR_ERR_STATE for a sequence that holds generated ids (the penalty history is the call's own: cr_kv_truncate / cr_kv_fork / cr_kv_reset give a
+ * sequence without ids).  Enqueued on `stream`.  Added within ABI v13. */
+int cr_llm_score_batch(cr_ctx* ctx, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host,
+                       float penalty, int top_n, float* lp, int32_t* top_ids, float* top_lp, float* logits, void* stream);
 /* Parity tooling: while `dst` is not NULL, every cr_llm_prefill / cr_llm_prefill_batch also copies rows [row0, row0 + rows) of the
  * residual stream (row index into the concatenated prompt rows) into dst [llm_layers + 1][rows][4096] bf16 (device): slot 0 = the
  * decoder stack's input, slot l + 1 = the output of InternLM2DecoderLayer l (InternVL/modeling_internlm2.py:621-681; what
@@ -451,6 +474,13 @@ int cr_op_constrain(const cr_constraints* c, float* logits, int n, int vocab, co
  * (not modified), ids [n] int64 = the id scored in each row; lp [n], top_ids [n][8], top_lp [n][8] as above with top_n alternatives (1..8, CR_ERR_ARG
  * otherwise; vocab >= 8, n <= 65535).  All pointers are DEVICE arrays.  Synchronises `stream`.  Added within ABI v13. */
 int cr_op_logprobs(const float* logits, int n, int vocab, const int64_t* ids, int top_n, float* lp, int32_t* top_ids, float* top_lp, void* stream);
+/* The score kernels of cr_llm_score_batch alone (test entry; the stage launches the same three kernels): logits [n][vocab] fp32 = raw rows (DEVICE, not
+ * modified); targets_host [n] int64 = the id scored in each row, row_seq_host [n] int32 = which history the row belongs to (0 .. n - 1), hist_index_host [n]
+ * int32 = its ordinal j in that history (HOST arrays): row r is penalised at the targets of the rows of the same history with a smaller ordinal.  lp [n],
+ * top_ids [n][8], top_lp [n][8] (DEVICE) as above with top_n alternatives (0..8; top_* may be NULL when top_n == 0).  vocab >= 8, n <= 65535, every target
+ * inside the vocabulary, penalty finite and > 0 (CR_ERR_ARG otherwise).  Synchronises `stream`.  Added within ABI v13. */
+int cr_op_score_rows(const float* logits, int n, int vocab, const int64_t* targets_host, const int32_t* row_seq_host, const int32_t* hist_index_host,
+                     float penalty, int top_n, float* lp, int32_t* top_ids, float* top_lp, void* stream);
 /* One beam-search step of cr_kv_set_beam alone (test entry; the prefill and decode launch the same three kernels): logits [n][vocab] fp32 (OVERWRITTEN with the
  * penalised log-probabilities), history [n][hist_cap] int64 with hist_len[n] ids per row (both updated: re-ordered, the new id appended), group[n] = the first row
  * of the row's beam group (every row belongs to one; a group's rows are consecutive, in beam order), fin_ids [n][hist_cap] int64 = ids of the finished slots
