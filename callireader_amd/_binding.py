@@ -65,6 +65,7 @@ SIGNATURES = {
     'cr_kv_reset': (i32, [vp, i32, vp]),
     'cr_kv_truncate': (i32, [vp, i32, i32, vp]),
     'cr_kv_fork': (i32, [vp, i32, C.POINTER(C.c_int32), i32, i32, vp]),
+    'cr_kv_fanout': (i32, [vp, i32, C.POINTER(C.c_int32), i32, C.POINTER(C.c_uint64), vp, vp]),
     'cr_kv_read': (i32, [vp, i32, i32, i32, i32, vp, vp]),
     'cr_kv_generated': (i32, [vp, i32, C.POINTER(i64), i32, vp]),
     'cr_kv_set_stop': (i32, [vp, i32, i32, i32, vp]),

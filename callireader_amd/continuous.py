@@ -126,7 +126,7 @@ class ContinuousPipeline:
         self.worker.start()
 
     # ---- caller side ----------------------------------------------------------------------------
-    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None, logprobs=0, constraints=None, draft_ids=None):
+    def submit(self, embeds, max_new_tokens=None, sampling=None, seed=None, logprobs=0, constraints=None, draft_ids=None, num_return_sequences=1):
         """Queue one page's prompt embeddings ([S, hidden] on the device) with its budget of new ids (default, and at most, the pipeline's);
         returns its ticket.  Prefills a group when one is complete.  ValueError for a budget the pipeline cannot take.  sampling (a
         sampling.SamplingParams) with a 64-bit `seed`: the page samples (its sequence's state is set after its reset, before its prefill);
@@ -135,6 +135,9 @@ class ContinuousPipeline:
         if draft_ids is not None:
             from .draft import refuse
             refuse('ContinuousPipeline (its rows stop on the device, its worker never waits for a step)')
+        if num_return_sequences not in (1, None):
+            raise NotImplementedError(f'num_return_sequences={num_return_sequences}: ContinuousPipeline owns its cache, one decode slot per page (several '
+                                      'sampled answers per page: generate_pages / chat_ocr_pages)')
         t0 = time.perf_counter()
         self._raise_worker_error()
         logprobs = check_top_n(logprobs, 'logprobs', allow_zero=True)

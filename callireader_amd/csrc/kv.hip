@@ -11,7 +11,9 @@
 //                       is read once however many branches there are: traffic (1 + n_dst) * layers * 16 * n_tokens * 256 bytes.  The grid follows the byte
 //                       count; positions >= n_tokens of a destination are never written.  The first workgroup also writes the destinations' state, which no
 //                       other workgroup reads.  src is never a destination (checked on the host), so no address is both read and written.
-// These three use no atomics of any kind; plain vector stores only.
+//   kv_fanout_state_kernel  cr_kv_fanout, behind kv_fork_kernel: the destinations take the source's sampling parameters, stop criteria and score setting, and
+//                       each its own seed; sample.hip's fan-out pick and logprobs.hip's fan-out merge then give each its first id and that id's scores.
+// These four use no atomics of any kind; plain vector stores only.
 #include <algorithm>
 #include <initializer_list>
 
@@ -83,6 +85,20 @@ __global__ __launch_bounds__(FORK_THREADS) void kv_fork_kernel(KvState s, bf16* 
             if (p < pieces) dp[p] = r[u];
         }
     }
+}
+
+// cr_kv_fanout's state, after the fork's cleared state: destination j samples as src does, with seeds.s[j]; it stops where src stops (the criteria only: it
+// has no id and no stop yet); it records scores as src does.  One thread per destination.
+struct FanSeeds { uint64_t s[FAN_MAX]; };
+__global__ __launch_bounds__(64) void kv_fanout_state_kernel(KvState s, int32_t* __restrict__ topk, float* __restrict__ topp, uint64_t* __restrict__ seed, int src,
+                                                             FanSeqs dsts, FanSeeds seeds) {
+    const int j = threadIdx.x;
+    if (j >= dsts.n) return;
+    const int d = dsts.seq[j], N = s.n_seqs;
+    s.temp[d] = s.temp[src]; topk[d] = topk[src]; topp[d] = topp[src]; seed[d] = seeds.s[j];
+    s.stop[1 + 2 * N + d] = s.stop[1 + 2 * N + src];
+    s.stop[1 + 3 * N + d] = s.stop[1 + 3 * N + src];
+    if (s.lpn) { s.lpn[d] = s.lpn[src]; s.lpdone[d] = 0; }
 }
 
 // cr_kv_set_stop: install the criteria of `seq` and apply them to the ids it has generated already (a call after the prefill sees its first id).
@@ -280,6 +296,62 @@ int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_to
                        (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD, kv->max_tokens, src, d, n_tokens);
     CR_HIP(hipGetLastError());
     for (int j = 0; j < n_dst; j++) kv->seq[d.seq[j]].clear(n_tokens);
+    return CR_OK;
+}
+
+int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const uint64_t* seeds_host, const float* last_logits, void* stream) {
+    if (!kv || !dsts_host || src < 0 || src >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_fanout: bad argument (null cache or destinations, or a source out of range)");
+    if (n_dst < 1 || n_dst > kv->n_seqs - 1 || n_dst > FAN_MAX)
+        return cr_fail(CR_ERR_ARG, "cr_kv_fanout: %d destinations (want 1..%d)", n_dst, kv->n_seqs - 1 < FAN_MAX ? kv->n_seqs - 1 : FAN_MAX);
+    KvSeqs d{};
+    FanSeqs f{};
+    d.n = f.n = n_dst;
+    for (int j = 0; j < n_dst; j++) {
+        const int s = dsts_host[j];
+        if (s < 0 || s >= kv->n_seqs || s == src) return cr_fail(CR_ERR_ARG, "cr_kv_fanout: destination %d (want 0..%d, not the source %d)", s, kv->n_seqs - 1, src);
+        for (int i = 0; i < j; i++) if (dsts_host[i] == s) return cr_fail(CR_ERR_ARG, "cr_kv_fanout: destination %d listed twice", s);
+        d.seq[j] = f.seq[j] = s;
+    }
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_fanout: the copy moves bf16 rows only, as cr_kv_fork's (an e4m3 cache is not fanned out)");
+    if (!seeds_host || !last_logits) return cr_fail(CR_ERR_ARG, "cr_kv_fanout: null seeds or last_logits");
+    const Seq q = kv->seq[src];
+    if (q.bgrp >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_fanout: the source %d belongs to the beam group of sequence %d", src, q.bgrp);
+    for (int j = 0; j < n_dst; j++)
+        if (kv->seq[d.seq[j]].bgrp >= 0)
+            return cr_fail(CR_ERR_STATE, "cr_kv_fanout: destination %d belongs to the beam group of sequence %d", d.seq[j], kv->seq[d.seq[j]].bgrp);
+    if (!q.sampled) return cr_fail(CR_ERR_STATE, "cr_kv_fanout: the source %d does not sample (cr_kv_set_sampling with a temperature > 0 before its prefill)", src);
+    if (q.constrained) return cr_fail(CR_ERR_STATE, "cr_kv_fanout: the source %d carries logits constraints (its last row is not what its pick chose from)", src);
+    if (q.ngen != 1 || q.len < 1)
+        return cr_fail(CR_ERR_STATE, "cr_kv_fanout: the source %d holds %d generated ids and %d tokens (want the state right behind its prefill: one id)", src, q.ngen, q.len);
+    CR_HIP(hipSetDevice(kv->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int V = kv->ctx->d.vocab;
+    if (q.scored && !kv->d_fan) {
+        const int r = kv_lazy_blocks(kv, {{&kv->d_fan, logprobs_scratch_bytes(1, V), -1}}, st);
+        if (r == CR_ERR_NOMEM) return cr_fail(CR_ERR_NOMEM, "cr_kv_fanout: %zu bytes of score partials", logprobs_scratch_bytes(1, V));
+        CR_TRY(r);
+    }
+    // the prefix: kv_fork_kernel as cr_kv_fork launches it (the source read once, rows >= q.len of a destination not written, the cleared state)
+    const int pieces = q.len * 16;
+    hipLaunchKernelGGL(kv_fork_kernel, dim3((pieces + FORK_TILE - 1) / FORK_TILE, kv->layers * 16), dim3(FORK_THREADS), 0, st, kv_state(kv), kv->k, kv->v,
+                       (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD, kv->max_tokens, src, d, q.len);
+    FanSeeds seeds{};
+    for (int j = 0; j < n_dst; j++) seeds.s[j] = seeds_host[j];
+    hipLaunchKernelGGL(kv_fanout_state_kernel, dim3(1), dim3(64), 0, st, kv_state(kv), kv->d_topk, kv->d_topp, kv->d_seed, src, f, seeds);
+    CR_HIP(hipGetLastError());
+    SampleLaunch p{};
+    p.h = kv_hist(kv, nullptr);
+    p.temp = kv->d_temp; p.topk = kv->d_topk; p.topp = kv->d_topp; p.seed = kv->d_seed; p.lens = kv->d_len; p.stop = kv->d_stop; p.n_seqs = kv->n_seqs;
+    CR_TRY(launch_sample_fan(last_logits, V, f, p, st));
+    if (q.scored) {
+        const LogprobsLaunch lp{last_logits, V, V, 1, kv_hist(kv, nullptr), kv->d_lpn, 0, kv->d_lpdone, kv->d_fan, kv->d_lp, kv->d_top_id, kv->d_top_lp};
+        CR_TRY(launch_logprobs_fan(last_logits, V, f, lp, st));
+    }
+    for (int j = 0; j < n_dst; j++) {
+        Seq& t = kv->seq[d.seq[j]];
+        t.clear(q.len);
+        t.ngen = 1; t.sampled = true; t.scored = q.scored;
+    }
     return CR_OK;
 }
 

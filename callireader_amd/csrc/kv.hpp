@@ -54,6 +54,8 @@ struct cr_kv {
     // beam groups (cr_kv_set_beam; beam.hip), allocated by the first call: d_beam BeamState[n] (a group's state at its first sequence), d_bgrp int32[n] = first
     // sequence of the sequence's group (< 0: none), d_bfin [n][gen_cap] ids of the finished slots.  Seq::bgrp / bnum mirror the group and its size on the host:
     // a launch without a group launches nothing new
+    // cr_kv_fanout's score partials of its one logits row (logprobs_scratch_bytes(1, vocab)), allocated by the first fan-out of a sequence that records scores
+    void* d_fan = nullptr;
     BeamState* d_beam = nullptr;
     int32_t* d_bgrp = nullptr;
     int64_t* d_bfin = nullptr;

@@ -23,6 +23,7 @@
 // (weighted by the term's share of the sum: below 5e-7 for |z| <= 32) and expf's ulp (1.2e-7 relative): under 5e-6 absolute in all.
 #include "ctx.hpp"
 #include "logprobs_dev.hpp"
+#include "pick.hpp"
 
 namespace {
 
@@ -68,6 +69,24 @@ __global__ __launch_bounds__(64) void logprobs_merge_kernel(const float* __restr
     merge_row(row, chunks, n, slot, zi, lane, pm, ps, pv, pi, out_lp, out_id, out_tlp);
 }
 
+// cr_kv_fanout: wave j merges the partials of the ONE row (partial row 0) for sequence dsts.seq[j], as logprobs_merge_kernel does for a cache row
+__global__ __launch_bounds__(64) void logprobs_fan_merge_kernel(const float* __restrict__ row, int vocab, int chunks, FanSeqs dsts, const int32_t* __restrict__ lpn,
+                                                               const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen, int gen_cap,
+                                                               int32_t* __restrict__ done, const float* __restrict__ pm, const double* __restrict__ ps,
+                                                               const float* __restrict__ pv, const int32_t* __restrict__ pi, float* __restrict__ out_lp,
+                                                               int32_t* __restrict__ out_id, float* __restrict__ out_tlp) {
+    const int seq = dsts.seq[blockIdx.x], lane = threadIdx.x;
+    const int n = lpn[seq];
+    if (n <= 0) return;
+    const int t = ngen[seq] - 1;
+    if (t < 0 || t != done[seq]) return;
+    const int64_t id = gen[(int64_t)seq * gen_cap + t];
+    const int64_t slot = (int64_t)seq * gen_cap + t;
+    if (lane == 0) done[seq] = t + 1;
+    const float zi = (id >= 0 && id < vocab) ? row[id] : NAN;
+    merge_row(0, chunks, n, slot, zi, lane, pm, ps, pv, pi, out_lp, out_id, out_tlp);
+}
+
 __global__ __launch_bounds__(64) void set_logprobs_kernel(int32_t* __restrict__ lpn, int32_t* __restrict__ done, int seq, int top_n) {
     if (threadIdx.x == 0) { lpn[seq] = top_n; done[seq] = 0; }
 }
@@ -92,6 +111,19 @@ int launch_logprobs(const LogprobsLaunch& p, hipStream_t st) {
     hipLaunchKernelGGL(logprobs_merge_kernel, dim3(p.rows), dim3(64), 0, st, p.logits, p.ld, p.vocab, chunks, p.h.seqs, p.lpn, p.top_n, (const int64_t*)p.h.gen,
                        (const int32_t*)p.h.ngen, p.h.gen_cap, p.done, (const float*)pm, (const double*)ps, (const float*)pv, (const int32_t*)pi, p.out_lp, p.out_id,
                        p.out_tlp);
+    CR_HIP(hipGetLastError());
+    return CR_OK;
+}
+
+int launch_logprobs_fan(const float* row, int vocab, const FanSeqs& dsts, const LogprobsLaunch& p, hipStream_t st) {
+    const int chunks = logprobs_chunks(vocab);
+    double* ps = (double*)(((uintptr_t)p.scratch + 255) & ~(uintptr_t)255);
+    float* pm = (float*)(ps + chunks);
+    float* pv = pm + chunks;
+    int32_t* pi = (int32_t*)(pv + (size_t)chunks * TOPN);
+    hipLaunchKernelGGL(logprobs_chunk_kernel, dim3(chunks, 1), dim3(THREADS), 0, st, row, (int64_t)vocab, vocab, chunks, (const int32_t*)nullptr, p.lpn, pm, ps, pv, pi);
+    hipLaunchKernelGGL(logprobs_fan_merge_kernel, dim3(dsts.n), dim3(64), 0, st, row, vocab, chunks, dsts, p.lpn, (const int64_t*)p.h.gen, (const int32_t*)p.h.ngen,
+                       p.h.gen_cap, p.done, (const float*)pm, (const double*)ps, (const float*)pv, (const int32_t*)pi, p.out_lp, p.out_id, p.out_tlp);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }

@@ -19,3 +19,7 @@ struct LogprobsLaunch {
 };
 int launch_logprobs(const LogprobsLaunch& p, hipStream_t st);
 int launch_set_logprobs(int32_t* lpn, int32_t* done, int seq, int top_n, hipStream_t st);
+// cr_kv_fanout's scores: the one fp32 `row` [vocab] is reduced once (logprobs_chunk_kernel, one row) and merged once per sequence of `dsts` that has scores on
+// (lpn > 0) into the slot of the id its pick has just appended -- what launch_logprobs writes for a row of these bits.  scratch: logprobs_scratch_bytes(1, vocab).
+struct FanSeqs;
+int launch_logprobs_fan(const float* row, int vocab, const FanSeqs& dsts, const LogprobsLaunch& p, hipStream_t st);

@@ -79,6 +79,14 @@ struct SampleLaunch {
 };
 int launch_sample(const SampleLaunch& p, hipStream_t st);
 
+// The sequences of one cr_kv_fanout, by value in the launches that take them (no staging buffer)
+constexpr int FAN_MAX = 63;
+struct FanSeqs { int32_t n; int32_t seq[FAN_MAX]; };
+// cr_kv_fanout's picks, one launch (sample.hip sample_fan_kernel): sequence dsts.seq[j], which holds no id yet, draws its first id from the one fp32 `row`
+// [vocab] (read only) with its own sampling state -- sample_kernel's thresholds and draw at step 0 -- and appends it with the stop check; lens are not
+// advanced.  p gives the histories (h.gen / h.ngen / h.gen_cap), temp / topk / topp / seed, lens, stop and n_seqs; its other fields are not read.
+int launch_sample_fan(const float* row, int vocab, const FanSeqs& dsts, const SampleLaunch& p, hipStream_t st);
+
 // ---- what follows the LM head in a prefill / decode call (pick.hip; host) ----
 struct cr_kv; struct Arena; struct BeamLaunch; struct BeamCache;
 

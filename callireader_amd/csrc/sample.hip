@@ -214,24 +214,22 @@ __device__ uint32_t select_key(const float* lg, int vocab, float temp, float zma
     return khi;
 }
 
-__global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty, const int32_t* __restrict__ seqs,
-                                                      int64_t* __restrict__ gen, int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_,
-                                                      const int32_t* __restrict__ topk_, const float* __restrict__ topp_, const uint64_t* __restrict__ seed_,
-                                                      const int32_t* __restrict__ step_, int append, int32_t* __restrict__ lens, int len_add,
-                                                      int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_kept,
-                                                      const float* __restrict__ orig, const int32_t* __restrict__ bgrp) {
+// The pick of one row by its workgroup of 1024: the body of both kernels below.  lg: the row's scores, read only; lgw: the same row where the penalty may
+// write it, NULL for a row that is never written (sample_fan_kernel: several workgroups read one row).
+__device__ __forceinline__ void sample_row(const float* lg, float* lgw, int row, int seq, int vocab, float penalty, int64_t* __restrict__ gen,
+                                           int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_, const int32_t* __restrict__ topk_,
+                                           const float* __restrict__ topp_, const uint64_t* __restrict__ seed_, const int32_t* __restrict__ step_, int append,
+                                           int32_t* __restrict__ lens, int len_add, int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids,
+                                           int32_t* __restrict__ out_kept, const float* orig_row) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     __shared__ SelShared s;
     __shared__ double rs[16];
     __shared__ int ri[16], rk[16];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int seq = seqs ? seqs[row] : row;
-    if (bgrp && bgrp[seq] >= 0) return;                     // a beam row: beam.hip picks for it
-    float* lg = logits + (int64_t)row * ld;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int ng = ngen[seq] < gen_cap ? ngen[seq] : gen_cap;       // (a KV cache never holds more; cr_op_sample's hist_len may)
     int64_t* g = gen + (int64_t)seq * gen_cap;
-    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid, orig ? orig + (int64_t)row * ld : nullptr);
+    if (lgw && penalty != 1.0f && ng > 0) apply_penalty(lgw, g, ng, penalty, tid, orig_row);
     const float temp = temp_[seq];
     int64_t id;
     int kept = 0;
@@ -319,7 +317,39 @@ __global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits
     }
 }
 
+__global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty, const int32_t* __restrict__ seqs,
+                                                      int64_t* __restrict__ gen, int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_,
+                                                      const int32_t* __restrict__ topk_, const float* __restrict__ topp_, const uint64_t* __restrict__ seed_,
+                                                      const int32_t* __restrict__ step_, int append, int32_t* __restrict__ lens, int len_add,
+                                                      int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_kept,
+                                                      const float* __restrict__ orig, const int32_t* __restrict__ bgrp) {
+    const int row = blockIdx.x;
+    const int seq = seqs ? seqs[row] : row;
+    if (bgrp && bgrp[seq] >= 0) return;                     // a beam row: beam.hip picks for it
+    float* lg = logits + (int64_t)row * ld;
+    sample_row(lg, lg, row, seq, vocab, penalty, gen, ngen, gen_cap, temp_, topk_, topp_, seed_, step_, append, lens, len_add, stop, n_seqs, out_ids, out_kept,
+               orig ? orig + (int64_t)row * ld : nullptr);
+}
+
+// cr_kv_fanout's picks: workgroup j draws the first id of sequence dsts.seq[j] from the ONE row `lg` (the raw last row of the source's prefill), which no
+// workgroup writes -- the sequences hold no ids yet, so there is no penalty to apply -- and appends it with the stop check; the cached length stays.
+__global__ __launch_bounds__(1024) void sample_fan_kernel(const float* __restrict__ lg, int vocab, FanSeqs dsts, int64_t* __restrict__ gen,
+                                                          int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_,
+                                                          const int32_t* __restrict__ topk_, const float* __restrict__ topp_,
+                                                          const uint64_t* __restrict__ seed_, int32_t* __restrict__ lens, int32_t* __restrict__ stop, int n_seqs) {
+    const int row = blockIdx.x;
+    sample_row(lg, nullptr, row, dsts.seq[row], vocab, 1.0f, gen, ngen, gen_cap, temp_, topk_, topp_, seed_, nullptr, 1, lens, 0, stop, n_seqs, nullptr, nullptr,
+               nullptr);
+}
+
 }  // namespace
+
+int launch_sample_fan(const float* row, int vocab, const FanSeqs& dsts, const SampleLaunch& p, hipStream_t st) {
+    hipLaunchKernelGGL(sample_fan_kernel, dim3(dsts.n), dim3(1024), 0, st, row, vocab, dsts, p.h.gen, p.h.ngen, p.h.gen_cap, p.temp, p.topk, p.topp, p.seed, p.lens,
+                       p.stop, p.n_seqs);
+    CR_HIP(hipGetLastError());
+    return CR_OK;
+}
 
 int launch_sample(const SampleLaunch& p, hipStream_t st) {
     hipLaunchKernelGGL(sample_kernel, dim3(p.rows), dim3(1024), 0, st, p.logits, p.ld, p.vocab, p.penalty, p.h.seqs, p.h.gen, p.h.ngen, p.h.gen_cap, p.temp, p.topk,

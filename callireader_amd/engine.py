@@ -354,6 +354,25 @@ class KVCache:
         for d in dsts:
             self._top_n.pop(d, None)
 
+    def fanout(self, src, dsts, seeds, last_logits):
+        """cr_kv_fanout on the current stream: `src` has just been prefilled with sampling on (one generated id); every sequence of `dsts` becomes what a
+        lone prefill of the same prompt with seeds[j] would have left -- src's cached prefix (the source read once), its own first id drawn from
+        `last_logits` (the raw fp32 row [vocab] that src's prefill returned with want_logits), src's sampling parameters, stop criteria and score
+        setting.  bf16 caches, at most 63 destinations; src is not changed."""
+        dsts, seeds = [int(d) for d in dsts], [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+        if len(seeds) != len(dsts):
+            raise ValueError(f'fanout: {len(seeds)} seeds for {len(dsts)} destinations')
+        lg = last_logits
+        if lg is not None:
+            if not (torch.is_tensor(lg) and lg.is_cuda and lg.dtype == torch.float32 and lg.is_contiguous() and lg.numel() == self.eng.dims.vocab):
+                raise ValueError(f'fanout: last_logits has to be one contiguous fp32 row of {self.eng.dims.vocab} scores on the device')
+        B.check(B.lib.cr_kv_fanout(self._h, int(src), (C.c_int32 * len(dsts))(*dsts), len(dsts), (C.c_uint64 * len(seeds))(*seeds), _p(lg), _stream()),
+                'cr_kv_fanout')
+        for d in dsts:
+            self._top_n.pop(d, None)
+            if src in self._top_n:
+                self._top_n[d] = self._top_n[src]
+
     def read(self, layer, seq, pos, which=0):
         """(8, 128) bf16: K (which=0, after RoPE) or V (which=1) of one cached position, all KV heads."""
         out = torch.empty(8, 128, device=self.eng.device, dtype=torch.bfloat16)

@@ -65,7 +65,9 @@ def single_rec(model, tokenizer, detect_model, generation_config, image_path, pr
     """scores = n > 0 (--scores): the page's token scores are taken with n alternatives; prints one more line (`confidence <c> min <p> at token <k>
     (<piece>)`) and returns (response, scores.ResponseScores).
     draft = 'align' (--draft): the page's CalliAlign indices draft its answer (chat_ocr(draft='align')); the same response, one more line (`draft: <s> decode
-    steps for <n> ids, <a> of <d> drafted ids accepted`)."""
+    steps for <n> ids, <a> of <d> drafted ids accepted`).
+    generation_config['num_return_sequences'] = N > 1 (--num_return_sequences, with --do_sample): the response is the list of N sampled responses, printed
+    one `Assistant[j]:` line each -- with scores, `total logprob <t>` and the summary line behind each -- and the scores are a list of N."""
     bx = None
     if use_p and (boxes is not None or detect_model is None):
         bx = boxes_for(image_path, boxes)
@@ -73,6 +75,10 @@ def single_rec(model, tokenizer, detect_model, generation_config, image_path, pr
                          drop_zero=drop_zero, repetition_penalty=repetition_penalty, return_history=True,
                          verbose=verbose, boxes=bx, **(dict(return_scores=scores) if scores else {}), **(dict(draft=draft) if draft else {}))
     response = out[0]
+    if not quiet and isinstance(response, list):
+        print(f'User: {prompt}')
+        print_samples(response, out[2] if scores else None)
+        return (response, out[2]) if scores else response
     if not quiet:
         print(f'User: {prompt}\nAssistant: {response}')
         if draft:
@@ -81,6 +87,19 @@ def single_rec(model, tokenizer, detect_model, generation_config, image_path, pr
         if scores:
             print(out[2].summary_line())
     return (response, out[2]) if scores else response
+
+
+def print_samples(responses, scores=None):
+    """The N sampled responses of one page, one `Assistant[j]: <response>` line each; with scores `  total logprob <t> | <summary line>` under each."""
+    for j, r in enumerate(responses):
+        print(f'Assistant[{j}]: {r}')
+        if scores is not None:
+            print(f'  total logprob {scores[j].total_logprob:.4f} | {scores[j].summary_line()}')
+
+
+def scores_json(sc):
+    """to_json of a page's ResponseScores; of a list of them (N sampled responses) the list, each with its total_logprob."""
+    return [x.to_json(total=True) for x in sc] if isinstance(sc, list) else sc.to_json()
 
 
 def answer_scores_name(save_name):
@@ -150,13 +169,17 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
         if isinstance(response, BaseException):
             print(f'An error has occured:\n{response}')
             response = 'ERROR!'
-        print(f'User: {prompt}\nAssistant: {response}')
+        if isinstance(response, list):
+            print(f'User: {prompt}')
+            print_samples(response, page_scores.get(pic_path) if scores else None)
+        else:
+            print(f'User: {prompt}\nAssistant: {response}')
         responses[pic_path] = response
 
-    beams = generation_config.get('num_beams', 1) or 1
+    beams = max(generation_config.get('num_beams', 1) or 1, generation_config.get('num_return_sequences', 1) or 1)
     if beams > 1 and batch_pages > 1:
-        # beam search: the pipelines decode one row per page, so the images go through chat_ocr_pages, as many pages per batch as fit the decode rows
-        # with `beams` rows each; a batch that fails as a whole runs page by page, like the other modes
+        # beam search, or several sampled answers per page: the pipelines decode one row per page, so the images go through chat_ocr_pages, as many pages
+        # per batch as fit the decode rows with `beams` rows each; a batch that fails as a whole runs page by page, like the other modes
         boxes, ready = {}, []
         for pic_path in paths:
             try:
@@ -171,10 +194,10 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
                 res = model.chat_ocr_pages(tokenizer, detect_model, b, prompt, generation_config,
                                            boxes_list=[boxes[p] for p in b] if (use_p and detect_model is None) else None, use_p=use_p, drop_zero=drop_zero,
                                            hard_vq=hard_vq, repetition_penalty=repetition_penalty, errors='return', **skw)
-                for pic_path, r in zip(b, res):
+                for pic_path, r in zip(b, zip(*res) if scores else res):      # (with scores: (responses, scores) -> one pair per page)
                     put(pic_path, r)
             except NotImplementedError:
-                raise                                            # an option beams do not take (--scores): not a page's failure
+                raise                                            # an option beams or samples do not take: not a page's failure
             except Exception as e:
                 print(f'[folder_rec] a batch failed as a whole ({e}); its {len(b)} pages run one by one')
                 for pic_path in b:
@@ -240,7 +263,7 @@ def folder_rec(model, tokenizer, detect_model, generation_config, folder_path, p
     with open(save_name, 'w', encoding='utf-8') as f:
         json.dump(results, f, ensure_ascii=False, indent=4)           # utils/utils.py:59-62 save_json
     if scores:
-        doc = [{'imagePath': p, 'scores': None if (responses[p] == 'ERROR!' or page_scores.get(p) is None) else page_scores[p].to_json()} for p in paths]
+        doc = [{'imagePath': p, 'scores': None if (responses[p] == 'ERROR!' or page_scores.get(p) is None) else scores_json(page_scores[p])} for p in paths]
         with open(scores_name(save_name), 'w', encoding='utf-8') as f:
             json.dump(doc, f, ensure_ascii=False, indent=4)
     return results
@@ -288,6 +311,9 @@ def build_parser():
     parser.add_argument('--temperature', type=float, default=None, help='with --do_sample (default 1.0)')
     parser.add_argument('--top_k', type=int, default=None, help='with --do_sample (default 50; 0: off)')
     parser.add_argument('--top_p', type=float, default=None, help='with --do_sample (default 1.0: off)')
+    parser.add_argument('--num_return_sequences', type=int, default=1, metavar='N',
+                        help='with --do_sample: N sampled answers per page from one visual stage and one prefill (pages x N <= 64 decode rows); the console prints '
+                             'the N answers (with --scores their total log-probabilities), the results JSON holds the list of N as `response` (only when N > 1)')
     parser.add_argument('--seed', type=int, default=None, help='torch.manual_seed before the run: --do_sample output becomes reproducible')
     parser.add_argument('--num_beams', type=int, default=1, help='beam search with this many beams (2..8; transformers\' deterministic beam search, on the device); 1: the greedy default')
     parser.add_argument('--length_penalty', type=float, default=None, help='with --num_beams > 1: exponent of the hypothesis length a finished score is divided by (default 1.0)')
@@ -333,6 +359,8 @@ def main(argv=None):
     if args.do_sample:
         generation_config['do_sample'] = True
         generation_config.update({k: getattr(args, k) for k in ('temperature', 'top_k', 'top_p') if getattr(args, k) is not None})
+    if args.num_return_sequences != 1:
+        generation_config['num_return_sequences'] = args.num_return_sequences
     generation_config.update(beam_config(args))
     generation_config.update(constraint_config(args))
     if args.seed is not None:

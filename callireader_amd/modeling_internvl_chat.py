@@ -31,8 +31,8 @@ from . import scoring
 from .generation import admit, check_fits, decode_rows, decode_rows_drafted, per_page_sampling, read_scores, reply_shape, reply_text
 from .pipeline import PagePipeline
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
-from .sampling import base_seed, page_seeds, parse as sampling_parse, parse_beams, splitmix64
-from .scores import ResponseScores, TokenScores, generate_output, parse as scores_parse, per_page as scores_per_page
+from .sampling import base_seed, check_rows, fan_seeds, page_seeds, parse as sampling_parse, parse_beams, parse_returns, splitmix64
+from .scores import generate_outputs, ResponseScores, TokenScores, generate_output, parse as scores_parse, per_page as scores_per_page
 
 
 class InternVLChatModel:
@@ -298,12 +298,18 @@ class InternVLChatModel:
         where: _generate's kv / seq / reset (a session's turn; no beams there).  draft_ids among the keywords: _generate's draft."""
         generate_kwargs = dict(generate_kwargs)
         draft_ids = generate_kwargs.pop('draft_ids', None)
-        max_new, eos, sp = self._gen_args(generate_kwargs, allow_beams=True)
+        max_new, eos, sp = self._gen_args(generate_kwargs, allow_beams=True, allow_returns=True)
         beams = parse_beams(generate_kwargs)
+        nret = parse_returns(generate_kwargs)
         if draft_ids is not None:
             if beams is not None:
                 drafting.refuse(f'num_beams={beams.num_beams}')
+            if nret > 1:
+                drafting.refuse(f'num_return_sequences={nret} (sampled answers)')
             draft_ids = [int(t) for t in draft_ids]
+        if nret > 1 and where:
+            raise NotImplementedError(f'num_return_sequences={nret} in a page session: the samples need sequences of their own beside the trunk '
+                                      '(use chat_ocr(history=...), or ask_many for several questions)')
         cons = constraints_parse(generate_kwargs, eos)          # (NotImplementedError with beams or do_sample)
         if cons is not None:
             where = dict(where, constraints=cons)
@@ -321,6 +327,18 @@ class InternVLChatModel:
         if draft_ids is not None:
             where = dict(where, draft_ids=draft_ids)
         n = scores_parse(generate_kwargs)
+        if nret > 1:                               # several sampled answers: one prefill, the page's samples decode as one batch (generate_pages)
+            outs = self.generate_pages([input_embeds], max_new, eos, repetition_penalty, sampling=sp, logprobs=n, num_return_sequences=nret)
+            ids, tss = (outs[0][0], outs[1][0]) if n else (outs[0], None)
+            pad = generate_kwargs.get('pad_token_id')
+            pad = (eos if eos is not None else 0) if pad is None else pad         # transformers: pad_token_id defaults to the EOS id
+            seq = torch.full((nret, max(len(r) for r in ids)), int(pad), dtype=torch.long)
+            for j, r in enumerate(ids):
+                seq[j, :len(r)] = torch.tensor(r, dtype=torch.long)
+            seq = seq.to(self.device)
+            if not generate_kwargs.get('return_dict_in_generate', False):
+                return seq
+            return generate_outputs(seq, tss)
         if not generate_kwargs.get('return_dict_in_generate', False):
             return self._generate(input_embeds, max_new, eos, repetition_penalty, sp, **where)
         if not n:
@@ -328,14 +346,20 @@ class InternVLChatModel:
         return generate_output(*self._generate(input_embeds, max_new, eos, repetition_penalty, sp, logprobs=n, **where))
 
     @staticmethod
-    def _gen_args(generate_kwargs, allow_beams=False):
+    def _gen_args(generate_kwargs, allow_beams=False, allow_returns=False):
         """(max_new_tokens, eos_token_id, SamplingParams or None for greedy): transformers' defaults and validation (sampling.parse).  These are the
         arguments of the one-row-per-page loops: a caller that has no beam path (the pipelines, the sharded entry points, chat) gets NotImplementedError for
-        num_beams > 1; the callers that run beams (allow_beams) parse them with sampling.parse_beams."""
+        num_beams > 1; the callers that run beams (allow_beams) parse them with sampling.parse_beams.  Likewise num_return_sequences > 1: the callers that
+        fan a page out (allow_returns) read the count with sampling.parse_returns, the others raise NotImplementedError."""
         if not allow_beams and parse_beams(generate_kwargs) is not None:
             raise NotImplementedError(f"num_beams={generate_kwargs.get('num_beams')}: this entry point decodes one row per page (num_beams=1); beam search runs "
                                       'through generate / generate_ocr / generate_origin, chat_ocr, dynamic_chat, generate_pages and chat_ocr_pages')
-        return generate_kwargs.get('max_new_tokens', 1024), generate_kwargs.get('eos_token_id', EOS_TOKEN_ID), sampling_parse(generate_kwargs)
+        sp = sampling_parse(generate_kwargs)
+        if not allow_returns and parse_returns(generate_kwargs) > 1:
+            raise NotImplementedError(f"num_return_sequences={generate_kwargs.get('num_return_sequences')}: this entry point returns one answer per page (the "
+                                      'pipelines, the sharded entry points and page sessions own their caches); several sampled answers per page come from '
+                                      'generate / generate_ocr / generate_origin, chat_ocr, dynamic_chat, chat_ocr_pages and generate_pages')
+        return generate_kwargs.get('max_new_tokens', 1024), generate_kwargs.get('eos_token_id', EOS_TOKEN_ID), sp
 
     @staticmethod
     def _score_args(generation_config, return_scores):
@@ -352,8 +376,22 @@ class InternVLChatModel:
     def _with_scores(tokenizer, out):
         """(ids tensor, ResponseScores or None) of what a generate_* call returned."""
         if hasattr(out, 'sequences'):
+            if isinstance(out.scores, list):       # num_return_sequences > 1: one ResponseScores per sample, over its own (unpadded) ids
+                return out.sequences, [ResponseScores.build(tokenizer, row[:len(ts)].tolist(), ts) for row, ts in zip(out.sequences, out.scores)]
             return out.sequences, ResponseScores.build(tokenizer, out.sequences[0].tolist(), out.scores)
         return out, None
+
+    @staticmethod
+    def _reply_texts(tokenizer, out, sep):
+        """reply_text of a generate_* call's ids: the response, or for num_return_sequences > 1 (an [n, L] tensor, right-padded) the list of n responses."""
+        if out.shape[0] == 1:
+            return reply_text(tokenizer, out, sep)
+        return [reply_text(tokenizer, out[j:j + 1], sep) for j in range(out.shape[0])]
+
+    @staticmethod
+    def _first(response):
+        """What the history keeps of a turn: the response, sample 0's when several were returned."""
+        return response[0] if isinstance(response, list) else response
 
     @torch.no_grad()
     def generate_ocr(self, pixel_values=None, input_ids=None, attention_mask=None, visual_features=None,
@@ -453,6 +491,8 @@ class InternVLChatModel:
                  boxes=None, return_scores=False, draft=None):
         """:649-762.  return_scores (True, or the number of alternatives per token): a scores.ResponseScores is returned after the response
         (after `history` when that is returned); a detection failure still returns its message alone.
+        num_return_sequences = n > 1 in the generation_config (with do_sample=True): the response is a LIST of n sampled responses from one visual stage
+        and one prefill, the scores a list of n ResponseScores (total_logprob ranks them); the history keeps sample 0's response.
         draft (None: off): 'align' drafts the answer with this call's CalliAlign indices -- the rows of the LLM's own embedding table that the VQ step
         snapped the character boxes to (draft.from_indices; needs use_p) -- or a list of ids does; the response is the same, in fewer decode steps where
         the draft is right."""
@@ -460,6 +500,8 @@ class InternVLChatModel:
             drafting.refuse('return_scores')
         if isinstance(draft, str) and (draft != 'align' or not use_p):
             raise ValueError(f"chat_ocr: draft={draft!r} (want None, 'align' with use_p=True, or a list of ids)")
+        if self._returns(generation_config, 1) > 1 and draft is not None:      # refused before the visual stage
+            drafting.refuse('num_return_sequences > 1 (sampled answers)')
         pixel_values = None
         sub_img = None
         page = None                       # the decoded page, handed on to calli_align (the reference opens the file a second time there, :558: 14.5 ms of JPEG decode on the example page)
@@ -532,8 +574,8 @@ class InternVLChatModel:
     def _ocr_reply(self, tokenizer, out, template, question, history, return_history, return_scores):
         """chat_ocr after the language model (:752-762): the response text, appended to the history, in the shape the caller asked for."""
         out, sc = self._with_scores(tokenizer, out)
-        response = reply_text(tokenizer, out, template.sep)                     # :752-753
-        history.append((question, response))
+        response = self._reply_texts(tokenizer, out, template.sep)              # :752-753
+        history.append((question, self._first(response)))
         return reply_shape(response, history, sc, return_history, return_scores)
 
     def open_page(self, tokenizer, detect_model, img_path, use_p=True, drop_zero=False, hard_vq=False, boxes=None, max_branches=1, verbose=False):
@@ -582,7 +624,7 @@ class InternVLChatModel:
                 off += num_patches
                 out, sc = self._with_scores(tokenizer, gen(pixel_values=px, input_ids=ids, **generation_config))
                 all_sc.append(sc)
-                responses.append(reply_text(tokenizer, out, template.sep))
+                responses.append(self._reply_texts(tokenizer, out, template.sep))
             return (responses, all_sc) if return_scores else responses
         assert isinstance(questions, str)
         if num_patches_list is None:
@@ -605,8 +647,8 @@ class InternVLChatModel:
         out = gen(pixel_values=pixel_values, input_ids=model_inputs['input_ids'], attention_mask=model_inputs['attention_mask'],
                   **generation_config)
         out, sc = self._with_scores(tokenizer, out)
-        response = reply_text(tokenizer, out, template.sep)
-        history.append((questions, response))
+        response = self._reply_texts(tokenizer, out, template.sep)
+        history.append((questions, self._first(response)))
         if verbose and not return_history and not return_scores:               # only on the plain-response return
             print(query.replace(IMG_CONTEXT_TOKEN, '').replace(f'{IMG_START_TOKEN}{IMG_END_TOKEN}', '<image>'), response)
         return reply_shape(response, history, sc, return_history, return_scores)
@@ -624,15 +666,27 @@ class InternVLChatModel:
         constraints_parse(generation_config, 0)                 # refused before the visual stage (the EOS id does not change what is refused)
         _, lpn = self._score_args(generation_config, return_scores)
         beams = parse_beams(dict(generation_config, return_scores=return_scores))
+        nret = self._returns(generation_config, len(images))    # (so are too many rows and an e4m3 cache)
         embeds, meta = self._ocr_embeds(tokenizer, detect_model, images, question, generation_config, boxes_list, use_p, drop_zero,
-                                        hard_vq, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, errors=errors)
+                                        hard_vq, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, errors=errors, allow_returns=True)
         if beams is not None:                      # every page's beams in one decode batch; a page gets what its own chat_ocr call gives
             outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, num_beams=beams.num_beams, length_penalty=beams.length_penalty,
                                        early_stopping=beams.early_stopping)[0] if embeds else []
             return self._answer(tokenizer, outs, meta, False)
         outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, sampling=meta['sampling'],
-                                   seeds=self._ok_seeds(meta), logprobs=lpn, constraints=meta['constraints']) if embeds else []
+                                   seeds=self._ok_seeds(meta, nret), logprobs=lpn, constraints=meta['constraints'],
+                                   num_return_sequences=nret) if embeds else []
         return self._answer(tokenizer, outs, meta, return_scores)
+
+    def _returns(self, generation_config, P):
+        """num_return_sequences of a call over P pages, with what can be refused before the visual stage runs."""
+        nret = parse_returns(dict(generation_config))
+        if nret > 1:
+            check_rows(P, nret)
+            if self.kv_cache_dtype != 'bf16':
+                raise NotImplementedError(f"num_return_sequences={nret} with kv_cache_dtype='e4m3': the fan-out copies bf16 rows (cr_kv_fanout); call the "
+                                          'entry point n times, or use a bf16 cache')
+        return nret
 
     def _answer(self, tokenizer, outs, meta, return_scores):
         """_responses of a batch, or with return_scores (outs = (ids, TokenScores) lists, or empty) the pair (responses, ResponseScores per page: None for
@@ -642,16 +696,17 @@ class InternVLChatModel:
         outs, tss = outs if outs else ([], [])
         sc = [None] * meta['n']
         for i, o, ts in zip(meta['ok'], outs, tss):
-            sc[i] = ResponseScores.build(tokenizer, o, ts)
+            sc[i] = [ResponseScores.build(tokenizer, oj, tj) for oj, tj in zip(o, ts)] if isinstance(ts, list) else ResponseScores.build(tokenizer, o, ts)
         return self._responses(tokenizer, outs, meta), sc
 
     @staticmethod
-    def _ok_seeds(meta):
-        """Seeds of the pages that reach the language model: page j of the call (input order, failed pages included) has page_seeds(n)[j]."""
+    def _ok_seeds(meta, nret=1):
+        """Seeds of the pages that reach the language model: page j of the call (input order, failed pages included) has page_seeds(n)[j]; with nret
+        returned sequences per page its sample k has page_seeds(n * nret)[j * nret + k] (sampling.fan_seeds), flat in page order."""
         if meta['sampling'] is None:
             return None
-        seeds = page_seeds(meta['n'])
-        return [seeds[i] for i in meta['ok']]
+        seeds = fan_seeds(meta['n'], nret)
+        return [sd for i in meta['ok'] for sd in seeds[i]]
 
     @staticmethod
     def _responses(tokenizer, outs, meta):
@@ -659,7 +714,7 @@ class InternVLChatModel:
         sep = meta['template'].sep
         res = [None] * meta['n']
         for i, o in zip(meta['ok'], outs):
-            res[i] = reply_text(tokenizer, o, sep)
+            res[i] = [reply_text(tokenizer, oj, sep) for oj in o] if o and isinstance(o[0], list) else reply_text(tokenizer, o, sep)
         for i, e in meta['failed'].items():
             res[i] = e
         return res
@@ -677,6 +732,8 @@ class InternVLChatModel:
             raise NotImplementedError('chat_ocr_stream: beam search does not go through PagePipeline (use chat_ocr_pages)')
         if draft is not None:
             drafting.refuse('PagePipeline (chat_ocr_stream: its decode thread issues steps without waiting for them)')
+        if parse_returns(dict(generation_config)) > 1:
+            raise NotImplementedError('chat_ocr_stream: num_return_sequences > 1 does not go through PagePipeline, which owns its caches (use chat_ocr_pages)')
         constraints_parse(generation_config, 0)                 # refused before the first batch is pulled
         _, lpn = self._score_args(generation_config, return_scores)
         pipe, pending = None, None
@@ -790,6 +847,9 @@ class InternVLChatModel:
             raise NotImplementedError('chat_ocr_continuous: beam search does not go through ContinuousPipeline (use chat_ocr_pages)')
         if draft is not None:
             drafting.refuse('ContinuousPipeline (chat_ocr_continuous: its rows stop on the device, its worker never waits for a step)')
+        if parse_returns(dict(generation_config)) > 1:
+            raise NotImplementedError('chat_ocr_continuous: num_return_sequences > 1 does not go through ContinuousPipeline, which owns its caches '
+                                      '(use chat_ocr_pages)')
         from .continuous import ContinuousPipeline
         _, lpn = self._score_args(generation_config, return_scores)
         images = list(images)
@@ -913,7 +973,7 @@ class InternVLChatModel:
         return torch.cat([sid[:pi], img, sid[pi + 1:pr], torch.full((n_ref,), self.aligned_token_id, dtype=sid.dtype), sid[pr + 1:]])
 
     def _ocr_embeds(self, tokenizer, detect_model, images, question, generation_config, boxes_list, use_p, drop_zero, hard_vq,
-                    IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, tiles=None, errors='raise', mark=None):
+                    IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, tiles=None, errors='raise', mark=None, allow_returns=False):
         """Everything of chat_ocr_pages before the language model: the pages' prompt embeddings with both splices done, and
         meta = {n, ok: batch indices of the pages in `embeds`, failed: {index: exception}, max_new, eos, template}.  The host side (decode, boxes, tiles) is
         pageio.PageFeeder's; nothing on this thread's stream waits for a pageable copy."""
@@ -923,7 +983,7 @@ class InternVLChatModel:
         template = get_conv_template(self.template)
         generation_config = dict(generation_config)
         generation_config['eos_token_id'] = tokenizer.convert_tokens_to_ids(template.sep)
-        max_new, eos, sp = self._gen_args(generation_config, allow_beams=True)      # (the pipelines that call this have refused beams on entry)
+        max_new, eos, sp = self._gen_args(generation_config, allow_beams=True, allow_returns=allow_returns)      # (the pipelines that call this have refused beams on entry)
         meta = {'n': len(images), 'ok': [], 'failed': dict(batch.failed), 'max_new': max_new, 'eos': eos, 'template': template, 'sampling': sp,
                 'constraints': constraints_parse(generation_config, eos)}
         if not batch.ok:
@@ -1007,7 +1067,7 @@ class InternVLChatModel:
 
     def generate_pages(self, embeds_list, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0,
                        check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0, num_beams=1, length_penalty=1.0, early_stopping=False,
-                       constraints=None, drafts=None):
+                       constraints=None, drafts=None, num_return_sequences=1):
         """Prefill every page, then decode all unfinished pages as ONE batch per step: the 14.7 GB of LLM weights are
         streamed once per step for all pages.  Per page the ids equal the single-page greedy result.
         sampling: None (every page greedy), one sampling.SamplingParams for every page, or a list with one entry (or None: greedy) per page;
@@ -1023,10 +1083,25 @@ class InternVLChatModel:
         the batch keep their ids bit for bit.
         drafts: None, or a list with one entry per page -- a list of ids that guesses the page's answer, or None -- checked several per decode step
         (generation.decode_rows_drafted); every page's ids are what they are without drafts.  Greedy pages on a bf16 cache, without scores, constraints
-        or beams."""
+        or beams.
+        num_return_sequences = n > 1: n sampled answers per page from ONE prefill of it (_generate_pages_fanout; P * n <= 64).  The return value nests:
+        ids[i][j] is sample j of page i -- exactly what this call gives for page i alone with seeds=[seeds[i * n + j]] -- and with logprobs the scores
+        nest the same way.  seeds: P * n entries (default page_seeds(P * n): sampling.fan_seeds).  Sampled pages on a bf16 cache, without constraints,
+        drafts or beams."""
         P = len(embeds_list)
         cons = constraints_per_page(constraints, P)
         beams = parse_beams(dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping))
+        sps = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * P
+        nret = 1                                    # (1: today's path, nothing new is parsed)
+        if not (num_return_sequences is None or (type(num_return_sequences) is int and num_return_sequences == 1)):
+            nret = parse_returns(dict(num_return_sequences=num_return_sequences, num_beams=num_beams, do_sample=bool(sps) and all(sp is not None for sp in sps)))
+        if nret > 1:
+            if drafts is not None:
+                drafting.refuse(f'num_return_sequences={nret} (sampled answers)')
+            if any(c is not None for c in cons):
+                raise NotImplementedError('generate_pages: logits constraints on a sampled page are not implemented (greedy decoding only)')
+            return self._generate_pages_fanout(embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds,
+                                               scores_per_page(logprobs, P), nret)
         if drafts is not None:
             if len(drafts) != P:
                 raise ValueError(f'drafts: {len(drafts)} entries for {P} pages')
@@ -1101,6 +1176,41 @@ class InternVLChatModel:
         toks, ts = self.score_pages([prompt], [scoring.answer_to_ids(tokenizer, answer)], penalty, top_n, eos_token_id=gc['eos_token_id'], score_eos=score_eos)
         return scoring.response_scores(tokenizer, toks[0], ts[0])
 
+    def _generate_pages_fanout(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds, lpn, n):
+        """generate_pages with n > 1 sampled answers per page: page i is prefilled ONCE, into sequence fan_slots(i, n)[0] with the seed of its sample 0, and
+        KVCache.fanout gives its other n - 1 sequences the cached prompt and each its own first id from the prefill's raw last row; the P * n rows then
+        decode as one batch per step through decode_rows.  A decode row's bits do not depend on its batch and a draw depends only on (seed, step, row,
+        history), so sample (i, j) is the lone call's answer for page i with seed seeds[i * n + j], id for id."""
+        P = len(embeds_list)
+        check_rows(P, n)
+        if self.kv_cache_dtype != 'bf16':
+            raise NotImplementedError(f"num_return_sequences={n} with kv_cache_dtype='e4m3': the fan-out copies bf16 rows (cr_kv_fanout); call the entry "
+                                      'point n times, or use a bf16 cache')
+        if seeds is None:
+            seeds = [sd for row in fan_seeds(P, n) for sd in row]
+        if len(seeds) != P * n:
+            raise ValueError(f'seeds: {len(seeds)} entries for {P} pages x {n} returned sequences')
+        for e in embeds_list:
+            check_fits(e.shape[0], max_new_tokens, self.max_tokens)
+        kv = self.kv(P * n)
+        kv.reset()
+        first = [fan_slots(i, n)[0] for i in range(P)]
+        for i, sp in enumerate(sps):
+            kv.set_sampling(first[i], sp.temperature, sp.top_k, sp.top_p, int(seeds[i * n]))
+            if lpn[i]:
+                kv.set_logprobs(first[i], lpn[i])
+        for i0 in range(0, P, prefill_batch):
+            idx = list(range(i0, min(P, i0 + prefill_batch)))
+            rows = self.engine.prefill_batch(kv, [first[i] for i in idx], [embeds_list[i] for i in idx], penalty=repetition_penalty, want_logits=True)
+            for k, i in enumerate(idx):
+                kv.fanout(first[i], fan_slots(i, n)[1:], seeds[i * n + 1:(i + 1) * n], rows[k])
+        outs = decode_rows(self.engine, kv, list(range(P * n)), max_new_tokens, eos_token_id, repetition_penalty, check_every)
+        ids = [outs[i * n:(i + 1) * n] for i in range(P)]
+        if not any(lpn):
+            return ids
+        ts = read_scores(kv, [m for m in lpn for _ in range(n)], outs)
+        return ids, [ts[i * n:(i + 1) * n] for i in range(P)]
+
     def _generate_pages_beams(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams):
         """generate_pages with beam search: page i is the beam group of sequences beam_slots(i, B); the done flags are read every check_every steps,
         where the greedy loop reads EOS."""
@@ -1141,6 +1251,11 @@ class InternVLChatModel:
 def beam_slots(page, num_beams):
     """Cache sequences of page `page` when every page of a batch runs `num_beams` beams: consecutive, the group's first sequence first."""
     return list(range(page * num_beams, (page + 1) * num_beams))
+
+
+def fan_slots(page, n):
+    """Cache sequences of page `page` when every page of a batch returns `n` sampled answers: consecutive, the prefilled one (sample 0) first."""
+    return list(range(page * n, (page + 1) * n))
 
 
 def load_boxes_json(path):

@@ -381,6 +381,8 @@ def sharded_generate(model, page_tiles, char_tiles, input_ids, *, img_id, ref_id
     if generate_kw.get('drafts') is not None or generate_kw.get('draft_ids') is not None:
         from .draft import refuse
         refuse('sharded_generate (a page and its draft may live on different ranks)')
+    if generate_kw.get('num_return_sequences', 1) not in (1, None):
+        raise NotImplementedError('sharded_generate: num_return_sequences > 1 is not implemented across GPUs (every rank owns its cache; use generate_pages on one)')
     from .constraints import parse as constraints_parse
     if constraints_parse(generate_kw, 0) is not None:
         raise NotImplementedError('sharded_generate: logits constraints are not implemented across GPUs (use generate_pages on one)')
@@ -461,6 +463,9 @@ def chat_ocr_pages_sharded(model, tokenizer, detect_model, images, question, gen
     from .constraints import parse as constraints_parse
     if constraints_parse(dict(generation_config), 0) is not None:
         raise NotImplementedError('chat_ocr_pages_sharded: logits constraints are not implemented across GPUs (use chat_ocr_pages / chat_ocr_continuous on one)')
+    if dict(generation_config).get('num_return_sequences', 1) not in (1, None):
+        raise NotImplementedError('chat_ocr_pages_sharded: num_return_sequences > 1 is not implemented across GPUs (every rank owns its cache; use '
+                                  'chat_ocr_pages on one)')
     if dict(generation_config).get('do_sample', False):
         raise NotImplementedError('chat_ocr_pages_sharded: do_sample=True is not implemented across GPUs yet (it needs the per-call seed broadcast '
                                   'to every rank); use chat_ocr_pages / chat_ocr_continuous on one GPU')

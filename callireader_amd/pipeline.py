@@ -102,12 +102,15 @@ class PagePipeline:
             raise out
         return out
 
-    def start(self, embeds_list, budgets=None, sampling=None, seeds=None, logprobs=0, constraints=None):
+    def start(self, embeds_list, budgets=None, sampling=None, seeds=None, logprobs=0, constraints=None, num_return_sequences=1):
         """Prefill a batch on the caller's stream and hand it to the decode thread; returns the previous batch's ids (None if there
         was none), waiting for them if they are not there yet.  budgets: optional per-page max_new_tokens (<= the pipeline's): a page
         leaves the batch at the first EOS check at or past its budget and its ids are cut there, as its own generate_pages call would.
         sampling / seeds / logprobs: as generate_pages takes them; a batch started with a non-zero logprobs is returned as (ids, scores).
         constraints: None, one constraints.Constraints for every page, or a list with one (or None) per page."""
+        if num_return_sequences not in (1, None):
+            raise NotImplementedError(f'num_return_sequences={num_return_sequences}: PagePipeline owns its two caches, one sequence per page (several sampled '
+                                      'answers per page: generate_pages / chat_ocr_pages)')
         P = len(embeds_list)
         per_page = per_page_sampling(sampling, seeds, P)
         lpn = scores_per_page(logprobs, P)

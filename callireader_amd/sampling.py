@@ -17,7 +17,10 @@ DEFAULT_TEMPERATURE, DEFAULT_TOP_K, DEFAULT_TOP_P = 1.0, 50, 1.0
 UNSUPPORTED = {'min_p': None, 'typical_p': 1.0, 'epsilon_cutoff': 0.0, 'eta_cutoff': 0.0, 'no_repeat_ngram_size': 0,
                'encoder_no_repeat_ngram_size': 0, 'bad_words_ids': None, 'sequence_bias': None, 'suppress_tokens': None,
                'begin_suppress_tokens': None, 'diversity_penalty': 0.0, 'num_beam_groups': 1, 'penalty_alpha': None, 'guidance_scale': None,
-               'num_return_sequences': 1, 'renormalize_logits': False}
+               'renormalize_logits': False}
+
+# rows of one batched decode step (the decode kernels' limit): pages x returned sequences of one call
+MAX_ROWS = 64
 
 
 @dataclass(frozen=True)
@@ -103,10 +106,40 @@ def parse_beams(kwargs):
     return BeamParams(int(b), 1.0 if lp is None else lp, False if es is None else es)
 
 
+def parse_returns(kwargs):
+    """num_return_sequences of a generation config: n >= 1 sampled answers per page (1, the default: today's single answer).  ValueError for a value
+    that is no integer >= 1, and -- transformers 4.45.2's GenerationConfig.validate, in its words -- for n > 1 with do_sample=False and num_beams=1.
+    With num_beams > 1 it is parse_beams that speaks (n > 1 is not implemented there)."""
+    n = kwargs.get('num_return_sequences', 1)
+    if n is None:
+        n = 1
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f'`num_return_sequences` has to be a positive integer, but is {n!r}')
+    n = int(n)
+    if n > 1 and parse_beams(kwargs) is None and not kwargs.get('do_sample', False):
+        raise ValueError(f'Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n}).')
+    return n
+
+
+def check_rows(P, n):
+    """P pages x n returned sequences have to fit one batched decode step."""
+    if P * n > MAX_ROWS:
+        raise ValueError(f'{P} pages x {n} returned sequences = {P * n} decode rows: at most {MAX_ROWS} (the batched decode kernels)')
+
+
+def fan_seeds(P, n, base=None):
+    """Seeds of one call over P pages with n returned sequences each, [P][n]: sample j of page i has page_seeds(P * n, base)[i * n + j] -- the row order
+    of transformers' repeat_interleave expansion.  With n = 1 these are page_seeds(P, base)."""
+    flat = page_seeds(P * n, base)
+    return [flat[i * n:(i + 1) * n] for i in range(P)]
+
+
 def parse(kwargs):
     """SamplingParams for do_sample=True, None for greedy or beam search (do_sample=False ignores temperature, top_k and top_p, as transformers does).
-    Raises what parse_beams raises for num_beams, and NotImplementedError for any other sampling knob set to a non-default value."""
+    Raises what parse_beams raises for num_beams, what parse_returns raises for num_return_sequences (the count itself is parse_returns'), and
+    NotImplementedError for any other sampling knob set to a non-default value."""
     parse_beams(kwargs)
+    parse_returns(kwargs)
     if not kwargs.get('do_sample', False):
         return None
     for k, off in UNSUPPORTED.items():

@@ -103,6 +103,16 @@ def generate_output(sequences, ts=None):
     return GenerateOutput(sequences, torch.from_numpy(ts.logprobs)[None], torch.from_numpy(ts.top_ids)[None], torch.from_numpy(ts.top_logprobs)[None], ts)
 
 
+def generate_outputs(sequences, tss=None):
+    """The GenerateOutput of num_return_sequences = n > 1: `sequences` [n, L] (right-padded), and with scores the per-sequence fields as LISTS of n --
+    token_logprobs[j] [T_j], top_ids[j] / top_logprobs[j] [T_j, k] for sample j's own T_j ids, `scores` the n TokenScores."""
+    import torch
+    if tss is None:
+        return GenerateOutput(sequences, None, None, None, None)
+    return GenerateOutput(sequences, [torch.from_numpy(t.logprobs) for t in tss], [torch.from_numpy(t.top_ids) for t in tss],
+                          [torch.from_numpy(t.top_logprobs) for t in tss], list(tss))
+
+
 @dataclass
 class TokenScore:
     id: int

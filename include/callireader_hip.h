@@ -167,6 +167,23 @@ int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream);
  * a destination equal to src, repeated or out of range, or an e4m3 cache (left out, as for the beam re-order: it keeps no bf16 prefix for a continued
  * prefill to read anyway); CR_ERR_STATE for a beam-group member on either side.  Enqueued on `stream`.  Added within ABI v13. */
 int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream);
+/* Several sampled answers from one prefill.  `src` has just been prefilled (cr_llm_prefill / cr_llm_prefill_batch) with sampling on: S cached positions, ONE
+ * generated id.  Each of the n_dst sequences dsts_host[] (host array) becomes what a lone prefill of the same prompt into it would have left behind
+ * cr_kv_set_sampling(dst, src's temperature / top_k / top_p, seeds_host[j]) -- and cr_kv_set_logprobs(dst, src's top_n) if src records scores:
+ *   - cache positions [0, S) of every layer, KV head, K and V are src's bits, the cached length is S (positions >= S of a destination are not written);
+ *   - it holds one generated id, drawn at step 0 with seeds_host[j] from last_logits (device, [vocab] fp32): the raw last row the prefill of src returned
+ *     through its `logits` argument.  The thresholds and the draw are the sampling pick's own code: the id is cr_op_sample's on that row, seed and step.
+ *     The first pick sees no history, so no repetition penalty applies, and the row is read only;
+ *   - its stop criteria (cr_kv_set_stop) are src's and have been applied to that id: a sequence whose first id is the EOS id, or whose budget is 1, is
+ *     pushed onto the finished queue;
+ *   - if src records token scores, slot 0 holds the id's log-probability and the row's top-n, bit-equal to what the prefill recorded for src's row.
+ * src is not changed.  Launches: the copy kernel of cr_kv_fork (the source read once), one small state kernel, ONE pick launch for all destinations (a
+ * workgroup of 1024 each), and with scores one reduction of the row and one merge per destination.  No LM head, no float atomics, enqueued on `stream`
+ * with no device-wide synchronisation (the first scored call of a cache allocates its partials and synchronises `stream` once).
+ * Checked before anything is enqueued, nothing changes on refusal: CR_ERR_ARG for n_dst outside 1..min(n_seqs - 1, 63), a destination equal to src,
+ * repeated or out of range, an e4m3 cache (as for cr_kv_fork), null seeds_host or last_logits; CR_ERR_STATE for a beam-group member on either side, a
+ * src that does not sample (temperature 0), that carries logits constraints, or that does not hold exactly one generated id.  Added within ABI v13. */
+int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const uint64_t* seeds_host, const float* last_logits, void* stream);
 /* One cached position as the reference's tuple cache holds it (InternVL/modeling_internlm2.py:383-388, K after RoPE):
  * out [8 kv heads][128] bf16 (device) = past_key_values[layer][which][seq, :, pos, :]; which 0 = K, 1 = V.  Parity tests. */
 int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, void* stream);
