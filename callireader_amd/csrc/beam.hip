@@ -40,20 +40,20 @@ constexpr int KMAX = 2 * BEAM_MAX;
 // (value, index) order of candidates: larger value first, the lower index on an exact tie.  NaN compares false either way.
 __device__ __forceinline__ bool before(float v, int64_t i, float v2, int64_t i2) { return v > v2 || (v == v2 && i < i2); }
 
-__global__ __launch_bounds__(1024) void beam_cand_kernel(BeamLaunch p) {
+__global__ __launch_bounds__(1024) void beam_cand_kernel(Rows rw, SeqState s, BeamLaunch p) {
     __shared__ float sf[1024];
     __shared__ double sd[1024];
     __shared__ int si[1024];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const int seq = p.seqs ? p.seqs[row] : row;
-    const int f = p.grp[seq];
+    const int seq = rw.seq(row);
+    const int f = s.bgrp[seq];
     if (f < 0) return;
     const BeamState* bs = p.state + f;
     if (bs->done) return;
-    const int V = p.vocab, K = 2 * bs->B;
+    const int V = rw.vocab, K = 2 * bs->B;
     const float run = bs->run[seq - f];
-    float* lg = p.logits + (int64_t)row * p.ld;
-    float* og = p.orig ? p.orig + (int64_t)row * p.ld : nullptr;
+    float* lg = rw.row(row);
+    float* og = rw.orig_row(row);
     // maximum
     float m = -INFINITY;
     for (int i = tid; i < V; i += 1024) { const float z = lg[i]; m = z > m ? z : m; }
@@ -65,9 +65,9 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamLaunch p) {
     }
     m = sf[0];
     // sum of exp(z - m) over the entries above -inf: thread order, then a fixed tree
-    double s = 0.0;
-    for (int i = tid; i < V; i += 1024) { const float z = lg[i]; if (z != -INFINITY) s += (double)expf(z - m); }
-    sd[tid] = s;
+    double sum = 0.0;
+    for (int i = tid; i < V; i += 1024) { const float z = lg[i]; if (z != -INFINITY) sum += (double)expf(z - m); }
+    sd[tid] = sum;
     __syncthreads();
     for (int o = 512; o > 0; o >>= 1) {
         if (tid < o) sd[tid] += sd[tid + o];
@@ -80,8 +80,8 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamLaunch p) {
         if (og) og[i] = l;
     }
     __syncthreads();
-    const int ng = p.ngen[seq] < p.gen_cap ? p.ngen[seq] : p.gen_cap;
-    if (p.penalty != 1.0f && ng > 0) apply_penalty(lg, p.gen + (int64_t)seq * p.gen_cap, ng, p.penalty, tid, og);
+    const int ng = s.ngen[seq] < s.gen_cap ? s.ngen[seq] : s.gen_cap;
+    if (rw.penalty != 1.0f && ng > 0) apply_penalty(lg, s.hist(seq), ng, rw.penalty, tid, og);
     // the row's K largest acc = run + lp: round r finds the best (value, id) strictly after round r - 1's winner
     float pv = INFINITY; int pi = -1;
     for (int r = 0; r < K; r++) {
@@ -102,20 +102,20 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamLaunch p) {
     }
 }
 
-__global__ __launch_bounds__(64) void beam_select_kernel(BeamLaunch p) {
+__global__ __launch_bounds__(64) void beam_select_kernel(Rows rw, SeqState s, BeamLaunch p) {
     __shared__ float tv[KMAX];
     __shared__ int tb[KMAX], ti[KMAX];
     __shared__ int ncopy, cp_phys[BEAM_MAX], cp_src[BEAM_MAX], cp_id[BEAM_MAX];
     const int row = blockIdx.x, lane = threadIdx.x;
-    const int seq = p.seqs ? p.seqs[row] : row;
-    const int f = p.grp[seq];
+    const int seq = rw.seq(row);
+    const int f = s.bgrp[seq];
     if (f < 0 || seq != f) return;
     BeamState* bs = p.state + f;
     const int B = bs->B, K = 2 * B, nrows = p.first_only ? 1 : B;
     if (bs->done) {
         if (lane == 0) {
             bs->skip = 1;
-            if (p.lens) for (int j = 0; j < nrows; j++) p.lens[f + j] += p.len_add;
+            if (s.len) for (int j = 0; j < nrows; j++) s.len[f + j] += p.len_add;
         }
         return;
     }
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamLaunch p) {
         if (c < nrows * K) {
             const int b = c / K, k = c % K;
             const int id = p.cand_i[(row + b) * KMAX + k];
-            if (id != 0x7fffffff) { cv[e] = p.cand_v[(row + b) * KMAX + k]; cx[e] = (int64_t)b * p.vocab + id; }
+            if (id != 0x7fffffff) { cv[e] = p.cand_v[(row + b) * KMAX + k]; cx[e] = (int64_t)b * rw.vocab + id; }
         }
     }
     float pv = INFINITY; int64_t px = -1;
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamLaunch p) {
         pv = bv; px = bx;
         if (lane == 0) {
             const bool have = bx != INT64_MAX;
-            tv[r] = bv; tb[r] = have ? (int)(bx / p.vocab) : 0; ti[r] = have ? (int)(bx % p.vocab) : 0;
+            tv[r] = bv; tb[r] = have ? (int)(bx / rw.vocab) : 0; ti[r] = have ? (int)(bx % rw.vocab) : 0;
         }
     }
     __syncthreads();
@@ -190,24 +190,17 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamLaunch p) {
         const int heur = bs->heur_ok && best > worst;
         const int stop = !heur || (bs->n_fin == B && early == 1) || nfinishing == K;
         bs->heur_ok = heur; bs->g = g + 1; bs->skip = 0; bs->done = stop;
-        if (p.lens) for (int j = 0; j < nrows; j++) p.lens[f + j] += p.len_add;
-        if (stop && p.stop) {
-            int32_t* at = p.stop + 1 + p.n_seqs;
-            if (at[f] == 0) {
-                at[f] = bs->n_fin > 0 ? bs->fin_len[0] : g + 1;
-                const int k = atomicAdd(p.stop, 1);
-                p.stop[1 + k % p.n_seqs] = f;
-            }
-        }
+        if (s.len) for (int j = 0; j < nrows; j++) s.len[f + j] += p.len_add;
+        if (stop) s.stop.record(f, bs->n_fin > 0 ? bs->fin_len[0] : g + 1);
         ncopy = nc;
     }
     __syncthreads();
     // the new hypotheses' ids: the source beam's history + the id.  In order: a later one of the same step may take the row of an earlier one
     for (int c = 0; c < ncopy; c++) {
-        int64_t* dst = p.fin_ids + (int64_t)(f + cp_phys[c]) * p.gen_cap;
-        const int64_t* srcp = p.gen + (int64_t)(f + cp_src[c]) * p.gen_cap;
-        for (int i = lane; i < g && i < p.gen_cap; i += 64) dst[i] = srcp[i];
-        if (lane == 0 && g < p.gen_cap) dst[g] = cp_id[c];
+        int64_t* dst = p.fin_ids + (int64_t)(f + cp_phys[c]) * s.gen_cap;
+        const int64_t* srcp = s.hist(f + cp_src[c]);
+        for (int i = lane; i < g && i < s.gen_cap; i += 64) dst[i] = srcp[i];
+        if (lane == 0 && g < s.gen_cap) dst[g] = cp_id[c];
         __syncthreads();
     }
 }
@@ -216,9 +209,9 @@ constexpr int REORDER_GROUPS = 32;      // groups per launch of the re-order (th
 struct BeamGroups { int row[REORDER_GROUPS]; };
 
 // grid (position chunks of 16, layers * 16 + 1, groups), 256 threads: thread = (position, 16-byte column) of one (layer, KV head, K | V); the last y moves the ids
-__global__ __launch_bounds__(256) void beam_reorder_kernel(BeamLaunch p, BeamCache c, BeamGroups gr, int append) {
+__global__ __launch_bounds__(256) void beam_reorder_kernel(Rows rw, SeqState s, BeamLaunch p, BeamCache c, BeamGroups gr, int append) {
     const int row = gr.row[blockIdx.z], tid = threadIdx.x;
-    const int f = p.seqs ? p.seqs[row] : row;          // the group's first sequence
+    const int f = rw.seq(row);                         // the group's first sequence
     BeamState* bs = p.state + f;
     if (bs->skip && append) return;
     const int B = bs->B;
@@ -228,26 +221,26 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(BeamLaunch p, BeamCac
     const int y = blockIdx.y;
     if (y == c.layers * 16) {
         if (blockIdx.x != 0) return;
-        const int n_old = append ? bs->g - 1 : p.ngen[f + src[0]];      // (without a step every beam of the group holds as many ids)
-        for (int i = tid; i < n_old && i < p.gen_cap; i += 256) {
+        const int n_old = append ? bs->g - 1 : s.ngen[f + src[0]];      // (without a step every beam of the group holds as many ids)
+        for (int i = tid; i < n_old && i < s.gen_cap; i += 256) {
             int64_t r[BEAM_MAX];
 #pragma unroll
-            for (int j = 0; j < BEAM_MAX; j++) if (j < B) r[j] = p.gen[(int64_t)(f + src[j]) * p.gen_cap + i];
+            for (int j = 0; j < BEAM_MAX; j++) if (j < B) r[j] = s.hist(f + src[j])[i];
 #pragma unroll
-            for (int j = 0; j < BEAM_MAX; j++) if (j < B && src[j] != j) p.gen[(int64_t)(f + j) * p.gen_cap + i] = r[j];
+            for (int j = 0; j < BEAM_MAX; j++) if (j < B && src[j] != j) s.hist(f + j)[i] = r[j];
         }
         if (tid < B) {
-            if (append && n_old < p.gen_cap) { p.gen[(int64_t)(f + tid) * p.gen_cap + n_old] = bs->next_id[tid]; p.ngen[f + tid] = n_old + 1; }
-            if (!append) p.ngen[f + tid] = n_old;
-            if (p.first_only && p.lens) {                                // the fan-out: the prompt's length for every beam (lens[f] is not written here)
-                p.lens[f + tid] = p.lens[f];
-                if (tid == 0) bs->prompt = p.lens[f];
+            if (append && n_old < s.gen_cap) { s.hist(f + tid)[n_old] = bs->next_id[tid]; s.ngen[f + tid] = n_old + 1; }
+            if (!append) s.ngen[f + tid] = n_old;
+            if (p.first_only && s.len) {                                 // the fan-out: the prompt's length for every beam (len[f] is not written here)
+                s.len[f + tid] = s.len[f];
+                if (tid == 0) bs->prompt = s.len[f];
             }
         }
         return;
     }
     if (!c.k) return;
-    const int len = p.lens[f], from = p.first_only ? 0 : bs->prompt;
+    const int len = s.len[f], from = p.first_only ? 0 : bs->prompt;
     const int pos = from + blockIdx.x * 16 + (tid >> 4), col = tid & 15;
     if (pos >= len) return;
     const int layer = y >> 4, h = (y >> 1) & 7;
@@ -274,20 +267,20 @@ __global__ __launch_bounds__(64) void set_beam_kernel(BeamState* state, int32_t*
 
 size_t beam_scratch_bytes(int rows) { return (size_t)rows * KMAX * 8; }
 
-int launch_beam_step(const BeamLaunch& p, hipStream_t st) {
-    hipLaunchKernelGGL(beam_cand_kernel, dim3(p.rows), dim3(1024), 0, st, p);
-    hipLaunchKernelGGL(beam_select_kernel, dim3(p.rows), dim3(64), 0, st, p);
+int launch_beam_step(const Rows& r, const SeqState& s, const BeamLaunch& p, hipStream_t st) {
+    hipLaunchKernelGGL(beam_cand_kernel, dim3(r.n), dim3(1024), 0, st, r, s, p);
+    hipLaunchKernelGGL(beam_select_kernel, dim3(r.n), dim3(64), 0, st, r, s, p);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
 
-int launch_beam_reorder(const BeamLaunch& p, const BeamCache& c, const int* first_rows, int n_groups, int max_span, int append, hipStream_t st) {
+int launch_beam_reorder(const Rows& r, const SeqState& s, const BeamLaunch& p, const BeamCache& c, const int* first_rows, int n_groups, int max_span, int append, hipStream_t st) {
     const int chunks = max_span > 0 ? (max_span + 15) / 16 : 1;
     for (int g0 = 0; g0 < n_groups; g0 += REORDER_GROUPS) {
         const int n = n_groups - g0 < REORDER_GROUPS ? n_groups - g0 : REORDER_GROUPS;
         BeamGroups gr{};
         for (int i = 0; i < n; i++) gr.row[i] = first_rows[g0 + i];
-        hipLaunchKernelGGL(beam_reorder_kernel, dim3(chunks, c.layers * 16 + 1, n), dim3(256), 0, st, p, c, gr, append);
+        hipLaunchKernelGGL(beam_reorder_kernel, dim3(chunks, c.layers * 16 + 1, n), dim3(256), 0, st, r, s, p, c, gr, append);
     }
     CR_HIP(hipGetLastError());
     return CR_OK;
@@ -308,17 +301,17 @@ extern "C" int cr_op_beam_step(float* logits, int n, int vocab, int64_t* history
     char* scratch = nullptr;
     const size_t cand = (beam_scratch_bytes(n) + 255) & ~(size_t)255;
     if (hipMalloc((void**)&scratch, cand + (deep ? (size_t)n * vocab * 4 : 0)) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "cr_op_beam_step: scratch");
-    BeamLaunch p{};
-    p.logits = logits; p.ld = vocab; p.vocab = vocab; p.penalty = penalty; p.rows = n; p.grp = group; p.state = (BeamState*)state;
-    p.gen = history; p.ngen = hist_len; p.gen_cap = hist_cap; p.orig = deep ? (float*)(scratch + cand) : nullptr;
-    p.cand_v = (float*)scratch; p.cand_i = (int32_t*)(scratch + (size_t)n * KMAX * 4); p.fin_ids = fin_ids;
-    int rc = launch_beam_step(p, st);
+    const Rows r{logits, vocab, vocab, n, nullptr, deep ? (float*)(scratch + cand) : nullptr, penalty};
+    SeqState s{};                                            // row = sequence; no cached lengths and no finished queue
+    s.gen = history; s.ngen = hist_len; s.gen_cap = hist_cap; s.bgrp = const_cast<int32_t*>(group);
+    const BeamLaunch p{(BeamState*)state, 0, (float*)scratch, (int32_t*)(scratch + (size_t)n * KMAX * 4), fin_ids, 0};
+    int rc = launch_beam_step(r, s, p, st);
     if (rc == CR_OK) {      // the groups' first rows: the entry cannot see the device array, so it reads it back once (a test entry)
         std::vector<int32_t> hg(n);
         if (hipMemcpyAsync(hg.data(), group, (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = CR_ERR_HIP;
         std::vector<int> firsts;
         for (int i = 0; i < n && rc == CR_OK; i++) if (hg[i] == i) firsts.push_back(i);
-        if (rc == CR_OK && !firsts.empty()) rc = launch_beam_reorder(p, BeamCache{}, firsts.data(), (int)firsts.size(), 0, 1, st);
+        if (rc == CR_OK && !firsts.empty()) rc = launch_beam_reorder(r, s, p, BeamCache{}, firsts.data(), (int)firsts.size(), 0, 1, st);
     }
     hipStreamSynchronize(st);
     hipFree(scratch);

@@ -1,6 +1,6 @@
 // Beam search (beam.hip): the kernels behind cr_kv_set_beam / cr_op_beam_step
 #pragma once
-#include "common.hpp"
+#include "seqstate.hpp"
 
 constexpr int BEAM_MAX = 8;            // num_beams 2..8, K = 2 * num_beams candidates per step
 
@@ -25,29 +25,26 @@ struct BeamState {
 };
 static_assert(sizeof(BeamState) == 256, "BeamState is 64 words");
 
-// One step over `rows` rows of fp32 logits (turned into penalised log-probabilities in place).  Row r belongs to sequence seqs[r] (seqs NULL: r); grp[seq] is the
-// first sequence of its beam group, or < 0 for a row that is no beam (left alone).  A group's rows are consecutive, in beam order, from its first sequence's
-// row; first_only: the launch holds only the group's first row (the prefill: step 0, whose candidates all come from that row).
+// One step over the rows r of fp32 logits (turned into penalised log-probabilities in place; r.orig: scratch, not a copy).  s.bgrp[seq] is the first sequence of
+// the row's beam group, or < 0 for a row that is no beam (left alone).  A group's rows are consecutive, in beam order, from its first sequence's row;
+// first_only: the launch holds only the group's first row (the prefill: step 0, whose candidates all come from that row).  s.len (may be NULL): every sequence
+// of a group gets len_add; s.stop (may be null): the cache's finished queue.  What the stage alone owns:
 struct BeamLaunch {
-    float* logits; int64_t ld; int vocab; float penalty; int rows;
-    const int32_t* seqs; const int32_t* grp; BeamState* state;
-    int64_t* gen; int32_t* ngen; int gen_cap;      // id histories [.][gen_cap] and their counts
-    int32_t* lens; int len_add;                    // cached lengths (may be NULL): every sequence of a group gets len_add
-    float* orig;                                   // [rows][ld] scratch for histories of more than 4096 ids (else NULL)
+    BeamState* state;
+    int len_add;
     float* cand_v; int32_t* cand_i;                // [rows][2 * BEAM_MAX] scratch: the rows' own candidates
     int64_t* fin_ids;                              // [.][gen_cap] ids of the finished slots, row = first sequence + fin_phys
-    int32_t* stop; int n_seqs;                     // the cache's finished queue (may be NULL)
     int first_only;
 };
-// bf16 cache [layers][n_seqs][8][max_tokens][128] for the re-order (k NULL: id histories only)
+// bf16 cache [layers][n_seqs][8][max_tokens][128] for the re-order (k NULL: id histories only) and for kv.hip's fork
 struct BeamCache { bf16* k; bf16* v; int64_t per_layer; int layers, max_tokens; };
 
 size_t beam_scratch_bytes(int rows);
 // candidates + select
-int launch_beam_step(const BeamLaunch& p, hipStream_t st);
-// re-order: sequence f + j of every group takes cache positions [from, lens[f]) and the id history of f + next_src[j]; from = 0 with p.first_only (the
+int launch_beam_step(const Rows& r, const SeqState& s, const BeamLaunch& p, hipStream_t st);
+// re-order: sequence f + j of every group takes cache positions [from, s.len[f]) and the id history of f + next_src[j]; from = 0 with p.first_only (the
 // fan-out, which also gives the group's other sequences the first one's length), else the group's prompt length.  The launch runs over the groups only:
 // first_rows[0 .. n_groups) (host) = the launch row of each group's first sequence; max_span = the most positions any of them moves.
 // append: the step's new ids go onto the histories (a step); 0: the histories' own counts are kept (cr_kv_beam_reorder).
-int launch_beam_reorder(const BeamLaunch& p, const BeamCache& c, const int* first_rows, int n_groups, int max_span, int append, hipStream_t st);
+int launch_beam_reorder(const Rows& r, const SeqState& s, const BeamLaunch& p, const BeamCache& c, const int* first_rows, int n_groups, int max_span, int append, hipStream_t st);
 int launch_set_beam(BeamState* state, int32_t* grp, int first, int B, float lp, int early, int eos, int max_new, hipStream_t st);

@@ -137,10 +137,6 @@ __device__ __forceinline__ uint2 pack8_e4m3(const bf16x8& v, float inv) {
     return make_uint2(lo, hi);
 }
 
-// The id histories the launch functions of the pick stage read (host side): row r of a launch belongs to sequence seqs[r] (device; NULL: r itself), whose
-// ngen[seq] ids are gen[seq][0 .. gen_cap)
-struct Hist { const int32_t* seqs; int64_t* gen; int32_t* ngen; int gen_cap; };
-
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -27,14 +27,13 @@
 
 namespace {
 
-__global__ __launch_bounds__(1024) void constrain_kernel(float* __restrict__ logits, int64_t ld, int vocab, const int32_t* __restrict__ seqs,
-                                                         const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen, int gen_cap, ConTables t) {
+__global__ __launch_bounds__(1024) void constrain_kernel(Rows r, SeqState s, ConTables t) {
     extern __shared__ uint32_t ban[];      // [mw]
     __shared__ int cnt[16];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int seq = seqs ? seqs[row] : row;
+    const int seq = r.seq(row), vocab = r.vocab;
     const int cs = t.per_seq ? seq : 0;
-    if (!t.on[cs]) return;                 // the whole workgroup: an unconstrained row is left untouched
+    if (!s.con_on[cs]) return;                // the whole workgroup: an unconstrained row is left untouched
     const int32_t* blk = t.blk + (int64_t)cs * t.stride;
     const int mw = (vocab + 31) >> 5;
     const int N = blk[0], m = blk[1], eos = blk[2], n_words = blk[3], has_mask = blk[4], has_begin = blk[5];
@@ -42,9 +41,9 @@ __global__ __launch_bounds__(1024) void constrain_kernel(float* __restrict__ log
     const uint32_t* bmask = mask + mw;
     const int32_t* woff = blk + CON_HDR + 2 * mw;
     const int32_t* wids = woff + CON_MAX_WORDS + 1;
-    int ng = ngen[seq];
-    ng = ng < gen_cap ? ng : gen_cap;
-    const int64_t* g = gen + (int64_t)seq * gen_cap;
+    int ng = s.ngen[seq];
+    ng = ng < s.gen_cap ? ng : s.gen_cap;
+    const int64_t* __restrict__ g = s.hist(seq);
     const bool begin = has_begin && ng == 0;
     for (int w = tid; w < mw; w += 1024) {
         uint32_t u = has_mask ? mask[w] : 0u;
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(1024) void constrain_kernel(float* __restrict__ log
         if (total >= vocab) ban[0] &= ~1u;                      // nothing survives: id 0 keeps its raw value
     }
     __syncthreads();
-    float* lg = logits + (int64_t)row * ld;
+    float* __restrict__ lg = r.row(row);
     for (int i = tid; i < vocab; i += 1024)
         if ((ban[i >> 5] >> (i & 31)) & 1u) lg[i] = -INFINITY;
 }
@@ -156,9 +155,8 @@ void con_pack(const cr_constraints* c, int vocab, std::vector<int32_t>& blk) {
     blk.resize(con_block_ints(vocab) - CON_MAX_WORD_IDS + ids);
 }
 
-int launch_constrain(const ConstrainLaunch& p, hipStream_t st) {
-    hipLaunchKernelGGL(constrain_kernel, dim3(p.rows), dim3(1024), (size_t)((p.vocab + 31) / 32) * 4, st, p.logits, p.ld, p.vocab, p.h.seqs, (const int64_t*)p.h.gen,
-                       (const int32_t*)p.h.ngen, p.h.gen_cap, p.t);
+int launch_constrain(const Rows& r, const SeqState& s, const ConTables& t, hipStream_t st) {
+    hipLaunchKernelGGL(constrain_kernel, dim3(r.n), dim3(1024), (size_t)((r.vocab + 31) / 32) * 4, st, r, s, t);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
@@ -181,8 +179,9 @@ extern "C" int cr_op_constrain(const cr_constraints* c, float* logits, int n, in
     hipError_t e = hipMemcpyAsync(d, blk.data(), (blk.size() - 1) * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_on, &blk.back(), 4, hipMemcpyHostToDevice, st);
     int r = CR_OK;
-    const ConstrainLaunch p{logits, vocab, vocab, n, {seqs, const_cast<int64_t*>(history), const_cast<int32_t*>(hist_len), hist_cap}, {d_on, d, 0, 0}};
-    if (e == hipSuccess) r = launch_constrain(p, st);
+    SeqState s{};                                               // the arrays stand for the histories; the one switch is on
+    s.gen = const_cast<int64_t*>(history); s.ngen = const_cast<int32_t*>(hist_len); s.gen_cap = hist_cap; s.con_on = d_on;
+    if (e == hipSuccess) r = launch_constrain({logits, vocab, vocab, n, seqs, nullptr, 1.0f}, s, {d, 0, 0}, st);
     const hipError_t e2 = hipStreamSynchronize(st);
     hipFree(d);
     if (e != hipSuccess || e2 != hipSuccess) return cr_fail(CR_ERR_HIP, "cr_op_constrain: %s", hipGetErrorString(e != hipSuccess ? e : e2));

@@ -6,73 +6,64 @@
 //                        which is what the embedding of the rows and pick.hpp's apply_penalty read.
 //   draft_pick_kernel    pick_kernel's penalty and first-max-wins argmax per row, over g[0 .. G + r), appending nothing: the pick p_r goes to a scratch array.
 //   draft_accept_kernel  one thread per sequence: a = the longest prefix with p_j == d[j]; p_0 .. p_a are appended in order (p_j == d[j] below a, so only slot
-//                        G + a changes), each with pick.hpp's stop check at its own count, ending behind the first id that stops the sequence; the id count and
+//                        G + a changes), each with seqstate.hpp's stop check at its own count, ending behind the first id that stops the sequence; the id count and
 //                        the cached length grow by the ids appended.  Cache rows past the new length are dead, as after cr_kv_truncate.
 // An accepted id is by construction the id the plain greedy step would have picked, so the ids never depend on what the draft holds.
 #include "draft.hpp"
 
 namespace {
 
-__global__ __launch_bounds__(64) void draft_stage_kernel(const int32_t* __restrict__ seqs, const DraftIndex ix, int n, int64_t* __restrict__ gen,
-                                                         const int32_t* __restrict__ ngen, int gen_cap) {
+__global__ __launch_bounds__(64) void draft_stage_kernel(const int32_t* __restrict__ seqs, const DraftIndex ix, int n, SeqState s) {
     const int i = threadIdx.x;
     if (i >= n) return;
-    const int s = seqs[ix.row0[i]], k = ix.klen[i], ng = ngen[s];
-    for (int j = 0; j < k && ng + j < gen_cap; j++) gen[(int64_t)s * gen_cap + ng + j] = ix.ids[i * DRAFT_MAX + j];
+    const int q = seqs[ix.row0[i]], k = ix.klen[i], ng = s.ngen[q];
+    for (int j = 0; j < k && ng + j < s.gen_cap; j++) s.hist(q)[ng + j] = ix.ids[i * DRAFT_MAX + j];
 }
 
 // One workgroup of 1024 per row, as pick_kernel; off == NULL: every row is its sequence's only one
-__global__ __launch_bounds__(1024) void draft_pick_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty, const int32_t* __restrict__ seqs,
-                                                          const int32_t* __restrict__ off, const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen,
-                                                          int gen_cap, const float* __restrict__ orig, int32_t* __restrict__ picks) {
+__global__ __launch_bounds__(1024) void draft_pick_kernel(Rows r, SeqState s, const int32_t* __restrict__ off, int32_t* __restrict__ picks) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const int seq = seqs[row];
-    float* lg = logits + (int64_t)row * ld;
-    const int ng = min(ngen[seq] + (off ? off[row] : 0), gen_cap);      // the history and the drafted ids before this row
-    const int64_t* g = gen + (int64_t)seq * gen_cap;
-    if (penalty != 1.0f && ng > 0) apply_penalty(lg, g, ng, penalty, tid, orig ? orig + (int64_t)row * ld : nullptr);
-    argmax_row(lg, vocab, tid, bv, bi);
+    const int seq = r.seqs[row];
+    float* lg = r.row(row);
+    const int ng = min(s.ngen[seq] + (off ? off[row] : 0), s.gen_cap);      // the history and the drafted ids before this row
+    if (r.penalty != 1.0f && ng > 0) apply_penalty(lg, s.hist(seq), ng, r.penalty, tid, r.orig_row(row));
+    argmax_row(lg, r.vocab, tid, bv, bi);
     if (tid == 0) picks[row] = bi[0];
 }
 
-__global__ __launch_bounds__(64) void draft_accept_kernel(const int32_t* __restrict__ seqs, const DraftIndex ix, int n, int64_t* __restrict__ gen,
-                                                          int32_t* __restrict__ ngen, int32_t* __restrict__ lens, int gen_cap, int32_t* stop, int n_seqs) {
+__global__ __launch_bounds__(64) void draft_accept_kernel(const int32_t* __restrict__ seqs, const DraftIndex ix, int n, SeqState s) {
     const int i = threadIdx.x;
     if (i >= n) return;
-    const int r0 = ix.row0[i], k = ix.klen[i], s = seqs[r0], ng = ngen[s];
-    int64_t* g = gen + (int64_t)s * gen_cap;
+    const int r0 = ix.row0[i], k = ix.klen[i], q = seqs[r0], ng = s.ngen[q];
+    int64_t* g = s.hist(q);
     int a = 0;
-    while (a < k && ng + a < gen_cap && ix.picks[r0 + a] == g[ng + a]) a++;
-    const volatile int32_t* at = stop + 1 + n_seqs;          // the stop counts, which stop_check writes through its own pointer
+    while (a < k && ng + a < s.gen_cap && ix.picks[r0 + a] == g[ng + a]) a++;
     int m = 0;
-    for (int j = 0; j <= a && ng + j < gen_cap; j++) {
+    for (int j = 0; j <= a && ng + j < s.gen_cap; j++) {
         const int64_t id = ix.picks[r0 + j];
         g[ng + j] = id;
         m = j + 1;
-        const int was = at[s];
-        stop_check(stop, n_seqs, s, id, ng + m);
-        if (was == 0 && at[s] != 0) break;                   // this id stopped the sequence: nothing is appended behind it
+        if (s.stop.check(q, id, ng + m)) break;              // this id stopped the sequence: nothing is appended behind it
     }
-    ngen[s] = ng + m;
-    lens[s] += m;
+    s.ngen[q] = ng + m;
+    s.len[q] += m;
     ix.app[i] = m;
 }
 
 }  // namespace
 
-int launch_draft_stage(const DraftLaunch& p, hipStream_t st) {
-    if (p.n < 1 || p.n > 64 || p.rows < p.n) return CR_ERR_ARG;
+int launch_draft_stage(const Rows& r, const SeqState& s, const DraftLaunch& p, hipStream_t st) {
+    if (p.n < 1 || p.n > 64 || r.n < p.n) return CR_ERR_ARG;
     if (!p.windows) return CR_OK;
-    hipLaunchKernelGGL(draft_stage_kernel, dim3(1), dim3(64), 0, st, p.seqs, p.ix, p.n, p.gen, p.ngen, p.gen_cap);
+    hipLaunchKernelGGL(draft_stage_kernel, dim3(1), dim3(64), 0, st, r.seqs, p.ix, p.n, s);
     return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
 }
 
-int launch_draft_pick_accept(const DraftLaunch& p, hipStream_t st) {
-    if (p.n < 1 || p.n > 64 || p.rows < p.n) return CR_ERR_ARG;
-    hipLaunchKernelGGL(draft_pick_kernel, dim3(p.rows), dim3(1024), 0, st, p.logits, p.ld, p.vocab, p.penalty, p.seqs, p.windows ? p.ix.off : nullptr, p.gen, p.ngen,
-                       p.gen_cap, p.orig, p.ix.picks);
-    hipLaunchKernelGGL(draft_accept_kernel, dim3(1), dim3(64), 0, st, p.seqs, p.ix, p.n, p.gen, p.ngen, p.lens, p.gen_cap, p.stop, p.n_seqs);
+int launch_draft_pick_accept(const Rows& r, const SeqState& s, const DraftLaunch& p, hipStream_t st) {
+    if (p.n < 1 || p.n > 64 || r.n < p.n) return CR_ERR_ARG;
+    hipLaunchKernelGGL(draft_pick_kernel, dim3(r.n), dim3(1024), 0, st, r, s, p.windows ? p.ix.off : nullptr, p.ix.picks);
+    hipLaunchKernelGGL(draft_accept_kernel, dim3(1), dim3(64), 0, st, r.seqs, p.ix, p.n, s);
     return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
 }

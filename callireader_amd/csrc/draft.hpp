@@ -21,16 +21,13 @@ inline DraftIndex draft_index(int64_t* p, int n, int M) {
     return {p, q, q + M, q + M + n, q + M + 2 * n, q + 2 * M + 2 * n};
 }
 
+// What the draft stage alone owns, beside the step's rows (seqs [rows]: a window's rows name the same cache slot) and the cache's per-sequence state
 struct DraftLaunch {
-    float* logits; int64_t ld; int vocab; float penalty; int rows, n;
-    const int32_t* seqs;                 // [rows] cache slot of every row (a window's rows name the same one)
+    int n;                               // sequences of the step
     DraftIndex ix;
     bool windows;                        // some sequence has a window: the rows carry offsets (else ix.off is not read, as in a plain step)
-    int64_t* gen; int32_t* ngen; int32_t* lens; int gen_cap;
-    int32_t* stop; int n_seqs;
-    const float* orig;                   // a copy of the rows made before the launch, for histories of more than 4096 ids (apply_penalty); may be NULL
 };
 // the drafted ids behind every sequence's history (slots past its count: dead until the accept step counts them in) -- before the rows are embedded
-int launch_draft_stage(const DraftLaunch& p, hipStream_t st);
+int launch_draft_stage(const Rows& r, const SeqState& s, const DraftLaunch& p, hipStream_t st);
 // every row's greedy pick over its sequence's history plus the drafted ids before the row, then per sequence the accepted prefix: ids, counts, lengths, stops
-int launch_draft_pick_accept(const DraftLaunch& p, hipStream_t st);
+int launch_draft_pick_accept(const Rows& r, const SeqState& s, const DraftLaunch& p, hipStream_t st);

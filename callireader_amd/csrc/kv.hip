@@ -1,6 +1,7 @@
 // The KV cache object: struct cr_kv (kv.hpp) and every cr_kv_* entry point -- alloc and free, the three ways of forgetting a sequence (reset, truncate, fork),
 // the per-sequence settings (stop, sampling, token scores, constraints, beams) and the readers.
 //
+// The per-sequence device state is described by seqstate.hpp's SeqState (kv.hpp: kv_seq_state builds it from a cache); every kernel here takes it by value.
 // "Forget a sequence" is defined once per side: kv_clear_state on the device, Seq::clear (kv.hpp) on the host.
 //   kv_reset_kernel     sequences [s0, s0 + n) get the cleared state with no cached position (cr_kv_reset).
 //   kv_truncate_kernel  state only: the listed sequences hold n_tokens cached positions and nothing else that cr_kv_reset forgets.  Cache rows are not touched:
@@ -26,48 +27,38 @@ namespace {
 constexpr int KV_FORK_MAX = 64;        // destinations of one fork (the batched decode takes 64 rows)
 constexpr int FORK_THREADS = 256, FORK_PIECES = 4, FORK_TILE = FORK_THREADS * FORK_PIECES;      // 16-byte pieces per workgroup
 
-// The per-sequence device state of a cache that cr_kv_reset clears.  lpn / lpdone are NULL while no sequence has switched scores on, con_on while none has
-// switched constraints on.
-struct KvState {
-    int32_t* len; int32_t* ngen;
-    int32_t* stop; int n_seqs;         // the stop block: [1 + n + s] stop count, [1 + 2n + s] EOS id, [1 + 3n + s] budget
-    float* temp;                       // sampling temperature (0: greedy)
-    int32_t* lpn; int32_t* lpdone;
-    int32_t* con_on;                   // logits constraints (0: off)
-};
 // The sequences a launch writes, by value: no staging buffer, so calls on different streams never share one
 struct KvSeqs { int32_t n; int32_t seq[KV_FORK_MAX]; };
 
 // the cleared state: length n_tokens, no ids, no criteria and no stop, greedy, scores off, constraints off
-__device__ __forceinline__ void kv_clear_state(const KvState& s, int seq, int n_tokens) {
+__device__ __forceinline__ void kv_clear_state(const SeqState& s, int seq, int n_tokens) {
     s.len[seq] = n_tokens;
     s.ngen[seq] = 0;
-    s.stop[1 + s.n_seqs + seq] = 0;                 // not stopped
-    s.stop[1 + 2 * s.n_seqs + seq] = -1;            // no EOS id
-    s.stop[1 + 3 * s.n_seqs + seq] = 0;             // no budget
+    *s.stop.at(seq) = 0;                            // not stopped
+    *s.stop.eos(seq) = -1;                          // no EOS id
+    *s.stop.budget(seq) = 0;                        // no budget
     s.temp[seq] = 0.f;                              // greedy
     if (s.lpn) { s.lpn[seq] = 0; s.lpdone[seq] = 0; }
     if (s.con_on) s.con_on[seq] = 0;
 }
 
 // ring: every sequence of the cache goes, and the finished ring starts over
-__global__ __launch_bounds__(256) void kv_reset_kernel(KvState s, int s0, int n, int ring) {
+__global__ __launch_bounds__(256) void kv_reset_kernel(SeqState s, int s0, int n, int ring) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) kv_clear_state(s, s0 + i, 0);
-    if (ring && blockIdx.x == 0 && threadIdx.x == 0) s.stop[0] = 0;
+    if (ring && blockIdx.x == 0 && threadIdx.x == 0) *s.stop.count() = 0;
 }
 
-__global__ __launch_bounds__(64) void kv_truncate_kernel(KvState s, KvSeqs seqs, int n_tokens) {
+__global__ __launch_bounds__(64) void kv_truncate_kernel(SeqState s, KvSeqs seqs, int n_tokens) {
     if ((int)threadIdx.x < seqs.n) kv_clear_state(s, seqs.seq[threadIdx.x], n_tokens);
 }
 
-__global__ __launch_bounds__(FORK_THREADS) void kv_fork_kernel(KvState s, bf16* __restrict__ k, bf16* __restrict__ v, int64_t per_layer, int max_tokens, int src,
-                                                               KvSeqs dsts, int n_tokens) {
+__global__ __launch_bounds__(FORK_THREADS) void kv_fork_kernel(SeqState s, BeamCache c, int src, KvSeqs dsts, int n_tokens) {
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid < dsts.n) kv_clear_state(s, dsts.seq[tid], n_tokens);
     const int run = blockIdx.y;                     // (layer, KV head, K|V)
     const int layer = run >> 4, head = (run >> 1) & 7;
-    bf16* base = ((run & 1) ? v : k) + (int64_t)layer * per_layer + (int64_t)head * max_tokens * 128;
-    const int64_t per_seq = (int64_t)8 * max_tokens * 128;
+    bf16* base = ((run & 1) ? c.v : c.k) + (int64_t)layer * c.per_layer + (int64_t)head * c.max_tokens * 128;
+    const int64_t per_seq = (int64_t)8 * c.max_tokens * 128;
     const int pieces = n_tokens * 16;               // 16-byte pieces of the run (max_tokens <= 32768: fits an int)
     const int p0 = blockIdx.x * FORK_TILE + tid;
     const uint4* sp = (const uint4*)(base + src * per_seq);
@@ -90,51 +81,40 @@ __global__ __launch_bounds__(FORK_THREADS) void kv_fork_kernel(KvState s, bf16* 
 // cr_kv_fanout's state, after the fork's cleared state: destination j samples as src does, with seeds.s[j]; it stops where src stops (the criteria only: it
 // has no id and no stop yet); it records scores as src does.  One thread per destination.
 struct FanSeeds { uint64_t s[FAN_MAX]; };
-__global__ __launch_bounds__(64) void kv_fanout_state_kernel(KvState s, int32_t* __restrict__ topk, float* __restrict__ topp, uint64_t* __restrict__ seed, int src,
-                                                             FanSeqs dsts, FanSeeds seeds) {
+__global__ __launch_bounds__(64) void kv_fanout_state_kernel(SeqState s, int src, FanSeqs dsts, FanSeeds seeds) {
     const int j = threadIdx.x;
     if (j >= dsts.n) return;
-    const int d = dsts.seq[j], N = s.n_seqs;
-    s.temp[d] = s.temp[src]; topk[d] = topk[src]; topp[d] = topp[src]; seed[d] = seeds.s[j];
-    s.stop[1 + 2 * N + d] = s.stop[1 + 2 * N + src];
-    s.stop[1 + 3 * N + d] = s.stop[1 + 3 * N + src];
+    const int d = dsts.seq[j];
+    s.temp[d] = s.temp[src]; s.topk[d] = s.topk[src]; s.topp[d] = s.topp[src]; s.seed[d] = seeds.s[j];
+    *s.stop.eos(d) = *s.stop.eos(src);
+    *s.stop.budget(d) = *s.stop.budget(src);
     if (s.lpn) { s.lpn[d] = s.lpn[src]; s.lpdone[d] = 0; }
 }
 
 // cr_kv_set_stop: install the criteria of `seq` and apply them to the ids it has generated already (a call after the prefill sees its first id).
 // A sequence that has stopped keeps its first stop (pushed once); only the criteria are replaced.  One workgroup.
-__global__ __launch_bounds__(256) void set_stop_kernel(int32_t* __restrict__ stop, int n_seqs, int seq, int eos, int budget,
-                                                       const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen, int gen_cap) {
+__global__ __launch_bounds__(256) void set_stop_kernel(SeqState s, int seq, int eos, int budget) {
     __shared__ int first;
     if (threadIdx.x == 0) first = 0x7fffffff;
     __syncthreads();
-    const int ng = ngen[seq];
+    const int ng = s.ngen[seq];
     if (eos >= 0)
         for (int i = threadIdx.x; i < ng; i += 256)
-            if (gen[(int64_t)seq * gen_cap + i] == eos) atomicMin(&first, i + 1);
+            if (s.hist(seq)[i] == eos) atomicMin(&first, i + 1);
     __syncthreads();
     if (threadIdx.x == 0) {
-        stop[1 + 2 * n_seqs + seq] = eos;
-        stop[1 + 3 * n_seqs + seq] = budget;
-        if (stop[1 + n_seqs + seq] == 0) {
-            int at = first <= ng ? first : 0;
-            if (budget > 0 && ng >= budget && (at == 0 || at > budget)) at = budget;
-            if (at) {
-                stop[1 + n_seqs + seq] = at;
-                const int k = atomicAdd(stop, 1);
-                stop[1 + k % n_seqs] = seq;
-            }
-        }
+        *s.stop.eos(seq) = eos;
+        *s.stop.budget(seq) = budget;
+        int at = first <= ng ? first : 0;
+        if (budget > 0 && ng >= budget && (at == 0 || at > budget)) at = budget;
+        if (at) s.stop.record(seq, at);
     }
 }
 
 // cr_kv_set_sampling: one sequence's sampling state
-__global__ __launch_bounds__(64) void set_sampling_kernel(float* __restrict__ temp, int32_t* __restrict__ topk, float* __restrict__ topp,
-                                                          uint64_t* __restrict__ seed, int seq, float t, int k, float p, uint64_t sd) {
-    if (threadIdx.x == 0) { temp[seq] = t; topk[seq] = k; topp[seq] = p; seed[seq] = sd; }
+__global__ __launch_bounds__(64) void set_sampling_kernel(SeqState s, int seq, float t, int k, float p, uint64_t sd) {
+    if (threadIdx.x == 0) { s.temp[seq] = t; s.topk[seq] = k; s.topp[seq] = p; s.seed[seq] = sd; }
 }
-
-KvState kv_state(cr_kv* kv) { return {kv->d_len, kv->d_ngen, kv->d_stop, kv->n_seqs, kv->d_temp, kv->d_lpn, kv->d_lpdone, kv->d_con_on}; }
 
 // one device block of the cache, recorded as owned
 template <class T> bool kv_malloc(cr_kv* kv, T** p, size_t bytes) {
@@ -202,16 +182,16 @@ int cr_kv_alloc_ex(cr_ctx* c, int n_seqs, int max_tokens, int format, cr_kv** ou
         ? kv_malloc(kv, &kv->k8, bytes) && kv_malloc(kv, &kv->v8, bytes) && kv_malloc(kv, &kv->ks, rows * 4) && kv_malloc(kv, &kv->vs, rows * 4)
         : kv_malloc(kv, &kv->k, bytes) && kv_malloc(kv, &kv->v, bytes);
     if (!data_ok || !kv_malloc(kv, &kv->d_len, n_seqs * 4) || !kv_malloc(kv, &kv->d_ngen, n_seqs * 4) ||
-        !kv_malloc(kv, &kv->d_stop, ((size_t)4 * n_seqs + 1) * 4) || !kv_malloc(kv, &kv->d_samp, (size_t)n_seqs * 24) ||
+        !kv_malloc(kv, &kv->d_stop, StopView::words(n_seqs) * 4) || !kv_malloc(kv, &kv->d_samp, (size_t)n_seqs * 24) ||
         !kv_malloc(kv, &kv->d_gen, (size_t)n_seqs * kv->gen_cap * 8)) {
         cr_kv_free(kv);
         return cr_fail(CR_ERR_NOMEM, "cr_kv_alloc: %zu bytes per K/V", bytes);
     }
     CR_HIP(hipMemset(kv->d_len, 0, n_seqs * 4));
     CR_HIP(hipMemset(kv->d_ngen, 0, n_seqs * 4));
-    CR_HIP(hipMemset(kv->d_stop, 0, ((size_t)2 * n_seqs + 1) * 4));
-    CR_HIP(hipMemset(kv->d_stop + 1 + 2 * n_seqs, 0xff, (size_t)n_seqs * 4));       // no EOS id
-    CR_HIP(hipMemset(kv->d_stop + 1 + 3 * n_seqs, 0, (size_t)n_seqs * 4));          // no budget
+    const StopView sv{kv->d_stop, n_seqs};
+    CR_HIP(hipMemset(kv->d_stop, 0, StopView::words(n_seqs) * 4));                   // nothing finished, nobody stopped, no budget
+    CR_HIP(hipMemset(sv.eos(0), 0xff, (size_t)n_seqs * 4));                          // no EOS id
     kv->d_seed = (uint64_t*)kv->d_samp; kv->d_temp = (float*)(kv->d_seed + n_seqs); kv->d_topk = (int32_t*)(kv->d_temp + n_seqs);
     kv->d_topp = (float*)(kv->d_topk + n_seqs);
     CR_HIP(hipMemset(kv->d_samp, 0, (size_t)n_seqs * 24));                           // greedy
@@ -237,17 +217,16 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
     CR_HIP(hipSetDevice(kv->ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int s0 = seq < 0 ? 0 : seq, n = seq < 0 ? kv->n_seqs : 1;
-    hipLaunchKernelGGL(kv_reset_kernel, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st, kv_state(kv), s0, n, seq < 0 ? 1 : 0);
+    hipLaunchKernelGGL(kv_reset_kernel, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st, kv_seq_state(kv), s0, n, seq < 0 ? 1 : 0);
     CR_HIP(hipGetLastError());
     for (int s = s0; s < s0 + n; s++) kv->seq[s].clear(0);
-    const int N = kv->n_seqs;
     if (kv->d_beam)                                                                     // a beam group goes as a whole with any of its sequences
         for (int s = s0; s < s0 + n; s++) {
             const int f = kv->seq[s].bgrp;
             if (f < 0) continue;
             const int B = kv->seq[f].bnum;
             CR_HIP(hipMemsetAsync(kv->d_bgrp + f, 0xff, (size_t)B * 4, st));
-            CR_HIP(hipMemsetAsync(kv->d_stop + 1 + N + f, 0, 4, st));                   // the group's stop record sits at its first sequence
+            CR_HIP(hipMemsetAsync(StopView{kv->d_stop, kv->n_seqs}.at(f), 0, 4, st));       // the group's stop record sits at its first sequence
             for (int j = 0; j < B; j++) kv->seq[f + j].bgrp = -1;
             kv->seq[f].bnum = 0;
         }
@@ -263,7 +242,7 @@ int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream) {
     CR_HIP(hipSetDevice(kv->ctx->device));
     KvSeqs one{};
     one.n = 1; one.seq[0] = seq;
-    hipLaunchKernelGGL(kv_truncate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv_state(kv), one, n_tokens);
+    hipLaunchKernelGGL(kv_truncate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv_seq_state(kv), one, n_tokens);
     CR_HIP(hipGetLastError());
     q.clear(n_tokens);
     return CR_OK;
@@ -292,8 +271,8 @@ int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_to
     // bf16 cache [layers][n_seqs][8][max_tokens][128] (k, v): positions [0, n_tokens) of `src` go to every destination, every layer, KV head, K and V, and the
     // destinations get the truncate's state -- one launch
     const int pieces = n_tokens * 16;
-    hipLaunchKernelGGL(kv_fork_kernel, dim3((pieces + FORK_TILE - 1) / FORK_TILE, kv->layers * 16), dim3(FORK_THREADS), 0, (hipStream_t)stream, kv_state(kv), kv->k, kv->v,
-                       (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD, kv->max_tokens, src, d, n_tokens);
+    hipLaunchKernelGGL(kv_fork_kernel, dim3((pieces + FORK_TILE - 1) / FORK_TILE, kv->layers * 16), dim3(FORK_THREADS), 0, (hipStream_t)stream, kv_seq_state(kv), beam_cache(kv),
+                       src, d, n_tokens);
     CR_HIP(hipGetLastError());
     for (int j = 0; j < n_dst; j++) kv->seq[d.seq[j]].clear(n_tokens);
     return CR_OK;
@@ -333,20 +312,14 @@ int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const 
     }
     // the prefix: kv_fork_kernel as cr_kv_fork launches it (the source read once, rows >= q.len of a destination not written, the cleared state)
     const int pieces = q.len * 16;
-    hipLaunchKernelGGL(kv_fork_kernel, dim3((pieces + FORK_TILE - 1) / FORK_TILE, kv->layers * 16), dim3(FORK_THREADS), 0, st, kv_state(kv), kv->k, kv->v,
-                       (int64_t)kv->n_seqs * NKV * kv->max_tokens * HD, kv->max_tokens, src, d, q.len);
+    const SeqState s = kv_seq_state(kv);
+    hipLaunchKernelGGL(kv_fork_kernel, dim3((pieces + FORK_TILE - 1) / FORK_TILE, kv->layers * 16), dim3(FORK_THREADS), 0, st, s, beam_cache(kv), src, d, q.len);
     FanSeeds seeds{};
     for (int j = 0; j < n_dst; j++) seeds.s[j] = seeds_host[j];
-    hipLaunchKernelGGL(kv_fanout_state_kernel, dim3(1), dim3(64), 0, st, kv_state(kv), kv->d_topk, kv->d_topp, kv->d_seed, src, f, seeds);
+    hipLaunchKernelGGL(kv_fanout_state_kernel, dim3(1), dim3(64), 0, st, s, src, f, seeds);
     CR_HIP(hipGetLastError());
-    SampleLaunch p{};
-    p.h = kv_hist(kv, nullptr);
-    p.temp = kv->d_temp; p.topk = kv->d_topk; p.topp = kv->d_topp; p.seed = kv->d_seed; p.lens = kv->d_len; p.stop = kv->d_stop; p.n_seqs = kv->n_seqs;
-    CR_TRY(launch_sample_fan(last_logits, V, f, p, st));
-    if (q.scored) {
-        const LogprobsLaunch lp{last_logits, V, V, 1, kv_hist(kv, nullptr), kv->d_lpn, 0, kv->d_lpdone, kv->d_fan, kv->d_lp, kv->d_top_id, kv->d_top_lp};
-        CR_TRY(launch_logprobs_fan(last_logits, V, f, lp, st));
-    }
+    CR_TRY(launch_sample_fan(last_logits, V, f, s, st));
+    if (q.scored) CR_TRY(launch_logprobs_fan(last_logits, V, f, s, {0, kv->d_fan, kv->d_lp, kv->d_top_id, kv->d_top_lp}, st));
     for (int j = 0; j < n_dst; j++) {
         Seq& t = kv->seq[d.seq[j]];
         t.clear(q.len);
@@ -361,8 +334,7 @@ int cr_kv_set_stop(cr_kv* kv, int seq, int eos_id, int max_new, void* stream) {
         return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: budget %d exceeds what the cache leaves after %d tokens (%d)", max_new, kv->seq[seq].len, kv->max_tokens);
     if (eos_id >= kv->ctx->d.vocab) return cr_fail(CR_ERR_ARG, "cr_kv_set_stop: EOS id %d outside the vocabulary", eos_id);
     CR_HIP(hipSetDevice(kv->ctx->device));
-    hipLaunchKernelGGL(set_stop_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kv->d_stop, kv->n_seqs, seq, eos_id < 0 ? -1 : eos_id,
-                       max_new > 0 ? max_new : 0, kv->d_gen, kv->d_ngen, kv->gen_cap);
+    hipLaunchKernelGGL(set_stop_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kv_seq_state(kv), seq, eos_id < 0 ? -1 : eos_id, max_new > 0 ? max_new : 0);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
@@ -374,8 +346,7 @@ int cr_kv_set_sampling(cr_kv* kv, int seq, float temperature, int top_k, float t
     if (!kv || seq < 0 || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: bad sequence");
     if (temperature > 0.f && kv->seq[seq].bgrp >= 0) return cr_fail(CR_ERR_ARG, "cr_kv_set_sampling: sequence %d belongs to a beam group (no beam sampling)", seq);
     CR_HIP(hipSetDevice(kv->ctx->device));
-    hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed, seq,
-                       temperature, top_k, top_p, seed);
+    hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv_seq_state(kv), seq, temperature, top_k, top_p, seed);
     CR_HIP(hipGetLastError());
     kv->seq[seq].sampled = temperature > 0.f;
     return CR_OK;
@@ -519,15 +490,13 @@ int cr_kv_beam_reorder(cr_kv* kv, int first_seq, int num_beams, const int32_t* s
     CR_TRY(beam_alloc(kv, st));
     // the slot of a sequence that is in no group is free: cr_kv_set_beam initialises it whole (pageable source: staged before the call returns)
     CR_HIP(hipMemcpyAsync(kv->d_beam + first_seq, &tmp, sizeof(tmp), hipMemcpyHostToDevice, st));
-    BeamLaunch p{};
-    p.rows = 1; p.seqs = nullptr; p.grp = kv->d_bgrp; p.state = kv->d_beam; p.gen = kv->d_gen; p.ngen = kv->d_ngen; p.gen_cap = kv->gen_cap; p.lens = kv->d_len;
-    const int row = first_seq;                 // seqs NULL: a row is its sequence
-    return launch_beam_reorder(p, beam_cache(kv), &row, 1, first.len - from, 0, st);
+    const int row = first_seq;                 // no seqs: a row is its sequence
+    return launch_beam_reorder(Rows{}, kv_seq_state(kv), {kv->d_beam}, beam_cache(kv), &row, 1, first.len - from, 0, st);
 }
 
 int cr_kv_poll_finished(cr_kv* kv, int32_t* host_out, int max, void* stream) {
     if (!kv || !host_out) return cr_fail(CR_ERR_ARG, "cr_kv_poll_finished: bad argument");
-    const int need = 1 + 2 * kv->n_seqs;
+    const int need = (int)StopView::polled(kv->n_seqs);
     if (max < need) return cr_fail(CR_ERR_ARG, "cr_kv_poll_finished: %d int32 of room, %d needed", max, need);
     CR_HIP(hipSetDevice(kv->ctx->device));
     CR_HIP(hipMemcpyAsync(host_out, kv->d_stop, (size_t)need * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));

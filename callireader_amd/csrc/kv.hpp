@@ -14,7 +14,7 @@ struct Seq {
     int len = 0, ngen = 0;                                       // tokens cached, ids generated
     bool sampled = false, scored = false, constrained = false;   // temperature > 0 / d_lpn != 0 / d_con_on != 0
     int bgrp = -1, bnum = 0;                                     // first sequence of its beam group (< 0: none); at that first sequence, the group's size
-    // the cleared state with n_tokens cached positions: the host side of kv.hip's kv_clear_state, what reset, truncate and fork restore.  A new per-sequence
+    // the cleared state with n_tokens cached positions: the host side of kv.hip's kv_clear_state (the device side, over seqstate.hpp's SeqState), what reset, truncate and fork restore.  A new per-sequence
     // flag is cleared in these two places.  (Group membership goes by the group: cr_kv_reset dissolves it, truncate and fork refuse a member.)
     void clear(int n_tokens) { len = n_tokens; ngen = 0; sampled = scored = constrained = false; }
 };
@@ -33,9 +33,7 @@ struct cr_kv {
     int32_t* d_len;      // [n_seqs] tokens cached
     int32_t* d_ngen;     // [n_seqs] ids generated
     int64_t* d_gen;      // [n_seqs][gen_cap]; gen_cap = max_tokens: every generated id costs a cached token, so the cache fills first
-    // stop tracking (cr_kv_set_stop / cr_kv_poll_finished), one block of 1 + 4 n_seqs int32:
-    //   [0] finished count (monotonic), [1, 1 + n) ring of finished sequence indices (entry k at 1 + k % n),
-    //   [1 + n, 1 + 2n) stop count per sequence (0 = not stopped), [1 + 2n, 1 + 3n) EOS id (< 0: none), [1 + 3n, 1 + 4n) budget (<= 0: none)
+    // stop tracking (cr_kv_set_stop / cr_kv_poll_finished), one block of StopView::words(n_seqs) int32: seqstate.hpp's StopView has the layout
     int32_t* d_stop;
     // sampling state (cr_kv_set_sampling), one block: temperature float[n] (<= 0: greedy), top_k int32[n], top_p float[n], seed uint64[n];
     // Seq::sampled mirrors "temperature > 0" on the host: a launch whose rows are all greedy keeps pick_kernel
@@ -63,8 +61,11 @@ struct cr_kv {
     std::vector<void*> owned;      // every device block of the cache, recorded where it is allocated: cr_kv_free frees this list
 };
 
-// the id histories of the cache's sequences as the launch functions take them, for the launch rows d_seqs (device)
-inline Hist kv_hist(const cr_kv* kv, const int32_t* d_seqs) { return {d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap}; }
+// the per-sequence device state of the cache as every kernel takes it (seqstate.hpp): built once per call
+inline SeqState kv_seq_state(const cr_kv* kv) {
+    return {kv->d_len, kv->d_ngen, kv->d_gen, kv->gen_cap, {kv->d_stop, kv->n_seqs}, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed, kv->d_lpn, kv->d_lpdone,
+            kv->d_con_on, kv->d_bgrp};
+}
 
 // which features the rows seqs[0 .. n) (host) of a prefill / decode call use: scanned once per call, kept in the call's HeadBufs
 RowFeatures kv_scan_rows(const cr_kv* kv, const int32_t* seqs, int n, float penalty);

@@ -664,7 +664,7 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     if (beams) {    // the fan-out: the prompt's cache rows, the first id and the length go from a group's first sequence to its others
         std::vector<int> firsts;
         for (int i = 0; i < n; i++) if (kv->seq[seqs[i]].bgrp == seqs[i]) firsts.push_back(i);
-        CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, c->d_seqs, penalty, 0, 1), beam_cache(kv), firsts.data(), (int)firsts.size(), max_S, 1, st));
+        CR_TRY(launch_beam_reorder(b.head.rows(c->d_seqs, penalty), kv_seq_state(kv), beam_launch(kv, b.head, 0, 1), beam_cache(kv), firsts.data(), (int)firsts.size(), max_S, 1, st));
     }
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
@@ -810,7 +810,8 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     CR_TRY(decode_head(c, *lw, b, st));
     CR_TRY(pick_rows(kv, b.head, d_seqs, penalty, 1, logits, st, false));
     if (beam_span > 0)
-        CR_TRY(launch_beam_reorder(beam_launch(kv, b.head, d_seqs, penalty, 1, 0), beam_cache(kv), beam_firsts.data(), (int)beam_firsts.size(), beam_span, 1, st));
+        CR_TRY(launch_beam_reorder(b.head.rows(d_seqs, penalty), kv_seq_state(kv), beam_launch(kv, b.head, 1, 0), beam_cache(kv), beam_firsts.data(),
+                                   (int)beam_firsts.size(), beam_span, 1, st));
     CR_HIP(hipGetLastError());
     for (int i = 0; i < n; i++) {
         Seq& q = kv->seq[seqs[i]];
@@ -882,19 +883,18 @@ int cr_llm_decode_draft(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const 
     CR_HIP(hipMemcpyAsync(b.index, hix.data(), hix.size() * 8, hipMemcpyHostToDevice, st));      // pageable source: staged before return
     CR_TRY(ctx_stage_seqs(c, row_seq.data(), M, st, false));
     const int32_t* d_seqs = c->d_seqs;
-    DraftLaunch dl{};
-    dl.logits = b.dec.head.lg; dl.ld = V; dl.vocab = V; dl.penalty = penalty; dl.rows = M; dl.n = n; dl.seqs = d_seqs; dl.ix = draft_index(b.index, n, M);
-    dl.windows = b.windows; dl.gen = kv->d_gen; dl.ngen = kv->d_ngen; dl.lens = kv->d_len; dl.gen_cap = kv->gen_cap; dl.stop = kv->d_stop; dl.n_seqs = kv->n_seqs;
-    dl.orig = b.dec.head.lg0;
-    CR_TRY(launch_draft_stage(dl, st));
+    const Rows rows = b.dec.head.rows(d_seqs, penalty);
+    const SeqState ss = kv_seq_state(kv);
+    const DraftLaunch dl{n, draft_index(b.index, n, M), b.windows};
+    CR_TRY(launch_draft_stage(rows, ss, dl, st));
     if (b.dec.off)
         hipLaunchKernelGGL(embed_rows_kernel<true>, dim3(M), dim3(256), 0, st, lw->embed, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, b.dec.off);
     else
         hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(M), dim3(256), 0, st, lw->embed, (const int64_t*)nullptr, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.dec.x, nullptr);
     CR_TRY(decode_layers(c, *lw, kv, b.dec, d_seqs, st));
     CR_TRY(decode_head(c, *lw, b.dec, st));
-    if (dl.orig) CR_HIP(hipMemcpyAsync(b.dec.head.lg0, b.dec.head.lg, (size_t)M * V * 4, hipMemcpyDeviceToDevice, st));
-    CR_TRY(launch_draft_pick_accept(dl, st));
+    if (rows.orig) CR_HIP(hipMemcpyAsync(b.dec.head.lg0, b.dec.head.lg, (size_t)M * V * 4, hipMemcpyDeviceToDevice, st));
+    CR_TRY(launch_draft_pick_accept(rows, ss, dl, st));
     CR_HIP(hipGetLastError());
     // the price of a variable step: the host's mirror of the lengths needs the counts, and the next window depends on them anyway
     CR_HIP(hipMemcpyAsync(appended_host, dl.ix.app, (size_t)n * 4, hipMemcpyDeviceToHost, st));

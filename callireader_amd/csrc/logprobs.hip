@@ -29,62 +29,54 @@ namespace {
 
 using namespace lpdev;
 
-// Partials of one (row, chunk), logprobs_dev.hpp reduce_chunk.  seqs NULL: every row is scored (cr_op_logprobs); else rows whose sequence has scores off exit.
-__global__ __launch_bounds__(THREADS) void logprobs_chunk_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int chunks,
-                                                                 const int32_t* __restrict__ seqs, const int32_t* __restrict__ lpn,
-                                                                 float* __restrict__ pm, double* __restrict__ ps, float* __restrict__ pv,
-                                                                 int32_t* __restrict__ pi) {
+// Partials of one (row, chunk), logprobs_dev.hpp reduce_chunk.  Op rows (s.lpn NULL): every row is scored; else rows whose sequence has scores off exit.
+__global__ __launch_bounds__(THREADS) void logprobs_chunk_kernel(Rows r, SeqState s, Partials q) {
     const int chunk = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
-    if (seqs && lpn[seqs[row]] <= 0) return;
+    if (s.lpn && s.lpn[r.seq(row)] <= 0) return;
     float z[PER];
-    load_chunk<false>(logits + (int64_t)row * ld, vocab, chunk * CHUNK, tid, z);
-    reduce_chunk(z, vocab, chunk * CHUNK, (int64_t)row * chunks + chunk, tid, pm, ps, pv, pi);
+    load_chunk<false>(r.row(row), r.vocab, chunk * CHUNK, tid, z);
+    reduce_chunk(z, r.vocab, chunk * CHUNK, (int64_t)row * q.chunks + chunk, tid, q.pm, q.ps, q.pv, q.pi);
+}
+
+// The slot of the id that the pick of this launch has just appended to `seq`, and the id; < 0 when there is none: a sequence whose history is full appended
+// nothing, so nothing is scored (lpdone[seq] counts the slots written)
+__device__ __forceinline__ int64_t scored_slot(const SeqState& s, int seq, int lane, int64_t& id) {
+    const int t = s.ngen[seq] - 1;
+    if (t < 0 || t != s.lpdone[seq]) return -1;
+    id = s.hist(seq)[t];
+    if (lane == 0) s.lpdone[seq] = t + 1;
+    return (int64_t)seq * s.gen_cap + t;
 }
 
 // One wave per row: lse from the chunk pairs in chunk order, the row's top-n from the chunks' candidates, the picked id's score (logprobs_dev.hpp merge_row).
-// Cache rows (seqs given): the slot is t = ngen[seq] - 1, the id gen[seq][t]; a sequence whose history is full appended nothing, so nothing is scored
-// (done[seq] counts the slots written).  Op rows (seqs NULL): slot `row`, id ids[row], n = top_n.
-__global__ __launch_bounds__(64) void logprobs_merge_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int chunks,
-                                                           const int32_t* __restrict__ seqs, const int32_t* __restrict__ lpn, int top_n,
-                                                           const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen, int gen_cap,
-                                                           int32_t* __restrict__ done, const float* __restrict__ pm, const double* __restrict__ ps,
-                                                           const float* __restrict__ pv, const int32_t* __restrict__ pi, float* __restrict__ out_lp,
-                                                           int32_t* __restrict__ out_id, float* __restrict__ out_tlp) {
+// Cache rows: the sequence's own count of alternatives and scored_slot.  Op rows (s.lpn NULL): slot `row`, id gen[row], n = top_n.
+__global__ __launch_bounds__(64) void logprobs_merge_kernel(Rows r, SeqState s, LogprobsLaunch p, Partials q) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    int n = top_n;
+    int n = p.top_n;
     int64_t slot = row, id;
-    if (seqs) {
-        const int seq = seqs[row];
-        n = lpn[seq];
+    if (s.lpn) {
+        const int seq = r.seq(row);
+        n = s.lpn[seq];
         if (n <= 0) return;
-        const int t = ngen[seq] - 1;
-        if (t < 0 || t != done[seq]) return;                  // nothing was appended by this launch's pick
-        id = gen[(int64_t)seq * gen_cap + t];
-        slot = (int64_t)seq * gen_cap + t;
-        if (lane == 0) done[seq] = t + 1;
+        slot = scored_slot(s, seq, lane, id);
+        if (slot < 0) return;
     } else {
-        id = gen[row];
+        id = s.gen[row];
     }
-    const float zi = (id >= 0 && id < vocab) ? logits[(int64_t)row * ld + id] : NAN;
-    merge_row(row, chunks, n, slot, zi, lane, pm, ps, pv, pi, out_lp, out_id, out_tlp);
+    const float zi = (id >= 0 && id < r.vocab) ? r.row(row)[id] : NAN;
+    merge_row(row, q.chunks, n, slot, zi, lane, q.pm, q.ps, q.pv, q.pi, p.out_lp, p.out_id, p.out_tlp);
 }
 
 // cr_kv_fanout: wave j merges the partials of the ONE row (partial row 0) for sequence dsts.seq[j], as logprobs_merge_kernel does for a cache row
-__global__ __launch_bounds__(64) void logprobs_fan_merge_kernel(const float* __restrict__ row, int vocab, int chunks, FanSeqs dsts, const int32_t* __restrict__ lpn,
-                                                               const int64_t* __restrict__ gen, const int32_t* __restrict__ ngen, int gen_cap,
-                                                               int32_t* __restrict__ done, const float* __restrict__ pm, const double* __restrict__ ps,
-                                                               const float* __restrict__ pv, const int32_t* __restrict__ pi, float* __restrict__ out_lp,
-                                                               int32_t* __restrict__ out_id, float* __restrict__ out_tlp) {
+__global__ __launch_bounds__(64) void logprobs_fan_merge_kernel(const float* __restrict__ row, int vocab, FanSeqs dsts, SeqState s, LogprobsLaunch p, Partials q) {
     const int seq = dsts.seq[blockIdx.x], lane = threadIdx.x;
-    const int n = lpn[seq];
+    const int n = s.lpn[seq];
     if (n <= 0) return;
-    const int t = ngen[seq] - 1;
-    if (t < 0 || t != done[seq]) return;
-    const int64_t id = gen[(int64_t)seq * gen_cap + t];
-    const int64_t slot = (int64_t)seq * gen_cap + t;
-    if (lane == 0) done[seq] = t + 1;
+    int64_t id;
+    const int64_t slot = scored_slot(s, seq, lane, id);
+    if (slot < 0) return;
     const float zi = (id >= 0 && id < vocab) ? row[id] : NAN;
-    merge_row(0, chunks, n, slot, zi, lane, pm, ps, pv, pi, out_lp, out_id, out_tlp);
+    merge_row(0, q.chunks, n, slot, zi, lane, q.pm, q.ps, q.pv, q.pi, p.out_lp, p.out_id, p.out_tlp);
 }
 
 __global__ __launch_bounds__(64) void set_logprobs_kernel(int32_t* __restrict__ lpn, int32_t* __restrict__ done, int seq, int top_n) {
@@ -100,30 +92,19 @@ size_t logprobs_scratch_bytes(int rows, int vocab) {
     return 256 + rc * 8 + rc * 4 + rc * TOPN * 8;
 }
 
-int launch_logprobs(const LogprobsLaunch& p, hipStream_t st) {
-    const int chunks = logprobs_chunks(p.vocab);
-    const size_t rc = (size_t)p.rows * chunks;
-    double* ps = (double*)(((uintptr_t)p.scratch + 255) & ~(uintptr_t)255);
-    float* pm = (float*)(ps + rc);
-    float* pv = pm + rc;
-    int32_t* pi = (int32_t*)(pv + rc * TOPN);
-    hipLaunchKernelGGL(logprobs_chunk_kernel, dim3(chunks, p.rows), dim3(THREADS), 0, st, p.logits, p.ld, p.vocab, chunks, p.h.seqs, p.lpn, pm, ps, pv, pi);
-    hipLaunchKernelGGL(logprobs_merge_kernel, dim3(p.rows), dim3(64), 0, st, p.logits, p.ld, p.vocab, chunks, p.h.seqs, p.lpn, p.top_n, (const int64_t*)p.h.gen,
-                       (const int32_t*)p.h.ngen, p.h.gen_cap, p.done, (const float*)pm, (const double*)ps, (const float*)pv, (const int32_t*)pi, p.out_lp, p.out_id,
-                       p.out_tlp);
+int launch_logprobs(const Rows& r, const SeqState& s, const LogprobsLaunch& p, hipStream_t st) {
+    const Partials q(p.scratch, r.n, logprobs_chunks(r.vocab));
+    hipLaunchKernelGGL(logprobs_chunk_kernel, dim3(q.chunks, r.n), dim3(THREADS), 0, st, r, s, q);
+    hipLaunchKernelGGL(logprobs_merge_kernel, dim3(r.n), dim3(64), 0, st, r, s, p, q);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
 
-int launch_logprobs_fan(const float* row, int vocab, const FanSeqs& dsts, const LogprobsLaunch& p, hipStream_t st) {
-    const int chunks = logprobs_chunks(vocab);
-    double* ps = (double*)(((uintptr_t)p.scratch + 255) & ~(uintptr_t)255);
-    float* pm = (float*)(ps + chunks);
-    float* pv = pm + chunks;
-    int32_t* pi = (int32_t*)(pv + (size_t)chunks * TOPN);
-    hipLaunchKernelGGL(logprobs_chunk_kernel, dim3(chunks, 1), dim3(THREADS), 0, st, row, (int64_t)vocab, vocab, chunks, (const int32_t*)nullptr, p.lpn, pm, ps, pv, pi);
-    hipLaunchKernelGGL(logprobs_fan_merge_kernel, dim3(dsts.n), dim3(64), 0, st, row, vocab, chunks, dsts, p.lpn, (const int64_t*)p.h.gen, (const int32_t*)p.h.ngen,
-                       p.h.gen_cap, p.done, (const float*)pm, (const double*)ps, (const float*)pv, (const int32_t*)pi, p.out_lp, p.out_id, p.out_tlp);
+int launch_logprobs_fan(const float* row, int vocab, const FanSeqs& dsts, const SeqState& s, const LogprobsLaunch& p, hipStream_t st) {
+    const Partials q(p.scratch, 1, logprobs_chunks(vocab));
+    // the one row as an op row: scored whatever a sequence's switch says
+    hipLaunchKernelGGL(logprobs_chunk_kernel, dim3(q.chunks, 1), dim3(THREADS), 0, st, Rows{const_cast<float*>(row), vocab, vocab, 1, nullptr, nullptr, 1.0f}, SeqState{}, q);
+    hipLaunchKernelGGL(logprobs_fan_merge_kernel, dim3(dsts.n), dim3(64), 0, st, row, vocab, dsts, s, p, q);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
@@ -142,8 +123,9 @@ extern "C" int cr_op_logprobs(const float* logits, int n, int vocab, const int64
     hipStream_t st = (hipStream_t)stream;
     void* scratch = nullptr;
     if (hipMalloc(&scratch, logprobs_scratch_bytes(n, vocab)) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "cr_op_logprobs: scratch");
-    const LogprobsLaunch p{logits, vocab, vocab, n, {nullptr, const_cast<int64_t*>(ids), nullptr, 0}, nullptr, top_n, nullptr, scratch, lp, top_ids, top_lp};
-    const int rc = launch_logprobs(p, st);
+    SeqState s{};                                            // op rows: the id of row r is ids[r]
+    s.gen = const_cast<int64_t*>(ids); s.gen_cap = 1;
+    const int rc = launch_logprobs({const_cast<float*>(logits), vocab, vocab, n, nullptr, nullptr, 1.0f}, s, {top_n, scratch, lp, top_ids, top_lp}, st);
     hipStreamSynchronize(st);
     hipFree(scratch);
     return rc;

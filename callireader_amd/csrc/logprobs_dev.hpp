@@ -27,6 +27,17 @@ __device__ __forceinline__ void wave_best(float& v, int& i) {
     }
 }
 
+// The chunk partials of `rows` rows in a launch's scratch (logprobs_scratch_bytes): per (row, chunk) the maximum, the sum and the top-8 as (value, id)
+struct Partials {
+    int chunks;                          // of a row (logprobs_chunks(vocab))
+    float* pm; double* ps; float* pv; int32_t* pi;
+    Partials(void* scratch, int rows, int chunks) : chunks(chunks) {
+        const size_t rc = (size_t)rows * chunks;
+        ps = (double*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+        pm = (float*)(ps + rc); pv = pm + rc; pi = (int32_t*)(pv + rc * TOPN);
+    }
+};
+
 // RepetitionPenaltyLogitsProcessor on one score, pick.hpp apply_penalty's arithmetic
 __device__ __forceinline__ float penalised(float v, float penalty) { return v < 0.f ? v * penalty : v / penalty; }
 

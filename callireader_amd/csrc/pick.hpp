@@ -1,19 +1,8 @@
-// Token choice shared by the greedy pick (pick.hip pick_kernel) and the sampling pick (sample.hip): the repetition penalty, the
-// first-max-wins argmax and the stop check run the same device code in both kernels, so a greedy row gets the same bits from either.
+// Token choice shared by the greedy pick (pick.hip pick_kernel) and the sampling pick (sample.hip): the repetition penalty and the first-max-wins argmax
+// run the same device code in both kernels, so a greedy row gets the same bits from either; both append through seqstate.hpp's SeqState::append, where the
+// per-sequence device state, the append rule and the stop check are described.
 #pragma once
-#include "common.hpp"
-
-// Stop criteria of cr_kv_set_stop, checked against the id a sequence has just appended (its `count`-th): the first time it is the EOS id or
-// the count reaches the budget, the count is recorded and the sequence index pushed onto the finished ring.  One thread per sequence per launch.
-__device__ inline void stop_check(int32_t* __restrict__ stop, int n_seqs, int seq, int64_t id, int count) {
-    int32_t* at = stop + 1 + n_seqs;
-    const int eos = stop[1 + 2 * n_seqs + seq], budget = stop[1 + 3 * n_seqs + seq];
-    if (at[seq] == 0 && ((eos >= 0 && id == eos) || (budget > 0 && count >= budget))) {
-        at[seq] = count;
-        const int k = atomicAdd(stop, 1);
-        stop[1 + k % n_seqs] = seq;
-    }
-}
+#include "seqstate.hpp"
 
 // RepetitionPenaltyLogitsProcessor (published 4.45.2 semantics) in place over the `ng` ids of history g.  Every thread of a 1024-thread workgroup
 // calls it.  The scores are gathered first, then scattered: duplicates of an id all see the ORIGINAL score.  Up to 4096 ids the gather stays in
@@ -63,29 +52,20 @@ __device__ __forceinline__ void argmax_row(const float* __restrict__ lg, int voc
     }
 }
 
-// Sampling pick (sample.hip) over `rows` rows of logits (modified in place: penalty).  Per row, seq = h.seqs[row] (NULL: seq = row) indexes the history and
-// the sampling state (temp / topk / topp / seed); a row whose temperature is not > 0 is greedy (pick_kernel's result).  step NULL: step = ngen[seq]; else
-// step[row].  append != 0: the id is appended to the sequence's history with pick_kernel's stop check and lens update (lens[seq] += len_add).  out_ids /
-// out_kept (may be NULL): the id and the size of the kept set of each row (0 for a greedy row).
-// orig (may be NULL): a copy of the rows made before the launch, for histories of more than 4096 ids (apply_penalty).
-// bgrp (may be NULL): [n_seqs] beam group of every sequence; a row whose sequence has one (>= 0) is left untouched (beam.hip picks for it).
-struct SampleLaunch {
-    float* logits; int64_t ld; int vocab; float penalty; int rows;
-    Hist h;
-    const float* temp; const int32_t* topk; const float* topp; const uint64_t* seed; const int32_t* step;
-    int append; int32_t* lens; int len_add; int32_t* stop; int n_seqs;
-    int64_t* out_ids; int32_t* out_kept;
-    const float* orig; const int32_t* bgrp;
-};
-int launch_sample(const SampleLaunch& p, hipStream_t st);
+// Sampling pick (sample.hip) over the rows r (modified in place: penalty).  A row's sequence indexes the history and the sampling state of s; a row whose
+// temperature is not > 0 is greedy (pick_kernel's result), a row whose sequence is in a beam group is left untouched (beam.hip picks for it).  step NULL:
+// step = ngen[seq]; else step[row].  append != 0: the id is appended as pick_kernel appends it (the cached length grows by len_add).  out_ids / out_kept (may
+// be NULL): the id and the size of the kept set of each row (0 for a greedy row).
+struct SampleLaunch { const int32_t* step; int append, len_add; int64_t* out_ids; int32_t* out_kept; };
+int launch_sample(const Rows& r, const SeqState& s, const SampleLaunch& p, hipStream_t st);
 
 // The sequences of one cr_kv_fanout, by value in the launches that take them (no staging buffer)
 constexpr int FAN_MAX = 63;
 struct FanSeqs { int32_t n; int32_t seq[FAN_MAX]; };
 // cr_kv_fanout's picks, one launch (sample.hip sample_fan_kernel): sequence dsts.seq[j], which holds no id yet, draws its first id from the one fp32 `row`
-// [vocab] (read only) with its own sampling state -- sample_kernel's thresholds and draw at step 0 -- and appends it with the stop check; lens are not
-// advanced.  p gives the histories (h.gen / h.ngen / h.gen_cap), temp / topk / topp / seed, lens, stop and n_seqs; its other fields are not read.
-int launch_sample_fan(const float* row, int vocab, const FanSeqs& dsts, const SampleLaunch& p, hipStream_t st);
+// [vocab] (read only) with its own sampling state -- sample_kernel's thresholds and draw at step 0 -- and appends it with the stop check; the cached lengths are not
+// advanced.
+int launch_sample_fan(const float* row, int vocab, const FanSeqs& dsts, const SeqState& s, hipStream_t st);
 
 // ---- what follows the LM head in a prefill / decode call (pick.hip; host) ----
 struct cr_kv; struct Arena; struct BeamLaunch; struct BeamCache;
@@ -106,6 +86,7 @@ struct HeadBufs {
     float* lg0;             // f.deep: the rows before the penalty, for the pick
     char* cand;             // f.beam_rows: beam.hip's candidate scratch
     void carve(Arena& ar);
+    Rows rows(const int32_t* d_seqs, float penalty) const { return {lg, V, V, n, d_seqs, lg0, penalty}; }
 };
 
 // The logits h.lg out to the caller (`out`, may be NULL), then the constraint masks of the rows that have any (the pick, the penalty's copy h.lg0 and the scores
@@ -114,5 +95,5 @@ struct HeadBufs {
 int pick_rows(cr_kv* kv, const HeadBufs& h, const int32_t* d_seqs, float penalty, int len_add, float* out, hipStream_t st, bool prefill);
 // The beam step of the launch's groups, after the picks of its other rows: candidates and select on the logits rows (first_only: a prefill, which holds a
 // group's first sequence only), and in a decode step the re-order behind them (the prefill's follows its set_len_kernel)
-BeamLaunch beam_launch(cr_kv* kv, const HeadBufs& h, const int32_t* d_seqs, float penalty, int len_add, int first_only);
+BeamLaunch beam_launch(cr_kv* kv, const HeadBufs& h, int len_add, int first_only);
 BeamCache beam_cache(const cr_kv* kv);

@@ -216,21 +216,17 @@ __device__ uint32_t select_key(const float* lg, int vocab, float temp, float zma
 
 // The pick of one row by its workgroup of 1024: the body of both kernels below.  lg: the row's scores, read only; lgw: the same row where the penalty may
 // write it, NULL for a row that is never written (sample_fan_kernel: several workgroups read one row).
-__device__ __forceinline__ void sample_row(const float* lg, float* lgw, int row, int seq, int vocab, float penalty, int64_t* __restrict__ gen,
-                                           int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_, const int32_t* __restrict__ topk_,
-                                           const float* __restrict__ topp_, const uint64_t* __restrict__ seed_, const int32_t* __restrict__ step_, int append,
-                                           int32_t* __restrict__ lens, int len_add, int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids,
-                                           int32_t* __restrict__ out_kept, const float* orig_row) {
+__device__ __forceinline__ void sample_row(const float* lg, float* lgw, int row, int seq, int vocab, float penalty, const float* orig_row, const SeqState& st,
+                                           const SampleLaunch& p) {
     __shared__ float bv[1024];
     __shared__ int bi[1024];
     __shared__ SelShared s;
     __shared__ double rs[16];
     __shared__ int ri[16], rk[16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int ng = ngen[seq] < gen_cap ? ngen[seq] : gen_cap;       // (a KV cache never holds more; cr_op_sample's hist_len may)
-    int64_t* g = gen + (int64_t)seq * gen_cap;
-    if (lgw && penalty != 1.0f && ng > 0) apply_penalty(lgw, g, ng, penalty, tid, orig_row);
-    const float temp = temp_[seq];
+    const int ng = st.ngen[seq] < st.gen_cap ? st.ngen[seq] : st.gen_cap;       // (a KV cache never holds more; cr_op_sample's hist_len may)
+    if (lgw && penalty != 1.0f && ng > 0) apply_penalty(lgw, st.hist(seq), ng, penalty, tid, orig_row);
+    const float temp = st.temp[seq];
     int64_t id;
     int kept = 0;
     if (!(temp > 0.f)) {                                    // greedy row: pick_kernel's argmax
@@ -252,15 +248,15 @@ __device__ __forceinline__ void sample_row(const float* lg, float* lgw, int row,
         const uint32_t kmin = s.kmin, kmax = s.kmax;
         __syncthreads();
         const float zmax = kfloat(kmax);
-        const int K = topk_[seq];
-        const float P = topp_[seq];
+        const int K = st.topk[seq];
+        const float P = st.topp[seq];
         uint32_t thr = kmin;
         const bool usable = kmin <= kmax;                       // false: every score is NaN
         if (usable && K > 0 && K < vocab) thr = select_key<false>(lg, vocab, temp, zmax, kmin, kmax, (unsigned long long)(vocab - K), 0.f, s, tid);
         if (usable && P < 1.0f) thr = select_key<true>(lg, vocab, temp, zmax, thr, kmax, 0ull, (float)(1.0 - (double)P), s, tid);
         // the draw over the kept ids: Philox words per group of four ids
-        const uint64_t seed = seed_[seq];
-        const uint32_t stp = (uint32_t)(step_ ? step_[row] : ng);
+        const uint64_t seed = st.seed[seq];
+        const uint32_t stp = (uint32_t)(p.step ? p.step[row] : ng);
         double best = -INFINITY; int besti = 0x7fffffff;
         for (int q = tid; q * 4 < vocab; q += 1024) {
             bool have = false;
@@ -305,55 +301,37 @@ __device__ __forceinline__ void sample_row(const float* lg, float* lgw, int row,
         }
     }
     if (tid == 0) {
-        if (out_ids) out_ids[row] = id;
-        if (out_kept) out_kept[row] = kept;
-        if (append) {
-            if (ng < gen_cap) {
-                g[ng] = id; ngen[seq] = ng + 1;
-                stop_check(stop, n_seqs, seq, id, ng + 1);
-            }
-            lens[seq] += len_add;
-        }
+        if (p.out_ids) p.out_ids[row] = id;
+        if (p.out_kept) p.out_kept[row] = kept;
+        if (p.append) st.append(seq, id, ng, p.len_add);
     }
 }
 
-__global__ __launch_bounds__(1024) void sample_kernel(float* __restrict__ logits, int64_t ld, int vocab, float penalty, const int32_t* __restrict__ seqs,
-                                                      int64_t* __restrict__ gen, int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_,
-                                                      const int32_t* __restrict__ topk_, const float* __restrict__ topp_, const uint64_t* __restrict__ seed_,
-                                                      const int32_t* __restrict__ step_, int append, int32_t* __restrict__ lens, int len_add,
-                                                      int32_t* __restrict__ stop, int n_seqs, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_kept,
-                                                      const float* __restrict__ orig, const int32_t* __restrict__ bgrp) {
+__global__ __launch_bounds__(1024) void sample_kernel(Rows r, SeqState s, SampleLaunch p) {
     const int row = blockIdx.x;
-    const int seq = seqs ? seqs[row] : row;
-    if (bgrp && bgrp[seq] >= 0) return;                     // a beam row: beam.hip picks for it
-    float* lg = logits + (int64_t)row * ld;
-    sample_row(lg, lg, row, seq, vocab, penalty, gen, ngen, gen_cap, temp_, topk_, topp_, seed_, step_, append, lens, len_add, stop, n_seqs, out_ids, out_kept,
-               orig ? orig + (int64_t)row * ld : nullptr);
+    const int seq = r.seq(row);
+    if (s.beam_row(seq)) return;                            // a beam row: beam.hip picks for it
+    float* lg = r.row(row);
+    sample_row(lg, lg, row, seq, r.vocab, r.penalty, r.orig_row(row), s, p);
 }
 
 // cr_kv_fanout's picks: workgroup j draws the first id of sequence dsts.seq[j] from the ONE row `lg` (the raw last row of the source's prefill), which no
 // workgroup writes -- the sequences hold no ids yet, so there is no penalty to apply -- and appends it with the stop check; the cached length stays.
-__global__ __launch_bounds__(1024) void sample_fan_kernel(const float* __restrict__ lg, int vocab, FanSeqs dsts, int64_t* __restrict__ gen,
-                                                          int32_t* __restrict__ ngen, int gen_cap, const float* __restrict__ temp_,
-                                                          const int32_t* __restrict__ topk_, const float* __restrict__ topp_,
-                                                          const uint64_t* __restrict__ seed_, int32_t* __restrict__ lens, int32_t* __restrict__ stop, int n_seqs) {
+__global__ __launch_bounds__(1024) void sample_fan_kernel(const float* __restrict__ lg, int vocab, FanSeqs dsts, SeqState s) {
     const int row = blockIdx.x;
-    sample_row(lg, nullptr, row, dsts.seq[row], vocab, 1.0f, gen, ngen, gen_cap, temp_, topk_, topp_, seed_, nullptr, 1, lens, 0, stop, n_seqs, nullptr, nullptr,
-               nullptr);
+    sample_row(lg, nullptr, row, dsts.seq[row], vocab, 1.0f, nullptr, s, SampleLaunch{nullptr, 1, 0, nullptr, nullptr});
 }
 
 }  // namespace
 
-int launch_sample_fan(const float* row, int vocab, const FanSeqs& dsts, const SampleLaunch& p, hipStream_t st) {
-    hipLaunchKernelGGL(sample_fan_kernel, dim3(dsts.n), dim3(1024), 0, st, row, vocab, dsts, p.h.gen, p.h.ngen, p.h.gen_cap, p.temp, p.topk, p.topp, p.seed, p.lens,
-                       p.stop, p.n_seqs);
+int launch_sample_fan(const float* row, int vocab, const FanSeqs& dsts, const SeqState& s, hipStream_t st) {
+    hipLaunchKernelGGL(sample_fan_kernel, dim3(dsts.n), dim3(1024), 0, st, row, vocab, dsts, s);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
 
-int launch_sample(const SampleLaunch& p, hipStream_t st) {
-    hipLaunchKernelGGL(sample_kernel, dim3(p.rows), dim3(1024), 0, st, p.logits, p.ld, p.vocab, p.penalty, p.h.seqs, p.h.gen, p.h.ngen, p.h.gen_cap, p.temp, p.topk,
-                       p.topp, p.seed, p.step, p.append, p.lens, p.len_add, p.stop, p.n_seqs, p.out_ids, p.out_kept, p.orig, p.bgrp);
+int launch_sample(const Rows& r, const SeqState& s, const SampleLaunch& p, hipStream_t st) {
+    hipLaunchKernelGGL(sample_kernel, dim3(r.n), dim3(1024), 0, st, r, s, p);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }
@@ -369,9 +347,8 @@ extern "C" int cr_op_sample(cr_ctx* c, const float* logits, int n, int vocab, co
     CR_TRY(ws_ensure(c, (size_t)n * vocab * 4));
     float* lg = (float*)c->ws;
     CR_HIP(hipMemcpyAsync(lg, logits, (size_t)n * vocab * 4, hipMemcpyDeviceToDevice, st));
-    SampleLaunch p{};
-    p.logits = lg; p.ld = vocab; p.vocab = vocab; p.penalty = penalty; p.rows = n;
-    p.h = {nullptr, const_cast<int64_t*>(history), const_cast<int32_t*>(hist_len), hist_cap};
-    p.temp = temperature; p.topk = top_k; p.topp = top_p; p.seed = seed; p.step = step; p.out_ids = out_ids; p.out_kept = out_kept;
-    return launch_sample(p, st);
+    SeqState s{};                                            // the arrays stand for per-sequence state: row = sequence, nothing is appended
+    s.ngen = const_cast<int32_t*>(hist_len); s.gen = const_cast<int64_t*>(history); s.gen_cap = hist_cap;
+    s.temp = const_cast<float*>(temperature); s.topk = const_cast<int32_t*>(top_k); s.topp = const_cast<float*>(top_p); s.seed = const_cast<uint64_t*>(seed);
+    return launch_sample({lg, vocab, vocab, n, nullptr, nullptr, penalty}, s, {step, 0, 0, out_ids, out_kept}, st);
 }

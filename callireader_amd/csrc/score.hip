@@ -34,30 +34,24 @@ __global__ __launch_bounds__(256) void score_table_kernel(const int64_t* __restr
 
 // block (chunk, i): row row0 + i of the index block, logits row i
 template <bool PEN>
-__global__ __launch_bounds__(THREADS) void score_chunk_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int chunks, int row0,
-                                                              const int32_t* __restrict__ hist, const int32_t* __restrict__ ord,
-                                                              const int32_t* __restrict__ first, float penalty, float* __restrict__ pm,
-                                                              double* __restrict__ ps, float* __restrict__ pv, int32_t* __restrict__ pi) {
+__global__ __launch_bounds__(THREADS) void score_chunk_kernel(ScoreLaunch p, Partials q) {
     const int chunk = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
+    const float* lg = p.logits + (int64_t)row * p.ld;
     float z[PER];
-    if (PEN) load_chunk<true>(logits + (int64_t)row * ld, vocab, chunk * CHUNK, tid, z, first + (int64_t)hist[row0 + row] * vocab, ord[row0 + row], penalty);
-    else load_chunk<false>(logits + (int64_t)row * ld, vocab, chunk * CHUNK, tid, z);
-    reduce_chunk(z, vocab, chunk * CHUNK, (int64_t)row * chunks + chunk, tid, pm, ps, pv, pi);
+    if (PEN) load_chunk<true>(lg, p.vocab, chunk * CHUNK, tid, z, p.first + (int64_t)p.ix.hist[p.row0 + row] * p.vocab, p.ix.ord[p.row0 + row], p.penalty);
+    else load_chunk<false>(lg, p.vocab, chunk * CHUNK, tid, z);
+    reduce_chunk(z, p.vocab, chunk * CHUNK, (int64_t)row * q.chunks + chunk, tid, q.pm, q.ps, q.pv, q.pi);
 }
 
-__global__ __launch_bounds__(64) void score_merge_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int chunks, int row0,
-                                                        const int64_t* __restrict__ tgt, const int32_t* __restrict__ hist, const int32_t* __restrict__ ord,
-                                                        const int32_t* __restrict__ first, float penalty, int top_n, const float* __restrict__ pm,
-                                                        const double* __restrict__ ps, const float* __restrict__ pv, const int32_t* __restrict__ pi,
-                                                        float* __restrict__ out_lp, int32_t* __restrict__ out_id, float* __restrict__ out_tlp) {
+__global__ __launch_bounds__(64) void score_merge_kernel(ScoreLaunch p, Partials q) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    const int64_t slot = (int64_t)row0 + row, y = tgt[slot];
+    const int64_t slot = (int64_t)p.row0 + row, y = p.ix.tgt[slot];
     float zi = NAN;
-    if (y >= 0 && y < vocab) {
-        zi = logits[(int64_t)row * ld + y];
-        if (first && first[(int64_t)hist[slot] * vocab + y] < ord[slot]) zi = penalised(zi, penalty);
+    if (y >= 0 && y < p.vocab) {
+        zi = p.logits[(int64_t)row * p.ld + y];
+        if (p.first && p.first[(int64_t)p.ix.hist[slot] * p.vocab + y] < p.ix.ord[slot]) zi = penalised(zi, p.penalty);
     }
-    merge_row(row, chunks, top_n, slot, zi, lane, pm, ps, pv, pi, out_lp, out_id, out_tlp);
+    merge_row(row, q.chunks, p.top_n, slot, zi, lane, q.pm, q.ps, q.pv, q.pi, p.out_lp, p.out_id, p.out_tlp);
 }
 
 }  // namespace
@@ -71,18 +65,9 @@ int launch_score_table(const ScoreIndex& ix, int rows, int n_hist, int vocab, in
 }
 
 int launch_score_rows(const ScoreLaunch& p, hipStream_t st) {
-    const int chunks = logprobs_chunks(p.vocab);
-    const size_t rc = (size_t)p.rows * chunks;
-    // the partials, laid out as launch_logprobs lays them out
-    double* ps = (double*)(((uintptr_t)p.scratch + 255) & ~(uintptr_t)255);
-    float* pm = (float*)(ps + rc);
-    float* pv = pm + rc;
-    int32_t* pi = (int32_t*)(pv + rc * TOPN);
-    hipLaunchKernelGGL(p.first ? score_chunk_kernel<true> : score_chunk_kernel<false>, dim3(chunks, p.rows), dim3(THREADS), 0, st, p.logits, p.ld, p.vocab, chunks,
-                       p.row0, (const int32_t*)p.ix.hist, (const int32_t*)p.ix.ord, p.first, p.penalty, pm, ps, pv, pi);
-    hipLaunchKernelGGL(score_merge_kernel, dim3(p.rows), dim3(64), 0, st, p.logits, p.ld, p.vocab, chunks, p.row0, (const int64_t*)p.ix.tgt,
-                       (const int32_t*)p.ix.hist, (const int32_t*)p.ix.ord, p.first, p.penalty, p.top_n, (const float*)pm, (const double*)ps, (const float*)pv,
-                       (const int32_t*)pi, p.out_lp, p.out_id, p.out_tlp);
+    const Partials q(p.scratch, p.rows, logprobs_chunks(p.vocab));      // laid out as launch_logprobs lays them out
+    hipLaunchKernelGGL(p.first ? score_chunk_kernel<true> : score_chunk_kernel<false>, dim3(q.chunks, p.rows), dim3(THREADS), 0, st, p, q);
+    hipLaunchKernelGGL(score_merge_kernel, dim3(p.rows), dim3(64), 0, st, p, q);
     CR_HIP(hipGetLastError());
     return CR_OK;
 }

@@ -278,6 +278,43 @@ def test_greedy_and_sampled_neighbours_keep_their_ids(llm):
         kv.free()
 
 
+def test_stopped_groups_reach_the_finished_queue(llm):
+    """include/callireader_hip.h: a beam group that stops is pushed once onto the cache's finished queue, at its FIRST sequence, with the length of its best
+    hypothesis as the stop count.  Without an EOS id every candidate finishes exactly at the length limit, and the early-stop heuristic cannot stop a group
+    while a finished slot is empty: the group of max_new 3 stops with 3 ids, the one of max_new 5 with 5, in that order."""
+    m, pages, _ = llm
+    eng, N = m.engine, 6
+    kv = eng.kv_alloc(N, 128)
+    try:
+        kv.set_beam(0, 2, 1.0, False, None, 3)
+        kv.set_beam(2, 3, 1.0, False, None, 5)
+        buf = torch.zeros(1 + 2 * N, dtype=torch.int32).pin_memory()
+        seen, pushed = {0: False, 2: False}, 0
+
+        def poll():                                   # the queue and the groups' `done` at the same point of the stream
+            nonlocal pushed
+            kv.poll_finished(buf)
+            torch.cuda.synchronize()
+            h = buf.tolist()
+            for f in seen:
+                done = kv.beam_result(f)[2]
+                pushed += done and not seen[f]
+                seen[f] = seen[f] or done
+            assert h[0] == pushed, (h, seen)          # the count rises by one exactly when a group first reports done
+            return h
+        eng.prefill_batch(kv, [0, 2], [pages[0], pages[4]])
+        poll()
+        for _ in range(6):
+            eng.decode(kv, [0, 1, 2, 3, 4])
+            h = poll()
+        assert seen == {0: True, 2: True} and h[0] == 2
+        assert h[1:3] == [0, 2]                                            # the ring, in the order the groups stopped
+        assert h[1 + N:1 + 2 * N] == [3, 0, 5, 0, 0, 0]                    # stop counts at the groups' first sequences, 0 everywhere else
+        assert [len(kv.beam_result(f)[0]) for f in (0, 2)] == [3, 5]       # ... each the length of the group's result
+    finally:
+        kv.free()
+
+
 def test_refusals_change_nothing(llm):
     from callireader_amd._binding import CalliReaderError
     m, pages, _ = llm
