@@ -92,6 +92,7 @@ SIGNATURES = {
     'cr_profile_stats': (i32, [vp, C.POINTER(i64)]),
     'cr_op_gemm': (i32, [i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     'cr_op_layernorm': (i32, [vp, vp, vp, vp, i64, i32, f32, i32, vp]),
+    'cr_op_layernorm_regroup': (i32, [vp, vp, vp, vp, i64, i32, f32, i32, i32, i32, vp]),
     'cr_op_rmsnorm': (i32, [vp, vp, vp, i64, i32, f32, vp]),
     'cr_op_norm_fp8': (i32, [vp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp]),
     'cr_op_gemm_q8': (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
@@ -99,6 +100,7 @@ SIGNATURES = {
     'cr_op_decode_gemm': (i32, [i32, i32, vp, i64, i32, i32, i32, vp, i64, vp, vp, f32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     'cr_op_attention': (i32, [vp, vp, vp, vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp]),
     'cr_op_attention_segments': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
+    'cr_op_perceiver_attention': (i32, [i32, vp, vp, vp, i32, vp]),
     'cr_op_decode_attention_scratch_floats': (i64, [i32, i32]),
     'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'cr_op_constrain': (i32, [C.POINTER(Constraints), vp, i32, i32, vp, vp, i32, vp, vp]),

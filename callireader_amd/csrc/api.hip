@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "attention.hpp"
+#include "calli.hpp"
 #include <stdlib.h>
 
 #include "ctx.hpp"
@@ -316,6 +317,17 @@ int cr_op_layernorm(const void* in, void* out, const void* gamma, const void* be
     return CR_OK;
 }
 
+int cr_op_layernorm_regroup(const void* in, void* out, const void* gamma, const void* beta, int64_t rows, int n, float eps, int in_group, int out_group,
+                            int out_off, void* stream) {
+    if (!in || !out || !gamma || !beta || rows < 0 || in_group < 0 || out_group < 0 || out_off < 0 || (out_group > 0 && (in_group <= 0 || out_off + in_group > out_group)))
+        return cr_fail(CR_ERR_ARG, "cr_op_layernorm_regroup: bad argument");
+    // the fill is the CalliAlign stage's own (norm.hpp: ln of calli.hip calls the same function)
+    const int r = launch_layernorm(regroup_norm_params((const bf16*)in, (bf16*)out, (const bf16*)gamma, (const bf16*)beta, rows, n, eps, in_group, out_group, out_off),
+                                   n, 0, (hipStream_t)stream);
+    if (r != CR_OK) return cr_fail(r, "cr_op_layernorm_regroup(rows=%lld, n=%d) rejected or failed", (long long)rows, n);
+    return CR_OK;
+}
+
 int cr_op_norm_fp8(const void* in, const void* gamma, const void* beta, int64_t rows, int n, float eps, void* out8, float* out_scale,
                    float* next_scale, const float* next_bound, void* stream) {
     if (!in || !gamma || !out8 || !out_scale || ((next_scale != nullptr) != (next_bound != nullptr))) return cr_fail(CR_ERR_ARG, "cr_op_norm_fp8: bad argument");
@@ -404,6 +416,13 @@ int cr_op_attention_segments(const void* q, const void* kc, const void* vc, void
     const AttnParams ap = segment_attn_params((const bf16*)kc, (const bf16*)vc, max_tokens, (const bf16*)q, (bf16*)o, H, kv_group, n, seg, Sq, s_div);
     const int r = launch_flash_attn(ap, 128, true, (hipStream_t)stream);
     if (r != CR_OK) return cr_fail(r, "cr_op_attention_segments(n=%d, Sq=%d, H=%d) rejected or failed", n, Sq, H);
+    return CR_OK;
+}
+
+int cr_op_perceiver_attention(int which, const void* q, const void* kv, void* out, int T, void* stream) {
+    if (!q || !kv || !out || T <= 0 || (which != 0 && which != 1)) return cr_fail(CR_ERR_ARG, "cr_op_perceiver_attention: bad argument");
+    const int r = launch_perceiver_attn(which, (const bf16*)q, (const bf16*)kv, (bf16*)out, T, (hipStream_t)stream);      // (calli.hpp: the resampler's own launch)
+    if (r != CR_OK) return cr_fail(r, "cr_op_perceiver_attention(which=%d, T=%d) rejected or failed", which, T);
     return CR_OK;
 }
 

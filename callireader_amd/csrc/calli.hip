@@ -2,6 +2,7 @@
 //   reference: models/perceiver_resampler.py:8-100,130-141; models/similarity.py:9-27;
 //              InternVL/modeling_internvl_chat.py:602-640
 #include "weights.hpp"
+#include "calli.hpp"
 #include "misc.hpp"
 #include "norm.hpp"
 
@@ -275,13 +276,18 @@ int gemm(cr_ctx* c, int epi, const bf16* A, int64_t lda, const bf16* Wt, int64_t
 }
 
 int ln(const bf16* in, bf16* out, const bf16* g, const bf16* b, int64_t rows, int in_group, int out_group, int out_off, hipStream_t st) {
-    NormParams np{};
-    np.in = in; np.ld_in = D; np.out = out; np.ld_out = D; np.gamma = g; np.beta = b; np.rows = rows; np.eps = 1e-5f;
-    np.in_group = in_group; np.out_group = out_group; np.out_off = out_off;
-    return launch_layernorm(np, D, 0, st);
+    return launch_layernorm(regroup_norm_params(in, out, g, b, rows, D, 1e-5f, in_group, out_group, out_off), D, 0, st);      // (norm.hpp; cr_op_layernorm_regroup fills its launch there too)
 }
 
 }  // namespace
+
+// the resampler's attention launch, made in ONE place for resample_chunk below and for the test entry cr_op_perceiver_attention (api.hip)
+int launch_perceiver_attn(int which, const bf16* q, const bf16* kv, bf16* out, int T, hipStream_t st) {
+    if (!q || !kv || !out || T <= 0 || (which != 0 && which != 1)) return CR_ERR_ARG;
+    if (which == 1) hipLaunchKernelGGL(perceiver_attn_v1_kernel, dim3(T, HEADS), dim3(64), 0, st, q, kv, out, 0.125f);
+    else hipLaunchKernelGGL(perceiver_attn_kernel, dim3(T, HEADS), dim3(64), 0, st, q, kv, out, 0.125f);
+    return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
+}
 
 int calli_finalize(cr_ctx* c, hipStream_t st) {
     const DevTensor* tb = WT(c, "normed_emb.weight");
@@ -337,8 +343,7 @@ static int resample_chunk(cr_ctx* c, const bf16* x, int T, bf16* out, hipStream_
         CR_TRY(ln(learns, lnl, nlw, nlb, R, 0, 0, 0, st));
         CR_TRY(gemm(c, EPI_STORE, lnl, D, wq, D, q, INNER, nullptr, nullptr, 0, (int)R, INNER, D, st, true));        // :35
         CR_TRY(gemm(c, EPI_STORE, kv_in, D, wkv, D, kv, 2 * INNER, nullptr, nullptr, 0, T * NKV, 2 * INNER, D, st));  // :39
-        if (c->perceiver_v1) hipLaunchKernelGGL(perceiver_attn_v1_kernel, dim3(T, HEADS), dim3(64), 0, st, q, kv, ao, 0.125f);
-        else hipLaunchKernelGGL(perceiver_attn_kernel, dim3(T, HEADS), dim3(64), 0, st, q, kv, ao, 0.125f);
+        CR_TRY(launch_perceiver_attn(c->perceiver_v1 ? 1 : 0, q, kv, ao, T, st));
         CR_TRY(gemm(c, EPI_RES, ao, INNER, wo, INNER, learns, D, nullptr, learns, D, (int)R, D, INNER, st, true));    // :51 + :97
         CR_TRY(ln(learns, lnl, fw0, fb0, R, 0, 0, 0, st));                                                         // FeedForward :134
         CR_TRY(gemm(c, EPI_GELU, lnl, D, fw1, D, ff, 4 * D, fb1, nullptr, 0, (int)R, 4 * D, D, st, true));

@@ -21,6 +21,16 @@ struct NormParams {
     float* next_scale; const float* next_bound;
 };
 
+// A LayerNorm over contiguous rows of n with the output-row regrouping above, filled in ONE place for the resampler's cat(norm_media(x), norm_learns(learns))
+// (calli.hip, ln) and for the test entry cr_op_layernorm_regroup (api.hip).  out_group = 0: out row = in row.
+inline NormParams regroup_norm_params(const bf16* in, bf16* out, const bf16* gamma, const bf16* beta, int64_t rows, int n, float eps, int in_group,
+                                      int out_group, int out_off) {
+    NormParams np{};
+    np.in = in; np.ld_in = n; np.out = out; np.ld_out = n; np.gamma = gamma; np.beta = beta; np.rows = rows; np.eps = eps;
+    np.in_group = in_group; np.out_group = out_group; np.out_off = out_off;
+    return np;
+}
+
 // mode 0: rows of n (1024 | 4096) bf16; mode 1: pixel-shuffle gather feeding mlp1's LayerNorm (n = 4096)
 int launch_layernorm(const NormParams& p, int n, int mode, hipStream_t stream);
 int launch_rmsnorm(const NormParams& p, int n, hipStream_t stream);

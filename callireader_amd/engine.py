@@ -601,6 +601,43 @@ def op_layernorm(x, gamma, beta, eps, pixel_shuffle=False):
     return out
 
 
+def op_layernorm_regroup(x, out, gamma, beta, eps, in_group=0, out_group=0, out_off=0):
+    """cr_op_layernorm_regroup: LayerNorm of x's rows written into `out` with the resampler's row regrouping (input row r -> output row
+    (r // in_group) * out_group + out_off + r % in_group; out_group = 0: row r).  x (rows, n), out (any rows, n) contiguous bf16.  That the last row written
+    lies inside `out` is checked here, where the shape is known; the group arguments themselves are the C entry's to reject."""
+    rows, n = x.shape
+    for t in (x, out, gamma, beta):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError('op_layernorm_regroup: contiguous bf16 tensors')
+    if out.dim() != 2 or out.shape[1] != n or gamma.numel() != n or beta.numel() != n:
+        raise ValueError('op_layernorm_regroup: x (rows, n), out (rows_out, n), gamma / beta (n,)')
+    if rows and out_group > 0 and in_group > 0:
+        last = ((rows - 1) // in_group) * out_group + out_off + (rows - 1) % in_group
+    else:
+        last = rows - 1
+    if last >= out.shape[0]:
+        raise ValueError(f'op_layernorm_regroup: output row {last} outside out ({out.shape[0]} rows)')
+    B.check(B.lib.cr_op_layernorm_regroup(_p(x), _p(out), _p(gamma), _p(beta), rows, n, eps, int(in_group), int(out_group), int(out_off), _stream()),
+            'cr_op_layernorm_regroup')
+    return out
+
+
+def op_perceiver_attention(q, kv, which=0, out=None):
+    """cr_op_perceiver_attention: the resampler's attention alone.  q (T * 3, 512), kv (T * 259, 1024) contiguous bf16 (K | V); returns out (T * 3, 512).
+    which = 0: the production kernel, 1: round 1's."""
+    if q.dim() != 2 or kv.dim() != 2 or q.shape[1] != 512 or kv.shape[1] != 1024 or q.shape[0] % 3 or kv.shape[0] != q.shape[0] // 3 * 259:
+        raise ValueError('op_perceiver_attention: q (T * 3, 512), kv (T * 259, 1024)')
+    if out is None:
+        out = torch.empty_like(q)
+    for t in (q, kv, out):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError('op_perceiver_attention: contiguous bf16 tensors')
+    if out.shape != q.shape:
+        raise ValueError('op_perceiver_attention: out has q\'s shape')
+    B.check(B.lib.cr_op_perceiver_attention(int(which), _p(q), _p(kv), _p(out), q.shape[0] // 3, _stream()), 'cr_op_perceiver_attention')
+    return out
+
+
 def op_rmsnorm(x, gamma, eps):
     out = torch.empty_like(x)
     B.check(B.lib.cr_op_rmsnorm(_p(x), _p(out), _p(gamma), x.shape[0], x.shape[1], eps, _stream()), 'cr_op_rmsnorm')

@@ -450,6 +450,13 @@ int cr_op_gemm(int epi, const void* A, int64_t lda, const void* W, int64_t ldw, 
 int cr_op_quantize_fp8(const void* w, int64_t ldw, int N, int K, void* q, float* scale, void* stream);
 int cr_op_layernorm(const void* in, void* out, const void* gamma, const void* beta, int64_t rows, int n, float eps,
                     int pixel_shuffle, void* stream);
+/* cr_op_layernorm's plain rows (n = 1024 | 4096) with the output-row regrouping the resampler uses to write cat(norm_media(x), norm_learns(learns)) in place
+ * (test entry; cr_resample fills its launches through the same function, regroup_norm_params, and drives the same kernel): input row r lands in output row
+ * (r / in_group) * out_group + out_off + r % in_group; out_group = 0: output row = input row, as cr_op_layernorm.  CR_ERR_ARG for out_group > 0 with
+ * in_group <= 0 or out_off + in_group > out_group (rows of two groups would overlap).  out holds ceil(rows / in_group) * out_group rows at the most; rows of
+ * out that no input row maps to are not written.  Added within ABI v13. */
+int cr_op_layernorm_regroup(const void* in, void* out, const void* gamma, const void* beta, int64_t rows, int n, float eps, int in_group, int out_group,
+                            int out_off, void* stream);
 int cr_op_rmsnorm(const void* in, void* out, const void* gamma, int64_t rows, int n, float eps, void* stream);
 /* the same norms with the fp8 output cr_enable_fp8_mfma uses: beta == NULL selects RMSNorm (n = 4096), otherwise LayerNorm
  * (n = 1024 | 4096); out8 = e4m3 [rows][n], out_scale = float[rows] */
@@ -520,6 +527,13 @@ int cr_op_attention(const void* q, const void* k, const void* v, void* o, const 
  * read; the caller guarantees first row + S <= rows, pos0 + S <= max_tokens and slot < n_slots (the entry cannot see the device array).  Added within ABI v13. */
 int cr_op_attention_segments(const void* q, const void* kc, const void* vc, void* o, const int32_t* seg, int n, int Sq, int H, int kv_group, int max_tokens,
                              float s_div, void* stream);
+/* PerceiverAttention's softmax(q k^T) v alone (test entry; cr_resample makes its launch through the same function, launch_perceiver_attn, and drives the same
+ * kernels): T tiles x 8 heads x 3 queries x 259 keys x 64 dims.  q [T * 3][512] bf16 (head h in columns 64 h .. 64 h + 63), kv [T * 259][1024] bf16 (a tile's
+ * 256 media rows then its 3 latent rows; K in columns 0..511, V in 512..1023), out [T * 3][512] bf16.  Rounding points of perceiver_resampler.py:43-51:
+ * q * 0.125 (exact), scores -> bf16, scores - row maximum -> bf16, fp32 softmax -> bf16, probabilities . v accumulated in fp32 -> bf16.  which = 0: the
+ * production kernel, 1: round 1's kernel (CR_PERCEIVER_ATTN_V1=1), bit-identical by construction.  Reads nothing outside q and kv.  CR_ERR_ARG for a null
+ * pointer, T <= 0 or another `which`.  Added within ABI v13. */
+int cr_op_perceiver_attention(int which, const void* q, const void* kv, void* out, int T, void* stream);
 
 /* Batched decode attention alone (test / tuning entry; cr_llm_decode drives the same launcher): row b = one new token of cache slot seqs[b], its H_kv x 4 query heads x 128 at
  * q + b * 4096 (InternLM2's GQA layout: the 4 query heads of KV head h at (4 h .. 4 h + 3) * 128), keys / values [n_slots][8][max_tokens][128] bf16, lens[slot] + 1 keys per row

@@ -9,6 +9,15 @@ import torch
 import torch.nn.functional as F
 
 
+def perceiver_softmax_pv(q, k, v, dim_head=64):
+    """The einsum path of PerceiverAttention.forward, perceiver_resampler.py:43-50: q (b, h, i, d), k / v (b, h, j, d) in the model's dtype."""
+    q = q * (dim_head ** -0.5)                                                 # :43
+    sim = torch.einsum('bhid,bhjd->bhij', q, k)                                # :46
+    sim = sim - sim.amax(dim=-1, keepdim=True)                                 # :47
+    attn = sim.softmax(dim=-1)                                                 # :48
+    return torch.einsum('bhij,bhjd->bhid', attn, v)                            # :50
+
+
 def perceiver_attention(sd, p, x, learns, heads=8, dim_head=64):
     """PerceiverAttention.forward, perceiver_resampler.py:28-51."""
     D = x.shape[-1]
@@ -22,11 +31,7 @@ def perceiver_attention(sd, p, x, learns, heads=8, dim_head=64):
     def split(t):                                                              # 'b n (h d) -> b h n d'
         return t.reshape(b, t.shape[1], heads, dim_head).permute(0, 2, 1, 3)
     q, k, v = split(q), split(k), split(v)
-    q = q * (dim_head ** -0.5)                                                 # :43
-    sim = torch.einsum('bhid,bhjd->bhij', q, k)                                # :46
-    sim = sim - sim.amax(dim=-1, keepdim=True)                                 # :47
-    attn = sim.softmax(dim=-1)                                                 # :48
-    out = torch.einsum('bhij,bhjd->bhid', attn, v)                             # :50
+    out = perceiver_softmax_pv(q, k, v, dim_head)                              # :43-50
     out = out.permute(0, 2, 1, 3).reshape(b, out.shape[2], heads * dim_head)   # :51
     return F.linear(out, sd[p + 'to_out.weight'])
 

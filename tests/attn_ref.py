@@ -1,6 +1,6 @@
 """The attention reference shared by test_gpu_ops.py and test_gpu_prefill_attention.py: plain PyTorch fp32 with the reference model's bf16 rounding
 points written out (attn_ref), the same operation in float64 without any rounding (attn_f64: what attn_ref's own error is measured against), and both
-over the segments of a prefill launch (segments_ref)."""
+over the segments of a prefill launch (segments_ref); the resampler's attention with ITS rounding points (perceiver_attn_ref, test_gpu_calli_ops.py)."""
 import torch
 
 
@@ -51,3 +51,39 @@ def segments_ref(q, kc, vc, segs, s_div, fn=attn_ref):
             heads.append(fn(qh, kh, vh, True, pos0, 1.0, s_div)[0])                                  # (g, S, D)
         out[i] = torch.cat(heads, 0).permute(1, 0, 2)
     return out
+
+
+P_NQ, P_NKV, P_HEADS, P_DH = 3, 259, 8, 64
+
+
+def perceiver_heads(q, kv):
+    """cr_op_perceiver_attention's operands per (tile, head): q (T * 3, 512), kv (T * 259, 1024) [K | V] -> q (T, 8, 3, 64), k, v (T, 8, 259, 64), same dtype."""
+    T = q.shape[0] // P_NQ
+    assert q.shape == (T * P_NQ, P_HEADS * P_DH) and kv.shape == (T * P_NKV, 2 * P_HEADS * P_DH)
+    qh = q.reshape(T, P_NQ, P_HEADS, P_DH).permute(0, 2, 1, 3)
+    kvh = kv.reshape(T, P_NKV, 2, P_HEADS, P_DH).permute(2, 0, 3, 1, 4)
+    return qh, kvh[0], kvh[1]
+
+
+def perceiver_attn_ref(q, kv, exact=False, *, drop_keys=(), round_sub=True, round_p=True):
+    """PerceiverAttention's softmax(q k^T) v (perceiver_resampler.py:43-51) on bf16 q (T * 3, 512) and kv (T * 259, 1024): fp32 with the reference's
+    rounding points written out -- q * 0.125 -> bf16 (exact), sim -> bf16, sim - amax -> bf16, fp32 softmax -> bf16, attn @ v summed in fp32 -> bf16.
+    Returns (T * 3, 512) fp32 holding bf16 values; exact=True: the same operation in float64, nothing rounded.
+    The keyword-only arguments are deliberate MISTAKES for test_attn_ref_cpu.py, which shows which of them the GPU tests' bound can see: keys left out of
+    the softmax, sim - amax left unrounded, the probabilities left unrounded."""
+    qh, k, v = perceiver_heads(q, kv)
+    if exact:
+        sim = (qh.double() * 0.125) @ k.double().transpose(-1, -2)
+        out = torch.softmax(sim, dim=-1) @ v.double()
+    else:
+        sim = rb(rb(qh.float() * 0.125) @ k.float().transpose(-1, -2))
+        for key in drop_keys:
+            sim[..., key] = float('-inf')
+        sim = sim - sim.amax(dim=-1, keepdim=True)
+        if round_sub:
+            sim = rb(sim)
+        attn = torch.softmax(sim, dim=-1)
+        if round_p:
+            attn = rb(attn)
+        out = rb(attn @ v.float())
+    return out.permute(0, 2, 1, 3).reshape(q.shape[0], P_HEADS * P_DH)

@@ -59,3 +59,131 @@ def test_peaked_cases_plant_what_they_say():
         s = T.rb(T.rb(torch.einsum('nd,kd->nk', q[5:7, 0].float(), kc[1, 0, :200].float())) / T.SDIV)
         assert float(s.max()) < -30
     assert set(T.PEAKED_FLOOR) == {(n, p) for n in T.PEAKED for p in T.PEAK_POS0}
+
+
+# ---- the perceiver attention's reference and cases (test_gpu_calli_ops.py) -------------------------------------------------------------------
+import test_gpu_calli_ops as C  # noqa: E402
+from attn_ref import perceiver_attn_ref, perceiver_heads  # noqa: E402
+
+
+def test_perceiver_ref_is_the_oracles_einsum_path():
+    """perceiver_attn_ref (fp32 with the rounding points written out) against oracle.calli_align.perceiver_softmax_pv on the bf16 tensors themselves -- the
+    einsum path perceiver_attention runs.  Bit for bit where achievable: the oracle's bf16 einsum sums in another order, so one bf16 step of the result is allowed and
+    the number of differing elements printed (0 or 1 of 7680 per case)."""
+    from oracle import calli_align
+    for name in C.DATA_CASES:
+        q, kv, ref = C.data_case(name)
+        q, kv, ref = *C.first_tiles(q, kv, 5), ref[:15]
+        qh, k, v = perceiver_heads(q, kv)
+        orc = calli_align.perceiver_softmax_pv(qh, k, v).permute(0, 2, 1, 3).reshape(15, 512)
+        assert orc.dtype == torch.bfloat16
+        diff = orc.float() != ref
+        step = 2.0 ** (torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126))) - 7)
+        print(f'perceiver_attn_ref vs the oracle, {name}: {int(diff.sum())} of {diff.numel()} elements differ')
+        assert bool(((orc.float() - ref).abs() <= step).all())
+
+
+PERCEIVER_MISTAKES = {
+    'key 258 masked': dict(drop_keys=(258,)),
+    'keys 256..258 masked': dict(drop_keys=(256, 257, 258)),
+    'sim - amax unrounded': dict(round_sub=False),
+    'probabilities unrounded': dict(round_p=False),
+}
+# Which (case, mistake) the data cases' bound -- assert_close(rtol = RTOL, atol = max(ATOL, 2 x floor)) against perceiver_attn_ref at T = 37 -- sees.
+# The key masks show on every case: among 888 rows some give a latent key a large weight (and the exact cases pin every key bit for bit).  The two
+# left-out roundings move an ordinary row by ~ 3e-3, and a bound of 2 x the reference's own distance from float64 cannot see that in principle: what
+# the rounding moves IS part of that distance.  So `random`, `spread`, `late` and `negative` do not see them; binade_case is built so that the
+# reference's roundings cancel and each alone does not (its docstring), and sees both.
+_MASKS = ('key 258 masked', 'keys 256..258 masked')
+PERCEIVER_SEEN = {
+    'random': _MASKS,
+    'spread': _MASKS,
+    'late': _MASKS,
+    'negative': _MASKS,
+    'binade': _MASKS + ('sim - amax unrounded', 'probabilities unrounded'),
+}
+
+
+def _passes(got, ref, atol):
+    try:
+        torch.testing.assert_close(got, ref, rtol=C.RTOL, atol=atol)
+        return True
+    except AssertionError:
+        return False
+
+
+def test_perceiver_bound_sees_the_mistakes_it_claims_to():
+    """Each mistake of PERCEIVER_MISTAKES, made in the reference, against the bound the GPU test uses: it must FAIL on the cases PERCEIVER_SEEN names (and
+    every mistake on at least one case), the true reference must pass, and so must its float64 form (that is what the floor means)."""
+    seen_somewhere = set()
+    for name in C.DATA_CASES:
+        q, kv, ref = C.data_case(name)
+        atol = C.allowed_atol(name, C.T_MAX)
+        assert _passes(perceiver_attn_ref(q, kv), ref, atol)
+        assert _passes(perceiver_attn_ref(q, kv, exact=True).float(), ref, atol)
+        for what, kw in PERCEIVER_MISTAKES.items():
+            got = perceiver_attn_ref(q, kv, **kw)
+            excess = float(((got - ref).abs() - C.RTOL * ref.abs()).max())
+            fails = not _passes(got, ref, atol)
+            print(f'{name:9s} {what:24s}: worst |mistake - ref| - rtol |ref| = {excess:10.3e} against {atol:.3e}: {"FAILS" if fails else "passes (not seen)"}')
+            assert fails == (what in PERCEIVER_SEEN[name]), (name, what, excess, atol)
+            if fails:
+                seen_somewhere.add(what)
+    assert seen_somewhere == set(PERCEIVER_MISTAKES)
+
+
+def test_perceiver_floors_are_the_measured_ones():
+    """DATA_FLOOR is what scripts/perceiver_attention_calibrate.py prints for the cases as they are built now (a changed builder must not keep an old floor)."""
+    for name in C.DATA_CASES:
+        q, kv, ref = C.data_case(name)
+        exact = perceiver_attn_ref(q, kv, exact=True)
+        for j, T in enumerate(C.TS):
+            floor = max(0.0, float(((ref[:T * 3].double() - exact[:T * 3]).abs() - C.RTOL * exact[:T * 3].abs()).max()))
+            assert abs(floor - C.DATA_FLOOR[name][j]) <= 1e-3 * floor + 1e-6, (name, T, floor)
+
+
+def test_perceiver_cases_plant_what_they_say():
+    rb = C.rb
+    # uniform: the expected output is what the reference gives, and every probability is 253 * 2^-16
+    q, kv, exp = C.uniform_case(5)
+    assert float(torch.tensor(1 / 259).to(torch.bfloat16)) == 253 * 2.0 ** -16
+    assert torch.equal(perceiver_attn_ref(q, kv), exp.float())
+    # selection: the reference returns the target's V row; every key is a target, the edges of the kernel's key loops among them
+    for per_query in (False, True):
+        q, kv, exp, tg = C.selection_case(per_query=per_query)
+        assert set(tg.reshape(-1).tolist()) == set(range(259)) and set(C.SELECT_MUST) <= set(tg.reshape(-1).tolist())
+        assert torch.equal(perceiver_attn_ref(q, kv), exp.float())
+        qh, k, _ = perceiver_heads(q, kv)
+        s = rb(rb(qh.float() * 0.125) @ k.float().transpose(-1, -2))
+        assert sorted(set(s.reshape(-1).tolist())) == [0.0, 128.0] and bool((s.argmax(-1) == tg).all()) and int((s == 128).sum()) == tg.numel()
+        assert float(torch.exp(torch.tensor(-128.0))) == 0.0
+        if per_query:
+            assert len({int(tg[0, 0, i]) for i in range(3)}) == 3
+    # spread / late / negative
+    qh, k, _ = perceiver_heads(*C.spread_case(5))
+    s = rb(rb(qh.float() * 0.125) @ k.float().transpose(-1, -2))
+    assert 2.7 < float(s.std()) < 3.3
+    qh, k, _ = perceiver_heads(*C.late_case())
+    s = rb(rb(qh.float() * 0.125) @ k.float().transpose(-1, -2))
+    keys = torch.tensor([[C.late_key(t, h) for h in range(8)] for t in range(C.T_MAX)])
+    assert bool((s[:, :, 1].argmax(-1) == keys).all()) and set(keys.reshape(-1).tolist()) == {256, 257, 258}
+    top2 = s[:, :, 1].topk(2, -1).values
+    assert float((top2[..., 0] - top2[..., 1]).min()) > 0.5 and float(s[:, :, 1].softmax(-1).amax(-1).median()) > 0.9
+    qh, k, _ = perceiver_heads(*C.negative_case(5))
+    s = rb(rb(qh.float() * 0.125) @ k.float().transpose(-1, -2))
+    assert float(s[:, :, 2].max()) < -28 and float(s[:, :, 2].min()) > -56
+    # binade: the roundings its docstring lists
+    q, kv = C.binade_case(5)
+    qh, k, v = perceiver_heads(q, kv)
+    exact = (qh.double() * 0.125) @ k.double().transpose(-1, -2)
+    s = rb(exact.float())
+    dom = torch.tensor([[C.binade_key(t, h) for h in range(8)] for t in range(5)])
+    assert bool((s.argmax(-1) == dom[:, :, None]).all()) and {int(x) for x in dom.reshape(-1)} >= {256, 257, 258} and int(dom.min()) < 256
+    assert sorted(set(s.reshape(-1).tolist())) == [-6.0, 0.5234375] and abs(float(exact.min()) + 6.006165) < 1e-6
+    d = s - s.amax(-1, keepdim=True)
+    assert sorted(set(d.reshape(-1).tolist())) == [-6.5234375, 0.0] and sorted(set(rb(d).reshape(-1).tolist())) == [-6.53125, 0.0]
+    p = torch.softmax(rb(d), -1)
+    assert sorted(set(rb(p).reshape(-1).tolist())) == [0.00106048583984375, 0.7265625]
+    for x in sorted(set(p.reshape(-1).tolist())):                                              # far from a rounding boundary: > 0.2 % either side
+        assert float(rb(torch.tensor(x * 1.002))) == float(rb(torch.tensor(x * 0.998)))
+    assert float(v.float().abs().min()) >= 32 and float(perceiver_attn_ref(q, kv).abs().max()) < 0.5
