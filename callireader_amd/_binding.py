@@ -80,6 +80,8 @@ SIGNATURES = {
     'cr_llm_prefill': (i32, [vp, vp, i32, vp, i32, f32, vp, vp]),
     'cr_llm_prefill_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), f32, vp, vp]),
     'cr_llm_score_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), C.POINTER(i64), f32, i32, vp, vp, vp, vp, vp]),
+    'cr_llm_ground_batch': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, C.POINTER(C.c_int32), C.POINTER(i64), f32, i32, vp, vp, vp, _i32p, _i32p, i32, i32, vp, i32,
+                            vp]),
     'cr_llm_hidden_probe': (i32, [vp, vp, i32, i32]),
     'cr_llm_decode': (i32, [vp, vp, C.POINTER(C.c_int32), i32, vp, f32, vp, vp]),
     'cr_llm_decode_draft': (i32, [vp, vp, C.POINTER(C.c_int32), i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, f32, C.POINTER(C.c_int32), vp]),
@@ -100,6 +102,7 @@ SIGNATURES = {
     'cr_op_decode_gemm': (i32, [i32, i32, vp, i64, i32, i32, i32, vp, i64, vp, vp, f32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     'cr_op_attention': (i32, [vp, vp, vp, vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp]),
     'cr_op_attention_segments': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
+    'cr_op_span_mass': (i32, [vp, i32, vp, i32, i32, i32, i32, _i32p, i32, C.c_char_p, _i32p, _i32p, f32, vp, i32, vp]),
     'cr_op_perceiver_attention': (i32, [i32, vp, vp, vp, i32, vp]),
     'cr_op_decode_attention_scratch_floats': (i64, [i32, i32]),
     'cr_op_sample': (i32, [vp, vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp]),

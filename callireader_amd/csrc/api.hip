@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "attention.hpp"
+#include "ground.hpp"
 #include "calli.hpp"
 #include <stdlib.h>
 
@@ -416,6 +417,61 @@ int cr_op_attention_segments(const void* q, const void* kc, const void* vc, void
     const AttnParams ap = segment_attn_params((const bf16*)kc, (const bf16*)vc, max_tokens, (const bf16*)q, (bf16*)o, H, kv_group, n, seg, Sq, s_div);
     const int r = launch_flash_attn(ap, 128, true, (hipStream_t)stream);
     if (r != CR_OK) return cr_fail(r, "cr_op_attention_segments(n=%d, Sq=%d, H=%d) rejected or failed", n, Sq, H);
+    return CR_OK;
+}
+
+int cr_op_span_mass(const void* q, int q_rows, const void* kc, int n_slots, int max_tokens, int H, int kv_group, const int32_t* seg_host, int n,
+                    const unsigned char* grounded_host, const int32_t* spans_host, const int32_t* span_counts_host, float s_div, float* mass, int mass_ld,
+                    void* stream) {
+    if (!q || !kc || !seg_host || !grounded_host || !spans_host || !span_counts_host || !mass || q_rows <= 0 || n_slots <= 0 || max_tokens <= 0 || n <= 0 ||
+        kv_group != GROUND_GROUP_HEADS || H <= 0 || H % kv_group != 0 || !(s_div > 0.f) || mass_ld < 0)
+        return cr_fail(CR_ERR_ARG, "cr_op_span_mass: bad argument");
+    std::vector<GroundSeq> gs(n);
+    int R = 0, total = 0, W = 0;
+    for (int i = 0; i < n; i++) {
+        const int32_t* sg = seg_host + 4 * i;
+        if (sg[0] < 0 || sg[1] <= 0 || sg[0] + sg[1] > q_rows || sg[2] < 0 || sg[2] + sg[1] > max_tokens || sg[3] < 0 || sg[3] >= n_slots)
+            return cr_fail(CR_ERR_ARG, "cr_op_span_mass: segment %d {%d, %d, %d, %d} outside q (%d rows) or the cache (%d slots of %d)", i, sg[0], sg[1], sg[2], sg[3],
+                           q_rows, n_slots, max_tokens);
+        for (int j = 0; j < i; j++) {
+            const int32_t* o = seg_host + 4 * j;
+            if (o[3] == sg[3] || (sg[0] < o[0] + o[1] && o[0] < sg[0] + sg[1])) return cr_fail(CR_ERR_ARG, "cr_op_span_mass: segments %d and %d share a slot or rows", j, i);
+        }
+        const int cnt = span_counts_host[i];
+        if (cnt < 0 || cnt > GROUND_MAX_SPANS || cnt > mass_ld) return cr_fail(CR_ERR_ARG, "cr_op_span_mass: %d spans for segment %d (want 0..%d, mass_ld %d)", cnt, i,
+                                                                               GROUND_MAX_SPANS, mass_ld);
+        const int bad = ground_check_spans(spans_host + 2 * (size_t)total, cnt, sg[2] + sg[1]);
+        if (bad) return cr_fail(CR_ERR_ARG, "cr_op_span_mass: span %d of segment %d is reversed, overlaps its predecessor, is out of order or leaves [0, %d)", bad - 1, i,
+                                sg[2] + sg[1]);
+        gs[i].slot = sg[3]; gs[i].spans = spans_host + 2 * (size_t)total; gs[i].n_spans = cnt;
+        for (int r = 0; r < sg[1]; r++)
+            if (grounded_host[sg[0] + r]) { gs[i].row_q.push_back(sg[0] + r); gs[i].row_pos.push_back(sg[2] + r); }
+        R += (int)gs[i].row_q.size(); total += cnt; W = std::max(W, cnt);
+    }
+    if (R == 0) return cr_fail(CR_ERR_ARG, "cr_op_span_mass: no grounded row");
+    const int G = ground_groups(gs);
+    std::vector<int32_t> h(ground_index_ints(R, G, n, total));
+    ground_fill_index(gs, h.data());
+    hipStream_t st = (hipStream_t)stream;
+    // a test entry: its index block and partials live for the call (stage entry points carve theirs out of the context's workspace)
+    int32_t* d_ix = nullptr;
+    float* d_part = nullptr;
+    const size_t part = std::max<size_t>(span_mass_partial_floats(H, R, W), 1);
+    if (hipMalloc((void**)&d_ix, h.size() * 4) != hipSuccess || hipMalloc((void**)&d_part, part * 4) != hipSuccess) {
+        if (d_ix) hipFree(d_ix);
+        return cr_fail(CR_ERR_NOMEM, "cr_op_span_mass: scratch");
+    }
+    int rc = hipMemcpyAsync(d_ix, h.data(), h.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess ? CR_OK : CR_ERR_HIP;
+    if (rc == CR_OK) {
+        SpanMassParams p{};
+        p.q = (const bf16*)q; p.k = (const bf16*)kc; p.H = H; p.max_tokens = max_tokens; p.s_div = s_div;
+        p.R = R; p.G = G; p.W = W; p.ix = ground_index(d_ix, R, G, n, total); p.partial = d_part; p.mass = mass; p.mass_ld = mass_ld;
+        p.first = 1; p.last = 1; p.scale = 1.0f / (float)H;
+        rc = launch_span_mass(p, st);
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    hipFree(d_ix); hipFree(d_part);
+    if (rc != CR_OK || e != hipSuccess) return cr_fail(rc != CR_OK ? rc : CR_ERR_HIP, "cr_op_span_mass(n=%d, R=%d, W=%d) rejected or failed", n, R, W);
     return CR_OK;
 }
 

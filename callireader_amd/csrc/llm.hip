@@ -19,6 +19,7 @@
 #include "attention.hpp"
 #include "decode.hpp"
 #include "draft.hpp"
+#include "ground.hpp"
 #include "kv.hpp"
 #include "logprobs.hpp"
 #include "norm.hpp"
@@ -242,12 +243,13 @@ LayerKV layer_kv(const cr_kv* kv, int l) {
     return {kv->k + l * per_layer, kv->v + l * per_layer, nullptr, nullptr, nullptr, nullptr};
 }
 
+constexpr float LLM_S_DIV = 11.313708498984761f;      // math.sqrt(128)
 // what every attention launch of the stage shares: K / V rows [slot][8][T][128], bf16-rounded scores divided by sqrt(128)
 AttnParams attn_params(const LayerKV& lk, int T, bf16* q, bf16* ao) {
     AttnParams ap{};
     ap.K = lk.k; ap.V = lk.v; ap.Q = q; ap.O = ao;
     ap.k_bs = ap.v_bs = (int64_t)NKV * T * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)T * HD;
-    ap.q_prescale = 1.0f; ap.s_div = 11.313708498984761f;      // math.sqrt(128)
+    ap.q_prescale = 1.0f; ap.s_div = LLM_S_DIV;
     return ap;
 }
 
@@ -276,6 +278,10 @@ PrefillRows prefill_rows(int32_t* p, int M, int n) {
     return {p, p + M, g, g + 4 * n, g + 8 * n, g + 9 * n, g + 13 * n, g + 17 * n};
 }
 
+// The grounding hook of a batched prefill (cr_llm_ground_batch): span_mass of ground.hip on layers [layer0, layer1), launched right after RoPE + split, when the
+// roped q of every row sits in b.q and the roped k in the cache.  p.k, p.first and p.last are filled in per layer.
+struct GroundHook { SpanMassParams p; int layer0, layer1; };
+
 // What a batched prefill (M prompt rows of n_pages pages, the longest max_S rows) takes from the workspace
 struct PrefillBufs {
     int M, n_pages, max_S, ff;
@@ -288,6 +294,7 @@ struct PrefillBufs {
     unsigned char* a8;  // any8: e4m3 rows of the attention output / the SwiGLU output
     PrefillRows rows;
     HeadBufs head;
+    const GroundHook* ground = nullptr;      // null: the call does not ground (nothing is launched for it)
 
     PrefillBufs(cr_ctx* c, int ff, const cr_kv* kv, int M, int n_pages, int max_S, const RowFeatures& f)
         : M(M), n_pages(n_pages), max_S(max_S), ff(ff), kv8(kv->fmt == CR_KV_E4M3), any8(c->fp8_mfma && M >= 256),
@@ -343,6 +350,11 @@ int prefill_layers(cr_ctx* c, const LlmWeights& lw, cr_kv* kv, const PrefillBufs
         // (bf16 cache: lk's e4m3 pointers are null, and the kernel takes no staging)
         hipLaunchKernelGGL(b.kv8 ? rope_split_kernel<true> : rope_split_kernel<false>, dim3(M, NKV), dim3(128), 0, st, b.qkv, cosT, sinT, b.q, lk.k, lk.v, 0, 0,
                            r.row_seq, nullptr, r.row_pos, kv->max_tokens, nullptr, 0, lk.k8, lk.v8, lk.ks, lk.vs, b.kv8 ? r.row_page : nullptr, b.kv8 ? b.max_S : 0, nullptr);
+        if (b.ground && l >= b.ground->layer0 && l < b.ground->layer1) {
+            SpanMassParams gp = b.ground->p;
+            gp.k = lk.k; gp.first = l == b.ground->layer0; gp.last = l + 1 == b.ground->layer1;
+            if (launch_span_mass(gp, st) != CR_OK) return cr_fail(CR_ERR_HIP, "span mass launch failed");
+        }
         // FINAL layer: only each page's last row is ever read again (the LM head, :1081-1082 + _sample; the reference computes every row).  K / V of
         // every row still go to the cache, so the norm, wqkv and RoPE + split run on all rows; attention, wo, the second norm, w1|w3 and w2 run on the n last rows
         // only -- 88 % of that layer's linear work.  Bit-exact: the tiled kernels give a row the same sum whatever it is batched with (LIN_PREFILL pins rows <= 64;
@@ -409,6 +421,11 @@ struct ScoreBufs {
     int32_t* gather;    // per scored row: its row in the prefill
     int64_t* index;     // score.hpp's index block
     int32_t* first;
+    // cr_llm_ground_batch: the hook, its index arrays and one layer's partials (g_ints = 0: the call does not ground).  head = false: grounding only, no LM head
+    bool head = true;
+    size_t g_ints = 0, g_part = 0;
+    int32_t* g_index = nullptr;
+    GroundHook hook{};
 
     ScoreBufs(cr_ctx* c, int ff, const cr_kv* kv, int M, int n_pages, int max_S, int R, bool pen)
         : pre(c, ff, kv, M, n_pages, max_S, RowFeatures{}), R(R), tile(std::min(R, SCORE_HEAD_ROWS)), V(c->d.vocab), pen(pen) {
@@ -418,12 +435,19 @@ struct ScoreBufs {
 
     void carve(Arena& ar) {
         pre.carve(ar);
-        xs = ar.take<bf16>((size_t)R * D); hl = ar.take<bf16>((size_t)tile * D);
-        lg = ar.take<float>((size_t)tile * V);
-        scratch = ar.take<char>(logprobs_scratch_bytes(tile, V));
-        gather = ar.take<int32_t>((size_t)R);
-        index = ar.take<int64_t>(score_index_words(R));
-        first = pen ? ar.take<int32_t>((size_t)pre.n_pages * V) : nullptr;
+        xs = hl = nullptr; lg = nullptr; scratch = nullptr; gather = nullptr; index = nullptr; first = nullptr;
+        if (head) {
+            xs = ar.take<bf16>((size_t)R * D); hl = ar.take<bf16>((size_t)tile * D);
+            lg = ar.take<float>((size_t)tile * V);
+            scratch = ar.take<char>(logprobs_scratch_bytes(tile, V));
+            gather = ar.take<int32_t>((size_t)R);
+            index = ar.take<int64_t>(score_index_words(R));
+            first = pen ? ar.take<int32_t>((size_t)pre.n_pages * V) : nullptr;
+        }
+        if (g_ints) {
+            g_index = ar.take<int32_t>(g_ints);
+            hook.p.partial = ar.take<float>(g_part);
+        }
     }
 };
 
@@ -689,32 +713,40 @@ int cr_llm_prefill(cr_ctx* c, cr_kv* kv, int seq, const void* embeds, int S, flo
     return cr_llm_prefill_batch(c, kv, &s, 1, embeds, &l, penalty, last_logits, stream);
 }
 
-int cr_llm_score_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host, float penalty,
-                       int top_n, float* lp, int32_t* top_ids, float* top_lp, float* logits, void* stream) {
-    if (top_n < 0 || top_n > LOGPROBS_MAX_TOP) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: top_n %d (want 0..%d)", top_n, LOGPROBS_MAX_TOP);
-    if (!c || !kv || !seqs || !lens || !embeds || !targets_host || !lp || (top_n > 0 && (!top_ids || !top_lp)) || n <= 0 || n > kv->n_seqs)
-        return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: bad argument");
-    if (!(penalty > 0.f) || penalty > FLT_MAX) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: penalty %g (want a finite value > 0)", penalty);
-    if (!c->finalized) return cr_fail(CR_ERR_STATE, "cr_llm_score_batch: call cr_finalize first");
-    CR_TRY(ctx_share_ok(c, "cr_llm_score_batch"));
+// What cr_llm_ground_batch adds to a scoring call (host arrays as the header describes them)
+struct GroundArgs { const int32_t* spans; const int32_t* counts; int layer0, layer1; float* mass; int mass_ld; };
+
+// cr_llm_score_batch and cr_llm_ground_batch: ONE function.  g = null: a scoring call, which launches what it always launched.  lp = null (grounding
+// calls only): no gather, no final norm, no LM head, no score kernels.
+static int score_rows_batch(const char* who, cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host,
+                            float penalty, int top_n, float* lp, int32_t* top_ids, float* top_lp, float* logits, const GroundArgs* g, void* stream) {
+    if (top_n < 0 || top_n > LOGPROBS_MAX_TOP) return cr_fail(CR_ERR_ARG, "%s: top_n %d (want 0..%d)", who, top_n, LOGPROBS_MAX_TOP);
+    if (!c || !kv || !seqs || !lens || !embeds || !targets_host || (!lp && !g) || (top_n > 0 && (!lp || !top_ids || !top_lp)) || n <= 0 || n > kv->n_seqs)
+        return cr_fail(CR_ERR_ARG, "%s: bad argument", who);
+    if (g && (!g->mass || !g->spans || !g->counts)) return cr_fail(CR_ERR_ARG, "%s: null mass, spans or span counts", who);
+    if (!(penalty > 0.f) || penalty > FLT_MAX) return cr_fail(CR_ERR_ARG, "%s: penalty %g (want a finite value > 0)", who, penalty);
+    if (!c->finalized) return cr_fail(CR_ERR_STATE, "%s: call cr_finalize first", who);
+    CR_TRY(ctx_share_ok(c, who));
     const LlmWeights* lw;
     CR_TRY(llm_weights(c, &lw));
-    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: an e4m3 cache (left out: a continued prefill needs the bf16 prefix)");
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "%s: an e4m3 cache (left out: a continued prefill needs the bf16 prefix)", who);
+    if (g && (g->layer0 < 0 || g->layer1 > c->d.llm_layers || g->layer0 >= g->layer1))
+        return cr_fail(CR_ERR_ARG, "%s: layers [%d, %d) (want a non-empty range inside [0, %d))", who, g->layer0, g->layer1, c->d.llm_layers);
     const int V = c->d.vocab;
     std::vector<Segment> segs;
     int M = 0, max_S = 0;
     for (int i = 0; i < n; i++) {
         const int s = seqs[i];
-        if (s < 0 || s >= kv->n_seqs || lens[i] <= 0) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: bad sequence %d / length %d", s, lens[i]);
-        for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: sequence %d listed twice", s);
+        if (s < 0 || s >= kv->n_seqs || lens[i] <= 0) return cr_fail(CR_ERR_ARG, "%s: bad sequence %d / length %d", who, s, lens[i]);
+        for (int j = 0; j < i; j++) if (seqs[j] == s) return cr_fail(CR_ERR_ARG, "%s: sequence %d listed twice", who, s);
         if (kv->seq[s].len + lens[i] > kv->max_tokens)
-            return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: %d + %d tokens exceed the cache (%d)", kv->seq[s].len, lens[i], kv->max_tokens);
-        if (kv->seq[s].bgrp >= 0) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: sequence %d belongs to the beam group of sequence %d", s, kv->seq[s].bgrp);
+            return cr_fail(CR_ERR_ARG, "%s: %d + %d tokens exceed the cache (%d)", who, kv->seq[s].len, lens[i], kv->max_tokens);
+        if (kv->seq[s].bgrp >= 0) return cr_fail(CR_ERR_ARG, "%s: sequence %d belongs to the beam group of sequence %d", who, s, kv->seq[s].bgrp);
         segs.push_back({s, M, lens[i], kv->seq[s].len});
         M += lens[i];
         max_S = std::max(max_S, lens[i]);
     }
-    // the scored rows, in row order: slot r of lp / top_* / logits; history = the call's sequence ordinal, ordinal = the row's place among that sequence's scored rows
+    // the scored rows, in row order: slot r of lp / top_* / logits / mass; history = the call's sequence ordinal, ordinal = the row's place among that sequence's scored rows
     std::vector<int32_t> gather;
     std::vector<int64_t> tgt;
     std::vector<int32_t> hist, ord;
@@ -723,46 +755,94 @@ int cr_llm_score_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const v
         for (int r = 0; r < segs[i].S; r++) {
             const int64_t y = targets_host[segs[i].row0 + r];
             if (y < 0) continue;
-            if (y >= V) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: target %lld of sequence %d outside the vocabulary (%d)", (long long)y, segs[i].seq, V);
+            if (y >= V) return cr_fail(CR_ERR_ARG, "%s: target %lld of sequence %d outside the vocabulary (%d)", who, (long long)y, segs[i].seq, V);
             gather.push_back(segs[i].row0 + r); tgt.push_back(y); hist.push_back(i); ord.push_back(j++);
         }
     }
     const int R = (int)gather.size();
-    if (R == 0) return cr_fail(CR_ERR_ARG, "cr_llm_score_batch: no scored row (every target < 0)");
+    if (R == 0) return cr_fail(CR_ERR_ARG, "%s: no scored row (every target < 0)", who);
+    // the grounded rows are the scored rows; a sequence's spans lie inside what it holds after the call
+    std::vector<GroundSeq> gseqs;
+    int g_total = 0, g_W = 0;
+    if (g) {
+        gseqs.resize(n);
+        for (int i = 0; i < n; i++) {
+            const int cnt = g->counts[i];
+            if (cnt < 0 || cnt > GROUND_MAX_SPANS) return cr_fail(CR_ERR_ARG, "%s: %d spans for sequence %d (want 0..%d)", who, cnt, segs[i].seq, GROUND_MAX_SPANS);
+            if (cnt > g->mass_ld) return cr_fail(CR_ERR_ARG, "%s: mass_ld %d below the %d spans of sequence %d", who, g->mass_ld, cnt, segs[i].seq);
+            const int bad = ground_check_spans(g->spans + 2 * (size_t)g_total, cnt, segs[i].pos0 + segs[i].S);
+            if (bad) return cr_fail(CR_ERR_ARG, "%s: span %d of sequence %d is reversed, overlaps its predecessor, is out of order or leaves [0, %d)", who, bad - 1,
+                                    segs[i].seq, segs[i].pos0 + segs[i].S);
+            gseqs[i].slot = segs[i].seq; gseqs[i].spans = g->spans + 2 * (size_t)g_total; gseqs[i].n_spans = cnt;
+            g_total += cnt; g_W = std::max(g_W, cnt);
+        }
+        for (int r = 0; r < R; r++) {
+            const Segment& sg = segs[hist[r]];
+            gseqs[hist[r]].row_q.push_back(gather[r]); gseqs[hist[r]].row_pos.push_back(sg.pos0 + gather[r] - sg.row0);
+        }
+    }
     for (int i = 0; i < n; i++)
         if (kv->seq[seqs[i]].ngen != 0)
-            return cr_fail(CR_ERR_STATE, "cr_llm_score_batch: sequence %d holds %d generated ids (the penalty history is the call's own: cr_kv_truncate / cr_kv_fork / "
-                           "cr_kv_reset give a sequence without ids)", seqs[i], kv->seq[seqs[i]].ngen);
+            return cr_fail(CR_ERR_STATE, "%s: sequence %d holds %d generated ids (the penalty history is the call's own: cr_kv_truncate / cr_kv_fork / "
+                           "cr_kv_reset give a sequence without ids)", who, seqs[i], kv->seq[seqs[i]].ngen);
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const bool pen = penalty != 1.0f;
     ScoreBufs b(c, lw->ff, kv, M, n, max_S, R, pen);
-    CR_TRY(ws_carve(c, "cr_llm_score_batch", b));
+    b.head = lp != nullptr;
+    const int G = g ? ground_groups(gseqs) : 0;
+    if (g) { b.g_ints = ground_index_ints(R, G, n, g_total); b.g_part = std::max<size_t>(span_mass_partial_floats(NH, R, g_W), 1); }
+    CR_TRY(ws_carve(c, who, b));
     CR_TRY(stage_prefill_rows(b.pre, segs, st));
-    {
+    if (g) {
+        std::vector<int32_t> h(b.g_ints);
+        ground_fill_index(gseqs, h.data());
+        CR_HIP(hipMemcpyAsync(b.g_index, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before return
+        SpanMassParams& gp = b.hook.p;
+        gp.q = b.pre.q; gp.H = NH; gp.max_tokens = kv->max_tokens; gp.s_div = LLM_S_DIV;
+        gp.R = R; gp.G = G; gp.W = g_W; gp.ix = ground_index(b.g_index, R, G, n, g_total);
+        gp.mass = g->mass; gp.mass_ld = g->mass_ld; gp.scale = 1.0f / (float)(NH * (g->layer1 - g->layer0));
+        b.hook.layer0 = g->layer0; b.hook.layer1 = g->layer1;
+        b.pre.ground = &b.hook;
+    }
+    if (b.head) {
         std::vector<int64_t> h(score_index_words(R));
         const ScoreIndex hx = score_index(h.data(), R);
         for (int r = 0; r < R; r++) { hx.tgt[r] = tgt[r]; hx.hist[r] = hist[r]; hx.ord[r] = ord[r]; }
         CR_HIP(hipMemcpyAsync(b.index, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));      // pageable sources: staged before return
         CR_HIP(hipMemcpyAsync(b.gather, gather.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
     }
-    const ScoreIndex ix = score_index(b.index, R);
     CR_HIP(hipMemcpyAsync(b.pre.x, embeds, (size_t)M * D * 2, hipMemcpyDeviceToDevice, st));
     CR_TRY(prefill_layers(c, *lw, kv, b.pre, st));
-    hipLaunchKernelGGL(move_rows_kernel<true>, dim3(R), dim3(256), 0, st, b.pre.x, b.gather, b.xs);
-    if (pen) CR_TRY(launch_score_table(ix, R, n, V, b.first, st));
-    // the head in tiles: LIN_PREFILL keeps a row's logits independent of the tile's size and of the row's place in it
-    for (int r0 = 0; r0 < R; r0 += b.tile) {
-        const int rows = std::min(b.tile, R - r0);
-        CR_TRY(rms(b.xs + (size_t)r0 * D, b.hl, lw->norm, rows, c->d.rms_eps, st));
-        CR_TRY(linear(c, EPI_F32, b.hl, lw->head, LIN_PREFILL, b.lg, rows, st));
-        if (logits) CR_HIP(hipMemcpyAsync(logits + (size_t)r0 * V, b.lg, (size_t)rows * V * 4, hipMemcpyDeviceToDevice, st));
-        CR_TRY(launch_score_rows(ScoreLaunch{b.lg, V, V, rows, r0, ix, b.first, penalty, top_n, b.scratch, lp, top_ids, top_lp}, st));
+    if (b.head) {
+        const ScoreIndex ix = score_index(b.index, R);
+        hipLaunchKernelGGL(move_rows_kernel<true>, dim3(R), dim3(256), 0, st, b.pre.x, b.gather, b.xs);
+        if (pen) CR_TRY(launch_score_table(ix, R, n, V, b.first, st));
+        // the head in tiles: LIN_PREFILL keeps a row's logits independent of the tile's size and of the row's place in it
+        for (int r0 = 0; r0 < R; r0 += b.tile) {
+            const int rows = std::min(b.tile, R - r0);
+            CR_TRY(rms(b.xs + (size_t)r0 * D, b.hl, lw->norm, rows, c->d.rms_eps, st));
+            CR_TRY(linear(c, EPI_F32, b.hl, lw->head, LIN_PREFILL, b.lg, rows, st));
+            if (logits) CR_HIP(hipMemcpyAsync(logits + (size_t)r0 * V, b.lg, (size_t)rows * V * 4, hipMemcpyDeviceToDevice, st));
+            CR_TRY(launch_score_rows(ScoreLaunch{b.lg, V, V, rows, r0, ix, b.first, penalty, top_n, b.scratch, lp, top_ids, top_lp}, st));
+        }
     }
     hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(256), 0, st, b.pre.rows.seg, n, kv->d_len);
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) kv->seq[sg.seq].len += sg.S;      // no pick: no id is appended
     return CR_OK;
+}
+
+int cr_llm_score_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host, float penalty,
+                       int top_n, float* lp, int32_t* top_ids, float* top_lp, float* logits, void* stream) {
+    return score_rows_batch("cr_llm_score_batch", c, kv, seqs, n, embeds, lens, targets_host, penalty, top_n, lp, top_ids, top_lp, logits, nullptr, stream);
+}
+
+int cr_llm_ground_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host, float penalty,
+                        int top_n, float* lp, int32_t* top_ids, float* top_lp, const int32_t* spans_host, const int32_t* span_counts_host, int layer0, int layer1,
+                        float* mass, int mass_ld, void* stream) {
+    const GroundArgs g{spans_host, span_counts_host, layer0, layer1, mass, mass_ld};
+    return score_rows_batch("cr_llm_ground_batch", c, kv, seqs, n, embeds, lens, targets_host, penalty, top_n, lp, top_ids, top_lp, nullptr, &g, stream);
 }
 
 int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_t* force_tokens, float penalty, float* logits,

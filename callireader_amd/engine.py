@@ -277,6 +277,55 @@ class Engine:
             r += k
         return (out, logits) if want_logits else out
 
+    def ground_batch(self, kv, seqs, embeds_list, targets_list, spans_list, layers=None, penalty=1.0, top_n=0, want_scores=True):
+        """cr_llm_ground_batch on the current stream: score_batch's pass, which also reports the attention mass every scored row puts on the spans of its
+        sequence.  spans_list[i] = [(start, end), ...] absolute cache positions of sequence seqs[i] (sorted, not overlapping, inside the sequence's length after
+        the call); layers = (layer0, layer1) or None for all.  Returns (scores, mass): one scores.TokenScores per sequence (None each with want_scores=False:
+        a grounding-only call that runs no LM head, top_n must be 0) and one float32 CPU tensor [T_i, len(spans_list[i])] per sequence.  Synchronises the
+        stream."""
+        from . import grounding
+        from .scores import TokenScores
+        n = len(seqs)
+        top_n = int(top_n)
+        if not 0 <= top_n <= 8:
+            raise ValueError(f'top_n has to be 0..8, got {top_n}')
+        if top_n and not want_scores:
+            raise ValueError('ground_batch: top_n > 0 needs want_scores')
+        if len(embeds_list) != n or len(targets_list) != n or len(spans_list) != n:
+            raise ValueError(f'ground_batch: {n} sequences, {len(embeds_list)} embeddings, {len(targets_list)} target lists, {len(spans_list)} span lists')
+        l0, l1 = grounding.check_layers(layers, self.dims.llm_layers)
+        es = [e.reshape(-1, self.dims.llm_hidden) for e in embeds_list]
+        lens = [e.shape[0] for e in es]
+        tg = [[int(t) for t in tl] for tl in targets_list]
+        for i in range(n):
+            if len(tg[i]) != lens[i]:
+                raise ValueError(f'ground_batch: sequence {seqs[i]} has {lens[i]} rows but {len(tg[i])} targets')
+        spans = [grounding.check_spans(sp) for sp in spans_list]
+        flat = [t for tl in tg for t in tl]
+        counts = [sum(1 for t in tl if t >= 0) for tl in tg]
+        R = sum(counts)
+        sp_counts = [len(sp) for sp in spans]
+        sp_flat = [v for sp in spans for se in sp for v in se] or [0]
+        ld = max(sp_counts + [1])
+        cat = es[0].contiguous() if n == 1 else torch.cat(es, dim=0)
+        lp = torch.empty(max(R, 1), device=self.device, dtype=torch.float32) if want_scores else None
+        ti = torch.empty(max(R, 1), 8, device=self.device, dtype=torch.int32) if top_n else None
+        tl = torch.empty(max(R, 1), 8, device=self.device, dtype=torch.float32) if top_n else None
+        mass = torch.empty(max(R, 1), ld, device=self.device, dtype=torch.float32)
+        B.check(B.lib.cr_llm_ground_batch(self._h, kv._h, (C.c_int32 * n)(*seqs), n, _p(cat), (C.c_int32 * n)(*lens), (C.c_int64 * len(flat))(*flat),
+                                          float(penalty), top_n, _p(lp), _p(ti), _p(tl), (C.c_int32 * len(sp_flat))(*sp_flat), (C.c_int32 * n)(*sp_counts),
+                                          l0, l1, _p(mass), ld, _stream()), 'cr_llm_ground_batch')
+        mass_h = mass.cpu()
+        lp_h = lp.cpu().numpy() if want_scores else None
+        ti_h = ti.cpu().numpy()[:, :top_n] if top_n else np.empty((R, 0), dtype=np.int32)
+        tl_h = tl.cpu().numpy()[:, :top_n] if top_n else np.empty((R, 0), dtype=np.float32)
+        out, ms, r = [], [], 0
+        for k, w in zip(counts, sp_counts):
+            out.append(TokenScores(lp_h[r:r + k].copy(), ti_h[r:r + k].copy(), tl_h[r:r + k].copy()) if want_scores else None)
+            ms.append(mass_h[r:r + k, :w].clone())
+            r += k
+        return out, ms
+
     def hidden_probe(self, rows=None, row0=0):
         """cr_llm_hidden_probe: `rows` > 0 arms it and returns the [llm_layers + 1, rows, 4096] bf16 tensor the next prefill fills
         (residual stream before layer 0 and after each layer); rows=None disarms."""
@@ -671,6 +720,33 @@ def op_attention_segments(q, kc, vc, o, segs, s_div=11.313708498984761, Sq=None)
     B.check(B.lib.cr_op_attention_segments(_p(q), _p(kc), _p(vc), _p(o), _p(d_seg), len(segs), int(Sq), H, H // n_kv, max_tokens, float(s_div), _stream()),
             'cr_op_attention_segments')
     return o
+
+
+def op_span_mass(q, kc, segs, spans_list, grounded=None, s_div=11.313708498984761, mass_ld=None):
+    """cr_op_span_mass: the span-mass kernels of cr_llm_ground_batch alone, on one layer.  q (rows, H, 128) bf16 roped queries, kc (n_slots, H / 4, max_tokens,
+    128) bf16 K cache holding every segment's keys, segs = [(first row, rows, first position, cache slot), ...], spans_list[i] = [(start, end), ...] of segment
+    i, grounded = a bool per row of q (default: every row).  Returns mass [R, mass_ld] float32 on the device, R = the grounded rows in segment then row order:
+    the mean over the H heads of the probability each row puts on each span."""
+    rows, H, hd = q.shape
+    n_slots, n_kv, max_tokens, _ = kc.shape
+    if hd != 128 or kc.shape[3] != 128 or H != 4 * n_kv or not segs or len(spans_list) != len(segs):
+        raise ValueError('op_span_mass: q (rows, H, 128), kc (n_slots, H / 4, max_tokens, 128), one span list per segment')
+    for t in (q, kc):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError('op_span_mass: contiguous bf16 tensors')
+    flags = bytes([1] * rows) if grounded is None else bytes(1 if g else 0 for g in grounded)
+    if len(flags) != rows:
+        raise ValueError(f'op_span_mass: {len(flags)} grounded flags for {rows} rows')
+    R = sum(sum(flags[r0:r0 + S]) for r0, S, _, _ in segs)
+    counts = [len(sp) for sp in spans_list]
+    ld = max(counts + [1]) if mass_ld is None else int(mass_ld)
+    sp_flat = [int(v) for sp in spans_list for se in sp for v in se] or [0]
+    seg_flat = [int(x) for s in segs for x in s]
+    mass = torch.empty(max(R, 1), ld, device=q.device, dtype=torch.float32)
+    B.check(B.lib.cr_op_span_mass(_p(q), rows, _p(kc), n_slots, max_tokens, H, H // n_kv, (C.c_int32 * len(seg_flat))(*seg_flat), len(segs), flags,
+                                  (C.c_int32 * len(sp_flat))(*sp_flat), (C.c_int32 * len(counts))(*counts), float(s_div), _p(mass), ld, _stream()),
+            'cr_op_span_mass')
+    return mass[:R]
 
 
 def op_decode_swizzle(which, W):

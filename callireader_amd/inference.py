@@ -129,6 +129,36 @@ def score_rec(model, tokenizer, detect_model, generation_config, image_path, pro
     return sc
 
 
+def grounding_name(save_name):
+    """The file of --ground / --ground_answer: `.grounding.json` in place of the results name's `json` ending."""
+    if not save_name.endswith('json'):
+        save_name += '_result.json'
+    return save_name[:-len('json')].rstrip('.') + '.grounding.json'
+
+
+def ground_rec(model, tokenizer, detect_model, generation_config, image_path, prompt, answer, save_name, use_p, hard_vq, drop_zero, repetition_penalty, verbose,
+               boxes=None):
+    """--ground (answer=None: the recognition itself, generated once and grounded over its cached prompt) / --ground_answer TEXT on a single image
+    (model.ground_ocr): which character box every piece of the reply came from.  Prints the recognition as single_rec does (or `Grounded: TEXT`), then one
+    `<piece> -> [x1, y1, x2, y2] <mass>` line per piece, and writes {imagePath, prompt, response, grounding: [{piece, box, mass}, ...]} to `save_name`.
+    Returns (response, grounding.Grounding)."""
+    bx = None
+    if boxes is not None or detect_model is None:
+        bx = boxes_for(image_path, boxes)
+    gc = {k: v for k, v in generation_config.items() if not (k == 'num_beams' and v == 1) and not (k == 'do_sample' and not v)}
+    if answer is not None:
+        gc.pop('max_new_tokens', None)
+    response, g = model.ground_ocr(tokenizer, detect_model, image_path, prompt, answer, gc, repetition_penalty=repetition_penalty, use_p=use_p,
+                                   hard_vq=hard_vq, drop_zero=drop_zero, boxes=bx, verbose=verbose)
+    print(f'User: {prompt}\nAssistant: {response}' if answer is None else f'Grounded: {answer}')
+    for piece, box, mass in g.pairs():
+        print(f'{piece} -> {box} {mass:.4f}')
+    os.makedirs(os.path.dirname(save_name) or '.', exist_ok=True)
+    with open(save_name, 'w', encoding='utf-8') as f:
+        json.dump({'imagePath': image_path, 'prompt': prompt, 'response': response, 'grounding': g.to_json()}, f, ensure_ascii=False, indent=4)
+    return response, g
+
+
 DEFAULT_BATCH_PAGES = 64       # pages per decode batch in folder mode: the most rows the batched decode kernels take, and the batch the headline is measured on
 
 
@@ -331,6 +361,11 @@ def build_parser():
     parser.add_argument('--score_answer', type=str, default=None, metavar='TEXT',
                         help='single image: besides the recognition, score TEXT as the reply to --prompt (per-token log-probabilities of a text you bring: a ground '
                              'truth, a candidate); prints its confidence line and total log-probability and writes results/<save_name minus json>.answer_scores.json')
+    parser.add_argument('--ground', action='store_true',
+                        help='single image: ground the recognition -- which character box every piece of the response came from (attention mass of the piece\'s '
+                             'row on the box\'s pseudo-tokens, averaged over heads and layers); prints one line per piece and writes '
+                             'results/<save_name minus json>.grounding.json with "grounding": [{"piece", "box": [x1, y1, x2, y2], "mass"}, ...] (greedy only; needs --use_p)')
+    parser.add_argument('--ground_answer', type=str, default=None, metavar='TEXT', help='single image: the same for TEXT as the reply to --prompt (a text you bring)')
     return parser
 
 
@@ -366,7 +401,11 @@ def main(argv=None):
     if args.seed is not None:
         torch.manual_seed(args.seed)
     detect_model = load_detector(args.params)
-    if is_image(args.tgt):
+    if is_image(args.tgt) and (args.ground or args.ground_answer is not None):
+        print('Single image recognition mode.')
+        ground_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, args.ground_answer,
+                   grounding_name(os.path.join('results', args.save_name)), args.use_p, args.hard_vq, args.drop_zero, args.repetition_penalty, args.verbose, args.boxes)
+    elif is_image(args.tgt):
         print('Single image recognition mode.')
         single_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, args.use_p, args.hard_vq, args.drop_zero,
                    args.repetition_penalty, args.verbose, args.boxes, scores=args.scores, draft='align' if args.draft else None)
@@ -377,6 +416,8 @@ def main(argv=None):
     elif os.path.isdir(args.tgt):
         if args.score_answer is not None:
             raise ValueError('--score_answer works on a single image')
+        if args.ground or args.ground_answer is not None:
+            raise ValueError('--ground / --ground_answer work on a single image')
         print('Multiple images recognition mode')
         os.makedirs('results', exist_ok=True)
         folder_rec(model, tokenizer, detect_model, generation_config, args.tgt, args.prompt, os.path.join('results', args.save_name),

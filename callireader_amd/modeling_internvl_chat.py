@@ -27,6 +27,7 @@ from .conversation import get_conv_template
 from .engine import Engine
 from .constraints import parse as constraints_parse, per_page as constraints_per_page
 from . import draft as drafting
+from . import grounding
 from . import scoring
 from .generation import admit, check_fits, decode_rows, decode_rows_drafted, per_page_sampling, read_scores, reply_shape, reply_text
 from .pipeline import PagePipeline
@@ -1175,6 +1176,89 @@ class InternVLChatModel:
                                           img_id=self.img_context_token_id, ref_id=self.aligned_token_id)
         toks, ts = self.score_pages([prompt], [scoring.answer_to_ids(tokenizer, answer)], penalty, top_n, eos_token_id=gc['eos_token_id'], score_eos=score_eos)
         return scoring.response_scores(tokenizer, toks[0], ts[0])
+
+    @torch.no_grad()
+    def ground_pages(self, embeds_list, answer_ids_list, spans_list, layers=None, repetition_penalty=1.0, logprobs=None, eos_token_id=EOS_TOKEN_ID,
+                     score_eos=True):
+        """The twin of score_pages that also says WHERE every scored id's row looked: spans_list[i] = [(start, end), ...] ranges of page i's prompt positions
+        (grounding.spans_of finds the character boxes' pseudo-token runs), and ONE prefill-shaped pass (cr_llm_ground_batch) gives per scored id the
+        attention probability its row put on every span, averaged over the heads and over `layers` = (layer0, layer1), None: all layers.  Which layers ground
+        best can only be learned on a real checkpoint: no default is tuned here.  logprobs: None (no LM head runs), or 0..8 alternatives per id for the scores
+        of the same pass.  Returns (ids, masses, scores): per page the scored ids, a float32 CPU tensor [T, spans] and a scores.TokenScores (None without
+        logprobs).  A bf16 cache; nothing is generated."""
+        P = len(embeds_list)
+        if len(answer_ids_list) != P or len(spans_list) != P:
+            raise ValueError(f'ground_pages: {len(answer_ids_list)} answers and {len(spans_list)} span lists for {P} pages')
+        penalty = scoring.check_penalty(repetition_penalty)
+        top_n = 0 if logprobs is None else scoring.top_n_of(logprobs)
+        if self.kv_cache_dtype != 'bf16':
+            raise NotImplementedError("grounding continues a prefill in bf16: an e4m3 KV cache (kv_cache_dtype='e4m3') is not grounded")
+        es = [e.reshape(-1, e.shape[-1]) for e in embeds_list]
+        plans = [scoring.plan(e.shape[0], a, eos_token_id, score_eos, self.dims.vocab) for e, a in zip(es, answer_ids_list)]
+        spans = [grounding.check_spans(sp, e.shape[0] + len(pl.feed)) for sp, e, pl in zip(spans_list, es, plans)]
+        layers = grounding.check_layers(layers, self.dims.llm_layers)
+        for e, pl in zip(es, plans):
+            scoring.check_fits(e.shape[0] + len(pl.feed), 0, self.max_tokens)
+        kv, seqs = self.kv(P), list(range(P))
+        for s in seqs:
+            kv.reset(s)
+        rows = [torch.cat([e, self.engine.embed_splice(torch.tensor(pl.feed, dtype=torch.long))], dim=0) if pl.feed else e for e, pl in zip(es, plans)]
+        ts, ms = self.engine.ground_batch(kv, seqs, rows, [pl.targets for pl in plans], spans, layers=layers, penalty=penalty, top_n=top_n,
+                                          want_scores=logprobs is not None)
+        return [pl.ids for pl in plans], ms, ts
+
+    @torch.no_grad()
+    def ground_ocr(self, tokenizer, detect_model, img_path, question, answer=None, generation_config=None, layers=None, repetition_penalty=1.5,
+                   top_logprobs=None, history=None, use_p=True, drop_zero=False, hard_vq=False, boxes=None, score_eos=True, draft=None, verbose=False):
+        """Which character box every id of the reply came from.  answer (a string, or a list of ids): the text is the caller's, and the call works like
+        score_ocr -- one pass over prompt ++ answer.  answer=None: the reply is generated greedily as chat_ocr generates it (one visual stage, one prompt
+        prefill), the sequence is rolled back to the prompt's last row (cr_kv_truncate(seq, L - 1)) and the generated ids are grounded over the cached prompt
+        by one continued prefill of T + 1 rows.  The boxes are taken here (`boxes=`, or ordering.acquire_boxes as calli_align takes them) and handed to
+        calli_align, so the result carries the very boxes the pseudo-tokens were made from.  layers = (layer0, layer1), None: all layers -- which range
+        grounds best can only be learned on a real checkpoint.  top_logprobs: None, or 0..8 for the scores of the same pass (Grounding.scores).
+        Returns (response, grounding.Grounding).  Nothing that steers a generation (do_sample, num_beams > 1, constraints, a draft): ValueError; an e4m3 KV
+        cache: NotImplementedError."""
+        gc = scoring.refuse_generation(generation_config, draft, 'ground_ocr')
+        penalty = scoring.check_penalty(repetition_penalty)
+        top_n = None if top_logprobs is None else scoring.top_n_of(top_logprobs)
+        if not use_p:
+            raise ValueError('ground_ocr: use_p=False (the boxes reach the prompt as pseudo-tokens: there is nothing to ground on without them)')
+        if self.kv_cache_dtype != 'bf16':
+            raise NotImplementedError("grounding continues a prefill in bf16: an e4m3 KV cache (kv_cache_dtype='e4m3') is not grounded")
+        n_layers = getattr(getattr(self, 'dims', None), 'llm_layers', None)
+        if layers is not None and n_layers is not None:
+            layers = grounding.check_layers(layers, n_layers)
+        page, pixel_values = self._open_page(img_path)
+        if boxes is None:
+            from . import ordering
+            boxes = ordering.acquire_boxes(detect_model, page, self.sorter)
+        boxes = [[int(v) for v in b[:4]] for b in boxes]
+        out_tokens, indices = self.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
+        _, _, template, model_inputs, gc = self._ocr_prompt(tokenizer, question, history, len(pixel_values), out_tokens, use_p, None, gc, False)
+        ids = model_inputs['input_ids'].reshape(-1)
+        spans = grounding.check_spans(grounding.spans_of(ids, self.aligned_token_id, grounding.kept_per_box(indices) if drop_zero else 3))
+        if len(spans) != len(boxes):
+            raise ValueError(f'ground_ocr: the prompt holds the pseudo-tokens of {len(spans)} boxes, the page has {len(boxes)}')
+        prompt = self.engine.embed_splice(ids, self.extract_feature(pixel_values), out_tokens, img_id=self.img_context_token_id, ref_id=self.aligned_token_id)
+        if answer is not None:
+            toks, ms, ts = self.ground_pages([prompt], [scoring.answer_to_ids(tokenizer, answer)], [spans], layers, penalty, top_n,
+                                             eos_token_id=gc['eos_token_id'], score_eos=score_eos)
+            y, mass, ts = toks[0], ms[0], ts[0]
+            response = answer if isinstance(answer, str) else reply_text(tokenizer, torch.tensor([y], dtype=torch.long), template.sep)
+        else:
+            max_new, eos, _ = self._gen_args(gc)
+            kv = self.kv(1)
+            y = self._generate(prompt, max_new, eos, penalty, kv=kv, seq=0)[0].tolist()
+            response = reply_text(tokenizer, torch.tensor([y], dtype=torch.long), template.sep)
+            L = prompt.shape[0]
+            scoring.check_fits(len(y), L - 1, self.max_tokens)
+            kv.truncate(0, L - 1)
+            rows = torch.cat([prompt[L - 1:], self.engine.embed_splice(torch.tensor(y[:-1], dtype=torch.long))], dim=0) if len(y) > 1 else prompt[L - 1:]
+            tss, ms = self.engine.ground_batch(kv, [0], [rows], [y], [spans], layers=layers, penalty=penalty, top_n=top_n or 0, want_scores=top_n is not None)
+            mass, ts = ms[0], tss[0]
+        sc = scoring.response_scores(tokenizer, y, ts) if ts is not None else None
+        return response, grounding.Grounding.build(y, mass.numpy(), spans, grounding.pieces_of(tokenizer, y), boxes,
+                                                   layers if layers is not None else (0, n_layers or 0), grounding.special_ids_of(tokenizer), sc)
 
     def _generate_pages_fanout(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds, lpn, n):
         """generate_pages with n > 1 sampled answers per page: page i is prefilled ONCE, into sequence fan_slots(i, n)[0] with the seed of its sample 0, and

@@ -30,6 +30,7 @@ import torch
 
 from .constraints import parse as constraints_parse
 from . import draft as drafting
+from . import grounding
 from . import scoring
 from .generation import check_fits, decode_rows, decode_rows_drafted, reply_text
 from .sampling import page_seeds, parse_beams
@@ -66,7 +67,7 @@ def _refuse_e4m3(model):
 class PageSession:
     """See the module docstring.  Made by InternVLChatModel.open_page; a context manager (close() frees the cache)."""
 
-    def __init__(self, model, tokenizer, vit_embeds, ref_embeds, n_tiles, use_p=True, max_branches=1, indices=None):
+    def __init__(self, model, tokenizer, vit_embeds, ref_embeds, n_tiles, use_p=True, max_branches=1, indices=None, boxes=None, per_box=3):
         _refuse_e4m3(model)
         if max_branches < 1:
             raise ValueError(f'max_branches has to be >= 1, got {max_branches}')
@@ -78,6 +79,8 @@ class PageSession:
         self.rows_prefilled = []                 # rows of every prefill the session made (turns and ask_many), in order
         self.align_ids = drafting.from_indices(indices)      # draft='align': the page's CalliAlign indices as vocabulary ids, in reading order
         self.answer_ids = []                     # draft='previous': the ids of the last answer a turn on the trunk generated
+        self.boxes = None if boxes is None else [[int(v) for v in b[:4]] for b in boxes]      # ground(): the page's character boxes in reading order
+        self.per_box = per_box                   # ground(): pseudo-token rows per box (3, or drop_zero's kept counts)
 
     @classmethod
     def open(cls, model, tokenizer, detect_model, img_path, use_p=True, drop_zero=False, hard_vq=False, boxes=None, max_branches=1, verbose=False):
@@ -89,7 +92,7 @@ class PageSession:
         if use_p:
             out_tokens, indices = model.calli_align(page, detect_model, drop_zero=drop_zero, use_hard_vector_quant=hard_vq, verbose=verbose, boxes=boxes)
         return cls(model, tokenizer, model.extract_feature(pixel_values), out_tokens, pixel_values.shape[0], use_p=use_p, max_branches=max_branches,
-                   indices=indices)
+                   indices=indices, boxes=boxes, per_box=grounding.kept_per_box(indices) if (use_p and drop_zero) else 3)
 
     # ---- lifetime ----
     def close(self):
@@ -254,3 +257,53 @@ class PageSession:
         self.rows_prefilled.append(sum(r.shape[0] for r in rows))
         ts = m.engine.score_batch(kv, branches, rows, [pl.targets[p:] for pl in plans], penalty=penalty, top_n=top_n)
         return [scoring.response_scores(self.tokenizer, pl.ids, t) for pl, t in zip(plans, ts)]
+
+    @torch.no_grad()
+    def ground(self, question, answer=None, layers=None, repetition_penalty=1.5, history=None, top_logprobs=None, score_eos=True, generation_config=None,
+               draft=None):
+        """Which character box every id of the reply to `question` came from (model.ground_ocr's meaning), on a BRANCH forked off the trunk at the prefix the
+        prompt shares with it: the trunk is not changed.  answer (a string or a list of ids): the text to ground.  answer=None: the branch generates the
+        reply greedily first, is rolled back to the prompt's last row and grounds the generated ids by one continued prefill.  Returns (response,
+        grounding.Grounding); the Grounding carries the page's boxes when the session was opened with boxes=."""
+        gc = scoring.refuse_generation(generation_config, draft, 'PageSession.ground')
+        penalty = scoring.check_penalty(repetition_penalty)
+        top_n = None if top_logprobs is None else scoring.top_n_of(top_logprobs)
+        if not self.use_p:
+            raise ValueError('PageSession.ground: the session was opened with use_p=False (no pseudo-tokens to ground on)')
+        m, kv, b = self.m, self.kv, 1
+        _, _, template, ids, gc = self._prompt(question, None if history is None else list(history), gc)
+        spans = grounding.check_spans(grounding.spans_of(ids, m.aligned_token_id, self.per_box))
+        if self.boxes is not None and len(self.boxes) != len(spans):
+            raise ValueError(f'PageSession.ground: the prompt holds the pseudo-tokens of {len(spans)} boxes, the page has {len(self.boxes)}')
+        n_layers = getattr(getattr(m, 'dims', None), 'llm_layers', None)
+        if layers is not None and n_layers is not None:
+            layers = grounding.check_layers(layers, n_layers)
+        L = len(ids)
+        p = plan_prefix(self.cached_ids, ids)
+        if answer is not None:
+            pl = scoring.plan(L, scoring.answer_to_ids(self.tokenizer, answer), gc['eos_token_id'], score_eos, getattr(getattr(m, 'dims', None), 'vocab', None))
+            y = pl.ids
+            scoring.check_fits(L + len(pl.feed), 0, m.max_tokens)
+        else:
+            max_new, eos, _ = m._gen_args(gc)
+            check_fits(L, max_new, m.max_tokens)
+        if p > 0:
+            kv.fork(0, [b], p)
+        else:
+            kv.truncate(b, 0)
+        tail = self._embed(ids, p)
+        if answer is None:
+            self.rows_prefilled.append(L - p)
+            y = m._generate(tail, max_new, eos, penalty, kv=kv, seq=b, reset=False)[0].tolist()
+            kv.truncate(b, L - 1)
+            p, tail = L - 1, tail[L - 1 - p:]
+            response = reply_text(self.tokenizer, y, template.sep)
+        else:
+            response = answer if isinstance(answer, str) else reply_text(self.tokenizer, y, template.sep)
+        rows = torch.cat([tail, m.engine.embed_splice(torch.tensor(y[:-1], dtype=torch.long))], dim=0) if len(y) > 1 else tail
+        self.rows_prefilled.append(rows.shape[0])
+        tss, ms = m.engine.ground_batch(kv, [b], [rows], [[-1] * (L - 1 - p) + list(y)], [spans], layers=layers, penalty=penalty, top_n=top_n or 0,
+                                        want_scores=top_n is not None)
+        sc = scoring.response_scores(self.tokenizer, y, tss[0]) if tss[0] is not None else None
+        return response, grounding.Grounding.build(y, ms[0].numpy(), spans, grounding.pieces_of(self.tokenizer, y), self.boxes,
+                                                   layers if layers is not None else (0, n_layers or 0), grounding.special_ids_of(self.tokenizer), sc)

@@ -354,6 +354,24 @@ int cr_llm_prefill_batch(cr_ctx* ctx, cr_kv* kv, const int32_t* seqs, int n, con
  * sequence without ids).  Enqueued on `stream`.  Added within ABI v13. */
 int cr_llm_score_batch(cr_ctx* ctx, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host,
                        float penalty, int top_n, float* lp, int32_t* top_ids, float* top_lp, float* logits, void* stream);
+/* Grounding: cr_llm_score_batch's pass, which also reports WHERE every scored row looked.  Arguments up to top_lp are cr_llm_score_batch's (there is no
+ * logits output); lp may be NULL: a grounding-only call that runs every layer (the cache is what scoring leaves) but no final norm, LM head or score kernel,
+ * and top_n must then be 0.  The grounded rows are the scored rows, slot r as above.  spans_host holds (start, end) pairs of absolute cache positions, the
+ * call's sequences one after another, span_counts_host [n] how many each sequence has (0..1024).  A span is the half-open key range [start, end); per sequence
+ * the spans are sorted by start and do not overlap, a span may be empty, and it may lie anywhere in [0, cr_kv_length + lens[i]) -- so also behind a row, where
+ * the causal mask gives it 0.  For a grounded row r at position p, with H = 32 heads:
+ *     s_k      = bf16(bf16(q . k) * (1.0f / sqrtf(128)))      the prefill attention's own score arithmetic, the dot product in fp32
+ *     P_k      = exp(s_k - m) / sum over k' <= p of exp(s_k' - m)      in fp32, never rounded to bf16
+ *     mass[r][b] = 1 / (H * (layer1 - layer0)) * sum over layers layer0 <= l < layer1, heads h and keys k in span b with k <= p of P_k
+ * mass is a DEVICE array [R][mass_ld] fp32, mass_ld >= the largest span count; columns from a row's own sequence's count upward are written 0.  What the
+ * spans do not get, 1 - sum_b mass[r][b], is the caller's to compute.  A row's mass depends on its own sequence only: the same row alone and in a larger call
+ * gives the same bits (no float atomics; every sum has a fixed order).  lp / top_ids / top_lp and the cache are bit for bit cr_llm_score_batch's.
+ * Checked before anything is enqueued, nothing changes on refusal: everything cr_llm_score_batch refuses; CR_ERR_ARG for a null mass, spans_host or
+ * span_counts_host, a count outside 0..1024, spans that are unsorted, overlapping, reversed or outside [0, cr_kv_length + lens[i]), mass_ld below a count,
+ * layer0 < 0, layer1 > llm_layers, layer0 >= layer1, or top_n > 0 with a null lp.  Enqueued on `stream`.  Added within ABI v13. */
+int cr_llm_ground_batch(cr_ctx* ctx, cr_kv* kv, const int32_t* seqs, int n, const void* embeds, const int32_t* lens, const int64_t* targets_host,
+                        float penalty, int top_n, float* lp, int32_t* top_ids, float* top_lp, const int32_t* spans_host, const int32_t* span_counts_host,
+                        int layer0, int layer1, float* mass, int mass_ld, void* stream);
 /* Parity tooling: while `dst` is not NULL, every cr_llm_prefill / cr_llm_prefill_batch also copies rows [row0, row0 + rows) of the
  * residual stream (row index into the concatenated prompt rows) into dst [llm_layers + 1][rows][4096] bf16 (device): slot 0 = the
  * decoder stack's input, slot l + 1 = the output of InternLM2DecoderLayer l (InternVL/modeling_internlm2.py:621-681; what
@@ -527,6 +545,15 @@ int cr_op_attention(const void* q, const void* k, const void* v, void* o, const 
  * read; the caller guarantees first row + S <= rows, pos0 + S <= max_tokens and slot < n_slots (the entry cannot see the device array).  Added within ABI v13. */
 int cr_op_attention_segments(const void* q, const void* kc, const void* vc, void* o, const int32_t* seg, int n, int Sq, int H, int kv_group, int max_tokens,
                              float s_div, void* stream);
+/* The span-mass kernels of cr_llm_ground_batch alone, on ONE layer (test entry; the stage launches the same two kernels): q [q_rows][H][128] bf16 roped
+ * queries, kc [n_slots][H / kv_group][max_tokens][128] bf16 K cache that already holds every segment's keys (both DEVICE); seg_host = n x {first row, rows S,
+ * position of the first row pos0, cache slot} (HOST), grounded_host [q_rows] bytes (HOST): a segment's rows with a non-zero byte are its grounded rows;
+ * spans_host / span_counts_host as cr_llm_ground_batch (limit pos0 + S); mass [R][mass_ld] fp32 (DEVICE), R = the grounded rows in segment then row order,
+ * receives the mean over the H heads.  kv_group must be 4 and H a multiple of it.  CR_ERR_ARG for a null pointer, a segment outside q / the cache, segments
+ * that share rows of q or a slot, no grounded row, bad spans or mass_ld below a count.  Synchronises `stream`.  Added within ABI v13. */
+int cr_op_span_mass(const void* q, int q_rows, const void* kc, int n_slots, int max_tokens, int H, int kv_group, const int32_t* seg_host, int n,
+                    const unsigned char* grounded_host, const int32_t* spans_host, const int32_t* span_counts_host, float s_div, float* mass, int mass_ld,
+                    void* stream);
 /* PerceiverAttention's softmax(q k^T) v alone (test entry; cr_resample makes its launch through the same function, launch_perceiver_attn, and drives the same
  * kernels): T tiles x 8 heads x 3 queries x 259 keys x 64 dims.  q [T * 3][512] bf16 (head h in columns 64 h .. 64 h + 63), kv [T * 259][1024] bf16 (a tile's
  * 256 media rows then its 3 latent rows; K in columns 0..511, V in 512..1023), out [T * 3][512] bf16.  Rounding points of perceiver_resampler.py:43-51:
