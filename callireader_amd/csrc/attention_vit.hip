@@ -379,7 +379,7 @@ __device__ __forceinline__ void vit_attn_body(const AttnParams& p, const int qb,
             tile(i + 1, std::integral_constant<int, 1>{});
         }
     };
-    // The lean sweep's verdict (NaN compares false: a non-finite row sum is flagged as well) goes to the block's flag word; flagged
+    // The lean sweep's verdict (a row sum >= 2^100, infinite or NaN: an integer compare of its bits) goes to the block's flag word; flagged
     // blocks are redone by vit_attn_exact_kernel.  (With the exact sweep inside this kernel -- a workgroup-uniform branch behind the
     // vote -- the kernel took 168 registers for code that all but never runs: 3 waves per SIMD; alone the lean form fits 128 and
     // four: 1.478 -> 1.412 ms per 255-tile launch in one process.)
@@ -392,8 +392,13 @@ __device__ __forceinline__ void vit_attn_body(const AttnParams& p, const int qb,
 #pragma unroll
         for (int j = 0; j < QB; j++) {   // query q's sum: lane q & 15, register q >> 4; + 1 for the CLS key (exp(0))
             const float v0 = __shfl(lsum[j][0], l31 & 15, 64), v1 = __shfl(lsum[j][1], l31 & 15, 64);
-            l_tot[j] = 1.0f + (l31 < 16 ? v0 : v1);
-            mine |= !(l_tot[j] < 1.2676506002282294e30f);
+            const float ls = l31 < 16 ? v0 : v1;
+            l_tot[j] = 1.0f + ls;
+            // The verdict is taken on the BITS of the sum (2^100 = 0x71800000; 1 + ls >= 2^100 exactly when ls is): this file is built with
+            // -fno-honor-nans, which turned !(l_tot < 2^100) into l_tot >= 2^100, false for a NaN -- and the row-sum MFMA gives query c the sum
+            // NaN, not inf, as soon as its partner c +- 16 holds an infinite probability (0 x inf in the 0/1 matrix's other rows).  A block
+            // whose queries ALL overflowed went unflagged and kept the lean sweep's NaNs.
+            mine |= (__float_as_uint(ls) & 0x7fffffffu) >= 0x71800000u;
         }
         const int bad = __syncthreads_or(mine);
         if (tid == 0) flags[((int64_t)batch * p.H + head) * gx + qb] = bad;

@@ -1,9 +1,11 @@
 """CPU checks of the shared attention reference (tests/attn_ref.py) and of the inputs test_gpu_prefill_attention.py builds: what the GPU tests rely on
 is confirmed here without a GPU."""
+import math
+
 import torch
 
 import test_gpu_prefill_attention as T
-from attn_ref import attn_f64, attn_ref, segments_ref
+from attn_ref import attn_f64, attn_ref, rb, segments_ref
 
 
 def test_reference_stays_finite_on_the_poisoned_launch():
@@ -187,3 +189,119 @@ def test_perceiver_cases_plant_what_they_say():
     for x in sorted(set(p.reshape(-1).tolist())):                                              # far from a rounding boundary: > 0.2 % either side
         assert float(rb(torch.tensor(x * 1.002))) == float(rb(torch.tensor(x * 0.998)))
     assert float(v.float().abs().min()) >= 32 and float(perceiver_attn_ref(q, kv).abs().max()) < 0.5
+
+
+# ---- the ViT attention's cases (test_gpu_vit_attention.py) ---------------------------------------------------------------------------------------------------
+import test_gpu_vit_attention as W  # noqa: E402
+
+
+def test_vit_codes_are_the_gold_set():
+    c = W.gold_codes()
+    assert c.shape == (4095, 63) and set(c.reshape(-1).tolist()) == {-1.0, 1.0}
+    gram = c @ c.T
+    assert bool((gram.diagonal() == 63).all())
+    assert set((gram - 63 * torch.eye(4095)).reshape(-1).tolist()) == {-17.0, -1.0, 0.0, 15.0}      # 0: the diagonal itself
+
+
+def test_vit_exact_cases_select_what_they_say():
+    """Every case of EXACT_CASES, as built: q, k, v survive a bf16 round trip; the reference's bf16 scores ARE the float64 scores; every query's largest score is
+    on its permutation's key, 24 or more above the runner-up; it lies the intended delta above the CLS key's score (a query that selects the CLS key: the CLS
+    key 30 or more above every patch key); every key is some query's target; attn_ref returns the V rows exactly."""
+    for name, kw in W.EXACT_CASES.items():
+        c = W.exact_case(**kw)
+        S, Bn, H, q, k, v, target, delta = (c[n] for n in ('S', 'Bn', 'H', 'q', 'k', 'v', 'target', 'delta'))
+        assert S in (257, 385, 1025) and q.shape == k.shape == v.shape == (Bn, H, S, 64)
+        for t in (q, k, v):
+            assert torch.equal(rb(t), t)
+        assert float(v.abs().min()) >= 1 and float(v.abs().max()) <= 64 and torch.equal(v, v.round())
+        s = rb(rb(q * 0.125) @ k.transpose(-1, -2))
+        assert torch.equal(s.double(), (q.double() * 0.125) @ k.double().transpose(-1, -2))
+        top = s.topk(2, -1)
+        assert torch.equal(top.indices[..., 0], target) and float((top.values[..., 0] - top.values[..., 1]).min()) >= 24, name
+        assert bool((target.sort(-1).values == torch.arange(S)).all())
+        to_cls = target == 0
+        assert torch.equal(to_cls, delta.isnan()) and int(to_cls.sum()) == Bn * H
+        assert torch.equal((top.values[..., 0] - s[..., 0])[~to_cls], delta[~to_cls])
+        assert float((s[..., 0] - s[..., 1:].amax(-1))[to_cls].min()) >= 30
+        want = torch.full((Bn, H, S), float(kw.get('delta', 40)))
+        for b, h, r0, r1, d in kw.get('flagged', ()):
+            want[b, h, r0:r1] = d
+            assert not bool(to_cls[b, h, r0:r1].any()) or r1 - r0 > 1, name                        # a single flagged query is flagged
+        assert torch.equal(delta[~to_cls], want[~to_cls])
+        assert torch.equal(attn_ref(q, k, v, False, 0, 0.125, 1.0), c['expected']), name
+        # the CLS query's targets over the (batch, head) pairs: every 32-key half of every block and the CLS key, where the launch has pairs enough
+        nch = W.n_cls_choices(S)
+        cls_t = target[:, :, 0].reshape(-1)
+        choice = torch.where(cls_t == 0, nch - 1, (cls_t - 1) // 32)
+        assert len(set(choice.tolist())) == min(nch, Bn * H), name
+    for names in (W.ORDINARY, W.CLS_EDGES):
+        for name in names:
+            c = W.exact_case(**W.EXACT_CASES[name])
+            assert c['Bn'] * c['H'] >= W.n_cls_choices(c['S'])
+    assert {W.EXACT_CASES[n]['S'] for n in W.ORDINARY} == {257, 385, 1025}
+    assert sum(((kw['S'] - 1) // 128 * kw['Bn'] * kw['H']) % 8 != 0 for kw in W.EXACT_CASES.values()) >= 2
+    assert len(W.ORDINARY) + len(W.DELTAS) + len(W.PLACED) + len(W.CLS_EDGES) == len(W.EXACT_CASES)
+
+
+def test_vit_exact_cases_are_exact_on_the_generic_kernel_too():
+    """attention.hip sums its fp32 probabilities and multiplies V by their bf16 roundings, so its weights sum to 1 only to bf16 accuracy.  On the delta = 40
+    cases its reference point is the first tile's maximum: 63 where the target (or, 93, the CLS key as target) is in that tile -- probability 1 -- and otherwise
+    23, the CLS key's score, since no other patch score exceeds 15.  Then the target's probability is bf16(e^40) against a row sum of e^40 (1 + 1e-17): the
+    output is V times a factor that rounds every integer |V| <= 64 back to itself."""
+    for name in W.ORDINARY:
+        c = W.exact_case(**W.EXACT_CASES[name])
+        s = rb(rb(c['q'] * 0.125) @ c['k'].transpose(-1, -2))
+        first = s[..., :64].amax(-1)
+        assert set(first.reshape(-1).tolist()) <= {23.0, 63.0, 93.0}
+    log2e = torch.tensor(1.4426950408889634, dtype=torch.float32)
+    p = torch.exp2(torch.tensor(63.0) * log2e - torch.tensor(23.0) * log2e)                        # fp32, as the kernel forms it
+    factor = float(rb(p)) / math.exp(40.0)
+    assert abs(factor - 1) < 4e-4
+    ints = torch.arange(1, 65).float()
+    for f in (factor * (1 - 1e-5), factor * (1 + 1e-5)):                                            # v_exp_f32 and the fp32 roundings: far inside
+        assert torch.equal(rb(ints * f), ints)
+
+
+def test_vit_uniform_case_sees_a_key_dropped_doubled_or_swapped():
+    """uniform_case: the float64 expectation per column, and what each mistake does to it -- any one key left out, any one key counted twice, any tile read in
+    place of a neighbour (whose tile % 4 differs): some column moves by more than two bf16 steps, the GPU test allows one."""
+    for S, Bn, H in W.UNIFORM_SHAPES:
+        q, k, v, expect = W.uniform_case(S, Bn, H)
+        assert not bool(q.any()) and torch.equal(rb(k), k) and torch.equal(rb(v), v) and bool((v == v[0, 0]).all())
+        v0 = v[0, 0].double()
+        tot = v0.sum(0)
+        assert torch.equal(expect, tot / S) and bool((tot == tot[0]).all())
+        torch.testing.assert_close(W._attn_ref(q, k, v, False, 0, 0.125, 1.0).double(), expect.expand(Bn, H, S, 64), rtol=0, atol=float(W.bf16_step(expect).max()))
+        step = W.bf16_step(expect)
+        dropped = ((tot - v0) / (S - 1) - expect).abs() / step                                      # row j: key j left out
+        doubled = ((tot + v0) / (S + 1) - expect).abs() / step
+        assert float(dropped.amax(-1).min()) > 2 and float(doubled.amax(-1).min()) > 2
+        nt = (S - 1) // 64
+        tiles = v0[1:].reshape(nt, 64, 64).sum(1)                                                    # (tile, column)
+        for t in range(nt):
+            for other in (t - 1, t + 1):
+                if 0 <= other < nt:
+                    assert t % 4 != other % 4
+                    moved = ((tot - tiles[t] + tiles[other]) / S - expect).abs() / step
+                    assert float(moved.max()) > 2
+
+
+def test_vit_strided_case_pads_with_nan_and_shares_no_stride():
+    for S, Bn, H in W.STRIDED_SHAPES:
+        bufs, lays, ref = W.strided_case(S, Bn, H)
+        for i in range(3):                                                                           # batch, head, row strides
+            assert len({lays[n][i] for n in 'qkvo'}) == 4
+        for n in 'qkv':
+            assert all(x % 8 == 0 for x in lays[n][:4])
+            inside = torch.zeros(lays[n][4], dtype=torch.bool)
+            W.strided_view(inside, lays[n], S, Bn, H).fill_(True)
+            assert int(inside.sum()) == Bn * H * S * 64                                              # no two elements share a place
+            assert bool(bufs[n][~inside].isnan().all()) and not bool(bufs[n][inside].isnan().any())
+            assert not bool(inside[:lays[n][3]].any()) and not bool(inside[-8:].any())               # padding in front of the first and behind the last element
+        assert all(x % 4 == 0 for x in lays['o'][:4]) and lays['o'][2] > H * 64
+        bs, hs, rs, off, _ = lays['k']                                                               # head-major planes: a NaN row before row 0 and after row S - 1
+        for b in range(Bn):
+            for h in range(H):
+                p0 = off + b * bs + h * hs
+                assert bool(bufs['k'][p0 - 64:p0].isnan().all()) and bool(bufs['k'][p0 + S * 64:p0 + S * 64 + 64].isnan().all())
+        assert bool(torch.isfinite(ref).all())

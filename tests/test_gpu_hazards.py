@@ -30,7 +30,8 @@ def test_kernel_tests_pass_on_the_poisoned_build():
     lib = os.path.join(ROOT, 'ab', 'libpoison.so')
     assert os.path.exists(lib)
     sel = 'gemm256 or gemm_epilogues or gelu or both_schedules or back_to_back or attention_vit or patch_rows or swiglu or argmax or tail_rows'
-    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_gpu_ops.py'), '-x', '-q', '-m', 'gpu', '-k', sel],
+    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_gpu_ops.py'), os.path.join(ROOT, 'tests', 'test_gpu_vit_attention.py'),
+                        '-x', '-q', '-m', 'gpu', '-k', sel],
                        capture_output=True, text=True, env=dict(env, CR_HIP_LIB=lib), cwd=ROOT, timeout=900)
     tail = r.stdout[-1500:]
     assert r.returncode == 0, tail
