@@ -65,6 +65,8 @@ SIGNATURES = {
     'cr_kv_reset': (i32, [vp, i32, vp]),
     'cr_kv_truncate': (i32, [vp, i32, i32, vp]),
     'cr_kv_fork': (i32, [vp, i32, C.POINTER(C.c_int32), i32, i32, vp]),
+    'cr_kv_fork_shared': (i32, [vp, i32, C.POINTER(C.c_int32), i32, i32, vp]),
+    'cr_kv_set_prefix_sharing': (i32, [vp, i32]),
     'cr_kv_fanout': (i32, [vp, i32, C.POINTER(C.c_int32), i32, C.POINTER(C.c_uint64), vp, vp]),
     'cr_kv_read': (i32, [vp, i32, i32, i32, i32, vp, vp]),
     'cr_kv_generated': (i32, [vp, i32, C.POINTER(i64), i32, vp]),
@@ -111,6 +113,7 @@ SIGNATURES = {
     'cr_op_score_rows': (i32, [vp, i32, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), f32, i32, vp, vp, vp, vp]),
     'cr_op_beam_step': (i32, [vp, i32, i32, vp, i32, vp, f32, vp, vp, vp, vp]),
     'cr_op_decode_attention': (i32, [i32, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
+    'cr_op_decode_attention_shared': (i32, [vp, vp, vp, i32, vp, vp, _i32p, _i32p, i32, i32, f32, vp, vp, vp]),
     'cr_op_decode_attention_e4m3': (i32, [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
 }
 

@@ -86,6 +86,37 @@ int ctx_stage_seqs(cr_ctx* c, const int32_t* seqs, int n, hipStream_t st, bool a
     return CR_OK;
 }
 
+// The share table of a decode call (rows that read a shared prompt) in the context's device staging, as ctx_stage_seqs stages the seqs[]: a pinned source, no
+// device-wide synchronisation and no allocation in the steady state, and no copy at all while the table is the one the device holds (it changes only when
+// the call's rows or a share change, not from step to step).
+int ctx_stage_share(cr_ctx* c, const std::vector<int32_t>& table, hipStream_t st) {
+    const int n = (int)table.size();
+    if (n > c->d_share_cap) {
+        CR_HIP(hipDeviceSynchronize());                 // the old staging may still be read by enqueued work
+        if (c->d_share) CR_HIP(hipFree(c->d_share));
+        c->d_share = nullptr; c->d_share_cap = 0; c->share_on_device.clear();
+        const int cap = n > 1024 ? n : 1024;            // 64 rows in chunks of one: 64 + 64 * 12 ints
+        if (hipMalloc((void**)&c->d_share, (size_t)cap * 4) != hipSuccess) return cr_fail(CR_ERR_NOMEM, "share table staging of %d entries", cap);
+        c->d_share_cap = cap;
+    }
+    if (c->share_on_device != table) {
+        cr_ctx::SeqStage& h = c->share_stage[c->share_stage_next++ % cr_ctx::SEQ_STAGES];
+        if (h.copied) CR_HIP(hipEventSynchronize(h.copied));
+        else CR_HIP(hipEventCreateWithFlags(&h.copied, hipEventDisableTiming));
+        if (h.cap < n) {
+            if (h.host) CR_HIP(hipHostFree(h.host));
+            h.host = nullptr; h.cap = 0;
+            CR_HIP(hipHostMalloc((void**)&h.host, (size_t)c->d_share_cap * 4, hipHostMallocDefault));
+            h.cap = c->d_share_cap;
+        }
+        memcpy(h.host, table.data(), (size_t)n * 4);
+        CR_HIP(hipMemcpyAsync(c->d_share, h.host, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        CR_HIP(hipEventRecord(h.copied, st));
+        c->share_on_device = table;
+    }
+    return CR_OK;
+}
+
 // Measurement (cr_profile): one event pair per GEMM launch on the launch stream.  Records are retired into per-class
 // accumulators as soon as their second event has completed (events of one stream complete in order, so the queue is
 // drained from the front with a non-blocking hipEventQuery); nothing is ever dropped.  Only when more than
@@ -205,10 +236,12 @@ int cr_destroy(cr_ctx* c) {
     if (c->ws) hipFree(c->ws);
     if (c->scratch) hipFree(c->scratch);
     if (c->d_seqs) hipFree(c->d_seqs);
-    for (auto& h : c->seq_stage) {
-        if (h.host) hipHostFree(h.host);
-        if (h.copied) hipEventDestroy(h.copied);
-    }
+    if (c->d_share) hipFree(c->d_share);
+    for (auto* stages : {c->seq_stage, c->share_stage})
+        for (int i = 0; i < cr_ctx::SEQ_STAGES; i++) {
+            if (stages[i].host) hipHostFree(stages[i].host);
+            if (stages[i].copied) hipEventDestroy(stages[i].copied);
+        }
     for (auto& r : c->prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto e : c->prof_pool) hipEventDestroy(e);
     delete c;
@@ -503,6 +536,43 @@ int cr_op_decode_attention(int which, const void* q, const void* kc, const void*
     ap.part_ml = scratch; ap.part_o = scratch + (size_t)B * NKV * ap.nsplit * G * 2;
     ap.force_matrix_core = which == 1;                    // launch_flash_attn_split keeps the matrix-core split kernel, as CR_DECODE_ATTN=0 does for a whole process
     if (launch_flash_attn_split(ap, HD, (hipStream_t)stream) != CR_OK) return cr_fail(CR_ERR_HIP, "cr_op_decode_attention: launch failed");
+    return CR_OK;
+}
+
+int cr_op_decode_attention_shared(const void* q, const void* kc, const void* vc, int max_tokens, const int32_t* seqs, const int32_t* lens, const int32_t* pfx_src,
+                                  const int32_t* pfx_len, int B, int max_keys, float s_div, float* scratch, void* out, void* stream) {
+    if (!q || !kc || !vc || !seqs || !lens || !pfx_src || !pfx_len || !scratch || !out || B <= 0 || max_keys <= 0 || max_tokens < max_keys)
+        return cr_fail(CR_ERR_ARG, "cr_op_decode_attention_shared: bad argument");
+    constexpr int HD = 128, NKV = 8, G = 4, D = NKV * G * HD;
+    hipStream_t st = (hipStream_t)stream;
+    // a test entry: the rows' slots come back to the host for the grouping (the LLM stage has them there already)
+    std::vector<int32_t> hseq(B);
+    CR_HIP(hipMemcpyAsync(hseq.data(), seqs, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    CR_HIP(hipStreamSynchronize(st));
+    for (int b = 0; b < B; b++)
+        if (pfx_src[b] >= 0 && (pfx_len[b] < 0 || (pfx_len[b] & 255) || pfx_len[b] > max_keys - 1))
+            return cr_fail(CR_ERR_ARG, "cr_op_decode_attention_shared: row %d shares %d positions (want a multiple of 256 below max_keys = %d)", b, pfx_len[b], max_keys);
+    AttnParams ap{};
+    ap.K = (const bf16*)kc; ap.V = (const bf16*)vc; ap.Q = (const bf16*)q; ap.O = (bf16*)out;
+    ap.k_bs = ap.v_bs = (int64_t)NKV * max_tokens * HD; ap.k_rs = ap.v_rs = HD; ap.k_hs = ap.v_hs = (int64_t)max_tokens * HD;
+    ap.q_prescale = 1.0f; ap.s_div = s_div;
+    ap.q_bs = D; ap.q_rs = HD; ap.q_hs = G * HD; ap.o_bs = D; ap.o_rs = HD; ap.o_hs = G * HD;
+    ap.B = B; ap.H = NKV; ap.Sq = G; ap.Sk = 0; ap.kv_group = 1; ap.q_pos0 = 0;
+    ap.seq_map = seqs; ap.sk_arr = lens; ap.sk_add = 1;
+    ap.nsplit = ((max_keys + 63) / 64 + ATTN_SPLIT_TILES - 1) / ATTN_SPLIT_TILES;
+    ap.part_ml = scratch; ap.part_o = scratch + (size_t)B * NKV * ap.nsplit * G * 2;
+    std::vector<int32_t> table;
+    int32_t* d_table = nullptr;
+    ap.share_n = attn_share_table(hseq.data(), pfx_src, pfx_len, B, table, &ap.share_splits);
+    if (ap.share_n > 0) {
+        CR_HIP(hipMalloc((void**)&d_table, table.size() * 4));
+        CR_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+        ap.share_skip = d_table; ap.share_chunks = d_table + B;
+    }
+    const int rc = launch_flash_attn_split(ap, HD, st);      // the launcher the LLM stage uses
+    const hipError_t e = hipStreamSynchronize(st);
+    if (d_table) hipFree(d_table);
+    if (rc != CR_OK || e != hipSuccess) return cr_fail(CR_ERR_HIP, "cr_op_decode_attention_shared: launch rejected or failed");
     return CR_OK;
 }
 

@@ -434,7 +434,9 @@ int launch_flash_attn_split(const AttnParams& p, int head_dim, hipStream_t strea
     if (p.Sq <= 0 || p.Sq > 32 || p.H <= 0 || p.B <= 0 || p.nsplit <= 0 || !p.part_ml || !p.part_o) return CR_ERR_ARG;
     if ((p.q_rs & 7) || (p.k_rs & 7) || (p.v_rs & 7)) return CR_ERR_ARG;
     const bool dv = p.s_div != 1.0f;
-    if (p.K8 || p.V8) {                                       // an e4m3 cache: attention_decode.hip's e4m3 kernel or nothing (never bytes read as bf16)
+    // a shared prompt is read by attention_decode.hip's group form or by nothing (the matrix-core split kernel would read a sharer's unwritten rows)
+    if (p.share_n > 0 && (p.K8 || p.V8 || !decode_attn_supported(p, head_dim))) return CR_ERR_ARG;
+    if (p.K8 || p.V8) {                                      // an e4m3 cache: attention_decode.hip's e4m3 kernel or nothing (never bytes read as bf16)
         if (!decode_attn8_supported(p, head_dim)) return CR_ERR_ARG;
         if (launch_decode_attn(p, stream) != CR_OK) return CR_ERR_HIP;
         hipLaunchKernelGGL((attn_combine_kernel<128>), dim3(p.Sq, p.H, p.B), dim3(128), 0, stream, p);

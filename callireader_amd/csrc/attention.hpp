@@ -1,4 +1,6 @@
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 // Strides are in elements.  Q/K/V/O are addressed as base + b*bs + row*rs + head*hs + d.
@@ -45,7 +47,22 @@ struct AttnParams {
     // The streaming bf16 kernel and the matrix-core split kernel take it (instances of their own: a launch without it runs the code it always ran); the folded
     // form and the e4m3 kernel do not (decode_attn_fold_supported / decode_attn8_supported are false)
     const int32_t* sk_off;
+    // decode with a shared prompt (cr_kv_fork_shared; attention_decode.hip), share_n = 0: none, and the launch is the one it always was.  share_chunks (device) =
+    // share_n chunks of ATTN_SHARE_CHUNK_INTS ints {source slot, shared splits, rows, 0, the rows' batch indices[8]}: one workgroup of the group form loads a split
+    // of the source slot once and runs every row of the chunk over it.  share_skip (device) [B]: the splits of batch b that the group form writes (0: none); the
+    // per-row form returns from them without writing.  share_splits = the most shared splits of any chunk.  attn_share_table builds all of it.
+    const int32_t* share_skip;
+    const int32_t* share_chunks;
+    int share_n, share_splits;
 };
+
+constexpr int ATTN_SHARE_ROWS = 8;                              // rows per chunk of the group form
+constexpr int ATTN_SHARE_CHUNK_INTS = 4 + ATTN_SHARE_ROWS;
+// The share table of one decode launch, built on the host: row b reads cache slot seqs[b], whose positions [0, pfx_len[b]) are those of slot pfx_src[b]
+// (pfx_src[b] < 0: its own; pfx_len a multiple of 256).  Rows with equal (pfx_src, pfx_len) form a group, the source's own row joins when it is in the launch,
+// and a group is cut into chunks of ATTN_SHARE_ROWS.  table = [B] skips, then the chunks.  Returns the number of chunks (0: no row shares, table left empty),
+// *max_splits = the most shared splits of any chunk.  Grouping is a matter of speed only: a row's partials are the same whatever it is grouped with.
+int attn_share_table(const int32_t* seqs, const int32_t* pfx_src, const int32_t* pfx_len, int B, std::vector<int32_t>& table, int* max_splits);
 
 bool decode_attn_fold_supported(const AttnParams& p, int head_dim);
 // e4m3 caches: false when the process runs with CR_DECODE_ATTN=0 (the matrix-core split kernel reads bf16 only); launch_flash_attn_split then refuses them
@@ -76,6 +93,8 @@ size_t attn_split_ws_floats(int B, int H, int Sq, int nsplit, int head_dim);
 // group); launch_flash_attn_split takes it by itself when the shape qualifies (CR_DECODE_ATTN=0: the matrix-core split kernel)
 bool decode_attn_supported(const AttnParams& p, int head_dim);
 int launch_decode_attn(const AttnParams& p, hipStream_t stream);
+// attention_decode_group.hip: the shared splits of a launch with p.share_n > 0 chunks (launch_decode_attn calls it, then the per-row form for everything else)
+int launch_decode_attn_group(const AttnParams& p, hipStream_t stream);
 
 // ViT layout (S = 1 + 128 n tokens, d = 64, no mask): attention_vit.hip.  launch_flash_attn takes this path by itself when
 // p.part_ml points at vit_attn_ws_floats(B, H, S) floats of scratch (the CLS query's partials) and the shape qualifies.

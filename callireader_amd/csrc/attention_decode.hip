@@ -14,34 +14,19 @@
 // reference's (bf16, / sqrt(128), bf16); each 16-lane group keeps ITS 16 keys' scores, so its softmax needs no running maximum (one exponential per lane and
 // key: lane c computes query head c & 3, the quad shares them by DPP); P.V by fp32 FMAs on bf16-rounded probabilities.  The 16 (wave, group) partials of the
 // workgroup meet in LDS and are merged in index order: a row's result depends on its own key count only, never on the batch.
+//
+// Everything from the scores to the partial's store is split_row (attention_decode_row.hpp), which the group form for shared prompts
+// (attention_decode_group.hip: one load of a split's keys, up to 8 rows over it) inlines as well.  Registers, from hipcc's resource summary
+// (-Rpass-analysis=kernel-resource-usage): per-row 190 VGPRs (FOLD: 234), group form 234, none spilled, two workgroups per CU each.
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "attention.hpp"
+#include "attention_decode_row.hpp"
 
 namespace {
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr int HD = 128, NQ = 4, IT = 16;      // head dimension, query heads per KV head, keys per lane group and wave (4 groups x 16 = 64 keys per wave)
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-__device__ __forceinline__ float rbf1(float x) {           // round to bf16, as an fp32 value, in one v_cvt_pk_bf16_f32 (attention.hip)
-    const f32x2_t v = {0.f, x};
-    return __uint_as_float(__builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)));
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-// sum over the 16 lanes of a DPP row, left in every lane (rotations: the order of the adds is the same in every lane group of every launch)
-__device__ __forceinline__ float row_sum16(float v) {
-    v += dpp<0x128>(v);      // row_ror:8
-    v += dpp<0x124>(v);      // row_ror:4
-    v += dpp<0x122>(v);      // row_ror:2
-    v += dpp<0x121>(v);      // row_ror:1
-    return v;
-}
 
 constexpr int FOLD_MAX_SPLITS = 8;       // K-slices of the wqkv partial-sum GEMM the folded prologue takes (gemm_skinny.hip: partial_geom gives 2..8)
 
@@ -55,15 +40,20 @@ constexpr int FOLD_MAX_SPLITS = 8;       // K-slices of the wqkv partial-sum GEM
 // OFF: batch b holds p.sk_off[b] keys more than its slot's length says (cr_llm_decode_draft: the rows of one sequence's draft window sit at consecutive
 // positions).  An instance of its own, so a launch without offsets runs the code it always ran; never with FOLD (a row would read cache rows that other workgroups
 // of the same launch are still writing).
-template <bool DIV, bool FOLD = false, bool OFF = false>
+// SHARE: a launch some of whose rows read a shared prompt (AttnParams::share_*).  Batch b returns at once, without writing, from the splits below
+// p.share_skip[b]: decode_attn_group_kernel below writes those partials.  Every other row and split runs as it always did.  An instance of its own, never with
+// FOLD or OFF (launch_decode_attn refuses both).
+template <bool DIV, bool FOLD = false, bool OFF = false, bool SHARE = false>
 __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const AttnParams p) {
     static_assert(!(FOLD && OFF), "the folded form takes one new token per sequence");
+    static_assert(!(SHARE && (FOLD || OFF)), "a launch with shares takes the separate RoPE + split and no draft window");
     __shared__ __attribute__((aligned(16))) float s_o[16][NQ][HD];      // the workgroup's 16 partials: un-normalised O ...
     __shared__ float s_ml[16][NQ][2];                                   // ... maximum and row sum
     __shared__ __attribute__((aligned(16))) bf16x8 s_qkv[FOLD ? 6 : 1][16];   // FOLD: the rotated q heads, the new K row, the new V row
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.x, head = blockIdx.y, batch = blockIdx.z;
+    if (SHARE && split < p.share_skip[batch]) return;         // the group form's split (workgroup-uniform)
     const int slot = p.seq_map ? p.seq_map[batch] : batch;
     const int Sk = (p.sk_arr ? p.sk_arr[slot] + p.sk_add : p.Sk) + (OFF ? p.sk_off[batch] : 0);
     const int64_t prow = (((int64_t)batch * p.H + head) * p.nsplit + split) * NQ;
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const AttnParams p)
         if (tid < NQ) { p.part_ml[(prow + tid) * 2] = -INFINITY; p.part_ml[(prow + tid) * 2 + 1] = 0.f; }
         return;
     }
-    const int ksub = lane >> 4, c = lane & 15, own = c & 3;
+    const int ksub = lane >> 4, c = lane & 15;
     const int key0 = split * 256 + wave * 64 + ksub;          // this lane's keys: key0 + 4 i
     // one uniform 64-bit base per (slot, head) plane + a 32-bit per-lane element offset (a plane is max_tokens x 128 elements: far below 2^31): the 64 x 64-bit
     // products of `key * stride` per load were a fifth of the kernel's vector instructions
@@ -148,89 +138,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const AttnParams p)
                 if (key0 + 4 * i >= Sk - 1) { kr[i] = kn; vr[i] = vn; }
         }
     }
-    const float inv_div = 1.0f / p.s_div;
-
-    // ---- scores of this lane's own query head for its group's 16 keys ----
-    float sc[IT];
-#pragma unroll
-    for (int i = 0; i < IT; i++) {
-        float d[NQ];
-#pragma unroll
-        for (int h = 0; h < NQ; h++) {
-            float a = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const bf16x2_t qq = {q[h][2 * e], q[h][2 * e + 1]}, kk = {kr[i][2 * e], kr[i][2 * e + 1]};
-                a = __builtin_amdgcn_fdot2_f32_bf16(qq, kk, a, false);
-            }
-            d[h] = row_sum16(a);
-        }
-        float s = own == 0 ? d[0] : own == 1 ? d[1] : own == 2 ? d[2] : d[3];
-        s = rbf1(s);                                          // scores are bf16 (:393), divided by sqrt(d) -> bf16
-        if (DIV) s = rbf1(s * inv_div);
-        sc[i] = key0 + 4 * i < Sk ? s : -INFINITY;
-    }
-    float m = sc[0];
-#pragma unroll
-    for (int i = 1; i < IT; i++) m = fmaxf(m, sc[i]);
-    const float m2 = (m == -INFINITY ? 0.f : m) * LOG2E;      // a group with no key below Sk: every P is exp(-inf) = 0
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < IT; i++) {
-        const float pe = __builtin_amdgcn_exp2f(fmaf(sc[i], LOG2E, -m2));
-        l += pe;                                              // fp32 softmax (:409): the sum of the un-rounded exponentials
-        sc[i] = rbf1(pe);                                     // probabilities go to bf16 before .V
-    }
-
-    // ---- O[h][8 dims of this lane] += P[h] . V ----
-    float o[NQ][8];
-#pragma unroll
-    for (int h = 0; h < NQ; h++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) o[h][e] = 0.f;
-#pragma unroll
-    for (int i = 0; i < IT; i++) {
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; e++) v[e] = (float)vr[i][e];
-        const float p0 = dpp<0x00>(sc[i]), p1 = dpp<0x55>(sc[i]), p2 = dpp<0xaa>(sc[i]), p3 = dpp<0xff>(sc[i]);     // quad_perm: lane (quad, h) holds head h's P
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            o[0][e] = fmaf(p0, v[e], o[0][e]);
-            o[1][e] = fmaf(p1, v[e], o[1][e]);
-            o[2][e] = fmaf(p2, v[e], o[2][e]);
-            o[3][e] = fmaf(p3, v[e], o[3][e]);
-        }
-    }
-
-    // ---- the 16 partials of the workgroup (wave, group) in LDS, merged in index order ----
-    const int j = wave * 4 + ksub;
-#pragma unroll
-    for (int h = 0; h < NQ; h++) {
-        *(f32x4*)&s_o[j][h][c * 8] = f32x4{o[h][0], o[h][1], o[h][2], o[h][3]};
-        *(f32x4*)&s_o[j][h][c * 8 + 4] = f32x4{o[h][4], o[h][5], o[h][6], o[h][7]};
-    }
-    if (c < NQ) { s_ml[j][c][0] = m; s_ml[j][c][1] = l; }     // lane c of a group holds head c's (m, l) (so do lanes c + 4, c + 8, c + 12)
-    __syncthreads();
-    {
-        const int h = tid >> 6, d0 = (tid & 63) * 2;
-        float M = -INFINITY;
-#pragma unroll
-        for (int jj = 0; jj < 16; jj++) M = fmaxf(M, s_ml[jj][h][0]);
-        float L = 0.f, a0 = 0.f, a1 = 0.f;
-        if (M != -INFINITY) {
-#pragma unroll
-            for (int jj = 0; jj < 16; jj++) {
-                const float mj = s_ml[jj][h][0];
-                const float w = mj == -INFINITY ? 0.f : __expf(mj - M);
-                L += w * s_ml[jj][h][1];
-                a0 += w * s_o[jj][h][d0];
-                a1 += w * s_o[jj][h][d0 + 1];
-            }
-        }
-        *(f32x2_t*)(p.part_o + (prow + h) * HD + d0) = f32x2_t{a0, a1};
-        if ((tid & 63) == 0) { p.part_ml[(prow + h) * 2] = M; p.part_ml[(prow + h) * 2 + 1] = L; }
-    }
+    split_row<DIV>(p, q, kr, vr, key0, Sk, prow, s_o, s_ml);
 }
 
 // ---- e4m3 cache (cr_kv_alloc_ex CR_KV_E4M3): the same streaming structure over 128-byte keys ----
@@ -243,7 +151,6 @@ __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const AttnParams p)
 // in registers (row_ror:8) in a fixed order, so the workgroup leaves 16 partials in LDS as the bf16 kernel does and merges them in index order: a row's
 // result depends on its own key count only.
 constexpr int IT8 = 8;                   // keys per lane group and wave (8 groups x 8 = 64 keys per wave)
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 // sum over the 8 lanes of a half DPP row, left in every lane (the same adds, in the same order, in every lane group)
 __device__ __forceinline__ float half_row_sum8(float v) {
@@ -442,8 +349,48 @@ bool decode_attn_fold_supported(const AttnParams& p, int head_dim) {
            (((uintptr_t)p.qkv_part | (uintptr_t)p.rope_cos | (uintptr_t)p.rope_sin) & 15) == 0;
 }
 
+int attn_share_table(const int32_t* seqs, const int32_t* pfx_src, const int32_t* pfx_len, int B, std::vector<int32_t>& table, int* max_splits) {
+    table.clear();
+    *max_splits = 0;
+    bool any = false;
+    for (int b = 0; b < B; b++) any |= pfx_src[b] >= 0 && pfx_len[b] >= 256;
+    if (!any) return 0;
+    table.assign(B, 0);
+    std::vector<char> placed(B, 0);
+    int n_chunks = 0;
+    for (int b = 0; b < B; b++) {
+        if (placed[b] || pfx_src[b] < 0 || pfx_len[b] < 256) continue;
+        const int src = pfx_src[b], len = pfx_len[b];
+        std::vector<int> rows;
+        for (int r = 0; r < B; r++) {
+            // the group's sharers, and the source's own row (the longest share of a source only: its row joins one group)
+            const bool sharer = pfx_src[r] == src && pfx_len[r] == len;
+            bool source = seqs[r] == src && pfx_src[r] < 0 && !placed[r];
+            for (int t = 0; source && t < B; t++) source = !(pfx_src[t] == src && pfx_len[t] > len);
+            if (sharer || source) { rows.push_back(r); placed[r] = 1; }
+        }
+        for (size_t r0 = 0; r0 < rows.size(); r0 += ATTN_SHARE_ROWS) {
+            const int n = (int)std::min<size_t>(ATTN_SHARE_ROWS, rows.size() - r0);
+            table.insert(table.end(), {src, len / 256, n, 0});
+            for (int j = 0; j < ATTN_SHARE_ROWS; j++) table.push_back(rows[r0 + (j < n ? j : 0)]);
+            n_chunks++;
+        }
+        for (int r : rows) table[r] = len / 256;
+        *max_splits = std::max(*max_splits, len / 256);
+    }
+    return n_chunks;
+}
+
 int launch_decode_attn(const AttnParams& p, hipStream_t stream) {
     const dim3 grid(p.nsplit, p.H, p.B);
+    if (p.share_n > 0) {
+        // shares: bf16, the separate RoPE + split, no draft window; the chunks' splits lie inside the launch's
+        if (p.K8 || p.qkv_part || p.sk_off || !p.share_chunks || !p.share_skip || p.share_splits < 1 || p.share_splits > p.nsplit || !p.Q) return CR_ERR_ARG;
+        if (launch_decode_attn_group(p, stream) != CR_OK) return CR_ERR_HIP;
+        if (p.s_div != 1.0f) hipLaunchKernelGGL((decode_attn_kernel<true, false, false, true>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((decode_attn_kernel<false, false, false, true>), grid, dim3(256), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? CR_OK : CR_ERR_HIP;
+    }
     if (p.K8) {
         if (!decode_attn8_supported(p, HD)) return CR_ERR_ARG;
         if (p.s_div != 1.0f) hipLaunchKernelGGL((decode_attn8_kernel<true>), grid, dim3(256), 0, stream, p);

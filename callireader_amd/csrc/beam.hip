@@ -235,12 +235,13 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(Rows rw, SeqState s, 
             if (p.first_only && s.len) {                                 // the fan-out: the prompt's length for every beam (len[f] is not written here)
                 s.len[f + tid] = s.len[f];
                 if (tid == 0) bs->prompt = s.len[f];
+                if (p.share && tid > 0 && s.len[f] >= 256) { s.pfx_src[f + tid] = f; s.pfx_len[f + tid] = s.len[f] & ~255; }      // the shared fan-out
             }
         }
         return;
     }
     if (!c.k) return;
-    const int len = s.len[f], from = p.first_only ? 0 : bs->prompt;
+    const int len = s.len[f], from = p.first_only ? (p.share ? len & ~255 : 0) : bs->prompt;
     const int pos = from + blockIdx.x * 16 + (tid >> 4), col = tid & 15;
     if (pos >= len) return;
     const int layer = y >> 4, h = (y >> 1) & 7;

@@ -35,6 +35,8 @@ struct BeamLaunch {
     float* cand_v; int32_t* cand_i;                // [rows][2 * BEAM_MAX] scratch: the rows' own candidates
     int64_t* fin_ids;                              // [.][gen_cap] ids of the finished slots, row = first sequence + fin_phys
     int first_only;
+    int share;                                     // with first_only (the fan-out of a cache in cr_kv_set_prefix_sharing mode): the group's other sequences take positions
+                                                   // [len & ~255, len) only and read the rest from the first (s.pfx_src / s.pfx_len, set here)
 };
 // bf16 cache [layers][n_seqs][8][max_tokens][128] for the re-order (k NULL: id histories only) and for kv.hip's fork
 struct BeamCache { bf16* k; bf16* v; int64_t per_layer; int layers, max_tokens; };
@@ -43,7 +45,7 @@ size_t beam_scratch_bytes(int rows);
 // candidates + select
 int launch_beam_step(const Rows& r, const SeqState& s, const BeamLaunch& p, hipStream_t st);
 // re-order: sequence f + j of every group takes cache positions [from, s.len[f]) and the id history of f + next_src[j]; from = 0 with p.first_only (the
-// fan-out, which also gives the group's other sequences the first one's length), else the group's prompt length.  The launch runs over the groups only:
+// fan-out, which also gives the group's other sequences the first one's length; with p.share, from = s.len[f] & ~255), else the group's prompt length.  The launch runs over the groups only:
 // first_rows[0 .. n_groups) (host) = the launch row of each group's first sequence; max_span = the most positions any of them moves.
 // append: the step's new ids go onto the histories (a step); 0: the histories' own counts are kept (cr_kv_beam_reorder).
 int launch_beam_reorder(const Rows& r, const SeqState& s, const BeamLaunch& p, const BeamCache& c, const int* first_rows, int n_groups, int max_span, int append, hipStream_t st);

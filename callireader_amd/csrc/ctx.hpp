@@ -58,6 +58,12 @@ struct cr_ctx {
     static constexpr int SEQ_STAGES = 8;
     SeqStage seq_stage[SEQ_STAGES];
     int seq_stage_next = 0;
+    // the share table of the last decode call with shared prompts (ctx_stage_share; attention.hpp: attn_share_table), staged as the seqs[] are
+    int32_t* d_share = nullptr;
+    int d_share_cap = 0;
+    std::vector<int32_t> share_on_device;  // what d_share holds
+    SeqStage share_stage[SEQ_STAGES];
+    int share_stage_next = 0;
     // small persistent device scratch (counters, argmax partials)
     char* scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -101,6 +107,8 @@ const DevTensor* WT(cr_ctx* c, const std::string& name);
 int ws_ensure(cr_ctx* c, size_t bytes);
 // the seqs[] of a prefill / decode call into c->d_seqs (api.hip)
 int ctx_stage_seqs(cr_ctx* c, const int32_t* seqs, int n, hipStream_t st, bool always);
+// the share table of a decode call into c->d_share (api.hip): copied only when it differs from what the device holds; no allocation once the capacity is there
+int ctx_stage_share(cr_ctx* c, const std::vector<int32_t>& table, hipStream_t st);
 
 // simple bump allocator over the workspace.  Without a base it only measures: the takes return null and bytes() is what they need.  With a capacity,
 // a take that would pass it returns null and clears ok(); the caller checks ok() before it launches anything (ws_carve below).  A caller that

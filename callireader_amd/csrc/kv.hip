@@ -40,6 +40,7 @@ __device__ __forceinline__ void kv_clear_state(const SeqState& s, int seq, int n
     s.temp[seq] = 0.f;                              // greedy
     if (s.lpn) { s.lpn[seq] = 0; s.lpdone[seq] = 0; }
     if (s.con_on) s.con_on[seq] = 0;
+    if (s.pfx_src) { s.pfx_src[seq] = -1; s.pfx_len[seq] = 0; }      // its own rows again (the host has given the count back at the source)
 }
 
 // ring: every sequence of the cache goes, and the finished ring starts over
@@ -48,19 +49,27 @@ __global__ __launch_bounds__(256) void kv_reset_kernel(SeqState s, int s0, int n
     if (ring && blockIdx.x == 0 && threadIdx.x == 0) *s.stop.count() = 0;
 }
 
-__global__ __launch_bounds__(64) void kv_truncate_kernel(SeqState s, KvSeqs seqs, int n_tokens) {
-    if ((int)threadIdx.x < seqs.n) kv_clear_state(s, seqs.seq[threadIdx.x], n_tokens);
+// pfx_len > 0: the sequences keep reading rows [0, pfx_len) of pfx_src (a sharer truncated at or above its shared length)
+__global__ __launch_bounds__(64) void kv_truncate_kernel(SeqState s, KvSeqs seqs, int n_tokens, int pfx_src, int pfx_len) {
+    if ((int)threadIdx.x >= seqs.n) return;
+    kv_clear_state(s, seqs.seq[threadIdx.x], n_tokens);
+    if (pfx_len > 0) { s.pfx_src[seqs.seq[threadIdx.x]] = pfx_src; s.pfx_len[seqs.seq[threadIdx.x]] = pfx_len; }
 }
 
-__global__ __launch_bounds__(FORK_THREADS) void kv_fork_kernel(SeqState s, BeamCache c, int src, KvSeqs dsts, int n_tokens) {
+// from > 0 (cr_kv_fork_shared; a multiple of 256): only positions [from, n_tokens) are copied -- fewer than 256 -- and the destinations read rows [0, from) of src
+// from then on (pfx_src / pfx_len); rows [0, from) of a destination are not written.
+__global__ __launch_bounds__(FORK_THREADS) void kv_fork_kernel(SeqState s, BeamCache c, int src, KvSeqs dsts, int n_tokens, int from) {
     const int tid = threadIdx.x;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < dsts.n) kv_clear_state(s, dsts.seq[tid], n_tokens);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < dsts.n) {
+        kv_clear_state(s, dsts.seq[tid], n_tokens);
+        if (from > 0) { s.pfx_src[dsts.seq[tid]] = src; s.pfx_len[dsts.seq[tid]] = from; }
+    }
     const int run = blockIdx.y;                     // (layer, KV head, K|V)
     const int layer = run >> 4, head = (run >> 1) & 7;
     bf16* base = ((run & 1) ? c.v : c.k) + (int64_t)layer * c.per_layer + (int64_t)head * c.max_tokens * 128;
     const int64_t per_seq = (int64_t)8 * c.max_tokens * 128;
     const int pieces = n_tokens * 16;               // 16-byte pieces of the run (max_tokens <= 32768: fits an int)
-    const int p0 = blockIdx.x * FORK_TILE + tid;
+    const int p0 = from * 16 + blockIdx.x * FORK_TILE + tid;
     const uint4* sp = (const uint4*)(base + src * per_seq);
     uint4 r[FORK_PIECES];
 #pragma unroll
@@ -151,7 +160,58 @@ int beam_alloc(cr_kv* kv, hipStream_t st) {
     return r == CR_ERR_NOMEM ? cr_fail(CR_ERR_NOMEM, "beam search: %zu bytes of beam state", N * (sizeof(BeamState) + 4 + (size_t)kv->gen_cap * 8)) : r;
 }
 
+// One fork launch: positions [from, n_tokens) of src to the destinations, their cleared state, and with from > 0 their share record (device and host)
+int launch_fork(cr_kv* kv, int src, const KvSeqs& d, int n_tokens, int from, hipStream_t st) {
+    if (from > 0) CR_TRY(kv_share_alloc(kv, st));
+    const int pieces = (n_tokens - from) * 16;
+    hipLaunchKernelGGL(kv_fork_kernel, dim3(std::max((pieces + FORK_TILE - 1) / FORK_TILE, 1), kv->layers * 16), dim3(FORK_THREADS), 0, st, kv_seq_state(kv), beam_cache(kv),
+                       src, d, n_tokens, from);
+    CR_HIP(hipGetLastError());
+    for (int j = 0; j < d.n; j++) {
+        Seq& t = kv->seq[d.seq[j]];
+        kv_release_share(kv, d.seq[j]);
+        t.clear(n_tokens);
+        if (from > 0) { t.pfx_src = src; t.pfx_len = from; kv->seq[src].sharers++; }
+    }
+    return CR_OK;
+}
+
+// what every fork refuses of shares, before anything is enqueued: a source that itself reads a shared prompt, a destination whose rows others read
+int fork_share_ok(const cr_kv* kv, const char* who, int src, const KvSeqs& d) {
+    CR_TRY(kv_refuse_sharer(kv, src, who, "fork from the sequence it shares with, or from an unshared copy (cr_kv_fork)"));
+    for (int j = 0; j < d.n; j++)
+        if (kv->seq[d.seq[j]].sharers > 0)
+            return cr_fail(CR_ERR_STATE, "%s: destination %d holds the prompt that %d other sequences share (cr_kv_reset them first)", who, d.seq[j], kv->seq[d.seq[j]].sharers);
+    return CR_OK;
+}
+
 }  // namespace
+
+int kv_share_floor(const cr_kv* kv, int seq) {
+    int floor = 0;
+    if (kv->seq[seq].sharers > 0)
+        for (const Seq& q : kv->seq) if (q.pfx_src == seq) floor = std::max(floor, q.pfx_len);
+    return floor;
+}
+
+void kv_release_share(cr_kv* kv, int seq) {
+    Seq& q = kv->seq[seq];
+    if (q.pfx_src >= 0) kv->seq[q.pfx_src].sharers--;
+    q.pfx_src = -1; q.pfx_len = 0;
+}
+
+int kv_share_alloc(cr_kv* kv, hipStream_t st) {
+    if (kv->d_pfx_src) return CR_OK;
+    const size_t N = kv->n_seqs;
+    const int r = kv_lazy_blocks(kv, {{(void**)&kv->d_pfx_src, N * 4, 0xff}, {(void**)&kv->d_pfx_len, N * 4, 0}}, st);
+    return r == CR_ERR_NOMEM ? cr_fail(CR_ERR_NOMEM, "shared prompts: %zu bytes of share records", N * 8) : r;
+}
+
+int kv_refuse_sharer(const cr_kv* kv, int seq, const char* who, const char* alt) {
+    const Seq& q = kv->seq[seq];
+    if (q.pfx_src < 0) return CR_OK;
+    return cr_fail(CR_ERR_STATE, "%s: sequence %d reads the first %d cached positions of sequence %d (cr_kv_fork_shared): %s", who, seq, q.pfx_len, q.pfx_src, alt);
+}
 
 RowFeatures kv_scan_rows(const cr_kv* kv, const int32_t* seqs, int n, float penalty) {
     RowFeatures f{};
@@ -160,6 +220,7 @@ RowFeatures kv_scan_rows(const cr_kv* kv, const int32_t* seqs, int n, float pena
         f.sampled |= s.sampled; f.scored |= s.scored; f.constrained |= s.constrained;
         f.deep |= penalty != 1.0f && s.ngen > 4096;
         f.beam_rows += s.bgrp >= 0;
+        f.shares |= s.pfx_src >= 0;
     }
     return f;
 }
@@ -216,10 +277,23 @@ int cr_kv_reset(cr_kv* kv, int seq, void* stream) {
     if (!kv || seq >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_reset: bad sequence");
     CR_HIP(hipSetDevice(kv->ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const int s0 = seq < 0 ? 0 : seq, n = seq < 0 ? kv->n_seqs : 1;
+    int s0 = seq < 0 ? 0 : seq, n = seq < 0 ? kv->n_seqs : 1;
+    if (seq >= 0) {
+        // shared prompts: a source goes after its sharers.  Dissolving a beam group releases its members' shares first (they read the group's first sequence), so
+        // resetting any sequence of a group works as it always did; members that shared hold no prompt of their own and go with it
+        const int f = kv->seq[seq].bgrp, B = f >= 0 ? kv->seq[f].bnum : 0;
+        int outside = 0, inside = 0;
+        for (int t = 0; t < kv->n_seqs; t++)
+            if (kv->seq[t].pfx_src >= 0 && (kv->seq[t].pfx_src == seq || (f >= 0 && kv->seq[t].pfx_src >= f && kv->seq[t].pfx_src < f + B)))
+                (f >= 0 && t >= f && t < f + B ? inside : outside)++;
+        if (outside)
+            return cr_fail(CR_ERR_STATE, "cr_kv_reset: %d other sequences read the prompt of sequence %d (cr_kv_fork_shared): reset them first", outside, seq);
+        if (inside) { s0 = f; n = B; }
+    }
     hipLaunchKernelGGL(kv_reset_kernel, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st, kv_seq_state(kv), s0, n, seq < 0 ? 1 : 0);
     CR_HIP(hipGetLastError());
-    for (int s = s0; s < s0 + n; s++) kv->seq[s].clear(0);
+    for (int s = s0; s < s0 + n; s++) { kv_release_share(kv, s); kv->seq[s].clear(0); }
+    if (seq < 0) for (Seq& q : kv->seq) q.sharers = 0;
     if (kv->d_beam)                                                                     // a beam group goes as a whole with any of its sequences
         for (int s = s0; s < s0 + n; s++) {
             const int f = kv->seq[s].bgrp;
@@ -239,44 +313,69 @@ int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream) {
     if (n_tokens < 0 || n_tokens > q.len) return cr_fail(CR_ERR_ARG, "cr_kv_truncate: n_tokens %d outside 0..%d, the tokens sequence %d holds", n_tokens, q.len, seq);
     if (q.bgrp >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_truncate: sequence %d belongs to the beam group of sequence %d (cr_kv_reset dissolves the group)", seq, q.bgrp);
     if (n_tokens == 0) return cr_kv_reset(kv, seq, stream);
+    if (n_tokens < q.pfx_len)
+        return cr_fail(CR_ERR_STATE, "cr_kv_truncate: sequence %d reads the first %d cached positions of sequence %d (cr_kv_fork_shared) and cannot be cut to %d, "
+                       "below them (cr_kv_reset gives the share up)", seq, q.pfx_len, q.pfx_src, n_tokens);
+    if (n_tokens < kv_share_floor(kv, seq))
+        return cr_fail(CR_ERR_STATE, "cr_kv_truncate: %d other sequences read the first %d cached positions of sequence %d (cr_kv_fork_shared): not below them (reset "
+                       "the sharers first)", q.sharers, kv_share_floor(kv, seq), seq);
     CR_HIP(hipSetDevice(kv->ctx->device));
     KvSeqs one{};
     one.n = 1; one.seq[0] = seq;
-    hipLaunchKernelGGL(kv_truncate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv_seq_state(kv), one, n_tokens);
+    const int psrc = q.pfx_src, plen = q.pfx_len;      // a sharer cut at or above its shared length keeps its share
+    hipLaunchKernelGGL(kv_truncate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kv_seq_state(kv), one, n_tokens, psrc, plen);
     CR_HIP(hipGetLastError());
     q.clear(n_tokens);
+    q.pfx_src = psrc; q.pfx_len = plen;
     return CR_OK;
 }
 
-int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream) {
-    if (!kv || !dsts_host || src < 0 || src >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_fork: bad argument (null cache or destinations, or a source out of range)");
-    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "cr_kv_fork: the fork copies bf16 rows only (an e4m3 cache keeps no bf16 prefix for a continued prefill to read)");
+// cr_kv_fork and cr_kv_fork_shared: one set of checks, one launch
+static int kv_fork(const char* who, bool shared, cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream) {
+    if (!kv || !dsts_host || src < 0 || src >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "%s: bad argument (null cache or destinations, or a source out of range)", who);
+    if (kv->fmt != CR_KV_BF16) return cr_fail(CR_ERR_ARG, "%s: the fork copies bf16 rows only (an e4m3 cache keeps no bf16 prefix for a continued prefill to read)", who);
     if (n_dst < 1 || n_dst > kv->n_seqs - 1 || n_dst > KV_FORK_MAX)
-        return cr_fail(CR_ERR_ARG, "cr_kv_fork: %d destinations (want 1..%d)", n_dst, kv->n_seqs - 1 < KV_FORK_MAX ? kv->n_seqs - 1 : KV_FORK_MAX);
+        return cr_fail(CR_ERR_ARG, "%s: %d destinations (want 1..%d)", who, n_dst, kv->n_seqs - 1 < KV_FORK_MAX ? kv->n_seqs - 1 : KV_FORK_MAX);
     if (n_tokens < 1 || n_tokens > kv->seq[src].len)
-        return cr_fail(CR_ERR_ARG, "cr_kv_fork: n_tokens %d outside 1..%d, the tokens sequence %d holds", n_tokens, kv->seq[src].len, src);
+        return cr_fail(CR_ERR_ARG, "%s: n_tokens %d outside 1..%d, the tokens sequence %d holds", who, n_tokens, kv->seq[src].len, src);
     KvSeqs d{};
     d.n = n_dst;
     for (int j = 0; j < n_dst; j++) {
         const int s = dsts_host[j];
-        if (s < 0 || s >= kv->n_seqs || s == src) return cr_fail(CR_ERR_ARG, "cr_kv_fork: destination %d (want 0..%d, not the source %d)", s, kv->n_seqs - 1, src);
-        for (int i = 0; i < j; i++) if (dsts_host[i] == s) return cr_fail(CR_ERR_ARG, "cr_kv_fork: destination %d listed twice", s);
+        if (s < 0 || s >= kv->n_seqs || s == src) return cr_fail(CR_ERR_ARG, "%s: destination %d (want 0..%d, not the source %d)", who, s, kv->n_seqs - 1, src);
+        for (int i = 0; i < j; i++) if (dsts_host[i] == s) return cr_fail(CR_ERR_ARG, "%s: destination %d listed twice", who, s);
         d.seq[j] = s;
     }
-    if (kv->seq[src].bgrp >= 0) return cr_fail(CR_ERR_STATE, "cr_kv_fork: the source %d belongs to the beam group of sequence %d", src, kv->seq[src].bgrp);
+    if (kv->seq[src].bgrp >= 0) return cr_fail(CR_ERR_STATE, "%s: the source %d belongs to the beam group of sequence %d", who, src, kv->seq[src].bgrp);
     for (int j = 0; j < n_dst; j++)
         if (kv->seq[d.seq[j]].bgrp >= 0)
-            return cr_fail(CR_ERR_STATE, "cr_kv_fork: destination %d belongs to the beam group of sequence %d", d.seq[j], kv->seq[d.seq[j]].bgrp);
+            return cr_fail(CR_ERR_STATE, "%s: destination %d belongs to the beam group of sequence %d", who, d.seq[j], kv->seq[d.seq[j]].bgrp);
+    CR_TRY(fork_share_ok(kv, who, src, d));
     CR_HIP(hipSetDevice(kv->ctx->device));
     // bf16 cache [layers][n_seqs][8][max_tokens][128] (k, v): positions [0, n_tokens) of `src` go to every destination, every layer, KV head, K and V, and the
-    // destinations get the truncate's state -- one launch
-    const int pieces = n_tokens * 16;
-    hipLaunchKernelGGL(kv_fork_kernel, dim3((pieces + FORK_TILE - 1) / FORK_TILE, kv->layers * 16), dim3(FORK_THREADS), 0, (hipStream_t)stream, kv_seq_state(kv), beam_cache(kv),
-                       src, d, n_tokens);
-    CR_HIP(hipGetLastError());
-    for (int j = 0; j < n_dst; j++) kv->seq[d.seq[j]].clear(n_tokens);
+    // destinations get the truncate's state -- one launch.  Shared: positions [n_tokens & ~255, n_tokens) only, the rest is read from src
+    return launch_fork(kv, src, d, n_tokens, shared ? n_tokens & ~255 : 0, (hipStream_t)stream);
+}
+
+int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream) {
+    return kv_fork("cr_kv_fork", false, kv, src, dsts_host, n_dst, n_tokens, stream);
+}
+
+int cr_kv_fork_shared(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream) {
+    return kv_fork("cr_kv_fork_shared", true, kv, src, dsts_host, n_dst, n_tokens, stream);
+}
+
+int cr_kv_set_prefix_sharing(cr_kv* kv, int on) {
+    if (!kv) return cr_fail(CR_ERR_ARG, "cr_kv_set_prefix_sharing: null cache");
+    if (on && kv->fmt != CR_KV_BF16)
+        return cr_fail(CR_ERR_ARG, "cr_kv_set_prefix_sharing: an e4m3 cache (the shared fork moves bf16 rows and the e4m3 decode kernel has no group form: use a bf16 cache)");
+    for (int s = 0; s < kv->n_seqs; s++)
+        if (kv->seq[s].len != 0 || kv->seq[s].pfx_src >= 0 || kv->seq[s].sharers != 0)
+            return cr_fail(CR_ERR_STATE, "cr_kv_set_prefix_sharing: sequence %d holds tokens or a share (switch the mode on an empty cache: cr_kv_reset(-1) first)", s);
+    kv->share_mode = on != 0;
     return CR_OK;
 }
+
 
 int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const uint64_t* seeds_host, const float* last_logits, void* stream) {
     if (!kv || !dsts_host || src < 0 || src >= kv->n_seqs) return cr_fail(CR_ERR_ARG, "cr_kv_fanout: bad argument (null cache or destinations, or a source out of range)");
@@ -298,6 +397,7 @@ int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const 
     for (int j = 0; j < n_dst; j++)
         if (kv->seq[d.seq[j]].bgrp >= 0)
             return cr_fail(CR_ERR_STATE, "cr_kv_fanout: destination %d belongs to the beam group of sequence %d", d.seq[j], kv->seq[d.seq[j]].bgrp);
+    CR_TRY(fork_share_ok(kv, "cr_kv_fanout", src, d));
     if (!q.sampled) return cr_fail(CR_ERR_STATE, "cr_kv_fanout: the source %d does not sample (cr_kv_set_sampling with a temperature > 0 before its prefill)", src);
     if (q.constrained) return cr_fail(CR_ERR_STATE, "cr_kv_fanout: the source %d carries logits constraints (its last row is not what its pick chose from)", src);
     if (q.ngen != 1 || q.len < 1)
@@ -310,10 +410,10 @@ int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const 
         if (r == CR_ERR_NOMEM) return cr_fail(CR_ERR_NOMEM, "cr_kv_fanout: %zu bytes of score partials", logprobs_scratch_bytes(1, V));
         CR_TRY(r);
     }
-    // the prefix: kv_fork_kernel as cr_kv_fork launches it (the source read once, rows >= q.len of a destination not written, the cleared state)
-    const int pieces = q.len * 16;
+    // the prefix: kv_fork_kernel as cr_kv_fork launches it (the source read once, rows >= q.len of a destination not written, the cleared state); with
+    // cr_kv_set_prefix_sharing on, as cr_kv_fork_shared launches it
+    CR_TRY(launch_fork(kv, src, d, q.len, kv->share_mode ? q.len & ~255 : 0, st));
     const SeqState s = kv_seq_state(kv);
-    hipLaunchKernelGGL(kv_fork_kernel, dim3((pieces + FORK_TILE - 1) / FORK_TILE, kv->layers * 16), dim3(FORK_THREADS), 0, st, s, beam_cache(kv), src, d, q.len);
     FanSeeds seeds{};
     for (int j = 0; j < n_dst; j++) seeds.s[j] = seeds_host[j];
     hipLaunchKernelGGL(kv_fanout_state_kernel, dim3(1), dim3(64), 0, st, s, src, f, seeds);
@@ -321,8 +421,7 @@ int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const 
     CR_TRY(launch_sample_fan(last_logits, V, f, s, st));
     if (q.scored) CR_TRY(launch_logprobs_fan(last_logits, V, f, s, {0, kv->d_fan, kv->d_lp, kv->d_top_id, kv->d_top_lp}, st));
     for (int j = 0; j < n_dst; j++) {
-        Seq& t = kv->seq[d.seq[j]];
-        t.clear(q.len);
+        Seq& t = kv->seq[d.seq[j]];      // (launch_fork has cleared it to q.len tokens)
         t.ngen = 1; t.sampled = true; t.scored = q.scored;
     }
     return CR_OK;
@@ -485,6 +584,9 @@ int cr_kv_beam_reorder(cr_kv* kv, int first_seq, int num_beams, const int32_t* s
             return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: sequences %d and %d hold different counts of tokens or ids", first_seq, first_seq + j);
     }
     if (from > first.len) return cr_fail(CR_ERR_ARG, "cr_kv_beam_reorder: from %d past the %d cached tokens", from, first.len);
+    for (int j = 0; j < num_beams; j++)
+        if (from < kv->seq[first_seq + j].pfx_len || from < kv_share_floor(kv, first_seq + j))
+            return cr_fail(CR_ERR_STATE, "cr_kv_beam_reorder: from %d lies inside a shared prompt of sequence %d (cr_kv_fork_shared): those rows are not moved", from, first_seq + j);
     CR_HIP(hipSetDevice(kv->ctx->device));
     hipStream_t st = (hipStream_t)stream;
     CR_TRY(beam_alloc(kv, st));

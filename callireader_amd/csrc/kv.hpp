@@ -14,9 +14,13 @@ struct Seq {
     int len = 0, ngen = 0;                                       // tokens cached, ids generated
     bool sampled = false, scored = false, constrained = false;   // temperature > 0 / d_lpn != 0 / d_con_on != 0
     int bgrp = -1, bnum = 0;                                     // first sequence of its beam group (< 0: none); at that first sequence, the group's size
+    // shared prompt (cr_kv_fork_shared): this sequence reads cache rows [0, pfx_len) of sequence pfx_src (< 0: its own; pfx_len a multiple of 256), and `sharers`
+    // live sequences read this one's.  A sequence's own share goes with clear() (the caller gives the count back at the source first: kv_release_share); the
+    // count belongs to the source's rows, not to its state, and stays.
+    int pfx_src = -1, pfx_len = 0, sharers = 0;
     // the cleared state with n_tokens cached positions: the host side of kv.hip's kv_clear_state (the device side, over seqstate.hpp's SeqState), what reset, truncate and fork restore.  A new per-sequence
     // flag is cleared in these two places.  (Group membership goes by the group: cr_kv_reset dissolves it, truncate and fork refuse a member.)
-    void clear(int n_tokens) { len = n_tokens; ngen = 0; sampled = scored = constrained = false; }
+    void clear(int n_tokens) { len = n_tokens; ngen = 0; sampled = scored = constrained = false; pfx_src = -1; pfx_len = 0; }
 };
 
 struct cr_kv {
@@ -54,6 +58,10 @@ struct cr_kv {
     // a launch without a group launches nothing new
     // cr_kv_fanout's score partials of its one logits row (logprobs_scratch_bytes(1, vocab)), allocated by the first fan-out of a sequence that records scores
     void* d_fan = nullptr;
+    // shared prompts (cr_kv_set_prefix_sharing / cr_kv_fork_shared), allocated by the first call that shares: d_pfx_src int32[n] (-1: none), d_pfx_len int32[n].
+    // Seq::pfx_src / pfx_len mirror them on the host: a launch without a sharer launches nothing new.  share_mode: cr_kv_fanout and a beam group's fan-out share
+    bool share_mode = false;
+    int32_t *d_pfx_src = nullptr, *d_pfx_len = nullptr;
     BeamState* d_beam = nullptr;
     int32_t* d_bgrp = nullptr;
     int64_t* d_bfin = nullptr;
@@ -64,8 +72,16 @@ struct cr_kv {
 // the per-sequence device state of the cache as every kernel takes it (seqstate.hpp): built once per call
 inline SeqState kv_seq_state(const cr_kv* kv) {
     return {kv->d_len, kv->d_ngen, kv->d_gen, kv->gen_cap, {kv->d_stop, kv->n_seqs}, kv->d_temp, kv->d_topk, kv->d_topp, kv->d_seed, kv->d_lpn, kv->d_lpdone,
-            kv->d_con_on, kv->d_bgrp};
+            kv->d_con_on, kv->d_bgrp, kv->d_pfx_src, kv->d_pfx_len};
 }
 
 // which features the rows seqs[0 .. n) (host) of a prefill / decode call use: scanned once per call, kept in the call's HeadBufs
 RowFeatures kv_scan_rows(const cr_kv* kv, const int32_t* seqs, int n, float penalty);
+
+// Shared prompts (kv.hip).  kv_share_floor: the largest pfx_len among the live sharers of `seq` (0: none) -- rows below it must not be rewritten.
+// kv_release_share: the host side of giving up seq's share (the device side is kv_clear_state's).  kv_share_alloc: the two device arrays, by the first call that
+// shares.  kv_refuse_sharer: CR_ERR_STATE with `alt` (the unshared alternative) if seq reads a shared prompt, else CR_OK.
+int kv_share_floor(const cr_kv* kv, int seq);
+void kv_release_share(cr_kv* kv, int seq);
+int kv_share_alloc(cr_kv* kv, hipStream_t st);
+int kv_refuse_sharer(const cr_kv* kv, int seq, const char* who, const char* alt);

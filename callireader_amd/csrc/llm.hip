@@ -471,6 +471,10 @@ struct DecodeBufs {
     // cr_llm_decode_draft: rows of one sequence's draft window.  off (NULL in a plain step, and in a draft step without a window): row i sits off[i] positions past
     // its sequence's cached length -- RoPE, the cache row and the key count follow it, and the RoPE-folded attention form is not taken.  Set by DraftBufs' carve.
     const int32_t* off = nullptr;
+    // rows that read a shared prompt (cr_kv_fork_shared): the launch's share table on the device (ctx_stage_share; attention.hpp: attn_share_table), share_n = 0:
+    // none, and the step launches what it always launched.  With shares the RoPE-folded attention form is not taken (the separate launch gives the same bits)
+    const int32_t* share = nullptr;
+    int share_n = 0, share_splits = 0;
 
     DecodeBufs(cr_ctx* c, int ff, const cr_kv* kv, int M, int nsplit, const RowFeatures& f)
         : M(M), nsplit(nsplit), ff(ff), kv8(kv->fmt == CR_KV_E4M3), s_qkv(gemm_partial_splits(QKV, D)),
@@ -500,6 +504,7 @@ AttnParams decode_attn_params(const cr_kv* kv, const LayerKV& lk, const DecodeBu
     ap.B = b.M; ap.H = NKV; ap.Sq = NH / NKV; ap.Sk = 0; ap.kv_group = 1; ap.q_pos0 = 0;
     ap.seq_map = d_seqs; ap.sk_arr = kv->d_len; ap.sk_add = 1; ap.sk_off = b.off;
     ap.nsplit = b.nsplit; ap.part_ml = b.part; ap.part_o = b.part + (size_t)b.M * NKV * b.nsplit * (NH / NKV) * 2;
+    if (b.share_n > 0) { ap.share_skip = b.share; ap.share_chunks = b.share + b.M; ap.share_n = b.share_n; ap.share_splits = b.share_splits; }
     return ap;
 }
 
@@ -558,7 +563,8 @@ int decode_layers(cr_ctx* c, const LlmWeights& lw, cr_kv* kv, const DecodeBufs& 
         fp.qkv_part = b.pbuf; fp.qkv_splits = b.s_qkv; fp.qkv_ld = QKV; fp.rope_cos = cosT; fp.rope_sin = sinT;
         // (never with a draft window's rows: a row would read cache rows that other workgroups of the same launch are still writing; decode_attn_fold_supported
         // refuses AttnParams::sk_off, and the separate launch below gives the same bits)
-        const bool rope_folded = b.sliced && c->fold_rope && !b.kv8 && decode_attn_fold_supported(fp, HD);
+        // (nor with rows that share a prompt: the group form reads q from b.q)
+        const bool rope_folded = b.sliced && c->fold_rope && !b.kv8 && b.share_n == 0 && decode_attn_fold_supported(fp, HD);
         if (rope_folded) ap = fp;
         // (b.pbuf: wqkv's K-slices when sliced, else null and the kernel reads b.qkv; of lk either the bf16 or the e4m3 pointers are null)
         else if (b.off)      // (bf16 caches only: cr_llm_decode_draft refuses an e4m3 one)
@@ -661,6 +667,10 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         if (kv->fmt == CR_KV_E4M3 && kv->seq[s].len != 0)
             return cr_fail(CR_ERR_ARG, "cr_llm_prefill: sequence %d of an e4m3 cache already holds %d tokens (the prefill attends in bf16 and an e4m3 cache "
                            "keeps no bf16 copy of a prefix: cr_kv_reset it first)", s, kv->seq[s].len);
+        CR_TRY(kv_refuse_sharer(kv, s, "cr_llm_prefill", "the prefill attention reads a sequence's own rows; continue an unshared copy (cr_kv_fork)"));
+        if (kv->seq[s].len < kv_share_floor(kv, s))
+            return cr_fail(CR_ERR_STATE, "cr_llm_prefill: %d other sequences read the first %d cached positions of sequence %d (cr_kv_fork_shared), and the prefill "
+                           "would write from position %d", kv->seq[s].sharers, kv_share_floor(kv, s), s, kv->seq[s].len);
         if (kv->seq[s].bgrp >= 0 && (kv->seq[s].bgrp != s || kv->seq[s].len != 0 || kv->seq[s].ngen != 0))
             return cr_fail(CR_ERR_ARG, "cr_llm_prefill: sequence %d belongs to the beam group of sequence %d: prefill the group's FIRST sequence, once, after "
                            "cr_kv_reset and cr_kv_set_beam", s, kv->seq[s].bgrp);
@@ -688,7 +698,9 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
     if (beams) {    // the fan-out: the prompt's cache rows, the first id and the length go from a group's first sequence to its others
         std::vector<int> firsts;
         for (int i = 0; i < n; i++) if (kv->seq[seqs[i]].bgrp == seqs[i]) firsts.push_back(i);
-        CR_TRY(launch_beam_reorder(b.head.rows(c->d_seqs, penalty), kv_seq_state(kv), beam_launch(kv, b.head, 0, 1), beam_cache(kv), firsts.data(), (int)firsts.size(), max_S, 1, st));
+        BeamLaunch bl = beam_launch(kv, b.head, 0, 1);
+        if (kv->share_mode) { CR_TRY(kv_share_alloc(kv, st)); bl.share = 1; }      // the shared fork: the last < 256 positions only, the rest is read from the first
+        CR_TRY(launch_beam_reorder(b.head.rows(c->d_seqs, penalty), kv_seq_state(kv), bl, beam_cache(kv), firsts.data(), (int)firsts.size(), max_S, 1, st));
     }
     CR_HIP(hipGetLastError());
     for (const Segment& sg : segs) {
@@ -696,7 +708,11 @@ int cr_llm_prefill_batch(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const
         q.len += sg.S;
         if (q.ngen < kv->gen_cap) q.ngen += 1;
         if (q.bgrp == sg.seq)
-            for (int j = 1; j < q.bnum; j++) { kv->seq[sg.seq + j].len = q.len; kv->seq[sg.seq + j].ngen = q.ngen; }
+            for (int j = 1; j < q.bnum; j++) {
+                Seq& m = kv->seq[sg.seq + j];
+                m.len = q.len; m.ngen = q.ngen;
+                if (kv->share_mode && q.len >= 256) { m.pfx_src = sg.seq; m.pfx_len = q.len & ~255; q.sharers++; }      // (beam_reorder_kernel wrote the device side)
+            }
     }
     return CR_OK;
 }
@@ -742,6 +758,10 @@ static int score_rows_batch(const char* who, cr_ctx* c, cr_kv* kv, const int32_t
         if (kv->seq[s].len + lens[i] > kv->max_tokens)
             return cr_fail(CR_ERR_ARG, "%s: %d + %d tokens exceed the cache (%d)", who, kv->seq[s].len, lens[i], kv->max_tokens);
         if (kv->seq[s].bgrp >= 0) return cr_fail(CR_ERR_ARG, "%s: sequence %d belongs to the beam group of sequence %d", who, s, kv->seq[s].bgrp);
+        CR_TRY(kv_refuse_sharer(kv, s, who, "the prefill attention reads a sequence's own rows; score an unshared copy (cr_kv_fork)"));
+        if (kv->seq[s].len < kv_share_floor(kv, s))
+            return cr_fail(CR_ERR_STATE, "%s: other sequences read the first %d cached positions of sequence %d (cr_kv_fork_shared), and the call would write from "
+                           "position %d", who, kv_share_floor(kv, s), s, kv->seq[s].len);
         segs.push_back({s, M, lens[i], kv->seq[s].len});
         M += lens[i];
         max_S = std::max(max_S, lens[i]);
@@ -870,6 +890,10 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
             if (seqs[i + j] != f + j) return cr_fail(CR_ERR_ARG, "cr_llm_decode: a beam group decodes whole: its %d sequences from %d on, consecutive in seqs[]", B, f);
         if (force_tokens) return cr_fail(CR_ERR_ARG, "cr_llm_decode: force_tokens with a beam group (sequence %d)", f);
         beam_span = std::max(beam_span, kv->seq[f].ngen + 1);
+        // the step's re-order moves rows [prompt length, length) only: past every shared prompt of the group (what the fan-out shared lies below the prompt's length)
+        for (int j = 0; j < B; j++)
+            if (kv->seq[f + j].pfx_len > kv->seq[f].len - kv->seq[f].ngen + 1)
+                return cr_fail(CR_ERR_STATE, "cr_llm_decode: sequence %d shares %d positions, more than its group's prompt holds", f + j, kv->seq[f + j].pfx_len);
         beam_firsts.push_back(i);
         i += B - 1;
     }
@@ -884,6 +908,13 @@ int cr_llm_decode(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const int64_
     DecodeBufs b(c, lw->ff, kv, n, nsplit, kv_scan_rows(kv, seqs, n, penalty));
     CR_TRY(ws_carve(c, "cr_llm_decode", b));
     CR_TRY(ctx_stage_seqs(c, seqs, n, st, false));
+    if (b.head.f.shares) {      // the groups of this launch, from the host's mirrors; sent again only when the rows or a share have changed
+        std::vector<int32_t> psrc(n), plen(n), table;
+        for (int i = 0; i < n; i++) { psrc[i] = kv->seq[seqs[i]].pfx_src; plen[i] = kv->seq[seqs[i]].pfx_len; }
+        b.share_n = attn_share_table(seqs, psrc.data(), plen.data(), n, table, &b.share_splits);
+        CR_TRY(ctx_stage_share(c, table, st));
+        b.share = c->d_share;
+    }
     const int32_t* d_seqs = c->d_seqs;
     hipLaunchKernelGGL(embed_rows_kernel<false>, dim3(n), dim3(256), 0, st, lw->embed, force_tokens, d_seqs, kv->d_gen, kv->d_ngen, kv->gen_cap, b.x, nullptr);
     CR_TRY(decode_layers(c, *lw, kv, b, d_seqs, st));
@@ -942,6 +973,7 @@ int cr_llm_decode_draft(cr_ctx* c, cr_kv* kv, const int32_t* seqs, int n, const 
         if (q.scored) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d records token scores (not with drafts)", seqs[i]);
         if (q.constrained) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d has logits constraints (not with drafts)", seqs[i]);
         if (q.bgrp >= 0) return cr_fail(CR_ERR_STATE, "cr_llm_decode_draft: sequence %d belongs to the beam group of sequence %d (not with drafts)", seqs[i], q.bgrp);
+        CR_TRY(kv_refuse_sharer(kv, seqs[i], "cr_llm_decode_draft", "a draft window's rows take the per-row attention forms only; draft on an unshared copy (cr_kv_fork)"));
     }
     CR_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;

@@ -74,6 +74,7 @@ struct cr_kv; struct Arena; struct BeamLaunch; struct BeamCache;
 struct RowFeatures {
     bool sampled, scored, constrained;      // a row samples / has token scores on / has logits constraints
     bool deep; int beam_rows;               // a row has more than 4096 ids under a penalty: the pick needs an untouched copy of the rows / rows in a beam group
+    bool shares;                            // a row reads a shared prompt (cr_kv_fork_shared): the decode attention takes its group form for the shared splits
 };
 
 // The LM head's n rows of a prefill / decode call, carved after the layer buffers

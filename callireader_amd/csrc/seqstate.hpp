@@ -36,7 +36,7 @@ struct StopView {
 static_assert(StopView::polled(5) == 1 + 5 + 5 && StopView::words(5) == StopView::polled(5) + 2 * 5, "the stop block: count, ring[n], stop count[n] | EOS[n], budget[n]");
 
 // Per-sequence state, every array indexed by the sequence.  lpn / lpdone are NULL while no sequence has switched scores on, con_on while none has switched
-// constraints on, bgrp while there is no beam group.
+// constraints on, bgrp while there is no beam group, pfx_src / pfx_len while no sequence has shared a prompt (cr_kv_fork_shared).
 struct SeqState {
     int32_t* len; int32_t* ngen;           // tokens cached, ids generated
     int64_t* gen; int gen_cap;             // id histories [.][gen_cap]
@@ -45,6 +45,7 @@ struct SeqState {
     int32_t* lpn; int32_t* lpdone;         // token scores: alternatives per sequence (0: off), slots written
     int32_t* con_on;                       // logits constraints (0: off)
     int32_t* bgrp;                         // first sequence of the sequence's beam group (< 0: none)
+    int32_t* pfx_src; int32_t* pfx_len;    // shared prompt: the sequence whose cache rows [0, pfx_len) this one reads (< 0: its own), a multiple of 256
     __device__ int64_t* hist(int seq) const { return gen + (int64_t)seq * gen_cap; }
     __device__ bool beam_row(int seq) const { return bgrp && bgrp[seq] >= 0; }
     // Append `id` to `seq`, which held ng ids: the history slot, the count, the stop check; the cached length grows by len_add whether or not the history

@@ -377,6 +377,7 @@ class KVCache:
         fmt = B.lib.cr_kv_format(h)
         self.format = {v: k for k, v in KV_DTYPES.items()}[fmt]      # 'bf16' | 'e4m3'
         self._top_n = {}                                             # seq -> alternatives recorded per id (set_logprobs)
+        self.prefix_sharing = False                                  # set_prefix_sharing
 
     def length(self, seq):
         return B.lib.cr_kv_length(self._h, seq)
@@ -402,6 +403,21 @@ class KVCache:
         B.check(B.lib.cr_kv_fork(self._h, int(src), (C.c_int32 * len(dsts))(*dsts), len(dsts), int(n), _stream()), 'cr_kv_fork')
         for d in dsts:
             self._top_n.pop(d, None)
+
+    def fork_shared(self, src, dsts, n):
+        """cr_kv_fork_shared on the current stream: as fork, but only positions [n & ~255, n) are copied; every sequence of `dsts` reads positions
+        [0, n & ~255) from `src` from then on (its share), and the decode attention loads those once for all the rows that share them.  Same bits as
+        fork.  While it has sharers `src` cannot be reset, cut below the share or prefilled below it: reset the sharers first."""
+        dsts = [int(d) for d in dsts]
+        B.check(B.lib.cr_kv_fork_shared(self._h, int(src), (C.c_int32 * len(dsts))(*dsts), len(dsts), int(n), _stream()), 'cr_kv_fork_shared')
+        for d in dsts:
+            self._top_n.pop(d, None)
+
+    def set_prefix_sharing(self, on=True):
+        """cr_kv_set_prefix_sharing: while on, fanout and a beam group's fan-out share the prompt instead of copying it (same results, bit for bit).
+        Only on a cache none of whose sequences holds tokens; bf16 caches only."""
+        B.check(B.lib.cr_kv_set_prefix_sharing(self._h, 1 if on else 0), 'cr_kv_set_prefix_sharing')
+        self.prefix_sharing = bool(on)
 
     def fanout(self, src, dsts, seeds, last_logits):
         """cr_kv_fanout on the current stream: `src` has just been prefilled with sampling on (one generated id); every sequence of `dsts` becomes what a
@@ -784,6 +800,25 @@ def op_decode_attention(q, kc, vc, seqs, lens, s_div=11.313708498984761, which=0
         out = torch.empty(Bn, 4096, device=q.device, dtype=torch.bfloat16)
     B.check(B.lib.cr_op_decode_attention(which, _p(q), _p(kc), _p(vc), max_tokens, _p(seqs), _p(lens), Bn, max_keys, float(s_div), _p(scratch), _p(out), _stream()),
             'cr_op_decode_attention')
+    return out
+
+
+def op_decode_attention_shared(q, kc, vc, seqs, lens, pfx_src, pfx_len, s_div=11.313708498984761, max_keys=None, scratch=None, out=None):
+    """cr_op_decode_attention_shared: op_decode_attention where row b reads positions [0, pfx_len[b]) from slot pfx_src[b] (-1: its own throughout) and the
+    rest from its own slot seqs[b].  pfx_src / pfx_len: one int per ROW, host sequences; pfx_len a multiple of 256.  Returns (B, 4096) bf16."""
+    Bn = q.shape[0]
+    max_tokens = kc.shape[2]
+    if max_keys is None:
+        max_keys = int(lens.max().item()) + 1
+    if scratch is None:
+        scratch = torch.empty(int(B.lib.cr_op_decode_attention_scratch_floats(Bn, max_keys)), device=q.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(Bn, 4096, device=q.device, dtype=torch.bfloat16)
+    ps, pl = [int(x) for x in pfx_src], [int(x) for x in pfx_len]
+    if len(ps) != Bn or len(pl) != Bn:
+        raise ValueError(f'op_decode_attention_shared: {len(ps)} / {len(pl)} share entries for {Bn} rows')
+    B.check(B.lib.cr_op_decode_attention_shared(_p(q), _p(kc), _p(vc), max_tokens, _p(seqs), _p(lens), (C.c_int32 * Bn)(*ps), (C.c_int32 * Bn)(*pl), Bn, max_keys,
+                                                float(s_div), _p(scratch), _p(out), _stream()), 'cr_op_decode_attention_shared')
     return out
 
 

@@ -38,6 +38,24 @@ def per_page_sampling(sampling, seeds, P):
     return [None if sp is None else (sp, int(sd)) for sp, sd in zip(sps, seeds)]
 
 
+def share_cache(kv, on):
+    """The cache's prefix-sharing mode for the call that has just reset it whole (KVCache.set_prefix_sharing is accepted on an empty cache only).  A call
+    that leaves the mode as it is -- every call without share_prompt on a cache that never shared -- issues nothing."""
+    if bool(getattr(kv, 'prefix_sharing', False)) != bool(on):
+        kv.set_prefix_sharing(bool(on))
+
+
+def release_shared(kv, groups):
+    """The end of a call that shared prompts.  groups: per page its sequences, the one the others read first.  Sharers are reset BEFORE their source (the
+    cache refuses the other order), then the mode goes off: the cache is left as a call without share_prompt expects it."""
+    for g in groups:
+        for s in g[1:]:
+            kv.reset(s)
+    for g in groups:
+        kv.reset(g[0])
+    share_cache(kv, False)
+
+
 def admit(engine, kv, seqs, embeds_list, penalty, per_page=None, lpn=(), prefill_batch=16, reset_each=False, constraints=()):
     """Put one prompt into each of the sequences `seqs`: reset (the whole cache in one call, or with reset_each only these sequences), then the sampled
     pages' state (per_page: per_page_sampling's list), then the constrained pages' (constraints: a constraints.Constraints or None per page), then the

@@ -344,6 +344,9 @@ def build_parser():
     parser.add_argument('--num_return_sequences', type=int, default=1, metavar='N',
                         help='with --do_sample: N sampled answers per page from one visual stage and one prefill (pages x N <= 64 decode rows); the console prints '
                              'the N answers (with --scores their total log-probabilities), the results JSON holds the list of N as `response` (only when N > 1)')
+    parser.add_argument('--share_prompt', action='store_true',
+                        help="with --num_beams > 1 or --num_return_sequences > 1: a page's beams / samples read ONE cached copy of its prompt in decode instead of one "
+                             'each (less cache traffic per step, the same responses bit for bit; bf16 cache only); with one row per page it does nothing')
     parser.add_argument('--seed', type=int, default=None, help='torch.manual_seed before the run: --do_sample output becomes reproducible')
     parser.add_argument('--num_beams', type=int, default=1, help='beam search with this many beams (2..8; transformers\' deterministic beam search, on the device); 1: the greedy default')
     parser.add_argument('--length_penalty', type=float, default=None, help='with --num_beams > 1: exponent of the hypothesis length a finished score is divided by (default 1.0)')
@@ -398,6 +401,8 @@ def main(argv=None):
         generation_config['num_return_sequences'] = args.num_return_sequences
     generation_config.update(beam_config(args))
     generation_config.update(constraint_config(args))
+    if args.share_prompt and (args.num_beams > 1 or args.num_return_sequences > 1):      # (one row per page: nothing to share, and the pipelines do not take the keyword)
+        generation_config['share_prompt'] = True
     if args.seed is not None:
         torch.manual_seed(args.seed)
     detect_model = load_detector(args.params)

@@ -29,10 +29,10 @@ from .constraints import parse as constraints_parse, per_page as constraints_per
 from . import draft as drafting
 from . import grounding
 from . import scoring
-from .generation import admit, check_fits, decode_rows, decode_rows_drafted, per_page_sampling, read_scores, reply_shape, reply_text
+from .generation import admit, check_fits, decode_rows, decode_rows_drafted, per_page_sampling, read_scores, release_shared, reply_shape, reply_text, share_cache
 from .pipeline import PagePipeline
 from .preprocess import load_image, load_image_2, plan_page, plan_chars_array
-from .sampling import base_seed, check_rows, fan_seeds, page_seeds, parse as sampling_parse, parse_beams, parse_returns, splitmix64
+from .sampling import base_seed, check_rows, fan_seeds, page_seeds, parse as sampling_parse, parse_beams, parse_returns, parse_share, refuse_share, splitmix64
 from .scores import generate_outputs, ResponseScores, TokenScores, generate_output, parse as scores_parse, per_page as scores_per_page
 
 
@@ -302,6 +302,13 @@ class InternVLChatModel:
         max_new, eos, sp = self._gen_args(generate_kwargs, allow_beams=True, allow_returns=True)
         beams = parse_beams(generate_kwargs)
         nret = parse_returns(generate_kwargs)
+        share = parse_share(generate_kwargs)       # (with one row per page it is accepted and does nothing)
+        if share and draft_ids is not None:
+            refuse_share('a draft (draft_ids / draft=)')
+        if share and where:
+            refuse_share('a page session (its turns continue prefills, which read a sequence\'s own rows)')
+        if share and self.kv_cache_dtype != 'bf16':
+            refuse_share("kv_cache_dtype='e4m3'")
         if draft_ids is not None:
             if beams is not None:
                 drafting.refuse(f'num_beams={beams.num_beams}')
@@ -318,7 +325,7 @@ class InternVLChatModel:
             raise NotImplementedError(f'num_beams={beams.num_beams} in a page session: cr_kv_set_beam needs empty sequences (use chat_ocr(history=...))')
         if beams is not None:                      # beam search: the page's beams decode as one batch (generate_pages)
             ids, sc = self.generate_pages([input_embeds], max_new, eos, repetition_penalty, num_beams=beams.num_beams, length_penalty=beams.length_penalty,
-                                          early_stopping=beams.early_stopping)
+                                          early_stopping=beams.early_stopping, share_prompt=share)
             seq = torch.tensor([ids[0]], dtype=torch.long, device=self.device)
             if not generate_kwargs.get('return_dict_in_generate', False):
                 return seq
@@ -329,7 +336,7 @@ class InternVLChatModel:
             where = dict(where, draft_ids=draft_ids)
         n = scores_parse(generate_kwargs)
         if nret > 1:                               # several sampled answers: one prefill, the page's samples decode as one batch (generate_pages)
-            outs = self.generate_pages([input_embeds], max_new, eos, repetition_penalty, sampling=sp, logprobs=n, num_return_sequences=nret)
+            outs = self.generate_pages([input_embeds], max_new, eos, repetition_penalty, sampling=sp, logprobs=n, num_return_sequences=nret, share_prompt=share)
             ids, tss = (outs[0][0], outs[1][0]) if n else (outs[0], None)
             pad = generate_kwargs.get('pad_token_id')
             pad = (eos if eos is not None else 0) if pad is None else pad         # transformers: pad_token_id defaults to the EOS id
@@ -356,6 +363,8 @@ class InternVLChatModel:
             raise NotImplementedError(f"num_beams={generate_kwargs.get('num_beams')}: this entry point decodes one row per page (num_beams=1); beam search runs "
                                       'through generate / generate_ocr / generate_origin, chat_ocr, dynamic_chat, generate_pages and chat_ocr_pages')
         sp = sampling_parse(generate_kwargs)
+        if not allow_returns and parse_share(generate_kwargs):      # the entry points that fan a page out are the ones that can share its prompt
+            refuse_share('this entry point (the pipelines, the sharded entry points, page sessions and chat decode one row per page or own their caches)')
         if not allow_returns and parse_returns(generate_kwargs) > 1:
             raise NotImplementedError(f"num_return_sequences={generate_kwargs.get('num_return_sequences')}: this entry point returns one answer per page (the "
                                       'pipelines, the sharded entry points and page sessions own their caches); several sampled answers per page come from '
@@ -656,27 +665,32 @@ class InternVLChatModel:
 
     def chat_ocr_pages(self, tokenizer, detect_model, images, question, generation_config, boxes_list=None, use_p=True,
                        drop_zero=False, hard_vq=False, repetition_penalty=1.5, IMG_START_TOKEN='<img>', IMG_END_TOKEN='</img>',
-                       IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise', return_scores=False):
+                       IMG_CONTEXT_TOKEN='<IMG_CONTEXT>', ALIGNED_TOKEN='[UNUSED_TOKEN_140]', errors='raise', return_scores=False, share_prompt=False):
         """Many pages at once (new: the reference's chat_ocr is one page per call, evaluate.py loops over it).  The
         character tiles of ALL pages go through the visual stage as one batch, the prompts are prefilled together and
         the pages decode as one batch; every page gets exactly the response its own chat_ocr call would produce.
         errors='return': a page whose own chat_ocr call would raise before generation (unreadable image, detector failure, no box, prompt too long) gets that
         exception object in its slot and the other pages run -- what folder mode's per-image try/except needs (inference.py:55-57).
         return_scores (True, or the number of alternatives per token): returns (responses, scores) with one scores.ResponseScores per page (None for a
-        page that failed)."""
+        page that failed).
+        share_prompt (or share_prompt=True in the generation_config): with beams or num_return_sequences > 1 a page's rows read one cached copy of its
+        prompt in decode (generate_pages); the responses are the same."""
         constraints_parse(generation_config, 0)                 # refused before the visual stage (the EOS id does not change what is refused)
         _, lpn = self._score_args(generation_config, return_scores)
         beams = parse_beams(dict(generation_config, return_scores=return_scores))
         nret = self._returns(generation_config, len(images))    # (so are too many rows and an e4m3 cache)
+        share = parse_share(dict(share_prompt=share_prompt)) or parse_share(generation_config)
+        if share and self.kv_cache_dtype != 'bf16':
+            refuse_share("kv_cache_dtype='e4m3'")
         embeds, meta = self._ocr_embeds(tokenizer, detect_model, images, question, generation_config, boxes_list, use_p, drop_zero,
                                         hard_vq, IMG_START_TOKEN, IMG_END_TOKEN, IMG_CONTEXT_TOKEN, ALIGNED_TOKEN, errors=errors, allow_returns=True)
         if beams is not None:                      # every page's beams in one decode batch; a page gets what its own chat_ocr call gives
             outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, num_beams=beams.num_beams, length_penalty=beams.length_penalty,
-                                       early_stopping=beams.early_stopping)[0] if embeds else []
+                                       early_stopping=beams.early_stopping, share_prompt=share)[0] if embeds else []
             return self._answer(tokenizer, outs, meta, False)
         outs = self.generate_pages(embeds, meta['max_new'], meta['eos'], repetition_penalty, sampling=meta['sampling'],
                                    seeds=self._ok_seeds(meta, nret), logprobs=lpn, constraints=meta['constraints'],
-                                   num_return_sequences=nret) if embeds else []
+                                   num_return_sequences=nret, share_prompt=share) if embeds else []
         return self._answer(tokenizer, outs, meta, return_scores)
 
     def _returns(self, generation_config, P):
@@ -731,6 +745,8 @@ class InternVLChatModel:
         chat_ocr_pages returns it."""
         if parse_beams(generation_config) is not None:
             raise NotImplementedError('chat_ocr_stream: beam search does not go through PagePipeline (use chat_ocr_pages)')
+        if parse_share(generation_config):
+            refuse_share('PagePipeline (chat_ocr_stream: it owns its caches and decodes one row per page)')
         if draft is not None:
             drafting.refuse('PagePipeline (chat_ocr_stream: its decode thread issues steps without waiting for them)')
         if parse_returns(dict(generation_config)) > 1:
@@ -846,6 +862,8 @@ class InternVLChatModel:
         (index, response, scores.ResponseScores), the scores None for a page that failed."""
         if parse_beams(generation_config) is not None:
             raise NotImplementedError('chat_ocr_continuous: beam search does not go through ContinuousPipeline (use chat_ocr_pages)')
+        if parse_share(generation_config):
+            refuse_share('ContinuousPipeline (chat_ocr_continuous: it owns its caches and refills rows one page at a time)')
         if draft is not None:
             drafting.refuse('ContinuousPipeline (chat_ocr_continuous: its rows stop on the device, its worker never waits for a step)')
         if parse_returns(dict(generation_config)) > 1:
@@ -1068,7 +1086,7 @@ class InternVLChatModel:
 
     def generate_pages(self, embeds_list, max_new_tokens=1024, eos_token_id=EOS_TOKEN_ID, repetition_penalty=1.0,
                        check_every=16, prefill_batch=16, sampling=None, seeds=None, logprobs=0, num_beams=1, length_penalty=1.0, early_stopping=False,
-                       constraints=None, drafts=None, num_return_sequences=1):
+                       constraints=None, drafts=None, num_return_sequences=1, share_prompt=False):
         """Prefill every page, then decode all unfinished pages as ONE batch per step: the 14.7 GB of LLM weights are
         streamed once per step for all pages.  Per page the ids equal the single-page greedy result.
         sampling: None (every page greedy), one sampling.SamplingParams for every page, or a list with one entry (or None: greedy) per page;
@@ -1088,7 +1106,15 @@ class InternVLChatModel:
         num_return_sequences = n > 1: n sampled answers per page from ONE prefill of it (_generate_pages_fanout; P * n <= 64).  The return value nests:
         ids[i][j] is sample j of page i -- exactly what this call gives for page i alone with seeds=[seeds[i * n + j]] -- and with logprobs the scores
         nest the same way.  seeds: P * n entries (default page_seeds(P * n): sampling.fan_seeds).  Sampled pages on a bf16 cache, without constraints,
-        drafts or beams."""
+        drafts or beams.
+        share_prompt=True: with beams or num_return_sequences > 1 the call's cache shares each page's prompt between its rows instead of copying it
+        (KVCache.set_prefix_sharing: the fan-out copies the last < 256 positions only, and each decode step loads the shared part once per page); ids, scores
+        and sequences_scores are the same, bit for bit.  With one row per page it is accepted and does nothing.  Not with drafts or an e4m3 cache."""
+        share = parse_share(dict(share_prompt=share_prompt))
+        if share and drafts is not None:
+            refuse_share('drafts')
+        if share and self.kv_cache_dtype != 'bf16':
+            refuse_share("kv_cache_dtype='e4m3'")
         P = len(embeds_list)
         cons = constraints_per_page(constraints, P)
         beams = parse_beams(dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping))
@@ -1102,7 +1128,7 @@ class InternVLChatModel:
             if any(c is not None for c in cons):
                 raise NotImplementedError('generate_pages: logits constraints on a sampled page are not implemented (greedy decoding only)')
             return self._generate_pages_fanout(embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds,
-                                               scores_per_page(logprobs, P), nret)
+                                               scores_per_page(logprobs, P), nret, share)
         if drafts is not None:
             if len(drafts) != P:
                 raise ValueError(f'drafts: {len(drafts)} entries for {P} pages')
@@ -1121,7 +1147,7 @@ class InternVLChatModel:
                 raise NotImplementedError('generate_pages: beam search takes neither sampling nor token scores')
             if any(c is not None for c in cons):
                 raise NotImplementedError('generate_pages: logits constraints with beam search are not implemented (greedy decoding only)')
-            return self._generate_pages_beams(embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams)
+            return self._generate_pages_beams(embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams, share)
         per_page = per_page_sampling(sampling, seeds, P)
         lpn = scores_per_page(logprobs, P)
         kv, seqs = self.kv(P), list(range(P))
@@ -1260,7 +1286,7 @@ class InternVLChatModel:
         return response, grounding.Grounding.build(y, mass.numpy(), spans, grounding.pieces_of(tokenizer, y), boxes,
                                                    layers if layers is not None else (0, n_layers or 0), grounding.special_ids_of(tokenizer), sc)
 
-    def _generate_pages_fanout(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds, lpn, n):
+    def _generate_pages_fanout(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds, lpn, n, share=False):
         """generate_pages with n > 1 sampled answers per page: page i is prefilled ONCE, into sequence fan_slots(i, n)[0] with the seed of its sample 0, and
         KVCache.fanout gives its other n - 1 sequences the cached prompt and each its own first id from the prefill's raw last row; the P * n rows then
         decode as one batch per step through decode_rows.  A decode row's bits do not depend on its batch and a draw depends only on (seed, step, row,
@@ -1278,6 +1304,16 @@ class InternVLChatModel:
             check_fits(e.shape[0], max_new_tokens, self.max_tokens)
         kv = self.kv(P * n)
         kv.reset()
+        share_cache(kv, share)                     # share: fanout copies the last < 256 positions and the samples read the rest from sample 0's sequence
+        try:
+            return self._fanout_decode(kv, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds, lpn, n)
+        finally:
+            if share:
+                release_shared(kv, [fan_slots(i, n) for i in range(P)])
+
+    def _fanout_decode(self, kv, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, sps, seeds, lpn, n):
+        """_generate_pages_fanout on a cache that has been reset: the prefills, the fan-outs, the decode, the read-back."""
+        P = len(embeds_list)
         first = [fan_slots(i, n)[0] for i in range(P)]
         for i, sp in enumerate(sps):
             kv.set_sampling(first[i], sp.temperature, sp.top_k, sp.top_p, int(seeds[i * n]))
@@ -1295,7 +1331,7 @@ class InternVLChatModel:
         ts = read_scores(kv, [m for m in lpn for _ in range(n)], outs)
         return ids, [ts[i * n:(i + 1) * n] for i in range(P)]
 
-    def _generate_pages_beams(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams):
+    def _generate_pages_beams(self, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams, share=False):
         """generate_pages with beam search: page i is the beam group of sequences beam_slots(i, B); the done flags are read every check_every steps,
         where the greedy loop reads EOS."""
         P, Bn = len(embeds_list), beams.num_beams
@@ -1305,6 +1341,16 @@ class InternVLChatModel:
         for e in embeds_list:
             check_fits(e.shape[0], max_new_tokens, self.max_tokens)
         kv.reset()
+        share_cache(kv, share)                     # share: a group's fan-out copies the last < 256 positions and its beams read the rest from its first sequence
+        try:
+            return self._beams_decode(kv, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams)
+        finally:
+            if share:
+                release_shared(kv, [beam_slots(i, Bn) for i in range(P)])
+
+    def _beams_decode(self, kv, embeds_list, max_new_tokens, eos_token_id, repetition_penalty, check_every, prefill_batch, beams):
+        """_generate_pages_beams on a cache that has been reset: the groups, the prefills, the decode, the results."""
+        P, Bn = len(embeds_list), beams.num_beams
         for i in range(P):
             kv.set_beam(beam_slots(i, Bn)[0], Bn, beams.length_penalty, beams.early_stopping, eos_token_id, max_new_tokens)
         for i0 in range(0, P, prefill_batch):

@@ -121,6 +121,26 @@ def parse_returns(kwargs):
     return n
 
 
+def parse_share(kwargs):
+    """share_prompt of a generation config (not one of transformers' keywords): False (the default), or True -- a page's beams or sampled answers read ONE
+    cached copy of its prompt in decode instead of one each (KVCache.set_prefix_sharing; the same ids, bit for bit).  ValueError for anything but a bool."""
+    v = kwargs.get('share_prompt', False)
+    if v is None:
+        return False
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f'`share_prompt` has to be True or False, but is {v!r}')
+    return bool(v)
+
+
+SHARE_ENTRY_POINTS = 'generate / generate_ocr / generate_origin, chat_ocr, dynamic_chat, chat_ocr_pages and generate_pages'
+
+
+def refuse_share(what):
+    """The NotImplementedError of an entry point or a feature that does not take share_prompt=True, naming the alternative."""
+    raise NotImplementedError(f'share_prompt=True is not implemented with {what}: leave it off there (the copying fan-out gives the same ids), or use '
+                              f'{SHARE_ENTRY_POINTS} on a bf16 cache')
+
+
 def check_rows(P, n):
     """P pages x n returned sequences have to fit one batched decode step."""
     if P * n > MAX_ROWS:

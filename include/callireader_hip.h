@@ -167,6 +167,24 @@ int cr_kv_truncate(cr_kv* kv, int seq, int n_tokens, void* stream);
  * a destination equal to src, repeated or out of range, or an e4m3 cache (left out, as for the beam re-order: it keeps no bf16 prefix for a continued
  * prefill to read anyway); CR_ERR_STATE for a beam-group member on either side.  Enqueued on `stream`.  Added within ABI v13. */
 int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream);
+/* cr_kv_fork without the copy of the prompt: cr_kv_fork's arguments, checks and resulting state, but only positions [n_tokens & ~255, n_tokens) of src are copied
+ * (fewer than 256, every layer, KV head, K and V) and every destination records that it READS positions [0, n_tokens & ~255) of src: its share (pfx_src = src,
+ * pfx_len = n_tokens & ~255, a multiple of the decode attention's 256-key split).  Rows [0, pfx_len) of a destination are not written.  With n_tokens < 256
+ * nothing is shared and the call is cr_kv_fork.  cr_llm_decode then loads each shared 256-key split of src once for all the rows of the call that share it
+ * (csrc/attention_decode_group.hip) and runs the per-row arithmetic of the unshared kernel for each: ids, logits and scores are bit-equal to cr_kv_fork's.
+ * The first call that shares allocates two int32[n_seqs] arrays and synchronises `stream` once.
+ * Lifetime, all CR_ERR_STATE, nothing changes on refusal.  While a source has sharers: cr_kv_reset of it, cr_kv_truncate of it below the largest pfx_len of its
+ * sharers, a prefill / scoring / grounding call that would write below that length, and a fork or fan-out INTO it are refused; cr_kv_reset(-1) always goes.
+ * cr_kv_reset of a sharer gives its share up; so does a fork or fan-out into it.  Resetting a sequence of a beam group dissolves the group as it always did: its
+ * members' shares (cr_kv_set_prefix_sharing) go first, and members that shared are reset with it.  On a sequence that shares: cr_kv_truncate below its pfx_len
+ * (at or above keeps the share), a continued prefill, cr_llm_score_batch, cr_llm_ground_batch, cr_llm_decode_draft, and cr_kv_fork / cr_kv_fork_shared /
+ * cr_kv_fanout FROM it are refused -- the prefill attention and the draft forms read a sequence's own rows; use cr_kv_fork for those.  Added within ABI v13. */
+int cr_kv_fork_shared(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_tokens, void* stream);
+/* Cache-level mode, default off: while on, cr_kv_fanout's copy and the fan-out of a beam group's prompt after its prefill are cr_kv_fork_shared's (the last
+ * n & ~255 .. n positions copied, the rest read from the source / the group's first sequence); everything else they do -- state, first ids, scores, lengths -- is
+ * unchanged, and so is every result (bit for bit).  Later beam steps re-order positions [prompt length, length) only, which lie past every share.  Accepted only
+ * while no sequence of the cache holds tokens or a share (CR_ERR_STATE otherwise); CR_ERR_ARG to switch it on for an e4m3 cache.  Added within ABI v13. */
+int cr_kv_set_prefix_sharing(cr_kv* kv, int on);
 /* Several sampled answers from one prefill.  `src` has just been prefilled (cr_llm_prefill / cr_llm_prefill_batch) with sampling on: S cached positions, ONE
  * generated id.  Each of the n_dst sequences dsts_host[] (host array) becomes what a lone prefill of the same prompt into it would have left behind
  * cr_kv_set_sampling(dst, src's temperature / top_k / top_p, seeds_host[j]) -- and cr_kv_set_logprobs(dst, src's top_n) if src records scores:
@@ -185,7 +203,8 @@ int cr_kv_fork(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, int n_to
  * src that does not sample (temperature 0), that carries logits constraints, or that does not hold exactly one generated id.  Added within ABI v13. */
 int cr_kv_fanout(cr_kv* kv, int src, const int32_t* dsts_host, int n_dst, const uint64_t* seeds_host, const float* last_logits, void* stream);
 /* One cached position as the reference's tuple cache holds it (InternVL/modeling_internlm2.py:383-388, K after RoPE):
- * out [8 kv heads][128] bf16 (device) = past_key_values[layer][which][seq, :, pos, :]; which 0 = K, 1 = V.  Parity tests. */
+ * out [8 kv heads][128] bf16 (device) = past_key_values[layer][which][seq, :, pos, :]; which 0 = K, 1 = V.  Parity tests.  The slot's OWN memory, with no
+ * redirection: below the pfx_len of a sequence that shares (cr_kv_fork_shared) it returns whatever the slot held before, not the source's rows. */
 int cr_kv_read(cr_kv* kv, int layer, int seq, int pos, int which, void* out, void* stream);
 /* The same position of an e4m3 cache (cr_kv_read refuses one): q_out [8 kv heads][128] e4m3 bytes, s_out [8] fp32 scales (both device).  Parity tests. */
 int cr_kv_read_e4m3(cr_kv* kv, int layer, int seq, int pos, int which, uint8_t* q_out, float* s_out, void* stream);
@@ -570,6 +589,13 @@ int cr_op_perceiver_attention(int which, const void* q, const void* kv, void* ou
 int64_t cr_op_decode_attention_scratch_floats(int B, int max_keys);
 int cr_op_decode_attention(int which, const void* q, const void* kc, const void* vc, int max_tokens, const int32_t* seqs, const int32_t* lens, int B, int max_keys,
                            float s_div, float* scratch, void* out, void* stream);
+/* The same with shared prompts (test entry; cr_llm_decode drives the same launcher): row b reads positions [0, pfx_len[b]) from slot pfx_src[b] and the rest from
+ * its own slot seqs[b]; pfx_src[b] < 0: all its own.  pfx_src / pfx_len are HOST arrays of B ints (a row's share, not a slot's), pfx_len a multiple of 256 and
+ * <= lens[seqs[b]]; seqs / lens are DEVICE arrays as above.  Rows with the same (pfx_src, pfx_len) -- and the row whose slot IS that source -- are grouped, in chunks
+ * of 8; the rows of a sharer's slot below pfx_len are never read.  Bit-equal to cr_op_decode_attention on a cache that holds copies.  Synchronises `stream`.
+ * CR_ERR_ARG for a pfx_len that is no multiple of 256 or reaches max_keys.  Added within ABI v13. */
+int cr_op_decode_attention_shared(const void* q, const void* kc, const void* vc, int max_tokens, const int32_t* seqs, const int32_t* lens, const int32_t* pfx_src,
+                                  const int32_t* pfx_len, int B, int max_keys, float s_div, float* scratch, void* out, void* stream);
 /* The same over an e4m3 cache (the reader cr_llm_decode uses on a CR_KV_E4M3 cache): kc / vc [n_slots][8][max_tokens][128] e4m3 bytes, ks / vs
  * [n_slots][8][max_tokens] fp32 row scales, arithmetic as under cr_kv_alloc_ex.  which = 0 only (1, the matrix-core kernel, reads bf16: CR_ERR_ARG).  ABI v13. */
 int cr_op_decode_attention_e4m3(int which, const void* q, const void* kc, const void* vc, const float* ks, const float* vs, int max_tokens, const int32_t* seqs,
